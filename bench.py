@@ -3,6 +3,7 @@
 compute with fp32 accumulate, online EMA teacher) on N MI355X GPUs, one process per GPU over RCCL.
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR     (+ the last timed step's outputs, DIR/*.npy)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line (rank 0).  A step = model(src), model(tgt), EMA-teacher forward on tgt, label_refine,
@@ -62,7 +63,41 @@ def parse():
                     'iterations on the same model and batch; adds "align_step" to the JSON')
     ap.add_argument('--tta-tiles', type=int, default=0, help='also time the teacher harness (SURVEY 8f.1): 8-view TTA '
                     'sliding-window inference of this many 512x512 target tiles; adds "teacher_harness" to the JSON')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last step of the reported timed window computed to DIR/<name>.npy (float32, rank 0): '
+                         'the step\'s losses and squared gradient norm, the pseudo labels, the prototypes, and fixed seeded '
+                         'samples of the updated weights and EMA shadow; the same arguments give the same inputs on every run')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
+
+
+DUMP_MAX_ELEMS = 1 << 22        # --dump-outputs: a larger array is written as this many elements at fixed seeded positions
+
+
+def snapshot_outputs(step, out):
+    """What the step that returned `out` computed, copied to the host as float32 arrays {name: array}.  A recorded
+    step overwrites these buffers on its next replay, so this is called right behind the timed window (which ends
+    with a device-wide synchronize).  An array of more than DUMP_MAX_ELEMS elements (the weight vectors) is flattened
+    and sampled at one position per block of numel // DUMP_MAX_ELEMS elements, drawn from a fixed seed: the same
+    positions on every run, under 64 MB in all."""
+    import numpy as np
+    import torch
+    arrays = {'loss_source': out[0], 'loss_target': out[1], 'grad_norm_sq': out[2],
+              'pseudo_labels': step.last_hard, 'prototypes': step.prototypes, 'weights_sample': step.model.flat_p}
+    if step.teacher is not None:
+        arrays['ema_weights_sample'] = step.teacher.flat_p
+    res = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            block = t.numel() // DUMP_MAX_ELEMS
+            pos = np.arange(DUMP_MAX_ELEMS) * block + np.random.default_rng(0).integers(0, block, DUMP_MAX_ELEMS)
+            t = t.reshape(-1)[torch.from_numpy(pos).to(t.device)]
+        res[name] = t.float().cpu().numpy()
+    assert sum(a.nbytes for a in res.values()) <= 64 << 20
+    return res
 
 
 def flush_c_stdio():
@@ -538,6 +573,7 @@ def main():
     # `value`: inputs resident in HBM when the timed region starts (the bench contract): the FIRST window of exactly K steps;
     # further windows of the same K steps only report the spread (a 0.4 - 0.8 s window on a freshly leased box moves by +-1 %)
     dt, t_host, out = timed_steps()
+    dumped = snapshot_outputs(step, out) if args.dump_outputs and rank == 0 else None
     windows = [dt / args.steps * 1e3] + [timed_steps()[0] / args.steps * 1e3 for _ in range(max(0, args.repeats))]
     dt_h2d = None
     if not args.no_h2d:
@@ -745,6 +781,11 @@ def main():
         except OSError as e:
             print(f'bench.py: could not write {full_path}: {e}', file=sys.stderr)
             full_path = None
+        if dumped is not None:
+            import numpy as np
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in dumped.items():
+                np.save(os.path.join(args.dump_outputs, name + '.npy'), a)
         # RCCL prints a version banner through C stdio, which a pipe or file buffers until the process exits -- behind
         # anything Python printed.  Drain it first so that the JSON line is the LAST line of stdout.
         flush_c_stdio()
