@@ -157,7 +157,9 @@ int rgda_proto_update(const float* feat, const int64_t* label, float* protos, in
  * bytes): f32 sums[c][k] = sum of feat over the pixels whose downscaled label is class c, f32 cnt[c] = their number,
  * then a flag word.  Both add over batches: the ranks all-reduce (sum) the first c * k + c floats and each calls
  * rgda_proto_apply -- local = sums / (cnt + 1e-7), the old prototype where cnt < 1 (:318-321), EMA (:435-438) -- which
- * gives the prototypes of the concatenated global batch on every rank.  rgda_proto_update == stats + apply. */
+ * gives the prototypes of the concatenated global batch on every rank.  rgda_proto_update == stats + apply.
+ * rgda_proto_apply takes 0 <= decay < 1: decay 0 on zero prototypes is Aligner.init_avg (alignment.py:121-122) over
+ * statistics summed across batches (update_avg, :107-119) -- classes without pixels stay 0. */
 int rgda_proto_stats(const float* feat, const int64_t* label, int64_t* label_ds, int b, int k, int c,
                      int h, int w, int scale, int ignore_label, float min_ratio, void* stats,
                      size_t stats_bytes, rgda_stream_t stream);
@@ -591,6 +593,26 @@ size_t rgda_pcl_loss_workspace(int C, int K);
 int rgda_pcl_loss(const float* feat, const int64_t* labels, const float* protos, float* loss, void* dfeat,
                   int lddf, int accumulate, int b, int K, int C, int h, int w, int ignore_label,
                   float temperature, float weight, void* ws, size_t ws_bytes, rgda_stream_t stream);
+
+/* CoralLoss (regda/gast/coral.py, is_sqrt=False) of Aligner.align_domain (regda/gast/alignment.py:79-84), forward +
+ * gradient w.r.t. both feature maps in one call (stage 1 and stage 2 with --align-domain 1):
+ *   feat_s f32 (bs, d, hws): element (image b, channel c, pixel p) at feat_s[b * ldbs + c * ldcs + p] (NCHW: ldcs = h*w,
+ *   ldbs = d*h*w); its ns = bs * hws pixels are the rows of Xs (n, d).  Same for feat_t (nt rows); ns != nt allowed.
+ *   mu = column means of X (fp32, fixed order);  Xc = bf16(X - mu), rounded once
+ *   Cs = Xcs^T Xcs / (ns - 1), Ct = Xct^T Xct / (nt - 1)   (bf16 products, fp32 sums; tiles on and above the diagonal)
+ *   D = Cs - Ct (fp32);  loss[0] += weight * sum(D * D) / (4 d^2)
+ *   dfeat_s (optional) bf16 [ns][ldds], pixel-major -- the layout rgda_instnorm_bwd consumes:
+ *            (+)= weight * Xcs . bf16(D) / (d^2 (ns - 1))        (accumulate != 0: added in fp32, rounded once)
+ *   dfeat_t (optional) bf16 [nt][lddt]: (+)= -weight * Xct . bf16(D) / (d^2 (nt - 1))
+ * (D is symmetric and the centred rows sum to zero, so the mean term of the backward vanishes.)  d % 32 == 0,
+ * ns >= 2, nt >= 2, ldd % 8 == 0 (RGDA_ERR_ARG before any launch otherwise).  Deterministic: no atomics, the split-K
+ * partials of the covariance product are reduced in a fixed order.  ws: rgda_coral_loss_workspace bytes (0 for
+ * arguments the entry point rejects). */
+size_t rgda_coral_loss_workspace(int ns, int nt, int d);
+int rgda_coral_loss(const float* feat_s, int bs, int hws, int64_t ldcs, int64_t ldbs,
+                    const float* feat_t, int bt, int hwt, int64_t ldct, int64_t ldbt, int d, float* loss,
+                    void* dfeat_s, int ldds, void* dfeat_t, int lddt, int accumulate, float weight, void* ws,
+                    size_t ws_bytes, rgda_stream_t stream);
 
 /* Factored form of the PPM heads' tap-shifted bilinear maps (regda/models/Encoder.py:30-51: Upsample(bilinear,
  * align_corners=False) of the s x s branches into the 3x3 / pad 1 conv_last): the map V[(y,x)][(jy,jx),(ky,kx)] =

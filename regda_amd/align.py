@@ -3,13 +3,15 @@ rank 2), on the same kernel plans as the SSL step (regda_amd/ssl.py):
 
     model(src) -> update_prototype -> model(tgt) -> the student's own (softmax(up x1) + softmax(up x2)) / 2 as soft
     labels -> label_refine -> pseudo_selection -> Homogenizer (LRH) -> DownscaleLabel
-    loss = loss_calc(src) + 0.5 * (PrototypeContrastiveLoss(src) + PrototypeContrastiveLoss(tgt))     [--align-domain 0]
+    loss = loss_calc(src) + 0.5 * (PrototypeContrastiveLoss(src) + PrototypeContrastiveLoss(tgt))
+           [+ CoralLoss(feat_s, feat_t)  with align_domain=True, --align-domain 1]
     -> backward -> clip_grad_norm_(32) -> SGD
 
 Differences to the SSL step that matter for the kernels: there is no CE on the target logits (their gradient is
 zero) and the loss reaches the network through the third forward output, the instance-normalised features
 (rgda_pcl_loss writes d loss / d feat pixel-major, `Deeplabv2._backward_plan(gfeat=...)` adds it in the
-instance-norm backward)."""
+instance-norm backward; with align_domain rgda_coral_loss then adds the CORAL gradient of both halves onto it).
+Data-parallel ranks compute CORAL on their local batch (regda_amd/source.py)."""
 import torch
 
 from . import ops
@@ -20,12 +22,14 @@ BF = torch.bfloat16
 
 
 class AlignStep(SSLStep):
-    def __init__(self, model, prototypes, pcl_temperature=8.0, **kw):
+    def __init__(self, model, prototypes, pcl_temperature=8.0, align_domain=False, **kw):
         kw.setdefault('proto_decay', 0.999)        # Aligner(decay=0.999), train_align_reg.py:112-113
         kw['ema_decay'] = None
         super().__init__(model, prototypes, **kw)
         self.pcl_temp = pcl_temperature
         self.loss_align = torch.zeros(1, device=model.device)
+        self.align_domain = bool(align_domain)     # --align-domain 1: + aligner.align_domain(feat_s, feat_t), :188
+        self.loss_domain = torch.zeros(1, device=model.device)
 
     def step(self, images_s, label_s, images_t, regs_t, lr):
         """One stage-2 iteration.  Returns device tensors (loss_seg, loss_align, grad_norm_sq)."""
@@ -88,6 +92,10 @@ class AlignStep(SSLStep):
                      dfeat=gfeat[:nb * h * w])
         ops.pcl_loss(feat_t, label_t, self.prototypes, self.pcl_temp, self.ig, 0.5, loss=self.loss_align,
                      dfeat=gfeat[nb * h * w:])
+        if self.align_domain:
+            self.loss_domain.zero_()
+            ops.coral_loss(feat_s, feat_t, 1.0, loss=self.loss_domain, dfeat_s=gfeat[:nb * h * w],
+                           dfeat_t=gfeat[nb * h * w:], accumulate=True)
         zero = torch.zeros_like(gs1)
         self._backward_and_update(T, main, torch.cat([gs1, zero]), torch.cat([gs2, zero]), gfeat=gfeat)
         self.last_hard, self.last_label_t, self.last_label_s_down = hard, label_t, label_s_down

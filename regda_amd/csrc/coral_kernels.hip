@@ -1,0 +1,375 @@
+// CORAL domain loss (regda/gast/coral.py::CoralLoss, is_sqrt=False) as used by Aligner.align_domain
+// (regda/gast/alignment.py:79-84): forward and the gradient w.r.t. both feature maps, deterministic (no atomics).
+//
+//   mean   : mu[c] = sum of the rows / n, fp32, fixed order                          coral_mean_kernel
+//   centre : Xc = bf16(X - mu), once, in two layouts: channel-major [d][n_pad] (the covariance product sums over
+//            pixels) and pixel-major [n][d] (the gradient product sums over channels)   coral_center_kernel
+//   cov    : per (upper 128x128 tile of the d x d matrix, K chunk of one domain's pixels): Xc^T Xc partials, fp32,
+//            one wavefront per job, split-K partials to the workspace                 coral_cov_kernel
+//   reduce : D = sum(source partials) / (ns - 1) - sum(target partials) / (nt - 1) in a fixed order; bf16(D) to both
+//            triangles; per-band sum of D^2                                           coral_reduce_kernel
+//   loss   : loss[0] += weight * sum(D^2) / (4 d^2), one thread, fixed order            coral_loss_kernel
+//   grad   : dX^T = D . Xc^T  ->  dfeat = (+/-) weight / (d^2 (n - 1)) * dX (+ dfeat)      coral_grad_kernel
+//
+// Both products are C[m][n] = sum_k P[m][k] Q[n][k] with P and Q row-major bf16 and K contiguous, so the MFMA
+// fragments are plain 16-byte loads from global memory (no LDS): a 128 x 128 tile per wavefront, 4 x 4
+// v_mfma_f32_32x32x16_bf16 accumulators, the next 32-wide K group loaded while the current one is multiplied.
+// Inside a K group the lane half h and element j of k-step s take k = 16h + 8s + j: A and B use the same
+// permutation, so the sum is unchanged, and the two lanes of a row read 64 contiguous bytes per group.
+#include "common.h"
+
+namespace {
+
+constexpr int CT = 128;          // tile edge (rows of P and of Q per job)
+constexpr int KG = 32;           // K per loop iteration (two k-steps of 16)
+constexpr int TILE_FLOATS = CT * CT;
+constexpr int GN = 64;           // pixels per wavefront of the gradient product (128 x 64 tiles)
+
+size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
+int round32(int x) { return (x + 31) & ~31; }
+
+// split-K of the covariance product: a few jobs per domain and upper tile so that about 1024 wavefronts (one per
+// SIMD of the 256 CUs) run in one round
+struct CoralPlan {
+    int d, ns, nt, nsp, ntp, T, U, Ss, St, chs, cht;
+    size_t off_mean, off_cts, off_ctt, off_xs, off_xt, off_part, off_dbf, off_lpart, bytes;
+};
+
+void split(int npad, int U, int& S, int& chunk) {
+    int want = 1024 / (2 * U);
+    if (want < 1) want = 1;
+    if (want > npad / KG) want = npad / KG;
+    chunk = round32(cdiv(npad, want));
+    S = cdiv(npad, chunk);
+}
+
+CoralPlan make_plan(int ns, int nt, int d) {
+    CoralPlan p;
+    p.d = d; p.ns = ns; p.nt = nt;
+    p.nsp = round32(ns); p.ntp = round32(nt);
+    p.T = cdiv(d, CT);
+    p.U = p.T * (p.T + 1) / 2;
+    split(p.nsp, p.U, p.Ss, p.chs);
+    split(p.ntp, p.U, p.St, p.cht);
+    size_t o = 0;
+    p.off_mean = o;  o += a256((size_t)2 * d * 4);
+    p.off_cts = o;   o += a256((size_t)d * p.nsp * 2);
+    p.off_ctt = o;   o += a256((size_t)d * p.ntp * 2);
+    p.off_xs = o;    o += a256((size_t)ns * d * 2);
+    p.off_xt = o;    o += a256((size_t)nt * d * 2);
+    p.off_part = o;  o += a256((size_t)p.U * (p.Ss + p.St) * TILE_FLOATS * 4);
+    p.off_dbf = o;   o += a256((size_t)d * d * 2);
+    p.off_lpart = o; o += a256((size_t)p.U * 4 * 4);
+    p.bytes = o;
+    return p;
+}
+
+struct Feat {
+    const float* x;
+    long long ldc, ldb;          // channel and image strides (elements); pixels of one image are contiguous
+    int hw, n;
+};
+
+}  // namespace
+
+// one workgroup per (channel, domain): fp32 sum over the n rows, thread-strided then a fixed tree
+__global__ void __launch_bounds__(256) coral_mean_kernel(Feat fs, Feat ft, float* __restrict__ mean, int d) {
+    __shared__ float red[4];
+    const int c = blockIdx.x;
+    const Feat f = blockIdx.y ? ft : fs;
+    const float* xc = f.x + (size_t)c * f.ldc;
+    float s = 0.f;
+    for (int g = threadIdx.x; g < f.n; g += 256) {
+        const int b = g / f.hw, p = g - b * f.hw;
+        s += xc[(size_t)b * f.ldb + p];
+    }
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) mean[blockIdx.y * d + c] = ((red[0] + red[1]) + (red[2] + red[3])) / (float)f.n;
+}
+
+// 64 channels x 64 rows per workgroup: bf16(x - mu) to the channel-major image (coalesced along the rows) and,
+// through LDS, to the pixel-major image (coalesced along the channels; skipped when xs == nullptr)
+__global__ void __launch_bounds__(256) coral_center_kernel(Feat fs, Feat ft, const float* __restrict__ mean,
+                                                           bf16_t* cts, bf16_t* ctt, int ldcs, int ldct,
+                                                           bf16_t* xs, bf16_t* xt, int d) {
+    __shared__ bf16_t tile[64][66];
+    const bool tgt = blockIdx.z != 0;
+    const Feat f = tgt ? ft : fs;
+    const int g0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
+    if (g0 >= f.n) return;
+    bf16_t* ct = tgt ? ctt : cts;
+    const int ldct_ = tgt ? ldct : ldcs;
+    bf16_t* xp = tgt ? xt : xs;
+    const float* mu = mean + (tgt ? d : 0);
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int g = g0 + tx;
+    const int b = g / f.hw, p = g - b * f.hw;
+    for (int cc = ty; cc < 64; cc += 4) {
+        const int c = c0 + cc;
+        if (c < d && g < f.n) {
+            const bf16_t v = f2bf(f.x[(size_t)b * f.ldb + (size_t)c * f.ldc + p] - mu[c]);
+            ct[(size_t)c * ldct_ + g] = v;
+            tile[tx][cc] = v;
+        }
+    }
+    if (!xp) return;
+    __syncthreads();
+    for (int gg = ty; gg < 64; gg += 4) {
+        const int c = c0 + tx;
+        if (g0 + gg < f.n && c < d) xp[(size_t)(g0 + gg) * d + c] = tile[gg][tx];
+    }
+}
+
+// acc[i][j] += P[prow0 + 32i .. +32][k0:k1] . Q[qrow0 + 32j .. +32][k0:k1]^T  (rows clamped to pmax / qmax: the
+// clamped rows compute values nobody stores); k1 - k0 a multiple of KG
+template <int NJ>
+static __device__ __forceinline__ void tile_nt(const bf16_t* __restrict__ P, size_t ldp, int prow0, int pmax,
+                                               const bf16_t* __restrict__ Q, size_t ldq, int qrow0, int qmax,
+                                               int k0, int k1, f32x16 (&acc)[4][NJ]) {
+    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    const bf16_t* pp[4];
+    const bf16_t* qp[NJ];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        pp[i] = P + (size_t)min(prow0 + 32 * i + r, pmax) * ldp + 16 * h;
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) qp[j] = Q + (size_t)min(qrow0 + 32 * j + r, qmax) * ldq + 16 * h;
+    uint4 a[2][4], b[2][NJ], na[2][4], nb[2][NJ];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a[s][i] = *(const uint4*)(pp[i] + k0 + 8 * s);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) b[s][j] = *(const uint4*)(qp[j] + k0 + 8 * s);
+    }
+    for (int k = k0; k < k1; k += KG) {
+        const int kn = (k + KG < k1) ? k + KG : k;      // the last iteration re-reads its own group (cached)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) na[s][i] = *(const uint4*)(pp[i] + kn + 8 * s);
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) nb[s][j] = *(const uint4*)(qp[j] + kn + 8 * s);
+        }
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < NJ; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[s][i]),
+                                                                        __builtin_bit_cast(bf16x8, b[s][j]), acc[i][j], 0, 0, 0);
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) a[s][i] = na[s][i];
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) b[s][j] = nb[s][j];
+        }
+    }
+}
+
+static __device__ __forceinline__ void upper_tile(int u, int T, int& I, int& J) {
+    I = 0;
+    while (u >= T - I) { u -= T - I; ++I; }
+    J = I + u;
+}
+
+// job = u * (Ss + St) + q: upper tile u, K chunk q (q < Ss: source, else target).  Partials in the accumulator's own
+// order: part[job][((i * 4 + j) * 16 + reg) * 64 + lane] (every store instruction writes 256 contiguous bytes)
+__global__ void __launch_bounds__(256, 1) coral_cov_kernel(const bf16_t* __restrict__ cts, const bf16_t* __restrict__ ctt,
+                                                           int nsp, int ntp, int Ss, int St, int chs, int cht, int T,
+                                                           int njobs, int d, float* __restrict__ part) {
+    const int job = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (job >= njobs) return;
+    const int S = Ss + St;
+    const int u = job / S, q = job - u * S;
+    int I, J;
+    upper_tile(u, T, I, J);
+    const bool tgt = q >= Ss;
+    const bf16_t* X = tgt ? ctt : cts;
+    const int ld = tgt ? ntp : nsp, ch = tgt ? cht : chs;
+    const int k0 = (tgt ? q - Ss : q) * ch;
+    const int k1 = min(k0 + ch, ld);
+    f32x16 acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = f32x16{};
+    tile_nt<4>(X, ld, I * CT, d - 1, X, ld, J * CT, d - 1, k0, k1, acc);
+    const int lane = threadIdx.x & 63;
+    float* out = part + (size_t)job * TILE_FLOATS + lane;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) out[((i * 4 + j) * 16 + r) * 64] = acc[i][j][r];
+}
+
+// one workgroup per (upper tile, 32-row band): D in fp32 from the partials (source chunks in order, then target
+// chunks), bf16(D) to D[row][col] and, for tiles off the diagonal, through LDS to D[col][row]; the band's sum of D^2
+// (off-diagonal tiles count twice) -> lpart[u * 4 + band]
+__global__ void __launch_bounds__(256) coral_reduce_kernel(const float* __restrict__ part, int Ss, int St, int T, int d,
+                                                           float inv_s, float inv_t, bf16_t* __restrict__ dbf,
+                                                           float* __restrict__ lpart) {
+    __shared__ float tr[CT][33];
+    __shared__ float red[4];
+    const int u = blockIdx.x, band = blockIdx.y;
+    int I, J;
+    upper_tile(u, T, I, J);
+    const int S = Ss + St;
+    const float* pb = part + (size_t)u * S * TILE_FLOATS + band * 4096;
+    float sq = 0.f;
+    for (int m = 0; m < 16; ++m) {
+        const int e = threadIdx.x + 256 * m;
+        const int lane = e & 63, reg = (e >> 6) & 15, j = e >> 10;
+        float cs = 0.f, ct = 0.f;
+        for (int q = 0; q < Ss; ++q) cs += pb[(size_t)q * TILE_FLOATS + e];
+        for (int q = Ss; q < S; ++q) ct += pb[(size_t)q * TILE_FLOATS + e];
+        const float v = cs * inv_s - ct * inv_t;
+        const int rl = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5), cl = 32 * j + (lane & 31);
+        const int row = I * CT + 32 * band + rl, col = J * CT + cl;
+        tr[cl][rl] = v;
+        if (row < d && col < d) {
+            dbf[(size_t)row * d + col] = f2bf(v);
+            sq += v * v;
+        }
+    }
+    if (I != J) {
+        __syncthreads();
+        for (int m = 0; m < 16; ++m) {
+            const int e = threadIdx.x + 256 * m;
+            const int rl = e & 31, cl = e >> 5;
+            const int row = I * CT + 32 * band + rl, col = J * CT + cl;
+            if (row < d && col < d) dbf[(size_t)col * d + row] = f2bf(tr[cl][rl]);
+        }
+        sq *= 2.f;
+    }
+    sq = wave_sum(sq);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
+    __syncthreads();
+    if (threadIdx.x == 0) lpart[u * 4 + band] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+__global__ void __launch_bounds__(256) coral_loss_kernel(const float* __restrict__ lpart, int nparts, float* loss, float scale) {
+    __shared__ float red[4];
+    float s = 0.f;
+    for (int i = threadIdx.x; i < nparts; i += 256) s += lpart[i];
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) loss[0] += scale * ((red[0] + red[1]) + (red[2] + red[3]));
+}
+
+// job < js: source, else target.  C[c'][p] = sum_c D[c'][c] Xc[p][c] = dX[p][c']: a lane's registers 4g .. 4g+3 are
+// four consecutive channels of one pixel -> one 8-byte store into the pixel-major bf16 gradient rows
+struct GradSide {
+    const bf16_t* x;
+    bf16_t* out;
+    int n, ld;
+    float scale;
+};
+__global__ void __launch_bounds__(256, 1) coral_grad_kernel(const bf16_t* __restrict__ dbf, GradSide gs, GradSide gt, int js,
+                                                            int njobs, int d, int accumulate) {
+    const int job = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (job >= njobs) return;
+    const bool tgt = job >= js;
+    const GradSide g = tgt ? gt : gs;
+    const int jj = tgt ? job - js : job;
+    const int T = (d + CT - 1) / CT;
+    const int mt = jj % T, nt = jj / T;
+    f32x16 acc[4][2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = f32x16{};
+    tile_nt<2>(dbf, d, mt * CT, d - 1, g.x, d, nt * GN, g.n - 1, 0, d, acc);
+    const int lane = threadIdx.x & 63, h = lane >> 5;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int p = nt * GN + 32 * j + (lane & 31);
+        bf16_t* orow = g.out + (size_t)min(p, g.n - 1) * g.ld;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int c = mt * CT + 32 * i + 8 * q + 4 * h;
+                float v0 = acc[i][j][4 * q] * g.scale, v1 = acc[i][j][4 * q + 1] * g.scale;
+                float v2 = acc[i][j][4 * q + 2] * g.scale, v3 = acc[i][j][4 * q + 3] * g.scale;
+                if (p < g.n && c < d) {
+                    uint2* dst = (uint2*)(orow + c);
+                    if (accumulate) {
+                        const uint2 o = *dst;
+                        v0 += __uint_as_float(o.x << 16);
+                        v1 += __uint_as_float(o.x & 0xffff0000u);
+                        v2 += __uint_as_float(o.y << 16);
+                        v3 += __uint_as_float(o.y & 0xffff0000u);
+                    }
+                    *dst = uint2{pack2bf(v0, v1), pack2bf(v2, v3)};
+                }
+            }
+    }
+}
+
+extern "C" size_t rgda_coral_loss_workspace(int ns, int nt, int d) {
+    if (ns < 2 || nt < 2 || d < 32 || (d & 31)) return 0;
+    return make_plan(ns, nt, d).bytes;
+}
+
+extern "C" int rgda_coral_loss(const float* feat_s, int bs, int hws, int64_t ldcs, int64_t ldbs,
+                               const float* feat_t, int bt, int hwt, int64_t ldct, int64_t ldbt, int d, float* loss,
+                               void* dfeat_s, int ldds, void* dfeat_t, int lddt, int accumulate, float weight, void* ws,
+                               size_t ws_bytes, rgda_stream_t stream) {
+    if (!feat_s || !feat_t || !loss || !ws) return RGDA_ERR_ARG;
+    if (bs <= 0 || bt <= 0 || hws <= 0 || hwt <= 0 || d < 32 || (d & 31)) return RGDA_ERR_ARG;
+    const long long ns = (long long)bs * hws, nt = (long long)bt * hwt;
+    if (ns < 2 || nt < 2 || ns > (1 << 30) || nt > (1 << 30)) return RGDA_ERR_ARG;
+    if (ldcs < hws || ldct < hwt || (bs > 1 && ldbs < ldcs * d) || (bt > 1 && ldbt < ldct * d)) return RGDA_ERR_ARG;
+    if (dfeat_s && (ldds < d || (ldds & 7) || ((uintptr_t)dfeat_s & 7))) return RGDA_ERR_ARG;
+    if (dfeat_t && (lddt < d || (lddt & 7) || ((uintptr_t)dfeat_t & 7))) return RGDA_ERR_ARG;
+    const CoralPlan p = make_plan((int)ns, (int)nt, d);
+    if (ws_bytes < p.bytes) return RGDA_ERR_WORKSPACE;
+    hipStream_t st = to_stream(stream);
+    char* w = (char*)ws;
+    float* mean = (float*)(w + p.off_mean);
+    bf16_t* cts = (bf16_t*)(w + p.off_cts);
+    bf16_t* ctt = (bf16_t*)(w + p.off_ctt);
+    const bool grad = dfeat_s || dfeat_t;
+    bf16_t* xs = grad ? (bf16_t*)(w + p.off_xs) : nullptr;
+    bf16_t* xt = grad ? (bf16_t*)(w + p.off_xt) : nullptr;
+    float* part = (float*)(w + p.off_part);
+    bf16_t* dbf = (bf16_t*)(w + p.off_dbf);
+    float* lpart = (float*)(w + p.off_lpart);
+    // the K padding of the channel-major images must be zero (it enters the covariance sums)
+    if (p.nsp != ns && zero_bytes(cts, (size_t)d * p.nsp * 2, stream) != RGDA_OK) return RGDA_ERR_LAUNCH;
+    if (p.ntp != nt && zero_bytes(ctt, (size_t)d * p.ntp * 2, stream) != RGDA_OK) return RGDA_ERR_LAUNCH;
+    const Feat fs{feat_s, (long long)ldcs, (long long)ldbs, hws, (int)ns};
+    const Feat ft{feat_t, (long long)ldct, (long long)ldbt, hwt, (int)nt};
+    coral_mean_kernel<<<dim3(d, 2), 256, 0, st>>>(fs, ft, mean, d);
+    RGDA_CHECK_LAUNCH();
+    coral_center_kernel<<<dim3(cdiv(ns > nt ? ns : nt, 64), cdiv(d, 64), 2), 256, 0, st>>>(fs, ft, mean, cts, ctt, p.nsp,
+                                                                                           p.ntp, xs, xt, d);
+    RGDA_CHECK_LAUNCH();
+    const int njobs = p.U * (p.Ss + p.St);
+    coral_cov_kernel<<<cdiv(njobs, 4), 256, 0, st>>>(cts, ctt, p.nsp, p.ntp, p.Ss, p.St, p.chs, p.cht, p.T, njobs, d, part);
+    RGDA_CHECK_LAUNCH();
+    coral_reduce_kernel<<<dim3(p.U, 4), 256, 0, st>>>(part, p.Ss, p.St, p.T, d, 1.f / (float)(ns - 1), 1.f / (float)(nt - 1),
+                                                      dbf, lpart);
+    RGDA_CHECK_LAUNCH();
+    coral_loss_kernel<<<1, 256, 0, st>>>(lpart, p.U * 4, loss, weight / (4.f * (float)d * (float)d));
+    RGDA_CHECK_LAUNCH();
+    if (!grad) return RGDA_OK;
+    const float dd = (float)d * (float)d;
+    const int T = p.T;
+    const int js = dfeat_s ? T * cdiv(ns, GN) : 0;
+    const int jt = dfeat_t ? T * cdiv(nt, GN) : 0;
+    const GradSide gs{xs, (bf16_t*)dfeat_s, (int)ns, ldds, weight / (dd * (float)(ns - 1))};
+    const GradSide gt{xt, (bf16_t*)dfeat_t, (int)nt, lddt, -weight / (dd * (float)(nt - 1))};
+    coral_grad_kernel<<<cdiv(js + jt, 4), 256, 0, st>>>(dbf, gs, gt, js, js + jt, d, accumulate);
+    RGDA_CHECK_LAUNCH();
+    return RGDA_OK;
+}

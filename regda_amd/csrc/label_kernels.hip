@@ -1106,7 +1106,7 @@ extern "C" int rgda_proto_stats(const float* feat, const int64_t* label, int64_t
 // local = sums / (cnt + 1e-7), the old prototype where cnt < 1 (alignment.py:318-321), then the EMA (:435-438)
 extern "C" int rgda_proto_apply(float* protos, const void* stats, int c, int k, float decay, rgda_stream_t stream) {
     if (!protos || !stats) return RGDA_ERR_ARG;
-    if (c <= 0 || k <= 0 || !(decay > 0.f && decay < 1.f)) return RGDA_ERR_ARG;
+    if (c <= 0 || k <= 0 || !(decay >= 0.f && decay < 1.f)) return RGDA_ERR_ARG;   // 0: Aligner.init_avg
     const float* sums = (const float*)stats;
     const float* cnt = sums + (size_t)c * k;
     float omd = (float)(1.0 - (double)decay);

@@ -1,11 +1,13 @@
-"""Aligner (prototype EMA + online soft-label re-weighting) -- mirror of the parts of
-regda/gast/alignment.py that sit on the SSL path: label_refine (:194-265,
-with and without the superpixel view; every `mode`), update_prototype (:86-90),
-DownscaleLabel (:456-481).  Stage-2 alignment losses are out of scope.
+"""Aligner (prototype EMA + online soft-label re-weighting + domain alignment) -- mirror of the parts of
+regda/gast/alignment.py that the authors' recipe (runs/regda/run_2potsdam.sh) uses: label_refine (:194-265,
+with and without the superpixel view; every `mode`), update_prototype (:86-90), align_domain (CORAL, :79-84),
+update_avg / init_avg (the prototype initialisation of tools/init_prototypes.py, :107-126), DownscaleLabel (:456-481).
+The other alignment losses (align_class, whitening, MMD) are not provided.
 """
 import torch
 
 from .. import ops
+from .coral import CoralLoss
 
 
 class DownscaleLabel(torch.nn.Module):
@@ -43,6 +45,51 @@ class Aligner:
         self.downscale_gt = DownscaleLabel(scale_factor=16, n_classes=class_num, ignore_label=ignore_label,
                                            min_ratio=0.75)
         self._classmax_ws = None
+        self.coral = CoralLoss()
+        self._avg_stats = None          # update_avg: f32 sums[c][k] then cnt[c], summed over the batches seen
+
+    def align_domain(self, feat_s, feat_t):
+        """CORAL between the pixel rows of two (b, k, h, w) feature maps (alignment.py:79-84).  The NCHW maps go to
+        rgda_coral_loss as they are (no permuted copy); gradients reach both inputs."""
+        assert feat_s.shape == feat_t.shape, 'tensor "feat_s" has the same shape as tensor "feat_t"'
+        assert len(feat_s.shape) == 4, 'tensor "feat_s" and "feat_t" must have 4 dimensions'
+        assert feat_s.shape[1] == self.feat_channels
+        return self.coral(feat_s, feat_t)
+
+    def update_avg(self, feat, label):
+        """Add a batch's per-class feature sums and pixel counts (of the downscaled label) to the running totals
+        (alignment.py:107-119; rgda_proto_stats)."""
+        stats, _ = ops.proto_stats(feat.detach(), label, 16, self.ignore_label, 0.75, self.class_num)
+        n = self.class_num * self.feat_channels + self.class_num
+        if self._avg_stats is None:
+            self._avg_stats = torch.zeros(n, dtype=torch.float32, device=stats.device)
+        self._avg_stats += stats[:n]
+
+    def init_avg(self):
+        """prototypes = sums / (cnt + 1e-7) (alignment.py:121-122): rgda_proto_apply with decay 0 on zero prototypes,
+        so a class without pixels stays 0.  The totals are kept (update_avg may go on adding)."""
+        protos = torch.zeros([self.class_num, self.feat_channels], device='cuda')
+        if self._avg_stats is not None:
+            ops.proto_apply(protos, self._avg_stats, 0.0)
+        self.prototypes = protos
+        if self.logger is not None:
+            self.logger.info('finish init prototypes!')
+            self.logger.info(f'examples cnt={self.data_cnt}')
+
+    @property
+    def data_cnt(self):
+        """Pixel counts per class accumulated by update_avg, (class_num, 1) (the reference's _data_cnt)."""
+        n = self.class_num * self.feat_channels
+        if self._avg_stats is None:
+            return torch.zeros([self.class_num, 1], device='cuda')
+        return self._avg_stats[n:n + self.class_num].view(-1, 1)
+
+    @property
+    def data_sum(self):
+        """Per-class feature sums accumulated by update_avg, (class_num, feat_channels) (the reference's _data_sum)."""
+        if self._avg_stats is None:
+            return torch.zeros([self.class_num, self.feat_channels], device='cuda')
+        return self._avg_stats[:self.class_num * self.feat_channels].view(self.class_num, self.feat_channels)
 
     def update_prototype(self, feat, label):
         """Update global prototypes by source features and labels (alignment.py:86-90)."""

@@ -863,6 +863,40 @@ def pcl_loss(feat, labels, protos, temperature=8.0, ignore_label=-1, weight=1.0,
     return loss
 
 
+def _coral_side(x):
+    """-> (tensor, b, hw, ld_channel, ld_image): NCHW (b, d, h, w), or (n, d) rows (b = n images of one pixel)."""
+    x = x.contiguous().float()
+    if x.dim() == 4:
+        b, d, h, w = x.shape
+        return x, b, h * w, h * w, d * h * w, d
+    assert x.dim() == 2, 'coral_loss: NCHW (b, d, h, w) features or (n, d) rows'
+    n, d = x.shape
+    return x, n, 1, 1, d, d
+
+
+def coral_loss(feat_s, feat_t, weight=1.0, loss=None, dfeat_s=None, dfeat_t=None, accumulate=False):
+    """CoralLoss(feat_s rows, feat_t rows) (regda/gast/coral.py, is_sqrt=False) as Aligner.align_domain computes it:
+    feat_s / feat_t f32 NCHW (b, d, h, w) (the pixels are the rows) or (n, d).  loss (f32[1]) += weight * CORAL;
+    dfeat_s / dfeat_t (optional) bf16 [n, >= d] pixel-major rows: (+)= weight * d CORAL / d feat (rgda_coral_loss).
+    Returns the (accumulating) fp32 loss tensor."""
+    _need_cuda(feat_s, feat_t, dfeat_s, dfeat_t)
+    xs, bs, hws, lcs, lbs, d = _coral_side(feat_s)
+    xt, bt, hwt, lct, lbt, dt = _coral_side(feat_t)
+    if d != dt:
+        raise ValueError(f'coral_loss: feature dimensions differ ({d} vs {dt})')
+    for g, n in ((dfeat_s, bs * hws), (dfeat_t, bt * hwt)):
+        if g is not None:
+            assert g.dtype == torch.bfloat16 and g.dim() == 2 and g.shape[0] == n and g.stride(1) == 1, (g.shape, n)
+    if loss is None:
+        loss = torch.zeros(1, device=xs.device)
+    L = lib()
+    ws = _ws(L.size('rgda_coral_loss_workspace', bs * hws, bt * hwt, d), xs.device)
+    L.call('rgda_coral_loss', xs.data_ptr(), bs, hws, lcs, lbs, xt.data_ptr(), bt, hwt, lct, lbt, d, loss.data_ptr(),
+           _p(dfeat_s), _ld(dfeat_s) if dfeat_s is not None else 0, _p(dfeat_t), _ld(dfeat_t) if dfeat_t is not None else 0,
+           int(bool(accumulate)), float(weight), ws.data_ptr(), ws.numel(), _stream())
+    return loss
+
+
 # ---------------------------------------------------------------- ASPP head (Classifier_Module)
 def _ptr_array(tensors):
     import ctypes

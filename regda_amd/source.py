@@ -1,0 +1,75 @@
+"""The stage-1 ("source") inner loop of tools/train_src.py:117-140 as one fused, sync-free step, on the same kernel
+plans as the SSL step (regda_amd/ssl.py):
+
+    model(src) [-> model(tgt)] -> loss = loss_calc(src) [+ CORAL(feat_s, feat_t)  with --align-domain 1]
+    -> backward -> clip_grad_norm_(32) -> SGD
+
+No EMA, no prototypes, no label path.  With align_domain the source and the target batch run through the network
+together as two BatchNorm groups (statistics per domain, as the reference's two forward calls); the target heads get
+a zero gradient (train_src.py discards the target logits) and CORAL reaches the network through the instance-normalised
+features: rgda_coral_loss writes d CORAL / d feat for both halves pixel-major, `Deeplabv2._backward_plan(gfeat=...)`
+adds it in the instance-norm backward.
+
+Data-parallel ranks compute CORAL on their local batch (the covariances of the rank's own source and target pixels),
+the same per-rank semantics as the per-GPU BatchNorm statistics: there is no extra collective."""
+import torch
+
+from . import ops
+from .ssl import SSLStep
+
+BF = torch.bfloat16
+
+
+class SourceStep(SSLStep):
+    def __init__(self, model, class_balancer_s=None, align_domain=False, class_num=6, **kw):
+        kw['ema_decay'] = None
+        kw.setdefault('sam_refine', False)
+        kw.setdefault('refine_label', False)
+        super().__init__(model, torch.zeros(class_num, 2048), class_num=class_num, class_balancer_s=class_balancer_s,
+                         **kw)
+        self.align_domain = bool(align_domain)
+        self.loss_domain = torch.zeros(1, device=model.device)
+
+    @torch.no_grad()
+    def step(self, images_s, label_s, images_t, lr):
+        """One stage-1 iteration.  Returns device tensors (loss_seg, loss_domain, grad_norm_sq); loss_domain stays 0
+        without align_domain.  images_t may be None when align_domain is off (no target forward then)."""
+        if self.align_domain and images_t is None:
+            raise ValueError('SourceStep(align_domain=True) needs the target images')
+        ops.set_f32(self.lr_dev, lr)
+        with ops.use_stream(torch.cuda.current_stream()):
+            return self._step(images_s, label_s, images_t)
+
+    def capture(self, *a, **k):
+        raise NotImplementedError('whole-step graph capture is provided for the SSL step only')
+
+    def record_plan(self, *a, **k):
+        raise NotImplementedError('plan replay is provided for the SSL step only')
+
+    def _step(self, images_s, label_s, images_t):
+        m = self.model
+        if not m.training:
+            m.train()
+        m._maybe_sync()
+        ops.fill_zero(m.flat_g)
+        nb = images_s.shape[0]
+        main = torch.cuda.current_stream()
+        if self.align_domain:
+            T = m.new_tape(groups=2)
+            x1, x2, feat = m._forward_plan([images_s.contiguous().float(), images_t.contiguous().float()], T)
+        else:
+            T = m.new_tape(groups=1)
+            x1, x2, feat = m._forward_plan(images_s.contiguous().float(), T)
+        # d(loss) / d(logits): the source rows from the CE kernel, the target rows (when there are any) zero
+        g1, g2 = torch.zeros_like(x1), torch.zeros_like(x2)
+        loss_seg, _, _ = ops.upsample_ce(x1[:nb], x2[:nb], label_s, self.ig,
+                                         self._class_weights(self.class_balancer_s, label_s), True, g1[:nb], g2[:nb])
+        self.loss_domain.zero_()
+        gfeat = None
+        if self.align_domain:
+            n, k, h, w = feat.shape
+            gfeat = torch.empty(n * h * w, k, dtype=BF, device=m.device)
+            ops.coral_loss(feat[:nb], feat[nb:], 1.0, loss=self.loss_domain, dfeat_s=gfeat[:nb * h * w],
+                           dfeat_t=gfeat[nb * h * w:])
+        self._backward_and_update(T, main, g1, g2, gfeat=gfeat)
+        return loss_seg, self.loss_domain, self.gn
