@@ -177,6 +177,39 @@ int rgda_upsample_ce(const float* p1, const float* p2, const int64_t* label,
                      int h, int w, int H, int W, int ignore_label, void* ws, size_t ws_bytes,
                      rgda_stream_t stream);
 
+/* loss_calc([p1,p2], label, loss_fn, multi=True) / loss_calc_uvem(..., label_soft, ...) with the losses of the --ls / --lt
+ * flags (tools/train_ssl_reg.py:52-63,134-158; tools/train_src.py:33-34; tools/train_align_reg.py:55-56), forward +
+ * d(loss)/d(logits), sync-free (every batch statistic stays on the device):
+ *   RGDA_LOSS_OHEM   OhemCrossEntropy (regda/gast/balance.py:104-133): n_min = #valid / 5; mean of the losses > thresh
+ *                    (thresh = f32 -log 0.7), or of the n_min largest when fewer are kept (ties: lowest pixel index
+ *                    first); class_weight optional.  All labels ignored: loss NaN, gradient 0.
+ *   RGDA_LOSS_FOCAL  FocalLoss(alpha=None, reduction='mean') (:136-158): mean of (1 - exp(-ce))^gamma * ce over ALL pixels.
+ *   RGDA_LOSS_GHM    GHMLoss(bins=30) (:161-216): acc_sum (device f32[30], in/out) = momentum * acc_sum + (1 - momentum)
+ *                    * histc(|p_y - 1|), once per head (head 1 first); weight 1 / acc_sum[bucketize(g) - 1];
+ *                    sum(ce * weight) / (#(label != -1) + 1e-7).  momentum 0: acc_sum = the histogram.
+ *   RGDA_LOSS_UPS    UPSLoss (:306-345): u = sum_c -s log s of the soft label `soft` (NCHW f32 (b,c,H,W)); CE where
+ *                    u <= t, times class_weight (optional); sum / (#(u <= t and valid) + 1e-7).
+ *   RGDA_LOSS_UVEM   UVEMLoss (:348-426): as UPS, times UVEMLoss.get_weight(u) with (m, t, gamma).
+ * Each loss is applied per head after the bilinear (align_corners=True) upsample to the label size and the two heads
+ * are averaged (regda/utils/tools.py:240-254, balance.py:438-460).  heads 1: one loss_fn call on one prediction (p2 == p1;
+ * the loss is that call's, g1 + g2 its gradient, GHM's acc_sum is updated once).  class_weight: NULL or f32[2][c] (per head, the
+ * ClassBalance state of that head's call); must be NULL for FOCAL and GHM.  Parameters a kind does not use are ignored.
+ * loss: f32[1].  g1, g2: NULL or NCHW f32 (b,c,h,w).  c must be 6; b * H * W < 2^31.  ws: rgda_upsample_loss_workspace
+ * bytes (0 = bad arguments); the per-pixel scratch is 8 (OHEM), 2 (GHM), 4 (UPS / UVEM) or 0 (focal) bytes per pixel.
+ * Deterministic: integer atomics for counts and histograms, fixed-order reductions, no float atomics. */
+enum rgda_loss_kind {
+    RGDA_LOSS_OHEM = 1,
+    RGDA_LOSS_FOCAL = 2,
+    RGDA_LOSS_GHM = 3,
+    RGDA_LOSS_UPS = 4,
+    RGDA_LOSS_UVEM = 5
+};
+size_t rgda_upsample_loss_workspace(int kind, int b, int c, int h, int w, int H, int W);
+int rgda_upsample_loss(int kind, int heads, const float* p1, const float* p2, const int64_t* label,
+                       const float* soft, const float* class_weight, float* acc_sum, double m, double t, double gamma, float thresh,
+                       double momentum, float* loss, float* g1, float* g2, int b, int c, int h, int w, int H,
+                       int W, int ignore_label, void* ws, size_t ws_bytes, rgda_stream_t stream);
+
 /* Deeplabv2 eval-branch output  regda/models/Encoder.py:152-155:
  * (softmax(up(x1)) + softmax(up(x2))) / 2, up = bilinear align_corners=True. */
 int rgda_teacher_probs(const float* p1, const float* p2, float* probs, int b, int c, int h, int w,

@@ -84,7 +84,11 @@ class AlignStep(SSLStep):
                            ws=self.lrh_ws)
         label_t = self._downscale(hard)                                              # aligner.downscale_gt, :180
         # ---- losses and their gradients
-        loss_seg, gs1, gs2 = ops.upsample_ce(s1, s2, label_s, self.ig, None, True)
+        if self.loss_fn_s is None:
+            loss_seg, gs1, gs2 = ops.upsample_ce(s1, s2, label_s, self.ig, None, True)
+        else:                                                                        # --ls OhemCrossEntropy
+            f = self.loss_fn_s
+            loss_seg, gs1, gs2 = f.launch(s1, s2, label_s, class_weight=self._class_weights(f.class_balancer, label_s))
         n, k, h, w = feat.shape
         gfeat = torch.empty(n * h * w, k, dtype=BF, device=m.device)
         self.loss_align.zero_()

@@ -52,6 +52,22 @@ static __device__ __forceinline__ float xor_add(float v) {
     }
 }
 
+// bilinear interpolation with align_corners=True: output index dst of `out` samples reads inputs i0, i1 of `in`
+struct Lerp {
+    int i0, i1;
+    float l0, l1;
+};
+static __device__ __forceinline__ Lerp lerp_ac(int dst, int in, int out) {
+    float scale = (out > 1) ? __fdiv_rn((float)(in - 1), (float)(out - 1)) : 0.f;
+    float src = __fmul_rn(scale, (float)dst);
+    Lerp r;
+    r.i0 = (int)src;
+    r.i1 = r.i0 + ((r.i0 < in - 1) ? 1 : 0);
+    r.l1 = __fsub_rn(src, (float)r.i0);
+    r.l0 = __fsub_rn(1.f, r.l1);
+    return r;
+}
+
 static __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));

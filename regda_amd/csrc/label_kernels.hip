@@ -485,20 +485,6 @@ extern "C" int rgda_pseudo_lrh(const float* soft, const float* classmax, const i
 // --------------------------------------------------------------------------------------
 // bilinear align_corners=True helpers (torch upsample_bilinear2d semantics)
 // --------------------------------------------------------------------------------------
-struct Lerp {
-    int i0, i1;
-    float l0, l1;
-};
-static __device__ __forceinline__ Lerp lerp_ac(int dst, int in, int out) {
-    float scale = (out > 1) ? __fdiv_rn((float)(in - 1), (float)(out - 1)) : 0.f;
-    float src = __fmul_rn(scale, (float)dst);
-    Lerp r;
-    r.i0 = (int)src;
-    r.i1 = r.i0 + ((r.i0 < in - 1) ? 1 : 0);
-    r.l1 = __fsub_rn(src, (float)r.i0);
-    r.l0 = __fsub_rn(1.f, r.l1);
-    return r;
-}
 static __device__ __forceinline__ float bilerp(const float* p, int w, const Lerp& ly, const Lerp& lx) {
     float v00 = p[ly.i0 * w + lx.i0], v01 = p[ly.i0 * w + lx.i1];
     float v10 = p[ly.i1 * w + lx.i0], v11 = p[ly.i1 * w + lx.i1];

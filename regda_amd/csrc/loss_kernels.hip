@@ -1,0 +1,587 @@
+// loss_calc(multi=True) with the non-CE losses of the --ls / --lt flags (tools/train_ssl_reg.py:52-63,134-158):
+// OhemCrossEntropy, FocalLoss, GHMLoss, UPSLoss, UVEMLoss (regda/gast/balance.py:104-216,306-435).
+//
+// Every one of them is a per-pixel function of the bilinearly upsampled logits whose gradient depends on a statistic of
+// the whole batch (a count, a histogram, a k-th largest value).  The same row-per-workgroup upsample / log-softmax /
+// horizontal-contraction scheme as rgda_upsample_ce (label_kernels.hip) runs twice around a global stage:
+//   stat     (one workgroup per output row; not for focal): the per-pixel decision value -- OHEM: the (class-weighted)
+//            CE, GHM: the bucket of |p_y - 1|, UPS / UVEM: the uncertainty weight of the soft label -- goes to scratch;
+//            counts and the GHM histograms go to integer atomics (order-independent, so deterministic)
+//   finalize (one workgroup): denominators, the GHM acc_sum EMA (head 1, then head 2), the OHEM branch
+//   select   (OHEM only, six passes that return at once unless the top-k branch is taken): radix select of the n_min-th
+//            largest 64-bit key (f32 bits of the loss : inverted pixel index); keys are unique, so exactly n_min pixels
+//            are kept and of equal losses the lowest pixel index goes first
+//   grad     (one workgroup per output row): the logits again, the per-pixel weight from scratch and the global scalars,
+//            per-row loss partials, d loss / d logits contracted horizontally
+//   col / reduce: vertical contraction; fixed-order double reduction of the row partials.
+// No float atomics anywhere; nothing is read back to the host.
+#include "common.h"
+
+namespace {
+
+constexpr int LC = 6;                    // class count (rgda_upsample_ce's restriction)
+constexpr int GHM_BINS = 30;
+constexpr int SEL_PASSES = 6;
+constexpr int SEL_BINS = 2048;
+// radix digits of the 64-bit OHEM key, from the top: the loss bits in 11 + 11 + 10, the inverted index in 11 + 11 + 10
+__constant__ int kSelShift[SEL_PASSES] = {53, 42, 32, 21, 10, 0};
+__constant__ int kSelWidth[SEL_PASSES] = {11, 11, 10, 11, 11, 10};
+
+// Counters and histograms are spread over CNT_REPL copies (workgroup i adds to copy i % CNT_REPL): thousands of
+// workgroups adding to ONE address serialise on it.  finalize sums the copies (integers: any order gives the same total).
+constexpr int CNT_REPL = 64;
+enum { CNT_VALID, CNT_LIT, CNT_U, CNT_KEPT0, CNT_KEPT1, CNT_SLOTS = 8 };
+
+struct LossHdr {
+    // zeroed at the start of every call (up to `cut`)
+    int cnt[CNT_REPL][CNT_SLOTS];        // label != ignore_label; label != -1 (GHMLoss's denominator uses the literal,
+                                         // balance.py:214); u <= t && valid (UPS / UVEM); OHEM: loss > thresh per head
+    int ghm_hist[CNT_REPL][2][32];
+    int sel_active[2];                   // OHEM: the top-k branch is still being resolved
+    int sel_arrived[SEL_PASSES][2];
+    int sel_hist[SEL_PASSES][2][SEL_BINS];
+    // written by finalize / select
+    unsigned long long cut[2];           // OHEM: a pixel is kept iff its key >= cut
+    unsigned long long prefix[2];
+    int rem[2];
+    float denom[2];
+    float acc[2][32];                    // GHM acc_sum after the head-1 and after the head-2 update
+};
+
+struct LossParams {
+    float thresh;                        // OHEM
+    float m, t, cl, cr, inv_gamma;       // UPS / UVEM
+    float gamma;                         // focal
+    float mom, omm;                      // GHM
+};
+
+static size_t align256_(size_t x) { return (x + 255) & ~(size_t)255; }
+
+static size_t scratch_bytes(int kind, size_t n) {
+    switch (kind) {
+        case RGDA_LOSS_OHEM: return 2 * n * 4;
+        case RGDA_LOSS_GHM: return 2 * n;
+        case RGDA_LOSS_UPS:
+        case RGDA_LOSS_UVEM: return n * 4;
+        default: return 0;
+    }
+}
+
+// the upsampled logits of one head at one output pixel, from the two low-res rows staged in LDS (upce_row_kernel's code)
+template <int C>
+__device__ __forceinline__ void up_logits(const float* rows, int w, int hd, const Lerp& ly, const Lerp& lx, float z[C],
+                                          float& m) {
+    m = -INFINITY;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        const float* r = rows + ((hd * C + c) * 2) * w;
+        float top = __fadd_rn(__fmul_rn(lx.l0, r[lx.i0]), __fmul_rn(lx.l1, r[lx.i1]));
+        float bot = __fadd_rn(__fmul_rn(lx.l0, r[w + lx.i0]), __fmul_rn(lx.l1, r[w + lx.i1]));
+        z[c] = __fadd_rn(__fmul_rn(ly.l0, top), __fmul_rn(ly.l1, bot));
+        m = fmaxf(m, z[c]);
+    }
+}
+
+template <int C>
+__device__ __forceinline__ void stage_rows(float* rows, const float* p1, const float* p2, int b, const Lerp& ly, int h,
+                                           int w) {
+    const int hw = h * w;
+    for (int i = threadIdx.x; i < 2 * C * 2 * w; i += 256) {
+        int x = i % w, r = (i / w) & 1, c = (i / (2 * w)) % C, hd = i / (2 * w * C);
+        const float* p = hd ? p2 : p1;
+        rows[i] = p[((size_t)b * C + c) * hw + (r ? ly.i1 : ly.i0) * w + x];
+    }
+}
+
+// UVEMLoss.get_weight (balance.py:398-426) in f32, branch for branch; NaN u (a soft label with an exact 0) falls through
+// to the right branch at x = 0, as in the reference
+__device__ __forceinline__ float uvem_weight(float u, const LossParams& p) {
+    float left = 1.f;
+    if (p.m > 0.f) {
+        float d = __fsub_rn((u <= p.m && u >= 0.f) ? u : 1.f, p.m);
+        float wl = __fadd_rn(__fmul_rn(p.cl, __fmul_rn(d, d)), 1.f);
+        left = powf(fminf(fmaxf(wl, 0.f), 1.f), p.inv_gamma);
+    }
+    float right = 0.f;
+    if (p.m < p.t) {
+        float d = __fsub_rn((u > p.m && u <= p.t) ? u : 0.f, p.m);
+        float wr = __fadd_rn(__fmul_rn(p.cr, __fmul_rn(d, d)), 1.f);
+        right = powf(fminf(fmaxf(wr, 0.f), 1.f), p.inv_gamma);
+    }
+    float wgt = (u <= p.m) ? left : right;
+    return (u >= p.t) ? 0.f : wgt;
+}
+
+// torch.bucketize(g, edges, right=False): the number of edges below g; edges = f32(k / 30), the last one f32(1 + 1e-3)
+__device__ __forceinline__ int ghm_bucket(float g, const float* edges) {
+    int k = (g > 0.f) ? min((int)__fmul_rn(g, (float)GHM_BINS), GHM_BINS) : 0;
+    while (k <= GHM_BINS && edges[k] < g) ++k;
+    while (k > 0 && !(edges[k - 1] < g)) --k;
+    return k;
+}
+
+// ---------------------------------------------------------------------------------------------------- stat pass
+template <int KIND>
+__global__ void __launch_bounds__(256) loss_stat_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
+                                                        const int64_t* __restrict__ label, const float* __restrict__ soft,
+                                                        const float* __restrict__ class_weight, LossHdr* hdr,
+                                                        void* scratch, int h, int w, int H, int W, int ignore_label,
+                                                        LossParams prm) {
+    constexpr int C = LC;
+    extern __shared__ float rows[];
+    __shared__ int s_cnt[3], s_kept[2], s_hist[2][32];
+    __shared__ float s_edges[GHM_BINS + 1];
+    const int b = blockIdx.y, Y = blockIdx.x;
+    const size_t n = (size_t)gridDim.y * H * W;
+    const Lerp ly = lerp_ac(Y, h, H);
+    if (threadIdx.x < 3) s_cnt[threadIdx.x] = 0;
+    if (threadIdx.x < 2) s_kept[threadIdx.x] = 0;
+    if (threadIdx.x < 64) s_hist[threadIdx.x >> 5][threadIdx.x & 31] = 0;
+    if (KIND == RGDA_LOSS_GHM && threadIdx.x <= GHM_BINS)
+        s_edges[threadIdx.x] = threadIdx.x < GHM_BINS ? (float)((double)threadIdx.x / GHM_BINS) : (float)(1.0 + 1e-3);
+    if (KIND == RGDA_LOSS_OHEM || KIND == RGDA_LOSS_GHM) stage_rows<C>(rows, p1, p2, b, ly, h, w);
+    __syncthreads();
+    int valid_n = 0, lit_n = 0, u_n = 0, kept0 = 0, kept1 = 0;
+    for (int X = threadIdx.x; X < W; X += 256) {
+        const size_t pix = ((size_t)b * H + Y) * W + X;
+        const long long lab = label[pix];
+        const bool valid = lab != ignore_label;
+        const int li = valid ? (int)lab : 0;
+        valid_n += valid;
+        lit_n += lab != -1;
+        if constexpr (KIND == RGDA_LOSS_OHEM || KIND == RGDA_LOSS_GHM) {
+            const Lerp lx = lerp_ac(X, w, W);
+#pragma unroll
+            for (int hd = 0; hd < 2; ++hd) {
+                float z[C], m, se = 0.f;
+                up_logits<C>(rows, w, hd, ly, lx, z, m);
+                float e[C], zl = 0.f;
+#pragma unroll
+                for (int c = 0; c < C; ++c) { e[c] = expf(z[c] - m); se += e[c]; zl = (c == li) ? z[c] : zl; }
+                if constexpr (KIND == RGDA_LOSS_OHEM) {
+                    // CE as log_softmax + nll: log(se) - (z_l - max) >= 0, ignored pixels 0; times the class weight
+                    float ce = valid ? logf(se) - (zl - m) : 0.f;
+                    float v = valid ? ce * (class_weight ? class_weight[hd * C + li] : 1.f) : 0.f;
+                    ((float*)scratch)[hd * n + pix] = v;
+                    if (v > prm.thresh) { if (hd == 0) ++kept0; else ++kept1; }
+                } else {
+                    float py = 0.f;
+#pragma unroll
+                    for (int c = 0; c < C; ++c) py = (c == li) ? e[c] / se : py;
+                    float g = valid ? fabsf(py - 1.f) : -1.f;
+                    if (g >= 0.f && g <= 1.f) atomicAdd(&s_hist[hd][min((int)__fmul_rn(g, (float)GHM_BINS), GHM_BINS - 1)], 1);
+                    ((uint8_t*)scratch)[hd * n + pix] = (uint8_t)ghm_bucket(g, s_edges);
+                }
+            }
+        } else {            // UPS / UVEM: u = sum_c -s log s of the soft label at full resolution
+            float u = 0.f;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                float s = soft[(((size_t)b * C + c) * H + Y) * W + X];
+                u += (-s) * logf(s);
+            }
+            u_n += (u <= prm.t) && valid;
+            float f = (u > prm.t) ? 0.f : (KIND == RGDA_LOSS_UVEM ? uvem_weight(u, prm) : 1.f);
+            ((float*)scratch)[pix] = f;
+        }
+    }
+    if (valid_n) atomicAdd(&s_cnt[0], valid_n);
+    if (lit_n) atomicAdd(&s_cnt[1], lit_n);
+    if (u_n) atomicAdd(&s_cnt[2], u_n);
+    if (kept0) atomicAdd(&s_kept[0], kept0);
+    if (kept1) atomicAdd(&s_kept[1], kept1);
+    __syncthreads();
+    const int rep = (blockIdx.y * gridDim.x + blockIdx.x) % CNT_REPL;
+    if (threadIdx.x == 0) {
+        int* cnt = hdr->cnt[rep];
+        atomicAdd(&cnt[CNT_VALID], s_cnt[0]);
+        atomicAdd(&cnt[CNT_LIT], s_cnt[1]);
+        atomicAdd(&cnt[CNT_U], s_cnt[2]);
+        atomicAdd(&cnt[CNT_KEPT0], s_kept[0]);
+        atomicAdd(&cnt[CNT_KEPT1], s_kept[1]);
+    }
+    if (KIND == RGDA_LOSS_GHM && threadIdx.x < 64) {
+        const int v = s_hist[threadIdx.x >> 5][threadIdx.x & 31];
+        if (v) atomicAdd(&hdr->ghm_hist[rep][threadIdx.x >> 5][threadIdx.x & 31], v);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- global stage
+__global__ void __launch_bounds__(64) loss_finalize_kernel(int kind, int heads, LossHdr* hdr, float* acc_sum,
+                                                           LossParams prm, long long npix) {
+    const int t = threadIdx.x;
+    if (kind == RGDA_LOSS_GHM && t < GHM_BINS) {
+        // acc_sum = momentum * acc_sum + (1 - momentum) * histc(g), once per head (balance.py:201-204); one head: the
+        // second "head" is the same prediction and reuses the first state
+        float a = acc_sum[t];
+        for (int hd = 0; hd < heads; ++hd) {
+            int n = 0;
+            for (int r = 0; r < CNT_REPL; ++r) n += hdr->ghm_hist[r][hd][t];
+            const float bins = (float)n;
+            a = prm.mom > 0.f ? __fadd_rn(__fmul_rn(prm.mom, a), __fmul_rn(prm.omm, bins)) : bins;
+            hdr->acc[hd][t] = a;
+        }
+        if (heads == 1) hdr->acc[1][t] = a;
+        acc_sum[t] = a;
+    }
+    __shared__ int s_tot[CNT_SLOTS];
+    if (t < CNT_SLOTS) {
+        int n = 0;
+        for (int r = 0; r < CNT_REPL; ++r) n += hdr->cnt[r][t];
+        s_tot[t] = n;
+    }
+    __syncthreads();
+    if (t >= 2) return;
+    float denom = 0.f;
+    if (kind == RGDA_LOSS_OHEM) {
+        const int n_min = s_tot[CNT_VALID] / 5;
+        const int kept = s_tot[CNT_KEPT0 + t];
+        if (kept < n_min) {              // loss.topk(n_min) (balance.py:130-131)
+            hdr->sel_active[t] = 1;
+            hdr->rem[t] = n_min;
+            hdr->prefix[t] = 0ull;
+            denom = (float)n_min;
+        } else {                         // loss[loss > thresh]: key >= (bits(thresh) + 1) : 0
+            hdr->cut[t] = (unsigned long long)(__float_as_uint(prm.thresh) + 1u) << 32;
+            denom = (float)kept;         // 0 when every label is ignored: NaN loss, zero gradient
+        }
+    } else if (kind == RGDA_LOSS_FOCAL) {
+        denom = (float)npix;
+    } else if (kind == RGDA_LOSS_GHM) {
+        denom = __fadd_rn((float)s_tot[CNT_LIT], 1e-7f);
+    } else {
+        denom = __fadd_rn((float)s_tot[CNT_U], 1e-7f);
+    }
+    hdr->denom[t] = denom;
+}
+
+// One radix pass of the OHEM top-k: histogram of one digit of the keys that match the prefix resolved so far; the last
+// workgroup to arrive finds the digit of the rem-th largest key.  Keys: f32 bits of the loss (>= 0, so the bit pattern
+// is monotone) in the high word, n - 1 - pixel index in the low word: unique, ties of the loss go to the lower index.
+__global__ void __launch_bounds__(256) ohem_select_kernel(LossHdr* hdr, const float* __restrict__ vbuf, long long n,
+                                                          int pass) {
+    const int hd = blockIdx.y;
+    if (!hdr->sel_active[hd]) return;    // the threshold branch, or resolved by an earlier pass
+    __shared__ int hist[SEL_BINS];
+    __shared__ int s_last;
+    const int shift = kSelShift[pass], width = kSelWidth[pass], top = shift + width;
+    const unsigned long long pre = hdr->prefix[hd];
+    const unsigned mask = (1u << width) - 1u;
+    for (int i = threadIdx.x; i < SEL_BINS; i += 256) hist[i] = 0;
+    __syncthreads();
+    const float* v = vbuf + (size_t)hd * n;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const unsigned long long key = ((unsigned long long)__float_as_uint(v[i]) << 32) | (unsigned)(n - 1 - i);
+        if (top == 64 || (key >> top) == (pre >> top)) atomicAdd(&hist[(unsigned)(key >> shift) & mask], 1);
+    }
+    __syncthreads();
+    int* gh = hdr->sel_hist[pass][hd];
+    for (int i = threadIdx.x; i <= (int)mask; i += 256)
+        if (hist[i]) atomicAdd(&gh[i], hist[i]);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __threadfence();                 // release: this workgroup's histogram adds before its arrival
+        s_last = atomicAdd(&hdr->sel_arrived[pass][hd], 1) == (int)gridDim.x - 1;
+    }
+    __syncthreads();
+    if (!s_last) return;
+    __threadfence();                     // acquire: every workgroup's adds are visible
+    // thread t owns the eight digits below nb - 8 t (from the top); a block scan finds the one whose count crosses rem
+    const int nb = (int)mask + 1, t = threadIdx.x;
+    int cnt[8], s = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int d = nb - 1 - (8 * t + j);
+        cnt[j] = d >= 0 ? __hip_atomic_load(&gh[d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+        s += cnt[j];
+    }
+    int* sc = hist;
+    sc[t] = s;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+        const int add = t >= off ? sc[t - off] : 0;
+        __syncthreads();
+        sc[t] += add;
+        __syncthreads();
+    }
+    const int incl = sc[t], excl = incl - s, rem = hdr->rem[hd];
+    if (excl < rem && rem <= incl) {
+        int above = excl, j = 0;
+        for (; j < 7; ++j) {
+            if (above + cnt[j] >= rem) break;
+            above += cnt[j];
+        }
+        const int d = nb - 1 - (8 * t + j);
+        const int left = rem - above;
+        const unsigned long long prefix = pre | ((unsigned long long)d << shift);
+        if (cnt[j] == left || pass == SEL_PASSES - 1) {
+            hdr->cut[hd] = prefix;       // every key of this digit is needed: the smallest one with the prefix
+            hdr->sel_active[hd] = 0;
+        } else {
+            hdr->prefix[hd] = prefix;
+            hdr->rem[hd] = left;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- grad pass
+template <int KIND>
+__global__ void __launch_bounds__(256) loss_grad_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
+                                                        const int64_t* __restrict__ label,
+                                                        const float* __restrict__ class_weight,
+                                                        const LossHdr* __restrict__ hdr, const void* __restrict__ scratch,
+                                                        float* partial, float* T, int h, int w, int H, int W,
+                                                        int ignore_label, LossParams prm, int want_grad) {
+    constexpr int C = LC;
+    extern __shared__ float lds[];
+    float* rows = lds;
+    float* G = lds + 2 * C * 2 * w;
+    int* lxi = (int*)(G + (want_grad ? 2 * C * W : 0));
+    float* lxl = (float*)(lxi + W);
+    __shared__ float s_acc[2][32];
+    const int b = blockIdx.y, Y = blockIdx.x;
+    const size_t n = (size_t)gridDim.y * H * W;
+    const Lerp ly = lerp_ac(Y, h, H);
+    if (KIND == RGDA_LOSS_GHM && threadIdx.x < 64) s_acc[threadIdx.x >> 5][threadIdx.x & 31] = hdr->acc[threadIdx.x >> 5][threadIdx.x & 31];
+    stage_rows<C>(rows, p1, p2, b, ly, h, w);
+    const float inv_d0 = 1.f / hdr->denom[0], inv_d1 = 1.f / hdr->denom[1];
+    const unsigned long long cut0 = hdr->cut[0], cut1 = hdr->cut[1];
+    __syncthreads();
+    float lsum0 = 0.f, lsum1 = 0.f;
+    for (int X = threadIdx.x; X < W; X += 256) {
+        const Lerp lx = lerp_ac(X, w, W);
+        lxi[X] = lx.i0;
+        lxl[X] = lx.l1;
+        const size_t pix = ((size_t)b * H + Y) * W + X;
+        const long long lab = label[pix];
+        const bool valid = lab != ignore_label;
+        const int li = valid ? (int)lab : 0;
+        float f = 0.f;
+        if constexpr (KIND == RGDA_LOSS_UPS || KIND == RGDA_LOSS_UVEM) f = ((const float*)scratch)[pix];
+#pragma unroll
+        for (int hd = 0; hd < 2; ++hd) {
+            float z[C], m, se = 0.f, e[C], zl = 0.f;
+            up_logits<C>(rows, w, hd, ly, lx, z, m);
+#pragma unroll
+            for (int c = 0; c < C; ++c) { e[c] = expf(z[c] - m); se += e[c]; zl = (c == li) ? z[c] : zl; }
+            const float ce = valid ? logf(se) - (zl - m) : 0.f;
+            const float cw = (valid && class_weight) ? class_weight[hd * C + li] : 1.f;
+            const float inv_d = hd ? inv_d1 : inv_d0;
+            float lp, dce;               // this pixel's term of the head's loss sum, d(head loss) / d ce
+            if constexpr (KIND == RGDA_LOSS_OHEM) {
+                const float v = ((const float*)scratch)[hd * n + pix];
+                const unsigned long long key = ((unsigned long long)__float_as_uint(v) << 32) | (unsigned)(n - 1 - pix);
+                const bool sel = key >= (hd ? cut1 : cut0);
+                lp = sel ? v : 0.f;
+                dce = sel ? cw * inv_d : 0.f;
+            } else if constexpr (KIND == RGDA_LOSS_FOCAL) {
+                // (1 - pt)^gamma * ce, pt = exp(-ce); d/d ce = (1 - pt)^gamma + gamma (1 - pt)^(gamma - 1) pt ce
+                const float pt = expf(-ce), q = 1.f - pt;
+                const float qg = prm.gamma == 2.f ? q * q : powf(q, prm.gamma);
+                const float qg1 = prm.gamma == 2.f ? q : powf(q, prm.gamma - 1.f);
+                lp = qg * ce;
+                dce = (qg + prm.gamma * qg1 * pt * ce) * inv_d;
+            } else if constexpr (KIND == RGDA_LOSS_GHM) {
+                const int ind = ((const uint8_t*)scratch)[hd * n + pix];
+                const float wg = (ind > 0 && ind <= GHM_BINS) ? 1.f / s_acc[hd][ind - 1] : 0.f;
+                lp = ce * wg;
+                dce = wg * inv_d;
+            } else {                     // UPS / UVEM: f = 0 where u > t (the gated CE), the uncertainty weight else
+                const float wt = f * cw;
+                lp = wt * ce;
+                dce = wt * inv_d;
+            }
+            if (hd == 0) lsum0 += lp; else lsum1 += lp;
+            if (want_grad) {
+                const float gs = valid ? dce * 0.5f : 0.f;            // / num heads (tools.py:252)
+#pragma unroll
+                for (int c = 0; c < C; ++c) G[(hd * C + c) * W + X] = (e[c] / se - ((c == li) ? 1.f : 0.f)) * gs;
+            }
+        }
+    }
+    __shared__ float red[2][4];
+    lsum0 = wave_sum(lsum0); lsum1 = wave_sum(lsum1);
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = lsum0; red[1][threadIdx.x >> 6] = lsum1; }
+    __syncthreads();
+    if (threadIdx.x < 2)
+        partial[((size_t)b * H + Y) * 2 + threadIdx.x] =
+            red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+    if (!want_grad) return;
+    // horizontal contraction: T[hd][c][x] = sum_X G[hd][c][X] * Rx[X][x]
+    const float inv_scale = (w > 1) ? (float)(W - 1) / (float)(w - 1) : 0.f;
+    for (int o = threadIdx.x; o < 2 * C * w; o += 256) {
+        int x = o % w, hc = o / w;
+        int lo = (w > 1) ? max(0, (int)floorf((float)(x - 1) * inv_scale) - 1) : 0;
+        int hi = (w > 1) ? min(W - 1, (int)ceilf((float)(x + 1) * inv_scale) + 1) : W - 1;
+        float acc = 0.f;
+        for (int X = lo; X <= hi; ++X) {
+            const int i0 = lxi[X], i1 = i0 + ((i0 < w - 1) ? 1 : 0);
+            const float l1 = lxl[X], l0 = __fsub_rn(1.f, l1);
+            float wt = ((i0 == x) ? l0 : 0.f) + ((i1 == x) ? l1 : 0.f);
+            acc += wt * G[hc * W + X];
+        }
+        T[(((size_t)b * H + Y) * 2 * C + hc) * w + x] = acc;
+    }
+}
+
+// vertical contraction T -> g[head][b][c][y][x]
+__global__ void __launch_bounds__(256) loss_col_kernel(const float* __restrict__ T, float* g1, float* g2, int b_n, int h,
+                                                       int w, int H) {
+    constexpr int C = LC;
+    int i = blockIdx.x * 256 + threadIdx.x;
+    int total = 2 * b_n * C * h * w;
+    if (i >= total) return;
+    int x = i % w, y = (i / w) % h, c = (i / (w * h)) % C, b = (i / (w * h * C)) % b_n, hd = i / (w * h * C * b_n);
+    const float inv_scale = (h > 1) ? (float)(H - 1) / (float)(h - 1) : 0.f;
+    int lo = (h > 1) ? max(0, (int)floorf((float)(y - 1) * inv_scale) - 1) : 0;
+    int hi = (h > 1) ? min(H - 1, (int)ceilf((float)(y + 1) * inv_scale) + 1) : H - 1;
+    float acc = 0.f;
+    for (int Y = lo; Y <= hi; ++Y) {
+        Lerp ly = lerp_ac(Y, h, H);
+        float wt = ((ly.i0 == y) ? ly.l0 : 0.f) + ((ly.i1 == y) ? ly.l1 : 0.f);
+        acc += wt * T[(((size_t)b * H + Y) * 2 * C + hd * C + c) * w + x];
+    }
+    float* g = hd ? g2 : g1;
+    g[(((size_t)b * C + c) * h + y) * w + x] = acc;
+}
+
+// per head: the row partials in a fixed order in double, / the head's denominator; then the mean over the two heads
+__global__ void __launch_bounds__(256) loss_reduce_kernel(const float* __restrict__ partial, const LossHdr* hdr,
+                                                          float* loss, int n) {
+    __shared__ double red[2][256];
+    double s0 = 0.0, s1 = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) { s0 += partial[2 * i]; s1 += partial[2 * i + 1]; }
+    red[0][threadIdx.x] = s0; red[1][threadIdx.x] = s1;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) { red[0][threadIdx.x] += red[0][threadIdx.x + o]; red[1][threadIdx.x] += red[1][threadIdx.x + o]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        float l0 = (float)(red[0][0] / (double)hdr->denom[0]), l1 = (float)(red[1][0] / (double)hdr->denom[1]);
+        loss[0] = (l0 + l1) / 2.f;
+    }
+}
+
+// dynamic LDS above 64 KB needs the kernel's attribute raised first (as label_kernels.hip does for pearson_sim_kernel)
+static int lds_attr(const void* kernel, size_t lds) {
+    if (lds <= 64 * 1024) return RGDA_OK;
+    return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess ? RGDA_OK
+                                                                                                            : RGDA_ERR_LAUNCH;
+}
+
+template <int KIND>
+static int launch_stat(dim3 g, size_t lds, hipStream_t st, const float* p1, const float* p2, const int64_t* label,
+                       const float* soft, const float* cw, LossHdr* hdr, void* scratch, int h, int w, int H, int W,
+                       int ig, const LossParams& prm) {
+    if (lds_attr((const void*)loss_stat_kernel<KIND>, lds) != RGDA_OK) return RGDA_ERR_LAUNCH;
+    loss_stat_kernel<KIND><<<g, 256, lds, st>>>(p1, p2, label, soft, cw, hdr, scratch, h, w, H, W, ig, prm);
+    return RGDA_OK;
+}
+
+template <int KIND>
+static int launch_grad(dim3 g, size_t lds, hipStream_t st, const float* p1, const float* p2, const int64_t* label,
+                       const float* cw, const LossHdr* hdr, const void* scratch, float* partial, float* T, int h,
+                       int w, int H, int W, int ig, const LossParams& prm, int want) {
+    if (lds_attr((const void*)loss_grad_kernel<KIND>, lds) != RGDA_OK) return RGDA_ERR_LAUNCH;
+    loss_grad_kernel<KIND><<<g, 256, lds, st>>>(p1, p2, label, cw, hdr, scratch, partial, T, h, w, H, W, ig, prm, want);
+    return RGDA_OK;
+}
+
+}  // namespace
+
+extern "C" size_t rgda_upsample_loss_workspace(int kind, int b, int c, int h, int w, int H, int W) {
+    if (kind < RGDA_LOSS_OHEM || kind > RGDA_LOSS_UVEM || b <= 0 || c <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0)
+        return 0;
+    const size_t n = (size_t)b * H * W;
+    return align256_(sizeof(LossHdr)) + align256_((size_t)b * H * 2 * 4) + align256_((size_t)b * H * 2 * c * w * 4) +
+           scratch_bytes(kind, n);
+}
+
+extern "C" int rgda_upsample_loss(int kind, int heads, const float* p1, const float* p2, const int64_t* label, const float* soft,
+                                  const float* class_weight, float* acc_sum, double m, double t, double gamma,
+                                  float thresh, double momentum, float* loss, float* g1, float* g2, int b, int c, int h,
+                                  int w, int H, int W, int ignore_label, void* ws, size_t ws_bytes,
+                                  rgda_stream_t stream) {
+    if (kind < RGDA_LOSS_OHEM || kind > RGDA_LOSS_UVEM || (heads != 1 && heads != 2)) return RGDA_ERR_ARG;
+    if (heads == 1 && p2 != p1) return RGDA_ERR_ARG;
+    if (!p1 || !p2 || !label || !loss || !ws || ((g1 == nullptr) != (g2 == nullptr))) return RGDA_ERR_ARG;
+    if (b <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return RGDA_ERR_ARG;
+    if ((long long)b * H * W >= (1ll << 31)) return RGDA_ERR_ARG;         // pixel index and OHEM key low word: 32 bits
+    const bool uv = kind == RGDA_LOSS_UPS || kind == RGDA_LOSS_UVEM;
+    if (uv && (!soft || !(t > 0.0))) return RGDA_ERR_ARG;
+    if (kind == RGDA_LOSS_UVEM && !(gamma > 0.0 && m >= 0.0)) return RGDA_ERR_ARG;
+    if (kind == RGDA_LOSS_GHM && (!acc_sum || !(momentum >= 0.0 && momentum < 1.0))) return RGDA_ERR_ARG;
+    if (kind == RGDA_LOSS_FOCAL && !(gamma >= 0.0)) return RGDA_ERR_ARG;
+    if (kind == RGDA_LOSS_OHEM && !(thresh >= 0.f)) return RGDA_ERR_ARG;
+    // the reference's FocalLoss / GHMLoss take no class balancer
+    if ((kind == RGDA_LOSS_FOCAL || kind == RGDA_LOSS_GHM) && class_weight) return RGDA_ERR_ARG;
+    if (c != LC) return RGDA_ERR_UNSUPPORTED;
+    if (ws_bytes < rgda_upsample_loss_workspace(kind, b, c, h, w, H, W)) return RGDA_ERR_WORKSPACE;
+    const int want = g1 != nullptr;
+    size_t lds_stat = (size_t)2 * LC * 2 * w * 4;
+    size_t lds_grad = ((size_t)2 * LC * 2 * w + (want ? (size_t)2 * LC * W : 0) + (size_t)2 * W) * 4;
+    if (lds_grad > 150 * 1024) return RGDA_ERR_UNSUPPORTED;
+    hipStream_t st = to_stream(stream);
+    const long long n = (long long)b * H * W;
+    char* base = (char*)ws;
+    LossHdr* hdr = (LossHdr*)base;
+    base += align256_(sizeof(LossHdr));
+    float* partial = (float*)base;
+    base += align256_((size_t)b * H * 2 * 4);
+    float* T = (float*)base;
+    base += align256_((size_t)b * H * 2 * c * w * 4);
+    void* scratch = base;
+    LossParams prm;
+    prm.thresh = thresh;
+    prm.m = (float)m;
+    prm.t = (float)t;
+    prm.cl = m > 0.0 ? (float)(-1.0 / (m * m)) : 0.f;                   // balance.py:408,417: -1 / m^2, -1 / (t - m)^2
+    prm.cr = m < t ? (float)(-1.0 / ((t - m) * (t - m))) : 0.f;
+    prm.inv_gamma = gamma > 0.0 ? (float)(1.0 / gamma) : 0.f;
+    prm.gamma = (float)gamma;
+    prm.mom = (float)momentum;
+    prm.omm = (float)(1.0 - momentum);
+    const dim3 rows_grid(H, b);
+    if (kind != RGDA_LOSS_FOCAL) {
+        const size_t zero = kind == RGDA_LOSS_OHEM ? offsetof(LossHdr, cut) : offsetof(LossHdr, sel_arrived);
+        if (zero_bytes(hdr, zero, stream) != RGDA_OK) return RGDA_ERR_LAUNCH;
+        const size_t lds = uv ? 0 : lds_stat;
+        int rc;
+        switch (kind) {
+            case RGDA_LOSS_OHEM: rc = launch_stat<RGDA_LOSS_OHEM>(rows_grid, lds, st, p1, p2, label, soft, class_weight, hdr, scratch, h, w, H, W, ignore_label, prm); break;
+            case RGDA_LOSS_GHM: rc = launch_stat<RGDA_LOSS_GHM>(rows_grid, lds, st, p1, p2, label, soft, class_weight, hdr, scratch, h, w, H, W, ignore_label, prm); break;
+            case RGDA_LOSS_UPS: rc = launch_stat<RGDA_LOSS_UPS>(rows_grid, lds, st, p1, p2, label, soft, class_weight, hdr, scratch, h, w, H, W, ignore_label, prm); break;
+            default: rc = launch_stat<RGDA_LOSS_UVEM>(rows_grid, lds, st, p1, p2, label, soft, class_weight, hdr, scratch, h, w, H, W, ignore_label, prm); break;
+        }
+        if (rc != RGDA_OK) return rc;
+        RGDA_CHECK_LAUNCH();
+    }
+    loss_finalize_kernel<<<1, 64, 0, st>>>(kind, heads, hdr, acc_sum, prm, n);
+    RGDA_CHECK_LAUNCH();
+    if (kind == RGDA_LOSS_OHEM) {
+        const int blocks = (int)min((long long)cdiv(n, 256 * 8), 512ll);
+        for (int pass = 0; pass < SEL_PASSES; ++pass) {
+            ohem_select_kernel<<<dim3(blocks, 2), 256, 0, st>>>(hdr, (const float*)scratch, n, pass);
+            RGDA_CHECK_LAUNCH();
+        }
+    }
+    int rc;
+    switch (kind) {
+        case RGDA_LOSS_OHEM: rc = launch_grad<RGDA_LOSS_OHEM>(rows_grid, lds_grad, st, p1, p2, label, class_weight, hdr, scratch, partial, T, h, w, H, W, ignore_label, prm, want); break;
+        case RGDA_LOSS_FOCAL: rc = launch_grad<RGDA_LOSS_FOCAL>(rows_grid, lds_grad, st, p1, p2, label, class_weight, hdr, scratch, partial, T, h, w, H, W, ignore_label, prm, want); break;
+        case RGDA_LOSS_GHM: rc = launch_grad<RGDA_LOSS_GHM>(rows_grid, lds_grad, st, p1, p2, label, class_weight, hdr, scratch, partial, T, h, w, H, W, ignore_label, prm, want); break;
+        case RGDA_LOSS_UPS: rc = launch_grad<RGDA_LOSS_UPS>(rows_grid, lds_grad, st, p1, p2, label, class_weight, hdr, scratch, partial, T, h, w, H, W, ignore_label, prm, want); break;
+        default: rc = launch_grad<RGDA_LOSS_UVEM>(rows_grid, lds_grad, st, p1, p2, label, class_weight, hdr, scratch, partial, T, h, w, H, W, ignore_label, prm, want); break;
+    }
+    if (rc != RGDA_OK) return rc;
+    RGDA_CHECK_LAUNCH();
+    if (want) {
+        loss_col_kernel<<<cdiv((long long)2 * b * LC * h * w, 256), 256, 0, st>>>(T, g1, g2, b, h, w, H);
+        RGDA_CHECK_LAUNCH();
+    }
+    loss_reduce_kernel<<<1, 256, 0, st>>>(partial, hdr, loss, b * H);
+    RGDA_CHECK_LAUNCH();
+    return RGDA_OK;
+}

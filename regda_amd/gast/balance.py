@@ -1,5 +1,7 @@
 """CrossEntropy + ClassBalance -- mirror of regda/gast/balance.py:15-101 (the "CE + reweight" of the
-SSL path).  The loss is evaluated by the fused bilinear-upsample + CE kernel (`rgda_upsample_ce`)."""
+SSL path).  The loss is evaluated by the fused bilinear-upsample + CE kernel (`rgda_upsample_ce`).
+The losses of the --ls / --lt flags -- OhemCrossEntropy, FocalLoss, GHMLoss, UPSLoss, UVEMLoss (balance.py:104-216,
+306-435) -- and loss_calc_uvem (:438-460) run on the fused upsample + loss kernels of `rgda_upsample_loss`."""
 import torch
 import torch.distributed as dist
 import torch.nn as nn
@@ -90,3 +92,216 @@ class CrossEntropy(nn.Module):
         assert len(preds) == 2
         cw = self._weights(labels, 2)
         return _UpCE.apply(preds[0], preds[1], labels.long(), self.ignore_label, cw)
+
+
+class _UpLoss(torch.autograd.Function):
+    """Autograd wrapper of a fused loss launch: `launch(p1, p2)` -> (loss f32[1], g1, g2)."""
+    @staticmethod
+    def forward(ctx, p1, p2, launch):
+        loss, g1, g2 = launch(p1, p2)
+        ctx.save_for_backward(g1, g2)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, go):
+        g1, g2 = ctx.saved_tensors
+        return g1 * go, g2 * go, None
+
+
+class _FusedLoss(nn.Module):
+    """Common surface of the --ls / --lt losses: the reference's per-prediction forward, and forward_multi for
+    loss_calc(multi=True) (both heads in one launch sequence).  `launch` is the raw device call the fused steps use.
+    Subclasses set `class_balancer` (None where the reference takes none) and `ignore_label` as instance attributes:
+    a ClassBalance is an nn.Module, so a class-level default would shadow it."""
+    kind = None
+
+    def _params(self):
+        return {}
+
+    def launch(self, p1, p2, labels, soft=None, class_weight=None, g1=None, g2=None, heads=2, want_grad=True):
+        return ops.upsample_loss(self.kind, p1, p2, labels, soft=soft, class_weight=class_weight,
+                                 ignore_label=self.ignore_label, want_grad=want_grad, g1=g1, g2=g2, heads=heads,
+                                 **self._params())
+
+    def _weights(self, labels, heads):
+        if self.class_balancer is None:
+            return None
+        # the balancer is EMA-updated once per head, as in the reference's per-head loss_fn calls
+        ws = [self.class_balancer.next_class_weight(labels) for _ in range(heads)]
+        return torch.stack(ws * 2 if heads == 1 else ws, 0)
+
+    def _run(self, preds, labels, soft):
+        labels = labels.long()
+        heads = 2 if isinstance(preds, (list, tuple)) else 1
+        p1, p2 = (preds[0], preds[1]) if heads == 2 else (preds, preds)
+        cw = self._weights(labels, heads)
+        if heads == 1:
+            # one prediction: the kernel's two "heads" are the same call, the gradient is g1 + g2
+            return _UpLoss.apply(p1, p2, lambda a, _b: self.launch(a, a, labels, soft, cw, heads=1))
+        return _UpLoss.apply(p1, p2, lambda a, b: self.launch(a, b, labels, soft, cw))
+
+
+class OhemCrossEntropy(_FusedLoss):
+    """balance.py:104-133: the mean of the per-pixel (class-weighted) CE above -log(thresh), or of the n_min = #valid / 5
+    largest when fewer pass.  Of equal losses at the k-th place the lowest pixel index is kept."""
+    kind = 'ohem'
+
+    def __init__(self, ignore_label=-1, class_balancer=None, thresh=0.7):
+        super().__init__()
+        self.thresh = -torch.log(torch.tensor(thresh, dtype=torch.float))
+        self.ignore_label = ignore_label
+        self.class_balancer = class_balancer
+
+    def _params(self):
+        return dict(thresh=float(self.thresh))
+
+    def forward(self, preds, labels):
+        return self._run(preds, labels, None)
+
+    def forward_multi(self, preds, labels):
+        assert len(preds) == 2
+        return self._run(tuple(preds), labels, None)
+
+
+class FocalLoss(_FusedLoss):
+    """balance.py:136-158 with alpha=None, reduction='mean' (what --lt focal constructs)."""
+    kind = 'focal'
+
+    def __init__(self, alpha=None, gamma=2.0, reduction='mean', ignore_label=-1):
+        super().__init__()
+        if alpha is not None or reduction != 'mean':
+            raise NotImplementedError('FocalLoss: only alpha=None, reduction="mean" (the --lt focal configuration)')
+        self.alpha, self.gamma, self.reduction, self.ignore_label = alpha, gamma, reduction, ignore_label
+        self.class_balancer = None
+
+    def _params(self):
+        return dict(gamma=float(self.gamma))
+
+    def forward(self, preds, targets):
+        return self._run(preds, targets, None)
+
+    def forward_multi(self, preds, targets):
+        assert len(preds) == 2
+        return self._run(tuple(preds), targets, None)
+
+
+class GHMLoss(_FusedLoss):
+    """balance.py:161-216.  acc_sum stays on the device and is updated in place (once per head), so a captured step
+    advances it at every replay."""
+    kind = 'ghm'
+
+    def __init__(self, bins=30, momentum=0.0, ignore_label=-1, device='cuda'):
+        super().__init__()
+        if bins != 30:
+            raise NotImplementedError('GHMLoss: bins=30 only (the --lt ghm configuration)')
+        self.bins_num, self.momentum, self.ignore_label = bins, momentum, ignore_label
+        self.class_balancer = None
+        edges = [float(x) / bins for x in range(bins + 1)]
+        edges[-1] = edges[-1] + 1e-3
+        self.edges = torch.tensor(edges, dtype=torch.float32, device=device)
+        self.acc_sum = torch.zeros(bins, device=device)
+
+    def _params(self):
+        return dict(acc_sum=self.acc_sum, momentum=float(self.momentum))
+
+    def forward(self, preds, targets):
+        return self._run(preds, targets, None)
+
+    def forward_multi(self, preds, targets):
+        assert len(preds) == 2
+        return self._run(tuple(preds), targets, None)
+
+    def get_g_distribution(self):
+        return self.acc_sum / (self.acc_sum.sum() + 1e-7)
+
+
+class UPSLoss(_FusedLoss):
+    """balance.py:306-345: CE where the soft label's entropy u <= threshold, / #(u <= threshold, valid)."""
+    kind = 'ups'
+
+    def __init__(self, threshold=0.7, class_balancer=None, class_num=7, ignore_label=-1):
+        super().__init__()
+        self.threshold, self.class_balancer = threshold, class_balancer
+        self.class_num, self.ignore_label = class_num, ignore_label
+
+    def _params(self):
+        return dict(t=float(self.threshold))
+
+    def forward(self, preds, targets, label_t_soft):
+        return self._run(preds, targets, label_t_soft)
+
+    def forward_multi(self, preds, targets, label_t_soft):
+        assert len(preds) == 2
+        return self._run(tuple(preds), targets, label_t_soft)
+
+
+class UVEMLoss(UPSLoss):
+    """balance.py:348-426: UPSLoss times the uncertainty weight get_weight(u)."""
+    kind = 'uvem'
+
+    def __init__(self, m=0.1, threshold=0.7, gamma=8.0, class_balancer=None, class_num=7, ignore_label=-1):
+        super().__init__(threshold, class_balancer, class_num, ignore_label)
+        self.m, self.gamma = m, gamma
+
+    def _params(self):
+        return dict(m=float(self.m), t=float(self.threshold), gamma=float(self.gamma))
+
+    def get_weight(self, uncertainties):
+        """The weight curve (balance.py:398-426) on a tensor of uncertainties, for inspection and plotting: the training
+        path evaluates it inside the fused kernel."""
+        u = uncertainties
+        left = torch.ones_like(u)
+        if self.m > 0:
+            x = torch.where((u <= self.m) & (u >= 0), u, left)
+            left = torch.clamp((-1 / (self.m ** 2)) * (x - self.m) ** 2 + 1, 0.0, 1.0) ** (1.0 / self.gamma)
+        right = torch.zeros_like(u)
+        if self.m < self.threshold:
+            x = torch.where((u > self.m) & (u <= self.threshold), u, right)
+            right = torch.clamp((-1 / ((self.threshold - self.m) ** 2)) * (x - self.m) ** 2 + 1, 0.0, 1.0) ** (1.0 / self.gamma)
+        w = torch.where(u <= self.m, left, right)
+        return torch.where(u >= self.threshold, torch.zeros_like(u), w)
+
+
+def loss_calc_uvem(pred, label, label_soft, loss_fn, multi=True):
+    """balance.py:438-460: loss_calc for the losses that also read the (full-resolution) soft label."""
+    if multi is True:
+        if hasattr(loss_fn, 'forward_multi') and len(pred) == 2:
+            return loss_fn.forward_multi(pred, label.long(), label_soft)
+        loss = 0
+        for p in pred:
+            loss += loss_fn(p, label.long(), label_soft)
+        return loss / len(pred)
+    return loss_fn(pred, label.long(), label_soft)
+
+
+SOURCE_LOSSES = ('CrossEntropy', 'OhemCrossEntropy')
+TARGET_LOSSES = ('ours', 'uvem', 'ohem', 'focal', 'ghm', 'ups', 'none')
+
+
+def source_loss(ls, class_balancer=None, ignore_label=-1):
+    """--ls with --bcs (tools/train_ssl_reg.py:134, train_src.py:93, train_align_reg.py:126): the balancer is honoured by
+    both choices."""
+    if ls not in SOURCE_LOSSES:
+        raise ValueError(f'--ls {ls!r}: one of {SOURCE_LOSSES}')
+    cls = CrossEntropy if ls == 'CrossEntropy' else OhemCrossEntropy
+    return cls(ignore_label=ignore_label, class_balancer=class_balancer)
+
+
+def target_loss(lt, class_balancer=None, uvem_m=0.2, uvem_t=0.7, uvem_g=4.0, class_num=6, ignore_label=-1,
+                device='cuda'):
+    """--lt with --bct and --uvem-m/-t/-g, exactly as tools/train_ssl_reg.py:135-158: ours / uvem and ups honour the
+    balancer, ohem, focal and ghm are built without one, none is CrossEntropy (with it)."""
+    if lt not in TARGET_LOSSES:
+        raise ValueError(f'--lt {lt!r}: one of {TARGET_LOSSES}')
+    if lt in ('ours', 'uvem'):
+        return UVEMLoss(m=uvem_m, threshold=uvem_t, gamma=uvem_g, class_balancer=class_balancer, class_num=class_num,
+                        ignore_label=ignore_label)
+    if lt == 'ohem':
+        return OhemCrossEntropy(ignore_label=ignore_label)
+    if lt == 'focal':
+        return FocalLoss(gamma=2.0, reduction='mean', ignore_label=ignore_label)
+    if lt == 'ghm':
+        return GHMLoss(bins=30, momentum=0.99, ignore_label=ignore_label, device=device)
+    if lt == 'ups':
+        return UPSLoss(threshold=0.7, class_balancer=class_balancer, class_num=class_num, ignore_label=ignore_label)
+    return CrossEntropy(ignore_label=ignore_label, class_balancer=class_balancer)

@@ -21,12 +21,12 @@ BF = torch.bfloat16
 
 
 class SourceStep(SSLStep):
-    def __init__(self, model, class_balancer_s=None, align_domain=False, class_num=6, **kw):
+    def __init__(self, model, class_balancer_s=None, align_domain=False, class_num=6, loss_s='CrossEntropy', **kw):
         kw['ema_decay'] = None
         kw.setdefault('sam_refine', False)
         kw.setdefault('refine_label', False)
         super().__init__(model, torch.zeros(class_num, 2048), class_num=class_num, class_balancer_s=class_balancer_s,
-                         **kw)
+                         loss_s=loss_s, **kw)
         self.align_domain = bool(align_domain)
         self.loss_domain = torch.zeros(1, device=model.device)
 
@@ -62,8 +62,7 @@ class SourceStep(SSLStep):
             x1, x2, feat = m._forward_plan(images_s.contiguous().float(), T)
         # d(loss) / d(logits): the source rows from the CE kernel, the target rows (when there are any) zero
         g1, g2 = torch.zeros_like(x1), torch.zeros_like(x2)
-        loss_seg, _, _ = ops.upsample_ce(x1[:nb], x2[:nb], label_s, self.ig,
-                                         self._class_weights(self.class_balancer_s, label_s), True, g1[:nb], g2[:nb])
+        loss_seg = self._source_loss(x1[:nb], x2[:nb], label_s, g1[:nb], g2[:nb])
         self.loss_domain.zero_()
         gfeat = None
         if self.align_domain:

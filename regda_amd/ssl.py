@@ -14,6 +14,7 @@ import torch
 from . import ops
 from . import plan
 from .ddp import FlatGradReducer, all_reduce_prototype_statistics
+from .gast.balance import source_loss, target_loss
 
 
 class SSLStep:
@@ -21,7 +22,8 @@ class SSLStep:
                  max_norm=32.0, cutoff_top=0.8, cutoff_low=0.6, percent=0.5, proto_decay=0.996, refine_temp=2.0,
                  sam_refine=True, refine_label=True, ema_decay=None, max_regions=4096, bucket_elems=12 << 20,
                  process_group=None, overlap_wgrad=True, overlap_comm=True, class_balancer_s=None,
-                 class_balancer_t=None, grad_payload='fp32', comm=None):
+                 class_balancer_t=None, grad_payload='fp32', comm=None, loss_s='CrossEntropy', loss_t='none',
+                 uvem_m=0.2, uvem_t=0.7, uvem_g=4.0):
         self.model = model
         self.C, self.ig = class_num, ignore_label
         self.momentum, self.wd, self.max_norm = momentum, weight_decay, max_norm
@@ -56,6 +58,12 @@ class SSLStep:
         # --bcs / --bct of tools/train_ssl_reg.py:54-58,125-158: regda_amd.gast.balance.ClassBalance objects whose
         # frequency EMA re-weights the source / target cross-entropy per class (None = plain CE, the default)
         self.class_balancer_s, self.class_balancer_t = class_balancer_s, class_balancer_t
+        # --ls / --lt (+ --uvem-m/-t/-g) of tools/train_ssl_reg.py:52-63,134-158: None = the CrossEntropy path above;
+        # otherwise a regda_amd.gast.balance loss whose fused kernels (rgda_upsample_loss) the step launches directly
+        src, tgt = source_loss(loss_s, class_balancer_s, ignore_label), target_loss(
+            loss_t, class_balancer_t, uvem_m, uvem_t, uvem_g, class_num, ignore_label, device=dev)
+        self.loss_fn_s = None if loss_s == 'CrossEntropy' else src
+        self.loss_fn_t = None if loss_t == 'none' else tgt
         self._graph = None
         self._plan = None
         self._proto_ready = None
@@ -87,7 +95,7 @@ class SSLStep:
         assert not self.first, 'run one eager step before capture()'
         if self.world > 1:
             raise RuntimeError('whole-step graphs are single-GPU; the multi-GPU path stays eager')
-        if self.class_balancer_s is not None or self.class_balancer_t is not None:
+        if self._host_balancers():
             # ClassBalance.next_class_weight rebinds its frequency tensor and is host arithmetic: a graph would keep the
             # address of the pre-capture tensor and never advance the EMA.  record_plan() re-runs it as a host action.
             raise RuntimeError('class balancing (--bcs / --bct) is host-side state: use record_plan(), not capture()')
@@ -207,6 +215,28 @@ class SSLStep:
         plan.host(update)
         return cw
 
+    def _host_balancers(self):
+        """Whether a ClassBalance takes part in the step's losses (ohem, focal and ghm targets take none)."""
+        used_t = self.class_balancer_t if self.loss_fn_t is None else self.loss_fn_t.class_balancer
+        return self.class_balancer_s is not None or used_t is not None
+
+    def _source_loss(self, s1, s2, label_s, g1, g2):
+        """loss_calc(source, loss_fn_s): its value; d loss / d logits written into g1, g2."""
+        f = self.loss_fn_s
+        if f is None:
+            return ops.upsample_ce(s1, s2, label_s, self.ig, self._class_weights(self.class_balancer_s, label_s), True,
+                                   g1, g2)[0]
+        return f.launch(s1, s2, label_s, class_weight=self._class_weights(f.class_balancer, label_s), g1=g1, g2=g2)[0]
+
+    def _target_loss(self, t1, t2, hard, soft, g1, g2):
+        """loss_calc / loss_calc_uvem(target, loss_fn_t) on the pseudo labels (ups / uvem also read the refined soft label)."""
+        f = self.loss_fn_t
+        if f is None:
+            return ops.upsample_ce(t1, t2, hard, self.ig, self._class_weights(self.class_balancer_t, hard), True,
+                                   g1, g2)[0]
+        return f.launch(t1, t2, hard, soft=soft if f.kind in ('ups', 'uvem') else None,
+                        class_weight=self._class_weights(f.class_balancer, hard), g1=g1, g2=g2)[0]
+
     def _mark(self, name, stream=None):
         if self.marks is not None:
             ev = torch.cuda.Event(enable_timing=True)
@@ -267,8 +297,7 @@ class SSLStep:
         if side is not None:
             plan.wait_event(side, plan.record_event(main))
             with ops.use_stream(side):
-                loss_s, _, _ = ops.upsample_ce(s1, s2, label_s, self.ig,
-                                               self._class_weights(self.class_balancer_s, label_s), True, g1[:nb], g2[:nb])
+                loss_s = self._source_loss(s1, s2, label_s, g1[:nb], g2[:nb])
         # pseudo_selection + LRH in ONE pass over the refined soft labels (rgda_pseudo_lrh: the selected label is never
         # written as an int64 tensor and read back) where the chain is the default one; tests that look at the selected
         # labels (keep_debug) and the other configurations take the two calls
@@ -325,10 +354,8 @@ class SSLStep:
                 plan.host(lambda: setattr(self, '_proto_ready', pside.record_event() if pside is not main else None))
         # ---- losses + d(loss)/d(logits)
         if side is None:
-            loss_s, _, _ = ops.upsample_ce(s1, s2, label_s, self.ig,
-                                           self._class_weights(self.class_balancer_s, label_s), True, g1[:nb], g2[:nb])
-        loss_t, _, _ = ops.upsample_ce(t1, t2, hard, self.ig, self._class_weights(self.class_balancer_t, hard), True,
-                                       g1[nb:], g2[nb:])
+            loss_s = self._source_loss(s1, s2, label_s, g1[:nb], g2[:nb])
+        loss_t = self._target_loss(t1, t2, hard, soft, g1[nb:], g2[nb:])
         if side is not None:
             plan.wait_event(main, source_done)       # source loss, its logit gradients, the new prototypes
         self._mark('label path + losses done')

@@ -1,0 +1,89 @@
+"""dev: the fused --ls / --lt losses (rgda_upsample_loss) against the CE call (rgda_upsample_ce) at 8 x 6 x 32 x 32 ->
+512 x 512 (HIP-event time per loss_calc call, with gradients; algorithmic bytes), and the step time of
+SSLStep(loss_t='uvem' / 'ohem') against the default, as bench.py builds it (ResNet-101, 8 + 8 images, recorded plan).
+    python scripts/dev/loss_bench.py [--no-step]"""
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+import torch
+
+from regda_amd import ops
+
+
+def t_of(fn, reps=50):
+    for _ in range(5):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps * 1e3
+
+
+def loss_calls():
+    g = torch.Generator().manual_seed(0)
+    b, c, h, H = 8, 6, 32, 512
+    p1, p2 = (torch.randn(b, c, h, h, generator=g) * 2).cuda(), (torch.randn(b, c, h, h, generator=g) * 2).cuda()
+    lab = torch.randint(-1, c, (b, H, H), generator=g).cuda()
+    # confident labels: OHEM takes the top-k (radix select) branch
+    base = torch.randn(b, c, h, h, generator=g) * 24
+    q1, q2 = (base + 0.2 * torch.randn(b, c, h, h, generator=g)).cuda(), (base + 0.2 * torch.randn(b, c, h, h, generator=g)).cuda()
+    lab_c = torch.nn.functional.interpolate(base, (H, H), mode='bilinear', align_corners=True).argmax(1).cuda()
+    soft = torch.softmax(torch.randn(b, c, H, H, generator=g) * 3, 1).cuda()
+    g1, g2 = torch.empty_like(p1), torch.empty_like(p2)
+    acc = torch.zeros(30, device='cuda')
+    npix = b * H * H
+    # algorithmic bytes: int64 labels (read by each pass), the soft label (ups / uvem), the per-pixel scratch written by
+    # the stat pass and read by the gradient pass, low-res logits and gradients (2 heads)
+    low = 2 * 2 * b * c * h * h * 4
+    passes = {'ce': 1, 'focal': 1}
+    scratch = {'ohem': 2 * npix * 4, 'ghm': 2 * npix, 'ups': npix * 4, 'uvem': npix * 4}
+    runs = [('ce', lambda: ops.upsample_ce(p1, p2, lab, -1, None, True, g1, g2))]
+    kw = dict(thresh=0.35667494, momentum=0.99, g1=g1, g2=g2)
+    runs += [('ohem', lambda: ops.upsample_loss('ohem', p1, p2, lab, **kw)),
+             ('ohem top-k', lambda: ops.upsample_loss('ohem', q1, q2, lab_c, **kw)),
+             ('focal', lambda: ops.upsample_loss('focal', p1, p2, lab, gamma=2.0, **kw)),
+             ('ghm', lambda: ops.upsample_loss('ghm', p1, p2, lab, acc_sum=acc, **kw)),
+             ('ups', lambda: ops.upsample_loss('ups', p1, p2, lab, soft=soft, t=0.7, **kw)),
+             ('uvem', lambda: ops.upsample_loss('uvem', p1, p2, lab, soft=soft, m=0.2, t=0.7, gamma=4.0, **kw))]
+    t_ce = None
+    for name, fn in runs:
+        t = t_of(fn)
+        t_ce = t if t_ce is None else t_ce
+        k = name.split()[0]
+        nbytes = passes.get(k, 2) * npix * 8 + 2 * scratch.get(k, 0) + low + (c * npix * 4 if k in ('ups', 'uvem') else 0)
+        print('%-11s %7.1f us  %.2fx CE   %6.1f MB algorithmic' % (name, t, t / t_ce, nbytes / 1e6), flush=True)
+
+
+def step_times():
+    from regda_amd.models.Encoder import Deeplabv2
+    from regda_amd.ssl import SSLStep
+    from regda_amd.synthetic import make_batch
+    batch = make_batch(b=8, size=512, seed=2333, with_soft=True)
+    protos = torch.randn(6, 2048, generator=torch.Generator().manual_seed(0))
+    for lt in ('none', 'uvem', 'ohem'):
+        torch.manual_seed(2333)
+        model = Deeplabv2(dict(backbone=dict(resnet_type='resnet101', output_stride=16, pretrained=False),
+                               multi_layer=True, cascade=False, use_ppm=True,
+                               ppm=dict(num_classes=6, use_aux=False, fc_dim=2048), inchannels=2048, num_classes=6,
+                               is_ins_norm=True))
+        model.sync_weights()
+        st = SSLStep(model, protos, loss_t=lt)
+        args = (batch['images_s'], batch['label_s'], batch['images_t'], batch['soft_t'], batch['regs_t'])
+        for _ in range(2):
+            st.step(*args, 1e-3)
+        st.record_plan(*args)
+        t = t_of(lambda: st.step(*args, 1e-3), reps=10) / 1e3
+        print('SSLStep(loss_t=%r): %.2f ms per step (recorded plan)' % (lt, t), flush=True)
+        del st, model
+        torch.cuda.empty_cache()
+
+
+if __name__ == '__main__':
+    loss_calls()
+    if '--no-step' not in sys.argv:
+        step_times()
