@@ -135,7 +135,7 @@ class CpuAlignStep(CpuStep):
                 hard = torch.from_numpy(labels.homogenize(hard.numpy(), regs_t.squeeze(1).numpy(),
                                                           self.percent, self.C, self.ig))
             label_t = torch.from_numpy(labels.downscale_label(hard.numpy(), 16, self.C, self.ig, 0.75))
-        loss_seg = labelpath.loss_calc([s1, s2], label_s, self.ig)
+        loss_seg = labelpath.loss_calc([s1, s2], label_s, self.ig, self.balancer_s)
         loss_align = (labelpath.prototype_contrastive_loss(self.prototypes, feat_s, label_s_down, self.pcl_temp, self.ig) +
                       labelpath.prototype_contrastive_loss(self.prototypes, feat_t, label_t, self.pcl_temp, self.ig)) * 0.5
         loss = loss_seg + loss_align

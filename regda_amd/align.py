@@ -83,12 +83,9 @@ class AlignStep(SSLStep):
             hard = ops.lrh(hard, regs.contiguous(), self.percent, self.C, self.ig, self.max_regions, check=False,
                            ws=self.lrh_ws)
         label_t = self._downscale(hard)                                              # aligner.downscale_gt, :180
-        # ---- losses and their gradients
-        if self.loss_fn_s is None:
-            loss_seg, gs1, gs2 = ops.upsample_ce(s1, s2, label_s, self.ig, None, True)
-        else:                                                                        # --ls OhemCrossEntropy
-            f = self.loss_fn_s
-            loss_seg, gs1, gs2 = f.launch(s1, s2, label_s, class_weight=self._class_weights(f.class_balancer, label_s))
+        # ---- losses and their gradients: d loss / d logits, the source rows from the loss kernels, the target rows zero
+        g1, g2 = torch.zeros_like(x1), torch.zeros_like(x2)
+        loss_seg = self._source_loss(s1, s2, label_s, g1[:nb], g2[:nb])
         n, k, h, w = feat.shape
         gfeat = torch.empty(n * h * w, k, dtype=BF, device=m.device)
         self.loss_align.zero_()
@@ -100,8 +97,7 @@ class AlignStep(SSLStep):
             self.loss_domain.zero_()
             ops.coral_loss(feat_s, feat_t, 1.0, loss=self.loss_domain, dfeat_s=gfeat[:nb * h * w],
                            dfeat_t=gfeat[nb * h * w:], accumulate=True)
-        zero = torch.zeros_like(gs1)
-        self._backward_and_update(T, main, torch.cat([gs1, zero]), torch.cat([gs2, zero]), gfeat=gfeat)
+        self._backward_and_update(T, main, g1, g2, gfeat=gfeat)
         self.last_hard, self.last_label_t, self.last_label_s_down = hard, label_t, label_s_down
         return loss_seg, self.loss_align, self.gn
 

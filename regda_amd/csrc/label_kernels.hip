@@ -1,5 +1,5 @@
 // Label path of the RegDA SSL step on gfx950: pseudo_selection, LRH (Homogenizer),
-// label_refine, update_prototype, fused bilinear-upsample + cross-entropy, teacher probs.
+// label_refine, update_prototype, teacher probs.
 // All fp32 / integer, HBM-bound: coalesced wide loads, LDS-resident small state,
 // wavefront-level pre-reduction in front of every atomic.  No fast-math: the
 // integer decisions must match the reference bit for bit (DESIGN.md "Parity").
@@ -1108,168 +1108,6 @@ extern "C" int rgda_proto_update(const float* feat, const int64_t* label, float*
     const int rc = rgda_proto_stats(feat, label, label_ds, b, k, c, h, w, scale, ignore_label, min_ratio, ws, ws_bytes, stream);
     if (rc != RGDA_OK) return rc;
     return rgda_proto_apply(protos, ws, c, k, decay, stream);
-}
-
-// --------------------------------------------------------------------------------------
-// loss_calc(multi=True) + CrossEntropy  (regda/utils/tools.py:240-254; regda/gast/balance.py:88-101)
-// forward and d(loss)/d(low-res logits) in one pass over the full-resolution pixels:
-//   stage 1 (one workgroup per output row): bilinear(ac=True) logits -> log-softmax -> loss
-//           partial; per-pixel gradient kept in LDS and contracted with the horizontal
-//           interpolation weights -> T[b][Y][head][c][x]
-//   stage 2: vertical contraction T -> g[head][b][c][y][x]; deterministic loss reduction.
-// --------------------------------------------------------------------------------------
-template <int C>
-__global__ void __launch_bounds__(256) upce_row_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
-                                                       const int64_t* __restrict__ label,
-                                                       const float* __restrict__ class_weight, float* partial,
-                                                       float* T, int h, int w, int H, int W, int ignore_label,
-                                                       float gscale, int want_grad) {
-    extern __shared__ float lds[];
-    // rows[2 heads][C][2][w] | G[2][C][W]
-    float* rows = lds;
-    float* G = lds + 2 * C * 2 * w;
-    // the horizontal interpolation of every output column, kept for the contraction below: recomputing lerp_ac there (an
-    // IEEE divide each) cost 13 000 calls per workgroup -- more than the per-pixel loss arithmetic
-    int* lxi = (int*)(G + (want_grad ? 2 * C * W : 0));
-    float* lxl = (float*)(lxi + W);
-    const int b = blockIdx.y, Y = blockIdx.x;
-    const int hw = h * w;
-    Lerp ly = lerp_ac(Y, h, H);
-    for (int i = threadIdx.x; i < 2 * C * 2 * w; i += 256) {
-        int x = i % w, r = (i / w) & 1, c = (i / (2 * w)) % C, hd = i / (2 * w * C);
-        const float* p = hd ? p2 : p1;
-        rows[i] = p[((size_t)b * C + c) * hw + (r ? ly.i1 : ly.i0) * w + x];
-    }
-    __syncthreads();
-    float lsum0 = 0.f, lsum1 = 0.f;
-    for (int X = threadIdx.x; X < W; X += 256) {
-        Lerp lx = lerp_ac(X, w, W);
-        lxi[X] = lx.i0;
-        lxl[X] = lx.l1;
-        long long lab = label[((size_t)b * H + Y) * W + X];
-        bool valid = lab != ignore_label;
-        int li = valid ? (int)lab : 0;
-#pragma unroll
-        for (int hd = 0; hd < 2; ++hd) {
-            float z[C], m = -INFINITY;
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const float* r = rows + ((hd * C + c) * 2) * w;
-                float top = __fadd_rn(__fmul_rn(lx.l0, r[lx.i0]), __fmul_rn(lx.l1, r[lx.i1]));
-                float bot = __fadd_rn(__fmul_rn(lx.l0, r[w + lx.i0]), __fmul_rn(lx.l1, r[w + lx.i1]));
-                z[c] = __fadd_rn(__fmul_rn(ly.l0, top), __fmul_rn(ly.l1, bot));
-                m = fmaxf(m, z[c]);
-            }
-            float se = 0.f, e[C];
-#pragma unroll
-            for (int c = 0; c < C; ++c) { e[c] = expf(z[c] - m); se += e[c]; }
-            float lse = m + logf(se);
-            float wgt = valid ? (class_weight ? class_weight[hd * C + li] : 1.f) : 0.f;
-            float zl = 0.f;
-#pragma unroll
-            for (int c = 0; c < C; ++c) zl = (c == li) ? z[c] : zl;
-            float lp = valid ? (lse - zl) * wgt : 0.f;
-            if (hd == 0) lsum0 += lp; else lsum1 += lp;
-            if (want_grad) {
-                float gs = wgt * gscale;
-#pragma unroll
-                for (int c = 0; c < C; ++c) G[(hd * C + c) * W + X] = (e[c] / se - ((c == li) ? 1.f : 0.f)) * gs;
-            }
-        }
-    }
-    __shared__ float red[2][4];
-    lsum0 = wave_sum(lsum0); lsum1 = wave_sum(lsum1);
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = lsum0; red[1][threadIdx.x >> 6] = lsum1; }
-    __syncthreads();
-    if (threadIdx.x < 2)
-        partial[((size_t)b * H + Y) * 2 + threadIdx.x] =
-            red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
-    if (!want_grad) return;
-    // horizontal contraction: T[hd][c][x] = sum_X G[hd][c][X] * Rx[X][x]
-    const float inv_scale = (w > 1) ? (float)(W - 1) / (float)(w - 1) : 0.f;
-    for (int o = threadIdx.x; o < 2 * C * w; o += 256) {
-        int x = o % w, hc = o / w;
-        int lo = (w > 1) ? max(0, (int)floorf((float)(x - 1) * inv_scale) - 1) : 0;
-        int hi = (w > 1) ? min(W - 1, (int)ceilf((float)(x + 1) * inv_scale) + 1) : W - 1;
-        float acc = 0.f;
-        for (int X = lo; X <= hi; ++X) {
-            const int i0 = lxi[X], i1 = i0 + ((i0 < w - 1) ? 1 : 0);
-            const float l1 = lxl[X], l0 = __fsub_rn(1.f, l1);
-            float wt = ((i0 == x) ? l0 : 0.f) + ((i1 == x) ? l1 : 0.f);
-            acc += wt * G[hc * W + X];
-        }
-        T[(((size_t)b * H + Y) * 2 * C + hc) * w + x] = acc;
-    }
-}
-
-template <int C>
-__global__ void __launch_bounds__(256) upce_col_kernel(const float* __restrict__ T, float* g1, float* g2, int b_n,
-                                                       int h, int w, int H) {
-    int i = blockIdx.x * 256 + threadIdx.x;           // over [hd][b][c][y][x]
-    int total = 2 * b_n * C * h * w;
-    if (i >= total) return;
-    int x = i % w, y = (i / w) % h, c = (i / (w * h)) % C, b = (i / (w * h * C)) % b_n, hd = i / (w * h * C * b_n);
-    const float inv_scale = (h > 1) ? (float)(H - 1) / (float)(h - 1) : 0.f;
-    int lo = (h > 1) ? max(0, (int)floorf((float)(y - 1) * inv_scale) - 1) : 0;
-    int hi = (h > 1) ? min(H - 1, (int)ceilf((float)(y + 1) * inv_scale) + 1) : H - 1;
-    float acc = 0.f;
-    for (int Y = lo; Y <= hi; ++Y) {
-        Lerp ly = lerp_ac(Y, h, H);
-        float wt = ((ly.i0 == y) ? ly.l0 : 0.f) + ((ly.i1 == y) ? ly.l1 : 0.f);
-        acc += wt * T[(((size_t)b * H + Y) * 2 * C + hd * C + c) * w + x];
-    }
-    float* g = hd ? g2 : g1;
-    g[(((size_t)b * C + c) * h + y) * w + x] = acc;
-}
-
-__global__ void __launch_bounds__(256) upce_loss_kernel(const float* __restrict__ partial, float* loss, int n,
-                                                        double inv_npix) {
-    // deterministic: fixed strided order, double accumulation
-    __shared__ double red[2][256];
-    double s0 = 0.0, s1 = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) { s0 += partial[2 * i]; s1 += partial[2 * i + 1]; }
-    red[0][threadIdx.x] = s0; red[1][threadIdx.x] = s1;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) { red[0][threadIdx.x] += red[0][threadIdx.x + o]; red[1][threadIdx.x] += red[1][threadIdx.x + o]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        float l0 = (float)(red[0][0] * inv_npix), l1 = (float)(red[1][0] * inv_npix);   // torch.mean per head
-        loss[0] = (l0 + l1) / 2.f;                                                       // loss / num (tools.py:252)
-    }
-}
-
-extern "C" size_t rgda_upsample_ce_workspace(int b, int c, int h, int w, int H, int W) {
-    (void)W;
-    return align256((size_t)b * H * 2 * 4) + (size_t)b * H * 2 * c * w * 4;
-}
-
-extern "C" int rgda_upsample_ce(const float* p1, const float* p2, const int64_t* label, const float* class_weight,
-                                float* loss, float* g1, float* g2, int b, int c, int h, int w, int H, int W,
-                                int ignore_label, void* ws, size_t ws_bytes, rgda_stream_t stream) {
-    if (!p1 || !p2 || !label || !loss || !ws || ((g1 == nullptr) != (g2 == nullptr))) return RGDA_ERR_ARG;
-    if (c != 6) return RGDA_ERR_UNSUPPORTED;
-    if (b <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return RGDA_ERR_ARG;
-    if (ws_bytes < rgda_upsample_ce_workspace(b, c, h, w, H, W)) return RGDA_ERR_WORKSPACE;
-    hipStream_t st = to_stream(stream);
-    float* partial = (float*)ws;
-    float* T = (float*)((char*)ws + align256((size_t)b * H * 2 * 4));
-    const int want = g1 != nullptr;
-    double npix = (double)b * H * W;
-    float gscale = (float)(0.5 / npix);
-    size_t lds = ((size_t)2 * 6 * 2 * w + (want ? (size_t)2 * 6 * W : 0) + (size_t)2 * W) * 4;
-    if (lds > 150 * 1024) return RGDA_ERR_UNSUPPORTED;
-    dim3 g(H, b);
-    upce_row_kernel<6><<<g, 256, lds, st>>>(p1, p2, label, class_weight, partial, T, h, w, H, W, ignore_label, gscale, want);
-    RGDA_CHECK_LAUNCH();
-    if (want) {
-        upce_col_kernel<6><<<cdiv((long long)2 * b * 6 * h * w, 256), 256, 0, st>>>(T, g1, g2, b, h, w, H);
-        RGDA_CHECK_LAUNCH();
-    }
-    upce_loss_kernel<<<1, 256, 0, st>>>(partial, loss, b * H, 1.0 / npix);
-    RGDA_CHECK_LAUNCH();
-    return RGDA_OK;
 }
 
 // --------------------------------------------------------------------------------------

@@ -1,10 +1,12 @@
-// loss_calc(multi=True) with the non-CE losses of the --ls / --lt flags (tools/train_ssl_reg.py:52-63,134-158):
-// OhemCrossEntropy, FocalLoss, GHMLoss, UPSLoss, UVEMLoss (regda/gast/balance.py:104-216,306-435).
+// loss_calc(multi=True) with the losses of the --ls / --lt flags (tools/train_ssl_reg.py:52-63,134-158):
+// CrossEntropy (rgda_upsample_ce; regda/utils/tools.py:240-254, regda/gast/balance.py:88-101) and OhemCrossEntropy,
+// FocalLoss, GHMLoss, UPSLoss, UVEMLoss (rgda_upsample_loss; balance.py:104-216,306-435).
 //
-// Every one of them is a per-pixel function of the bilinearly upsampled logits whose gradient depends on a statistic of
-// the whole batch (a count, a histogram, a k-th largest value).  The same row-per-workgroup upsample / log-softmax /
-// horizontal-contraction scheme as rgda_upsample_ce (label_kernels.hip) runs twice around a global stage:
-//   stat     (one workgroup per output row; not for focal): the per-pixel decision value -- OHEM: the (class-weighted)
+// Every one of them is a per-pixel function of the bilinearly upsampled logits.  One row-per-workgroup upsample /
+// log-softmax / horizontal-contraction pass computes the loss and d loss / d logits; except for CE and focal the gradient
+// also depends on a statistic of the whole batch (a count, a histogram, a k-th largest value), so the row pass runs twice
+// around a global stage.  CE is the stat-less kind: grad, col and reduce only, no header, no scratch.
+//   stat     (one workgroup per output row; not for CE / focal): the per-pixel decision value -- OHEM: the (class-weighted)
 //            CE, GHM: the bucket of |p_y - 1|, UPS / UVEM: the uncertainty weight of the soft label -- goes to scratch;
 //            counts and the GHM histograms go to integer atomics (order-independent, so deterministic)
 //   finalize (one workgroup): denominators, the GHM acc_sum EMA (head 1, then head 2), the OHEM branch
@@ -20,6 +22,8 @@
 namespace {
 
 constexpr int LC = 6;                    // class count (rgda_upsample_ce's restriction)
+constexpr int KIND_CE = 0;               // rgda_upsample_ce: a kind of this file only, not an rgda_loss_kind
+constexpr size_t MAX_ROW_LDS = 150 * 1024;   // dynamic LDS of the grad pass: the widest row served
 constexpr int GHM_BINS = 30;
 constexpr int SEL_PASSES = 6;
 constexpr int SEL_BINS = 2048;
@@ -53,6 +57,7 @@ struct LossParams {
     float m, t, cl, cr, inv_gamma;       // UPS / UVEM
     float gamma;                         // focal
     float mom, omm;                      // GHM
+    float gscale;                        // CE: 0.5 / #pixels (mean over all pixels, then over the two heads)
 };
 
 static size_t align256_(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -67,10 +72,12 @@ static size_t scratch_bytes(int kind, size_t n) {
     }
 }
 
-// the upsampled logits of one head at one output pixel, from the two low-res rows staged in LDS (upce_row_kernel's code)
+// the softmax of the upsampled logits z of one head at one output pixel, from the two low-res rows staged in LDS:
+// m = max z, e = exp(z - m), se = sum e (classes in order), zl = z of class li
 template <int C>
-__device__ __forceinline__ void up_logits(const float* rows, int w, int hd, const Lerp& ly, const Lerp& lx, float z[C],
-                                          float& m) {
+__device__ __forceinline__ void up_softmax(const float* rows, int w, int hd, const Lerp& ly, const Lerp& lx, int li,
+                                           float& m, float e[C], float& se, float& zl) {
+    float z[C];
     m = -INFINITY;
 #pragma unroll
     for (int c = 0; c < C; ++c) {
@@ -80,16 +87,37 @@ __device__ __forceinline__ void up_logits(const float* rows, int w, int hd, cons
         z[c] = __fadd_rn(__fmul_rn(ly.l0, top), __fmul_rn(ly.l1, bot));
         m = fmaxf(m, z[c]);
     }
+    se = 0.f;
+    zl = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) { e[c] = expf(z[c] - m); se += e[c]; zl = (c == li) ? z[c] : zl; }
 }
 
+// the vertical interpolation of output row Y: lerp_ac with its rounding spelled out.  FUSED: l1 = fma(scale, Y, -i0), one
+// rounding (the OHEM..UVEM kinds); else l1 = f32(scale * Y) - i0 (CE).  Which of the two the compiler made of lerp_ac
+// depended on where it placed the code; fixed here, every kind keeps its bits.
+template <bool FUSED>
+__device__ __forceinline__ Lerp row_lerp(int Y, int h, int H) {
+#pragma clang fp contract(off)
+    const float scale = (H > 1) ? __fdiv_rn((float)(h - 1), (float)(H - 1)) : 0.f;
+    const float src = scale * (float)Y;
+    Lerp r;
+    r.i0 = (int)src;
+    r.i1 = r.i0 + ((r.i0 < h - 1) ? 1 : 0);
+    r.l1 = FUSED ? __builtin_fmaf(scale, (float)Y, -(float)r.i0) : src - (float)r.i0;
+    r.l0 = 1.f - r.l1;
+    return r;
+}
+
+// rows[2 heads][C][2][w]: the low-res rows y0, y1 of both heads
 template <int C>
-__device__ __forceinline__ void stage_rows(float* rows, const float* p1, const float* p2, int b, const Lerp& ly, int h,
+__device__ __forceinline__ void stage_rows(float* rows, const float* p1, const float* p2, int b, int y0, int y1, int h,
                                            int w) {
     const int hw = h * w;
     for (int i = threadIdx.x; i < 2 * C * 2 * w; i += 256) {
         int x = i % w, r = (i / w) & 1, c = (i / (2 * w)) % C, hd = i / (2 * w * C);
         const float* p = hd ? p2 : p1;
-        rows[i] = p[((size_t)b * C + c) * hw + (r ? ly.i1 : ly.i0) * w + x];
+        rows[i] = p[((size_t)b * C + c) * hw + (r ? y1 : y0) * w + x];
     }
 }
 
@@ -133,13 +161,13 @@ __global__ void __launch_bounds__(256) loss_stat_kernel(const float* __restrict_
     __shared__ float s_edges[GHM_BINS + 1];
     const int b = blockIdx.y, Y = blockIdx.x;
     const size_t n = (size_t)gridDim.y * H * W;
-    const Lerp ly = lerp_ac(Y, h, H);
+    const Lerp ly = row_lerp<true>(Y, h, H);
     if (threadIdx.x < 3) s_cnt[threadIdx.x] = 0;
     if (threadIdx.x < 2) s_kept[threadIdx.x] = 0;
     if (threadIdx.x < 64) s_hist[threadIdx.x >> 5][threadIdx.x & 31] = 0;
     if (KIND == RGDA_LOSS_GHM && threadIdx.x <= GHM_BINS)
         s_edges[threadIdx.x] = threadIdx.x < GHM_BINS ? (float)((double)threadIdx.x / GHM_BINS) : (float)(1.0 + 1e-3);
-    if (KIND == RGDA_LOSS_OHEM || KIND == RGDA_LOSS_GHM) stage_rows<C>(rows, p1, p2, b, ly, h, w);
+    if (KIND == RGDA_LOSS_OHEM || KIND == RGDA_LOSS_GHM) stage_rows<C>(rows, p1, p2, b, ly.i0, ly.i1, h, w);
     __syncthreads();
     int valid_n = 0, lit_n = 0, u_n = 0, kept0 = 0, kept1 = 0;
     for (int X = threadIdx.x; X < W; X += 256) {
@@ -153,11 +181,8 @@ __global__ void __launch_bounds__(256) loss_stat_kernel(const float* __restrict_
             const Lerp lx = lerp_ac(X, w, W);
 #pragma unroll
             for (int hd = 0; hd < 2; ++hd) {
-                float z[C], m, se = 0.f;
-                up_logits<C>(rows, w, hd, ly, lx, z, m);
-                float e[C], zl = 0.f;
-#pragma unroll
-                for (int c = 0; c < C; ++c) { e[c] = expf(z[c] - m); se += e[c]; zl = (c == li) ? z[c] : zl; }
+                float m, e[C], se, zl;
+                up_softmax<C>(rows, w, hd, ly, lx, li, m, e, se, zl);
                 if constexpr (KIND == RGDA_LOSS_OHEM) {
                     // CE as log_softmax + nll: log(se) - (z_l - max) >= 0, ignored pixels 0; times the class weight
                     float ce = valid ? logf(se) - (zl - m) : 0.f;
@@ -326,6 +351,33 @@ __global__ void __launch_bounds__(256) ohem_select_kernel(LossHdr* hdr, const fl
 }
 
 // ---------------------------------------------------------------------------------------------------- grad pass
+// T[b][Y][hd][c][x] = sum_X G[hd][c][X] * Rx[X][x], the horizontal interpolation of every output column read back from
+// lxi / lxl: recomputing lerp_ac here (an IEEE divide each) cost 13 000 calls per workgroup -- more than the per-pixel
+// loss arithmetic
+template <int C>
+__device__ __forceinline__ void contract_row(const float* G, const int* lxi, const float* lxl, float* T, int b, int Y,
+                                             int w, int H, int W) {
+    const float inv_scale = (w > 1) ? (float)(W - 1) / (float)(w - 1) : 0.f;
+    for (int o = threadIdx.x; o < 2 * C * w; o += 256) {
+        int x = o % w, hc = o / w;
+        int lo = (w > 1) ? max(0, (int)floorf((float)(x - 1) * inv_scale) - 1) : 0;
+        int hi = (w > 1) ? min(W - 1, (int)ceilf((float)(x + 1) * inv_scale) + 1) : W - 1;
+        float acc = 0.f;
+        for (int X = lo; X <= hi; ++X) {
+            const int i0 = lxi[X], i1 = i0 + ((i0 < w - 1) ? 1 : 0);
+            const float l1 = lxl[X], l0 = __fsub_rn(1.f, l1);
+            float wt = ((i0 == x) ? l0 : 0.f) + ((i1 == x) ? l1 : 0.f);
+            acc += wt * G[hc * W + X];
+        }
+        T[(((size_t)b * H + Y) * 2 * C + hc) * w + x] = acc;
+    }
+}
+
+// dynamic LDS: rows[2 heads][C][2][w] | G[2][C][W] (with gradients) | lxi[W] | lxl[W]
+static size_t grad_lds(int w, int W, bool want) {
+    return ((size_t)2 * LC * 2 * w + (want ? (size_t)2 * LC * W : 0) + (size_t)2 * W) * 4;
+}
+
 template <int KIND>
 __global__ void __launch_bounds__(256) loss_grad_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
                                                         const int64_t* __restrict__ label,
@@ -342,11 +394,15 @@ __global__ void __launch_bounds__(256) loss_grad_kernel(const float* __restrict_
     __shared__ float s_acc[2][32];
     const int b = blockIdx.y, Y = blockIdx.x;
     const size_t n = (size_t)gridDim.y * H * W;
-    const Lerp ly = lerp_ac(Y, h, H);
+    const Lerp ly = row_lerp<KIND != KIND_CE>(Y, h, H);
     if (KIND == RGDA_LOSS_GHM && threadIdx.x < 64) s_acc[threadIdx.x >> 5][threadIdx.x & 31] = hdr->acc[threadIdx.x >> 5][threadIdx.x & 31];
-    stage_rows<C>(rows, p1, p2, b, ly, h, w);
-    const float inv_d0 = 1.f / hdr->denom[0], inv_d1 = 1.f / hdr->denom[1];
-    const unsigned long long cut0 = hdr->cut[0], cut1 = hdr->cut[1];
+    stage_rows<C>(rows, p1, p2, b, ly.i0, ly.i1, h, w);
+    float inv_d0 = 0.f, inv_d1 = 0.f;    // CE has no header
+    unsigned long long cut0 = 0ull, cut1 = 0ull;
+    if constexpr (KIND != KIND_CE) {
+        inv_d0 = 1.f / hdr->denom[0], inv_d1 = 1.f / hdr->denom[1];
+        cut0 = hdr->cut[0], cut1 = hdr->cut[1];
+    }
     __syncthreads();
     float lsum0 = 0.f, lsum1 = 0.f;
     for (int X = threadIdx.x; X < W; X += 256) {
@@ -361,40 +417,47 @@ __global__ void __launch_bounds__(256) loss_grad_kernel(const float* __restrict_
         if constexpr (KIND == RGDA_LOSS_UPS || KIND == RGDA_LOSS_UVEM) f = ((const float*)scratch)[pix];
 #pragma unroll
         for (int hd = 0; hd < 2; ++hd) {
-            float z[C], m, se = 0.f, e[C], zl = 0.f;
-            up_logits<C>(rows, w, hd, ly, lx, z, m);
-#pragma unroll
-            for (int c = 0; c < C; ++c) { e[c] = expf(z[c] - m); se += e[c]; zl = (c == li) ? z[c] : zl; }
-            const float ce = valid ? logf(se) - (zl - m) : 0.f;
-            const float cw = (valid && class_weight) ? class_weight[hd * C + li] : 1.f;
-            const float inv_d = hd ? inv_d1 : inv_d0;
-            float lp, dce;               // this pixel's term of the head's loss sum, d(head loss) / d ce
-            if constexpr (KIND == RGDA_LOSS_OHEM) {
-                const float v = ((const float*)scratch)[hd * n + pix];
-                const unsigned long long key = ((unsigned long long)__float_as_uint(v) << 32) | (unsigned)(n - 1 - pix);
-                const bool sel = key >= (hd ? cut1 : cut0);
-                lp = sel ? v : 0.f;
-                dce = sel ? cw * inv_d : 0.f;
-            } else if constexpr (KIND == RGDA_LOSS_FOCAL) {
-                // (1 - pt)^gamma * ce, pt = exp(-ce); d/d ce = (1 - pt)^gamma + gamma (1 - pt)^(gamma - 1) pt ce
-                const float pt = expf(-ce), q = 1.f - pt;
-                const float qg = prm.gamma == 2.f ? q * q : powf(q, prm.gamma);
-                const float qg1 = prm.gamma == 2.f ? q : powf(q, prm.gamma - 1.f);
-                lp = qg * ce;
-                dce = (qg + prm.gamma * qg1 * pt * ce) * inv_d;
-            } else if constexpr (KIND == RGDA_LOSS_GHM) {
-                const int ind = ((const uint8_t*)scratch)[hd * n + pix];
-                const float wg = (ind > 0 && ind <= GHM_BINS) ? 1.f / s_acc[hd][ind - 1] : 0.f;
-                lp = ce * wg;
-                dce = wg * inv_d;
-            } else {                     // UPS / UVEM: f = 0 where u > t (the gated CE), the uncertainty weight else
-                const float wt = f * cw;
-                lp = wt * ce;
-                dce = wt * inv_d;
+            float m, e[C], se, zl;
+            up_softmax<C>(rows, w, hd, ly, lx, li, m, e, se, zl);
+            float lp, gs;                // this pixel's term of the head's loss sum, d(call loss) / d ce
+            if constexpr (KIND == KIND_CE) {
+                // the CE arithmetic of its own: lse - z_l, not the generic log(se) - (z_l - m) below (other rounding)
+                const float lse = m + logf(se);
+                const float wgt = valid ? (class_weight ? class_weight[hd * C + li] : 1.f) : 0.f;
+                lp = valid ? (lse - zl) * wgt : 0.f;
+                gs = wgt * prm.gscale;
+            } else {
+                const float ce = valid ? logf(se) - (zl - m) : 0.f;
+                const float cw = (valid && class_weight) ? class_weight[hd * C + li] : 1.f;
+                const float inv_d = hd ? inv_d1 : inv_d0;
+                float dce;               // d(head loss) / d ce
+                if constexpr (KIND == RGDA_LOSS_OHEM) {
+                    const float v = ((const float*)scratch)[hd * n + pix];
+                    const unsigned long long key = ((unsigned long long)__float_as_uint(v) << 32) | (unsigned)(n - 1 - pix);
+                    const bool sel = key >= (hd ? cut1 : cut0);
+                    lp = sel ? v : 0.f;
+                    dce = sel ? cw * inv_d : 0.f;
+                } else if constexpr (KIND == RGDA_LOSS_FOCAL) {
+                    // (1 - pt)^gamma * ce, pt = exp(-ce); d/d ce = (1 - pt)^gamma + gamma (1 - pt)^(gamma - 1) pt ce
+                    const float pt = expf(-ce), q = 1.f - pt;
+                    const float qg = prm.gamma == 2.f ? q * q : powf(q, prm.gamma);
+                    const float qg1 = prm.gamma == 2.f ? q : powf(q, prm.gamma - 1.f);
+                    lp = qg * ce;
+                    dce = (qg + prm.gamma * qg1 * pt * ce) * inv_d;
+                } else if constexpr (KIND == RGDA_LOSS_GHM) {
+                    const int ind = ((const uint8_t*)scratch)[hd * n + pix];
+                    const float wg = (ind > 0 && ind <= GHM_BINS) ? 1.f / s_acc[hd][ind - 1] : 0.f;
+                    lp = ce * wg;
+                    dce = wg * inv_d;
+                } else {                 // UPS / UVEM: f = 0 where u > t (the gated CE), the uncertainty weight else
+                    const float wt = f * cw;
+                    lp = wt * ce;
+                    dce = wt * inv_d;
+                }
+                gs = valid ? dce * 0.5f : 0.f;                        // / num heads (tools.py:252)
             }
             if (hd == 0) lsum0 += lp; else lsum1 += lp;
             if (want_grad) {
-                const float gs = valid ? dce * 0.5f : 0.f;            // / num heads (tools.py:252)
 #pragma unroll
                 for (int c = 0; c < C; ++c) G[(hd * C + c) * W + X] = (e[c] / se - ((c == li) ? 1.f : 0.f)) * gs;
             }
@@ -408,21 +471,7 @@ __global__ void __launch_bounds__(256) loss_grad_kernel(const float* __restrict_
         partial[((size_t)b * H + Y) * 2 + threadIdx.x] =
             red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
     if (!want_grad) return;
-    // horizontal contraction: T[hd][c][x] = sum_X G[hd][c][X] * Rx[X][x]
-    const float inv_scale = (w > 1) ? (float)(W - 1) / (float)(w - 1) : 0.f;
-    for (int o = threadIdx.x; o < 2 * C * w; o += 256) {
-        int x = o % w, hc = o / w;
-        int lo = (w > 1) ? max(0, (int)floorf((float)(x - 1) * inv_scale) - 1) : 0;
-        int hi = (w > 1) ? min(W - 1, (int)ceilf((float)(x + 1) * inv_scale) + 1) : W - 1;
-        float acc = 0.f;
-        for (int X = lo; X <= hi; ++X) {
-            const int i0 = lxi[X], i1 = i0 + ((i0 < w - 1) ? 1 : 0);
-            const float l1 = lxl[X], l0 = __fsub_rn(1.f, l1);
-            float wt = ((i0 == x) ? l0 : 0.f) + ((i1 == x) ? l1 : 0.f);
-            acc += wt * G[hc * W + X];
-        }
-        T[(((size_t)b * H + Y) * 2 * C + hc) * w + x] = acc;
-    }
+    contract_row<C>(G, lxi, lxl, T, b, Y, w, H, W);
 }
 
 // vertical contraction T -> g[head][b][c][y][x]
@@ -446,9 +495,10 @@ __global__ void __launch_bounds__(256) loss_col_kernel(const float* __restrict__
     g[(((size_t)b * C + c) * h + y) * w + x] = acc;
 }
 
-// per head: the row partials in a fixed order in double, / the head's denominator; then the mean over the two heads
+// per head: the row partials in a fixed order in double, / the head's denominator -- CE (no header): * 1 / #pixels,
+// torch.mean; then the mean over the two heads
 __global__ void __launch_bounds__(256) loss_reduce_kernel(const float* __restrict__ partial, const LossHdr* hdr,
-                                                          float* loss, int n) {
+                                                          double inv_npix, float* loss, int n) {
     __shared__ double red[2][256];
     double s0 = 0.0, s1 = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) { s0 += partial[2 * i]; s1 += partial[2 * i + 1]; }
@@ -459,7 +509,12 @@ __global__ void __launch_bounds__(256) loss_reduce_kernel(const float* __restric
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        float l0 = (float)(red[0][0] / (double)hdr->denom[0]), l1 = (float)(red[1][0] / (double)hdr->denom[1]);
+        float l0, l1;
+        if (hdr) {
+            l0 = (float)(red[0][0] / (double)hdr->denom[0]), l1 = (float)(red[1][0] / (double)hdr->denom[1]);
+        } else {
+            l0 = (float)(red[0][0] * inv_npix), l1 = (float)(red[1][0] * inv_npix);
+        }
         loss[0] = (l0 + l1) / 2.f;
     }
 }
@@ -471,25 +526,97 @@ static int lds_attr(const void* kernel, size_t lds) {
                                                                                                             : RGDA_ERR_LAUNCH;
 }
 
+// one call's operands and the workspace pieces its entry point laid out (hdr and scratch: null for CE)
+struct LossCall {
+    const float *p1, *p2, *soft, *class_weight;
+    const int64_t* label;
+    float *acc_sum, *loss, *g1, *g2;
+    LossHdr* hdr;
+    void* scratch;
+    float *partial, *T;
+    int heads, b, h, w, H, W, ignore_label;
+    LossParams prm;
+};
+
+// the passes of one call, in stream order
 template <int KIND>
-static int launch_stat(dim3 g, size_t lds, hipStream_t st, const float* p1, const float* p2, const int64_t* label,
-                       const float* soft, const float* cw, LossHdr* hdr, void* scratch, int h, int w, int H, int W,
-                       int ig, const LossParams& prm) {
-    if (lds_attr((const void*)loss_stat_kernel<KIND>, lds) != RGDA_OK) return RGDA_ERR_LAUNCH;
-    loss_stat_kernel<KIND><<<g, 256, lds, st>>>(p1, p2, label, soft, cw, hdr, scratch, h, w, H, W, ig, prm);
+static int run_passes(const LossCall& a, rgda_stream_t stream) {
+    hipStream_t st = to_stream(stream);
+    const int want = a.g1 != nullptr;
+    const long long n = (long long)a.b * a.H * a.W;
+    const dim3 rows_grid(a.H, a.b);
+    if constexpr (KIND != KIND_CE) {
+        if constexpr (KIND != RGDA_LOSS_FOCAL) {
+            constexpr bool uv = KIND == RGDA_LOSS_UPS || KIND == RGDA_LOSS_UVEM;
+            const size_t zero = KIND == RGDA_LOSS_OHEM ? offsetof(LossHdr, cut) : offsetof(LossHdr, sel_arrived);
+            if (zero_bytes(a.hdr, zero, stream) != RGDA_OK) return RGDA_ERR_LAUNCH;
+            const size_t lds = uv ? 0 : (size_t)2 * LC * 2 * a.w * 4;
+            if (lds_attr((const void*)loss_stat_kernel<KIND>, lds) != RGDA_OK) return RGDA_ERR_LAUNCH;
+            loss_stat_kernel<KIND><<<rows_grid, 256, lds, st>>>(a.p1, a.p2, a.label, a.soft, a.class_weight, a.hdr,
+                                                                a.scratch, a.h, a.w, a.H, a.W, a.ignore_label, a.prm);
+            RGDA_CHECK_LAUNCH();
+        }
+        loss_finalize_kernel<<<1, 64, 0, st>>>(KIND, a.heads, a.hdr, a.acc_sum, a.prm, n);
+        RGDA_CHECK_LAUNCH();
+        if constexpr (KIND == RGDA_LOSS_OHEM) {
+            const int blocks = (int)min((long long)cdiv(n, 256 * 8), 512ll);
+            for (int pass = 0; pass < SEL_PASSES; ++pass) {
+                ohem_select_kernel<<<dim3(blocks, 2), 256, 0, st>>>(a.hdr, (const float*)a.scratch, n, pass);
+                RGDA_CHECK_LAUNCH();
+            }
+        }
+    }
+    const size_t lds = grad_lds(a.w, a.W, want);
+    if (lds_attr((const void*)loss_grad_kernel<KIND>, lds) != RGDA_OK) return RGDA_ERR_LAUNCH;
+    loss_grad_kernel<KIND><<<rows_grid, 256, lds, st>>>(a.p1, a.p2, a.label, a.class_weight, a.hdr, a.scratch,
+                                                        a.partial, a.T, a.h, a.w, a.H, a.W, a.ignore_label, a.prm, want);
+    RGDA_CHECK_LAUNCH();
+    if (want) {
+        loss_col_kernel<<<cdiv((long long)2 * a.b * LC * a.h * a.w, 256), 256, 0, st>>>(a.T, a.g1, a.g2, a.b, a.h, a.w,
+                                                                                       a.H);
+        RGDA_CHECK_LAUNCH();
+    }
+    loss_reduce_kernel<<<1, 256, 0, st>>>(a.partial, a.hdr, 1.0 / (double)n, a.loss, a.b * a.H);
+    RGDA_CHECK_LAUNCH();
     return RGDA_OK;
 }
 
-template <int KIND>
-static int launch_grad(dim3 g, size_t lds, hipStream_t st, const float* p1, const float* p2, const int64_t* label,
-                       const float* cw, const LossHdr* hdr, const void* scratch, float* partial, float* T, int h,
-                       int w, int H, int W, int ig, const LossParams& prm, int want) {
-    if (lds_attr((const void*)loss_grad_kernel<KIND>, lds) != RGDA_OK) return RGDA_ERR_LAUNCH;
-    loss_grad_kernel<KIND><<<g, 256, lds, st>>>(p1, p2, label, cw, hdr, scratch, partial, T, h, w, H, W, ig, prm, want);
-    return RGDA_OK;
+static int run_kind(int kind, const LossCall& a, rgda_stream_t stream) {
+    switch (kind) {
+        case KIND_CE: return run_passes<KIND_CE>(a, stream);
+        case RGDA_LOSS_OHEM: return run_passes<RGDA_LOSS_OHEM>(a, stream);
+        case RGDA_LOSS_FOCAL: return run_passes<RGDA_LOSS_FOCAL>(a, stream);
+        case RGDA_LOSS_GHM: return run_passes<RGDA_LOSS_GHM>(a, stream);
+        case RGDA_LOSS_UPS: return run_passes<RGDA_LOSS_UPS>(a, stream);
+        case RGDA_LOSS_UVEM: return run_passes<RGDA_LOSS_UVEM>(a, stream);
+        default: return RGDA_ERR_ARG;
+    }
 }
 
 }  // namespace
+
+extern "C" size_t rgda_upsample_ce_workspace(int b, int c, int h, int w, int H, int W) {
+    (void)W;
+    return align256_((size_t)b * H * 2 * 4) + (size_t)b * H * 2 * c * w * 4;
+}
+
+extern "C" int rgda_upsample_ce(const float* p1, const float* p2, const int64_t* label, const float* class_weight,
+                                float* loss, float* g1, float* g2, int b, int c, int h, int w, int H, int W,
+                                int ignore_label, void* ws, size_t ws_bytes, rgda_stream_t stream) {
+    if (!p1 || !p2 || !label || !loss || !ws || ((g1 == nullptr) != (g2 == nullptr))) return RGDA_ERR_ARG;
+    if (c != LC) return RGDA_ERR_UNSUPPORTED;
+    if (b <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return RGDA_ERR_ARG;
+    if (ws_bytes < rgda_upsample_ce_workspace(b, c, h, w, H, W)) return RGDA_ERR_WORKSPACE;
+    if (grad_lds(w, W, g1 != nullptr) > MAX_ROW_LDS) return RGDA_ERR_UNSUPPORTED;
+    LossCall a{};
+    a.p1 = p1, a.p2 = p2, a.label = label, a.class_weight = class_weight;
+    a.loss = loss, a.g1 = g1, a.g2 = g2;
+    a.partial = (float*)ws;
+    a.T = (float*)((char*)ws + align256_((size_t)b * H * 2 * 4));
+    a.heads = 2, a.b = b, a.h = h, a.w = w, a.H = H, a.W = W, a.ignore_label = ignore_label;
+    a.prm.gscale = (float)(0.5 / ((double)b * H * W));
+    return run_kind(KIND_CE, a, stream);
+}
 
 extern "C" size_t rgda_upsample_loss_workspace(int kind, int b, int c, int h, int w, int H, int W) {
     if (kind < RGDA_LOSS_OHEM || kind > RGDA_LOSS_UVEM || b <= 0 || c <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0)
@@ -509,8 +636,7 @@ extern "C" int rgda_upsample_loss(int kind, int heads, const float* p1, const fl
     if (!p1 || !p2 || !label || !loss || !ws || ((g1 == nullptr) != (g2 == nullptr))) return RGDA_ERR_ARG;
     if (b <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return RGDA_ERR_ARG;
     if ((long long)b * H * W >= (1ll << 31)) return RGDA_ERR_ARG;         // pixel index and OHEM key low word: 32 bits
-    const bool uv = kind == RGDA_LOSS_UPS || kind == RGDA_LOSS_UVEM;
-    if (uv && (!soft || !(t > 0.0))) return RGDA_ERR_ARG;
+    if ((kind == RGDA_LOSS_UPS || kind == RGDA_LOSS_UVEM) && (!soft || !(t > 0.0))) return RGDA_ERR_ARG;
     if (kind == RGDA_LOSS_UVEM && !(gamma > 0.0 && m >= 0.0)) return RGDA_ERR_ARG;
     if (kind == RGDA_LOSS_GHM && (!acc_sum || !(momentum >= 0.0 && momentum < 1.0))) return RGDA_ERR_ARG;
     if (kind == RGDA_LOSS_FOCAL && !(gamma >= 0.0)) return RGDA_ERR_ARG;
@@ -519,21 +645,20 @@ extern "C" int rgda_upsample_loss(int kind, int heads, const float* p1, const fl
     if ((kind == RGDA_LOSS_FOCAL || kind == RGDA_LOSS_GHM) && class_weight) return RGDA_ERR_ARG;
     if (c != LC) return RGDA_ERR_UNSUPPORTED;
     if (ws_bytes < rgda_upsample_loss_workspace(kind, b, c, h, w, H, W)) return RGDA_ERR_WORKSPACE;
-    const int want = g1 != nullptr;
-    size_t lds_stat = (size_t)2 * LC * 2 * w * 4;
-    size_t lds_grad = ((size_t)2 * LC * 2 * w + (want ? (size_t)2 * LC * W : 0) + (size_t)2 * W) * 4;
-    if (lds_grad > 150 * 1024) return RGDA_ERR_UNSUPPORTED;
-    hipStream_t st = to_stream(stream);
-    const long long n = (long long)b * H * W;
+    if (grad_lds(w, W, g1 != nullptr) > MAX_ROW_LDS) return RGDA_ERR_UNSUPPORTED;
+    LossCall a{};
+    a.p1 = p1, a.p2 = p2, a.soft = soft, a.class_weight = class_weight, a.label = label;
+    a.acc_sum = acc_sum, a.loss = loss, a.g1 = g1, a.g2 = g2;
     char* base = (char*)ws;
-    LossHdr* hdr = (LossHdr*)base;
+    a.hdr = (LossHdr*)base;
     base += align256_(sizeof(LossHdr));
-    float* partial = (float*)base;
+    a.partial = (float*)base;
     base += align256_((size_t)b * H * 2 * 4);
-    float* T = (float*)base;
+    a.T = (float*)base;
     base += align256_((size_t)b * H * 2 * c * w * 4);
-    void* scratch = base;
-    LossParams prm;
+    a.scratch = base;
+    a.heads = heads, a.b = b, a.h = h, a.w = w, a.H = H, a.W = W, a.ignore_label = ignore_label;
+    LossParams& prm = a.prm;
     prm.thresh = thresh;
     prm.m = (float)m;
     prm.t = (float)t;
@@ -543,45 +668,5 @@ extern "C" int rgda_upsample_loss(int kind, int heads, const float* p1, const fl
     prm.gamma = (float)gamma;
     prm.mom = (float)momentum;
     prm.omm = (float)(1.0 - momentum);
-    const dim3 rows_grid(H, b);
-    if (kind != RGDA_LOSS_FOCAL) {
-        const size_t zero = kind == RGDA_LOSS_OHEM ? offsetof(LossHdr, cut) : offsetof(LossHdr, sel_arrived);
-        if (zero_bytes(hdr, zero, stream) != RGDA_OK) return RGDA_ERR_LAUNCH;
-        const size_t lds = uv ? 0 : lds_stat;
-        int rc;
-        switch (kind) {
-            case RGDA_LOSS_OHEM: rc = launch_stat<RGDA_LOSS_OHEM>(rows_grid, lds, st, p1, p2, label, soft, class_weight, hdr, scratch, h, w, H, W, ignore_label, prm); break;
-            case RGDA_LOSS_GHM: rc = launch_stat<RGDA_LOSS_GHM>(rows_grid, lds, st, p1, p2, label, soft, class_weight, hdr, scratch, h, w, H, W, ignore_label, prm); break;
-            case RGDA_LOSS_UPS: rc = launch_stat<RGDA_LOSS_UPS>(rows_grid, lds, st, p1, p2, label, soft, class_weight, hdr, scratch, h, w, H, W, ignore_label, prm); break;
-            default: rc = launch_stat<RGDA_LOSS_UVEM>(rows_grid, lds, st, p1, p2, label, soft, class_weight, hdr, scratch, h, w, H, W, ignore_label, prm); break;
-        }
-        if (rc != RGDA_OK) return rc;
-        RGDA_CHECK_LAUNCH();
-    }
-    loss_finalize_kernel<<<1, 64, 0, st>>>(kind, heads, hdr, acc_sum, prm, n);
-    RGDA_CHECK_LAUNCH();
-    if (kind == RGDA_LOSS_OHEM) {
-        const int blocks = (int)min((long long)cdiv(n, 256 * 8), 512ll);
-        for (int pass = 0; pass < SEL_PASSES; ++pass) {
-            ohem_select_kernel<<<dim3(blocks, 2), 256, 0, st>>>(hdr, (const float*)scratch, n, pass);
-            RGDA_CHECK_LAUNCH();
-        }
-    }
-    int rc;
-    switch (kind) {
-        case RGDA_LOSS_OHEM: rc = launch_grad<RGDA_LOSS_OHEM>(rows_grid, lds_grad, st, p1, p2, label, class_weight, hdr, scratch, partial, T, h, w, H, W, ignore_label, prm, want); break;
-        case RGDA_LOSS_FOCAL: rc = launch_grad<RGDA_LOSS_FOCAL>(rows_grid, lds_grad, st, p1, p2, label, class_weight, hdr, scratch, partial, T, h, w, H, W, ignore_label, prm, want); break;
-        case RGDA_LOSS_GHM: rc = launch_grad<RGDA_LOSS_GHM>(rows_grid, lds_grad, st, p1, p2, label, class_weight, hdr, scratch, partial, T, h, w, H, W, ignore_label, prm, want); break;
-        case RGDA_LOSS_UPS: rc = launch_grad<RGDA_LOSS_UPS>(rows_grid, lds_grad, st, p1, p2, label, class_weight, hdr, scratch, partial, T, h, w, H, W, ignore_label, prm, want); break;
-        default: rc = launch_grad<RGDA_LOSS_UVEM>(rows_grid, lds_grad, st, p1, p2, label, class_weight, hdr, scratch, partial, T, h, w, H, W, ignore_label, prm, want); break;
-    }
-    if (rc != RGDA_OK) return rc;
-    RGDA_CHECK_LAUNCH();
-    if (want) {
-        loss_col_kernel<<<cdiv((long long)2 * b * LC * h * w, 256), 256, 0, st>>>(T, g1, g2, b, h, w, H);
-        RGDA_CHECK_LAUNCH();
-    }
-    loss_reduce_kernel<<<1, 256, 0, st>>>(partial, hdr, loss, b * H);
-    RGDA_CHECK_LAUNCH();
-    return RGDA_OK;
+    return run_kind(kind, a, stream);
 }

@@ -54,46 +54,6 @@ class ClassBalance(nn.Module):
                 ';\tselect probability: ' + ', '.join(f'{v:.3f}' for v in w))
 
 
-class _UpCE(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, p1, p2, label, ignore_label, class_weight):
-        loss, g1, g2 = ops.upsample_ce(p1, p2, label, ignore_label, class_weight, want_grad=True)
-        ctx.save_for_backward(g1, g2)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, go):
-        g1, g2 = ctx.saved_tensors
-        return g1 * go, g2 * go, None, None, None
-
-
-class CrossEntropy(nn.Module):
-    def __init__(self, ignore_label=-1, class_balancer=None):
-        super().__init__()
-        self.ignore_label = ignore_label
-        self.class_balancer = class_balancer
-
-    def _weights(self, labels, heads):
-        if self.class_balancer is None:
-            return None
-        # the balancer is EMA-updated once per head (balance.py:27-28 is called inside each loss_fn call)
-        ws = [self.class_balancer.next_class_weight(labels) for _ in range(heads)]
-        if heads == 1:
-            ws = ws * 2
-        return torch.stack(ws, 0)
-
-    def forward(self, preds, labels):
-        """preds [B,C,H,W] logits (any resolution), labels [B,H,W] -> mean over ALL pixels."""
-        cw = self._weights(labels, 1)
-        return _UpCE.apply(preds, preds, labels.long(), self.ignore_label, cw)
-
-    def forward_multi(self, preds, labels):
-        """loss_calc(multi=True) in one fused pass: mean over the two heads."""
-        assert len(preds) == 2
-        cw = self._weights(labels, 2)
-        return _UpCE.apply(preds[0], preds[1], labels.long(), self.ignore_label, cw)
-
-
 class _UpLoss(torch.autograd.Function):
     """Autograd wrapper of a fused loss launch: `launch(p1, p2)` -> (loss f32[1], g1, g2)."""
     @staticmethod
@@ -140,6 +100,27 @@ class _FusedLoss(nn.Module):
             return _UpLoss.apply(p1, p2, lambda a, _b: self.launch(a, a, labels, soft, cw, heads=1))
         return _UpLoss.apply(p1, p2, lambda a, b: self.launch(a, b, labels, soft, cw))
 
+    def forward(self, preds, labels):
+        return self._run(preds, labels, None)
+
+    def forward_multi(self, preds, labels):
+        assert len(preds) == 2
+        return self._run(tuple(preds), labels, None)
+
+
+class CrossEntropy(_FusedLoss):
+    """balance.py:88-101: the (class-weighted) CE, mean over ALL pixels (`rgda_upsample_ce`)."""
+    kind = 'ce'
+
+    def __init__(self, ignore_label=-1, class_balancer=None):
+        super().__init__()
+        self.ignore_label = ignore_label
+        self.class_balancer = class_balancer
+
+    def launch(self, p1, p2, labels, soft=None, class_weight=None, g1=None, g2=None, heads=2, want_grad=True):
+        # `soft` and `heads` unused: CE reads no soft label, and one prediction arrives as p1 == p2
+        return ops.upsample_ce(p1, p2, labels, self.ignore_label, class_weight, want_grad, g1, g2)
+
 
 class OhemCrossEntropy(_FusedLoss):
     """balance.py:104-133: the mean of the per-pixel (class-weighted) CE above -log(thresh), or of the n_min = #valid / 5
@@ -155,13 +136,6 @@ class OhemCrossEntropy(_FusedLoss):
     def _params(self):
         return dict(thresh=float(self.thresh))
 
-    def forward(self, preds, labels):
-        return self._run(preds, labels, None)
-
-    def forward_multi(self, preds, labels):
-        assert len(preds) == 2
-        return self._run(tuple(preds), labels, None)
-
 
 class FocalLoss(_FusedLoss):
     """balance.py:136-158 with alpha=None, reduction='mean' (what --lt focal constructs)."""
@@ -176,13 +150,6 @@ class FocalLoss(_FusedLoss):
 
     def _params(self):
         return dict(gamma=float(self.gamma))
-
-    def forward(self, preds, targets):
-        return self._run(preds, targets, None)
-
-    def forward_multi(self, preds, targets):
-        assert len(preds) == 2
-        return self._run(tuple(preds), targets, None)
 
 
 class GHMLoss(_FusedLoss):
@@ -203,13 +170,6 @@ class GHMLoss(_FusedLoss):
 
     def _params(self):
         return dict(acc_sum=self.acc_sum, momentum=float(self.momentum))
-
-    def forward(self, preds, targets):
-        return self._run(preds, targets, None)
-
-    def forward_multi(self, preds, targets):
-        assert len(preds) == 2
-        return self._run(tuple(preds), targets, None)
 
     def get_g_distribution(self):
         return self.acc_sum / (self.acc_sum.sum() + 1e-7)

@@ -315,14 +315,12 @@ def dropout_mask(out, p, seed):
     lib().call('rgda_dropout_mask', out.data_ptr(), out.numel(), float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, _stream())
 
 
-def upsample_ce(p1, p2, label, ignore_label=-1, class_weight=None, want_grad=True, g1=None, g2=None):
-    """-> (loss f32[1], g1, g2) ; g = d loss / d p (None if not want_grad; written into the given g1 / g2 when passed)."""
-    _need_cuda(p1, p2, label)
+def _upsample_operands(p1, p2, label, class_weight, want_grad, g1, g2):
+    """The operands of a fused upsample + loss call: f32 contiguous logits, the int64 label, the loss and gradient
+    outputs (g1 / g2 allocated unless given; None without gradients), the class weights."""
     p1, p2 = p1.contiguous().float(), p2.contiguous().float()
     label = label.contiguous()
     assert label.dtype == torch.int64
-    b, c, h, w = p1.shape
-    H, W = label.shape[-2:]
     loss = torch.empty(1, dtype=torch.float32, device=p1.device)
     if want_grad:
         g1 = torch.empty_like(p1) if g1 is None else g1
@@ -330,9 +328,18 @@ def upsample_ce(p1, p2, label, ignore_label=-1, class_weight=None, want_grad=Tru
         assert g1.is_contiguous() and g2.is_contiguous() and g1.shape == p1.shape and g2.shape == p2.shape
     else:
         g1 = g2 = None
+    cw = None if class_weight is None else class_weight.contiguous().float()
+    return p1, p2, label, cw, loss, g1, g2
+
+
+def upsample_ce(p1, p2, label, ignore_label=-1, class_weight=None, want_grad=True, g1=None, g2=None):
+    """-> (loss f32[1], g1, g2) ; g = d loss / d p (None if not want_grad; written into the given g1 / g2 when passed)."""
+    _need_cuda(p1, p2, label)
+    p1, p2, label, cw, loss, g1, g2 = _upsample_operands(p1, p2, label, class_weight, want_grad, g1, g2)
+    b, c, h, w = p1.shape
+    H, W = label.shape[-2:]
     L = lib()
     ws = _ws(L.size('rgda_upsample_ce_workspace', b, c, h, w, H, W), p1.device)
-    cw = None if class_weight is None else class_weight.contiguous().float()
     L.call('rgda_upsample_ce', p1.data_ptr(), p2.data_ptr(), label.data_ptr(), _p(cw), loss.data_ptr(), _p(g1),
            _p(g2), b, c, h, w, H, W, ignore_label, ws.data_ptr(), ws.numel(), _stream())
     return loss, g1, g2
@@ -348,9 +355,7 @@ def upsample_loss(kind, p1, p2, label, soft=None, class_weight=None, acc_sum=Non
     acc_sum: GHM's device state f32[30], updated in place; class_weight: None or f32[2, C] (OHEM, UPS, UVEM).
     heads=1: one loss_fn call on one prediction (p2 must be p1; the gradient is then g1 + g2)."""
     _need_cuda(p1, p2, label, soft, class_weight, acc_sum)
-    p1, p2 = p1.contiguous().float(), p2.contiguous().float()
-    label = label.contiguous()
-    assert label.dtype == torch.int64
+    p1, p2, label, cw, loss, g1, g2 = _upsample_operands(p1, p2, label, class_weight, want_grad, g1, g2)
     b, c, h, w = p1.shape
     H, W = label.shape[-2:]
     if soft is not None:
@@ -358,17 +363,9 @@ def upsample_loss(kind, p1, p2, label, soft=None, class_weight=None, acc_sum=Non
         assert soft.shape == (b, c, H, W)
     if acc_sum is not None:
         assert acc_sum.dtype == torch.float32 and acc_sum.is_contiguous() and acc_sum.numel() == 30
-    loss = torch.empty(1, dtype=torch.float32, device=p1.device)
-    if want_grad:
-        g1 = torch.empty_like(p1) if g1 is None else g1
-        g2 = torch.empty_like(p2) if g2 is None else g2
-        assert g1.is_contiguous() and g2.is_contiguous() and g1.shape == p1.shape and g2.shape == p2.shape
-    else:
-        g1 = g2 = None
     k = LOSS_KINDS[kind]
     L = lib()
     ws = _ws(L.size('rgda_upsample_loss_workspace', k, b, c, h, w, H, W), p1.device)
-    cw = None if class_weight is None else class_weight.contiguous().float()
     if heads == 1:
         p2 = p1
     L.call('rgda_upsample_loss', k, heads, p1.data_ptr(), p2.data_ptr(), label.data_ptr(), _p(soft), _p(cw), _p(acc_sum),

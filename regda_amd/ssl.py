@@ -58,12 +58,11 @@ class SSLStep:
         # --bcs / --bct of tools/train_ssl_reg.py:54-58,125-158: regda_amd.gast.balance.ClassBalance objects whose
         # frequency EMA re-weights the source / target cross-entropy per class (None = plain CE, the default)
         self.class_balancer_s, self.class_balancer_t = class_balancer_s, class_balancer_t
-        # --ls / --lt (+ --uvem-m/-t/-g) of tools/train_ssl_reg.py:52-63,134-158: None = the CrossEntropy path above;
-        # otherwise a regda_amd.gast.balance loss whose fused kernels (rgda_upsample_loss) the step launches directly
-        src, tgt = source_loss(loss_s, class_balancer_s, ignore_label), target_loss(
-            loss_t, class_balancer_t, uvem_m, uvem_t, uvem_g, class_num, ignore_label, device=dev)
-        self.loss_fn_s = None if loss_s == 'CrossEntropy' else src
-        self.loss_fn_t = None if loss_t == 'none' else tgt
+        # --ls / --lt (+ --uvem-m/-t/-g) of tools/train_ssl_reg.py:52-63,134-158: regda_amd.gast.balance losses whose
+        # fused kernels (rgda_upsample_ce / rgda_upsample_loss) the step launches directly
+        self.loss_fn_s = source_loss(loss_s, class_balancer_s, ignore_label)
+        self.loss_fn_t = target_loss(loss_t, class_balancer_t, uvem_m, uvem_t, uvem_g, class_num, ignore_label,
+                                     device=dev)
         self._graph = None
         self._plan = None
         self._proto_ready = None
@@ -217,23 +216,16 @@ class SSLStep:
 
     def _host_balancers(self):
         """Whether a ClassBalance takes part in the step's losses (ohem, focal and ghm targets take none)."""
-        used_t = self.class_balancer_t if self.loss_fn_t is None else self.loss_fn_t.class_balancer
-        return self.class_balancer_s is not None or used_t is not None
+        return self.loss_fn_s.class_balancer is not None or self.loss_fn_t.class_balancer is not None
 
     def _source_loss(self, s1, s2, label_s, g1, g2):
         """loss_calc(source, loss_fn_s): its value; d loss / d logits written into g1, g2."""
         f = self.loss_fn_s
-        if f is None:
-            return ops.upsample_ce(s1, s2, label_s, self.ig, self._class_weights(self.class_balancer_s, label_s), True,
-                                   g1, g2)[0]
         return f.launch(s1, s2, label_s, class_weight=self._class_weights(f.class_balancer, label_s), g1=g1, g2=g2)[0]
 
     def _target_loss(self, t1, t2, hard, soft, g1, g2):
         """loss_calc / loss_calc_uvem(target, loss_fn_t) on the pseudo labels (ups / uvem also read the refined soft label)."""
         f = self.loss_fn_t
-        if f is None:
-            return ops.upsample_ce(t1, t2, hard, self.ig, self._class_weights(self.class_balancer_t, hard), True,
-                                   g1, g2)[0]
         return f.launch(t1, t2, hard, soft=soft if f.kind in ('ups', 'uvem') else None,
                         class_weight=self._class_weights(f.class_balancer, hard), g1=g1, g2=g2)[0]
 

@@ -376,10 +376,12 @@ def _captured_replay_matches_eager(model, protos, ones, g, loss_t):
 
 def test_source_and_align_steps_with_ohem_source_loss(monkeypatch):
     """SourceStep and AlignStep with loss_s='OhemCrossEntropy' against the CPU steps (source loss restated); the
-    default SourceStep (loss_s='CrossEntropy') against the CPU step with the oracle's CE."""
+    default SourceStep (loss_s='CrossEntropy') against the CPU step with the oracle's CE; AlignStep with
+    loss_s='CrossEntropy' and a source balancer (--bcs) against the CPU step with the oracle's class-weighted CE."""
     from oracle import model as omodel
     from oracle.step import CpuAlignStep
     from regda_amd.align import AlignStep
+    from regda_amd.gast.balance import ClassBalance
     from regda_amd.source import SourceStep
     rt, sd, b, protos, ones, model = _shallow()
     g = {k: v.cuda() for k, v in b.items()}
@@ -400,27 +402,42 @@ def test_source_and_align_steps_with_ohem_source_loss(monkeypatch):
         if kind == 'ohem':
             ref_ohem = float(ref)
         else:
-            assert abs(float(ref) - ref_ohem) > 0.05 * ref_ohem      # the two losses do differ here
+            ref_ce = float(ref)
+            assert abs(ref_ce - ref_ohem) > 0.05 * ref_ohem          # the two losses do differ here
     # stage 2
-    _patch_oracle(monkeypatch, 'ohem', None)
-    ref = CpuAlignStep(sd, protos, resnet_type=rt, lr=1e-3).step(b['images_s'], b['label_s'], b['images_t'], b['regs_t'],
-                                                                  (ones, ones), (ones, ones))
-    monkeypatch.undo()
-    st = AlignStep(model(), protos, loss_s='OhemCrossEntropy')
-    ls, la, gn = st.step(g['images_s'], g['label_s'], g['images_t'], g['regs_t'], 1e-3)
-    assert ls.item() == pytest.approx(ref['loss_seg'], rel=STEP_LOSS_REL)
-    assert gn.sqrt().item() == pytest.approx(ref['grad_norm'], rel=STEP_GN_REL)
+    f0s = torch.tensor([0.05, 0.05, 0.1, 0.1, 0.2, 0.5])
+    for loss_s, balanced in (('OhemCrossEntropy', False), ('CrossEntropy', True)):
+        bal = bal_ref = None
+        if balanced:
+            bal_ref, bal = olp.ClassBalanceState(6, -1, 0.5, 0.5), ClassBalance(6, -1, 0.5, 0.5)
+            bal_ref.freq, bal.freq = f0s.clone(), f0s.cuda()
+        else:
+            _patch_oracle(monkeypatch, 'ohem', None)
+        ref = CpuAlignStep(sd, protos, resnet_type=rt, lr=1e-3, balancer_s=bal_ref).step(
+            b['images_s'], b['label_s'], b['images_t'], b['regs_t'], (ones, ones), (ones, ones))
+        monkeypatch.undo()
+        st = AlignStep(model(), protos, loss_s=loss_s, class_balancer_s=bal)
+        ls, la, gn = st.step(g['images_s'], g['label_s'], g['images_t'], g['regs_t'], 1e-3)
+        assert ls.item() == pytest.approx(ref['loss_seg'], rel=STEP_LOSS_REL), loss_s
+        assert gn.sqrt().item() == pytest.approx(ref['grad_norm'], rel=STEP_GN_REL), loss_s
+        if balanced:
+            assert abs(ref['loss_seg'] - ref_ce) > 0.05 * ref_ce         # the class weights do change the loss
+            np.testing.assert_allclose(bal.freq.cpu().numpy(), bal_ref.freq.numpy(), rtol=1e-6)
 
 
-def test_large_rows_raise_the_lds_limit():
-    """W = 2048: the gradient pass needs ~117 KB of dynamic LDS, above the 64 KB default (hipFuncSetAttribute)."""
+@pytest.mark.parametrize('kind', ['focal', 'ce'])
+def test_large_rows_raise_the_lds_limit(kind):
+    """W = 2048: the gradient pass needs ~117 KB of dynamic LDS, above the 64 KB default (hipFuncSetAttribute); CE
+    (CrossEntropy, rgda_upsample_ce) and focal (rgda_upsample_loss) run the same gradient pass."""
+    from regda_amd.gast.balance import CrossEntropy
     g = torch.Generator().manual_seed(8)
     p1, p2 = torch.randn(1, 6, 32, 32, generator=g) * 2, torch.randn(1, 6, 32, 32, generator=g) * 2
     lab = torch.randint(-1, 6, (1, 128, 2048), generator=g)
-    fn = loss_ref.make_loss('focal')
+    fn = loss_ref.make_loss(kind)
     r1, r2 = p1.clone().requires_grad_(True), p2.clone().requires_grad_(True)
     ref = loss_ref.loss_calc([r1, r2], lab, fn)
     ref.backward()
-    loss, g1, g2 = run_fused(fused('focal'), 'focal', p1, p2, lab, None)
+    ours = CrossEntropy(ignore_label=-1) if kind == 'ce' else fused(kind)
+    loss, g1, g2 = run_fused(ours, kind, p1, p2, lab, None)
     assert float(loss) == pytest.approx(float(ref), rel=1e-5)
     np.testing.assert_allclose(g1.numpy(), r1.grad.numpy(), rtol=1e-3, atol=1e-4 * float(r1.grad.abs().max()))
