@@ -604,6 +604,33 @@ int rgda_window_normalise(float* full, const float* count, int N, int C, int Hf,
 int rgda_resize_bilinear_ac(const float* src, float* dst, int N, int C, int h, int w, int H, int W,
                             rgda_stream_t stream);
 
+/* ------------------------------------------------------------- training augmentation of raw tiles */
+
+/* BaseData.__getitem__ + the training transforms (regda/datasets/basedata.py:68-98, regda/aug/augmentation.py; the
+ * albumentations pipeline of configs/ToPotsdam.py:43-56) for a batch of N raw tiles of one domain, one launch.
+ *   img       uint8 [N][Hi][Wi][3] (HWC, as imread returns it; 4-byte aligned)   -> img_out   f32 [N][3][Ho][Wo]
+ *   label     uint8 [N][Hi][Wi] or NULL                                            -> label_out int64 [N][Ho][Wo]
+ *   soft      f32 [N][C][Hi][Wi] or NULL (1 <= C <= 8)                             -> soft_out  f32 [N][C][Ho][Wo]
+ *   regs      int32 [N][Hi][Wi] or NULL                                            -> regs_out  int64 [N][1][Ho][Wo]
+ *   lut       f32 [3][256]: img_out = lut[channel][byte] -- the pipeline's normalisation (and clamp) tabulated on the host;
+ *   label_lut int32 [256]:   label_out = label_lut[byte] -- the dataset offset and `mask[mask >= n_classes] = ignore`;
+ *   params    int32 [N][4] (y0, x0, d, 0) per sample; lut, label_lut, params: DEVICE memory.
+ * Every output of sample n is gathered through one index map: output pixel (i, j) reads input pixel (y0 + y, x0 + x)
+ * with (u, v) = t ? (j, i) : (i, j), y = fr ? Ho-1-u : u, x = fc ? Wo-1-v : v, where the dihedral element
+ * d = t | fr << 1 | fc << 2 (t: transpose, fr: flip rows, fc: flip columns; t requires Ho == Wo).  With
+ * H = hflip (d 4), V = vflip (d 2) and R = torch.rot90(x, 1, [1, 2]) = np.rot90 on HW (R[i][j] = X[j][S-1-i], d 5):
+ *   reference (mag) pipeline: crop, then H, V, R, each drawn:  d = R ? (1 | V << 1 | !H << 2) : (V << 1 | H << 2)
+ *   albumentations pipeline:  crop, then at most one of H (4), V (2), R^k (k = 1: 5, 2: 6, 3: 3).
+ * The kernel does no floating-point arithmetic and no atomics.  Errors before any launch: null img / params / lut /
+ * img_out, N < 1, Ho > Hi or Wo > Wi, a label without label_lut / label_out, soft with C < 1 or without soft_out, regs
+ * without regs_out, a misaligned input (RGDA_ERR_ARG); C > 8 (RGDA_ERR_UNSUPPORTED).  params live on the device, so a
+ * sample whose crop leaves the input, whose d is outside 0..7 or odd with Ho != Wo is checked there: its outputs are
+ * not written and *flag (optional, device int) is set to 1. */
+int rgda_augment_tiles(const uint8_t* img, const uint8_t* label, const float* soft, const int32_t* regs,
+                       const int32_t* params, int N, int Hi, int Wi, int C, int Ho, int Wo, const float* lut,
+                       const int32_t* label_lut, float* img_out, int64_t* label_out, float* soft_out, int64_t* regs_out,
+                       int* flag, rgda_stream_t stream);
+
 /* ------------------------------------------------------------- evaluation path */
 
 /* cls.argmax(dim=1) of the (N,C,H,W) probabilities (regda/utils/eval.py:43): int64 (N,H,W), first maximum wins. */

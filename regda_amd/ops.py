@@ -862,6 +862,65 @@ def pad_rows(src, top, bottom):
     return dst
 
 
+# ----------------------------------------------------------------------------- training augmentation of raw tiles
+def check_augment_params(params, hi, wi, ho, wo):
+    """Host-side check of a CPU int32 [N][4] (y0, x0, d, 0) table: the crop lies inside the hi x wi input, d in 0..7,
+    and a transposing (odd) d only for a square output.  Raises ValueError."""
+    p = params.numpy()
+    if p.ndim != 2 or p.shape[1] != 4:
+        raise ValueError('augment params must be [N][4], got %s' % (tuple(p.shape),))
+    y0, x0, d = p[:, 0], p[:, 1], p[:, 2]
+    if (y0 < 0).any() or (x0 < 0).any() or (y0 > hi - ho).any() or (x0 > wi - wo).any():
+        raise ValueError('augment crop outside the %d x %d input' % (hi, wi))
+    if (d < 0).any() or (d > 7).any() or ((d & 1).astype(bool) & (ho != wo)).any():
+        raise ValueError('augment element d outside 0..7, or odd d with a non-square %d x %d output' % (ho, wo))
+
+
+def augment_tiles(img, params, lut, size, label=None, label_lut=None, soft=None, regs=None, out=None, flag=None):
+    """rgda_augment_tiles: crop + dihedral element + normalisation / label tables of N raw tiles, one launch.
+    img uint8 [N][Hi][Wi][3]; label uint8 [N][Hi][Wi]; soft f32 [N][C][Hi][Wi]; regs int32 [N][Hi][Wi] (each optional but
+    img, on the GPU); params int32 [N][4] (y0, x0, d, 0): a CPU tensor is checked (check_augment_params) and copied on
+    the current stream, a device tensor is used as it is; lut f32 [3][256], label_lut int32 [256] device tables;
+    size = (Ho, Wo).  out: {'image', 'label', 'soft', 'regs'} device tensors to write into (allocated where missing).
+    flag: optional device int32 tensor, set to 1 by a sample whose device-side params are invalid.
+    -> {'image': f32 [N][3][Ho][Wo], 'label': int64 [N][Ho][Wo], 'soft': f32 [N][C][Ho][Wo], 'regs': int64 [N][1][Ho][Wo]}
+    (None where the input is None)."""
+    _need_cuda(img, label, soft, regs, lut, label_lut)
+    n, hi, wi, three = img.shape
+    ho, wo = size
+    if three != 3 or img.dtype != torch.uint8:
+        raise ValueError('augment_tiles: img must be uint8 [N][H][W][3]')
+    want = dict(label=(label, torch.uint8, (n, hi, wi)), regs=(regs, torch.int32, (n, hi, wi)),
+                soft=(soft, torch.float32, (n, soft.shape[1] if soft is not None else 0, hi, wi)))
+    for k, (t, dt, shape) in want.items():
+        if t is not None and (t.dtype != dt or tuple(t.shape) != shape):
+            raise ValueError('augment_tiles: %s must be %s %s, got %s %s' % (k, dt, shape, t.dtype, tuple(t.shape)))
+    if label is not None and label_lut is None:
+        raise ValueError('augment_tiles: a label needs label_lut')
+    if not params.is_cuda:
+        check_augment_params(params, hi, wi, ho, wo)
+        params = params.to(img.device, torch.int32, non_blocking=True)
+    assert params.dtype == torch.int32 and tuple(params.shape) == (n, 4)
+    c = soft.shape[1] if soft is not None else 0
+    shapes = dict(image=((n, 3, ho, wo), torch.float32, img), label=((n, ho, wo), torch.int64, label),
+                  soft=((n, c, ho, wo), torch.float32, soft), regs=((n, 1, ho, wo), torch.int64, regs))
+    res = {}
+    for k, (shape, dt, src) in shapes.items():
+        t = None if out is None else out.get(k)
+        if src is None:
+            res[k] = None
+            continue
+        if t is None:
+            t = torch.empty(shape, dtype=dt, device=img.device)
+        assert tuple(t.shape) == shape and t.dtype == dt and t.is_contiguous(), k
+        res[k] = t
+    ptr = lambda t: None if t is None else t.contiguous().data_ptr()
+    lib().call('rgda_augment_tiles', ptr(img), ptr(label), ptr(soft), ptr(regs), ptr(params), n, hi, wi, c, ho, wo,
+               ptr(lut), ptr(label_lut), ptr(res['image']), ptr(res['label']), ptr(res['soft']), ptr(res['regs']),
+               ptr(flag), _stream())
+    return res
+
+
 # ----------------------------------------------------------------------------- evaluation path
 def argmax_nchw(probs):
     n, c, h, w = probs.shape

@@ -4,29 +4,63 @@ The reference moves every tensor of a batch with `.cuda()` inside the iteration 
 images_s, label_s, images_t, label_t_soft, regs_t), a synchronous pageable copy of ~84 MB per 8 + 8 batch of 512 x 512
 tiles with int64 labels / region maps.  Here the loader's batches sit in PINNED host memory and are copied by a
 dedicated HIP stream into one of `depth` device-resident slots while the previous step computes; the consumer only
-waits for an event.  The tensors keep the reference's dtypes and shapes (the int64 API is the boundary)."""
+waits for an event.  The tensors keep the reference's dtypes and shapes (the int64 API is the boundary).
+
+With `augment`, the host batches are RAW tiles (uint8 HWC images, uint8 labels, f32 soft labels, int32 region maps): they
+are copied into device staging buffers on the copy stream and the training augmentation (regda_amd.aug) writes the
+step's tensors from them on the same stream, one launch per domain, with each sample's parameters drawn on the host
+when the batch is staged, in batch order."""
 import torch
+
+from .. import ops
 
 
 class DevicePrefetcher:
-    def __init__(self, host_batches, device=None, depth=2, into=None):
+    def __init__(self, host_batches, device=None, depth=2, into=None, augment=None):
         """host_batches: list of {name: CPU tensor or None} with identical shapes; cycled through in order.
         into: {name: device tensor} -- stage every batch straight into THESE tensors (one slot: the static input
         buffers of a recorded step, SSLStep.static_inputs()); `release()` must then be given the event after which the
-        step no longer reads its inputs (SSLStep.inputs_consumed)."""
+        step no longer reads its inputs (SSLStep.inputs_consumed).
+        augment: list of (pipeline, roles), one per domain: a regda_amd.aug pipeline and {role: name} with the roles
+        'image' (uint8 [N][H][W][3]), 'mask' (uint8 [N][H][W] class labels), 'soft' (f32 [N][C][H][W]) and 'mask_sup'
+        (int32 [N][H][W] region ids); the named host tensors are raw and their slot tensors hold the pipeline's outputs
+        (f32 [N][3][Ho][Wo], int64 [N][Ho][Wo], f32 [N][C][Ho][Wo], int64 [N][1][Ho][Wo]).  Names in no role are
+        copied as they are."""
         assert host_batches and (into is not None or depth >= 2)
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self.host = [{k: (None if v is None else v.contiguous().pin_memory()) for k, v in b.items()} for b in host_batches]
+        self.augment = []
+        shapes = {k: (None if v is None else (tuple(v.shape), v.dtype)) for k, v in self.host[0].items()}
+        for pipe, roles in (augment or ()):
+            roles = {r: k for r, k in roles.items() if self.host[0].get(k) is not None}
+            img = self.host[0][roles['image']]
+            n, h, w, _ = img.shape
+            ho, wo = pipe.out_size(h, w)
+            out = dict(image=((n, 3, ho, wo), torch.float32), mask=((n, ho, wo), torch.int64),
+                       mask_sup=((n, 1, ho, wo), torch.int64))
+            if 'soft' in roles:
+                out['soft'] = ((n, self.host[0][roles['soft']].shape[1], ho, wo), torch.float32)
+            for r, k in roles.items():
+                shapes[k] = out[r]
+            # device staging of the raw batch (one set: written and read in copy-stream order), the device tables and
+            # the per-batch parameter table
+            raw = {r: torch.empty_like(self.host[0][k], device=self.device) for r, k in roles.items()}
+            tables = pipe.device_tables(self.device)
+            prm = torch.empty(n, 4, dtype=torch.int32, device=self.device)
+            self.augment.append((pipe, roles, raw, tables, prm))
         if into is not None:
             depth = 1
             self.slots = [{k: into.get(k) for k in self.host[0]}]
-            for k, v in self.host[0].items():
-                assert (v is None) == (self.slots[0][k] is None) and (v is None or (v.shape == self.slots[0][k].shape and v.dtype == self.slots[0][k].dtype)), k
+            for k, v in shapes.items():
+                t = self.slots[0][k]
+                assert (v is None) == (t is None) and (v is None or (tuple(t.shape) == v[0] and t.dtype == v[1])), k
         else:
-            self.slots = [{k: (None if v is None else torch.empty_like(v, device=self.device)) for k, v in self.host[0].items()}
-                          for _ in range(depth)]
+            self.slots = [{k: (None if v is None else torch.empty(v[0], dtype=v[1], device=self.device))
+                           for k, v in shapes.items()} for _ in range(depth)]
         self.single = into is not None
         self.copy_stream = torch.cuda.Stream(device=self.device)
+        if self.augment:
+            self.copy_stream.wait_stream(torch.cuda.current_stream())     # the staging buffers and tables made above
         self.copied = [None] * depth        # event: the slot holds its batch
         self.consumed = [None] * depth      # event: the step that read the slot has been enqueued and finished with it
         self.i = 0                          # index of the next batch handed out
@@ -39,13 +73,42 @@ class DevicePrefetcher:
 
     def _stage(self, i):
         slot = i % len(self.slots)
+        src = self.host[i % len(self.host)]
+        if self.augment:
+            self._stage_augmented(slot, src)
+            return
         if self.consumed[slot] is not None:
             self.copy_stream.wait_event(self.consumed[slot])
-        src = self.host[i % len(self.host)]
         with torch.cuda.stream(self.copy_stream):
             for k, dst in self.slots[slot].items():
                 if dst is not None:
                     dst.copy_(src[k], non_blocking=True)
+            self.copied[slot] = self.copy_stream.record_event()
+
+    def _stage_augmented(self, slot, src):
+        # the raw bytes and the drawn parameters go to the staging buffers first (nothing the step reads); only the
+        # writes into the slot wait for the step that reads it
+        with ops.use_stream(self.copy_stream):
+            done = set()
+            for pipe, roles, raw, _, prm in self.augment:
+                for r, k in roles.items():
+                    raw[r].copy_(src[k], non_blocking=True)
+                    done.add(k)
+                n, h, w, _ = raw['image'].shape
+                p = pipe.params(n, h, w)
+                ops.check_augment_params(p, h, w, *pipe.out_size(h, w))
+                prm.copy_(p.pin_memory(), non_blocking=True)
+            if self.consumed[slot] is not None:
+                self.copy_stream.wait_event(self.consumed[slot])
+            dst = self.slots[slot]
+            for k, t in dst.items():
+                if t is not None and k not in done:
+                    t.copy_(src[k], non_blocking=True)
+            for pipe, roles, raw, (lut, llut), prm in self.augment:
+                out = {'image': dst[roles['image']], 'label': dst.get(roles.get('mask')), 'soft': dst.get(roles.get('soft')),
+                       'regs': dst.get(roles.get('mask_sup'))}
+                ops.augment_tiles(raw['image'], prm, lut, tuple(out['image'].shape[2:]), label=raw.get('mask'),
+                                  label_lut=llut, soft=raw.get('soft'), regs=raw.get('mask_sup'), out=out)
             self.copied[slot] = self.copy_stream.record_event()
 
     def next(self):
