@@ -17,11 +17,20 @@ def _is_albu(transforms):
     return False
 
 
+def label_config(cfg):
+    """The label table of a task config as from_config's keyword arguments: dict(offset, num_class, ignore_label) from
+    the config's LABEL_OFFSET / NUM_CLASSES / IGNORE_LABEL, IsprsDA's (0, 6, -1) where a name is absent (the ISPRS
+    modules do not set them).  st.regda.2rural / 2urban: (-1, 7, -1)."""
+    return dict(offset=getattr(cfg, 'LABEL_OFFSET', 0), num_class=getattr(cfg, 'NUM_CLASSES', 6),
+                ignore_label=getattr(cfg, 'IGNORE_LABEL', -1))
+
+
 def from_config(data_config, rng=None, generator=None, offset=0, num_class=6, ignore_label=-1):
     """The pipeline of a loader config of configs/ (its `transforms` list): `st.regda.*` TARGET_DATA_CONFIG -> the
     reference (mag) pipeline with clamp; `To*` SOURCE_DATA_CONFIG -> the albumentations pipeline; EVAL / PSEUDO /
     TEST_DATA_CONFIG -> normalisation only.  rng / generator: see the two modules; offset / num_class / ignore_label:
-    the label table (IsprsDA: 0, 6, -1).  Unknown transform names raise ValueError."""
+    the label table (IsprsDA: 0, 6, -1; LoveDA: -1, 7, -1 -- `**label_config(cfg)` passes a config's).  Unknown
+    transform names raise ValueError."""
     transforms = data_config['transforms']
     lab = dict(offset=offset, num_class=num_class, ignore_label=ignore_label)
     if _is_albu(transforms):

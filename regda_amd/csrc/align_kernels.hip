@@ -172,7 +172,7 @@ extern "C" int rgda_pcl_loss(const float* feat, const int64_t* labels, const flo
                              int lddf, int accumulate, int b, int K, int C, int h, int w, int ignore_label,
                              float temperature, float weight, void* ws, size_t ws_bytes, rgda_stream_t stream) {
     if (!feat || !labels || !protos || !loss || !ws) return RGDA_ERR_ARG;
-    if (C != 6) return RGDA_ERR_UNSUPPORTED;       // ISPRS: 6 classes (regda/datasets/isprsda.py:18-26)
+    if (C != 6 && C != 7) return RGDA_ERR_UNSUPPORTED;   // ISPRS: 6 classes (regda/datasets/isprsda.py:18-26), LoveDA: 7
     if (b <= 0 || K < 8 || K > 4096 || (K & 7) || h <= 0 || w <= 0 || !(temperature > 0.f)) return RGDA_ERR_ARG;
     if (dfeat && ((lddf & 7) || lddf < K)) return RGDA_ERR_ARG;
     if (ws_bytes < rgda_pcl_loss_workspace(C, K)) return RGDA_ERR_WORKSPACE;
@@ -190,12 +190,17 @@ extern "C" int rgda_pcl_loss(const float* feat, const int64_t* labels, const flo
     RGDA_CHECK_LAUNCH();
     constexpr int PX = 32, SL = 16;
     const size_t lds = ((size_t)C * K + SL * PX * (C + 1) + PX * (C + 1)) * 4 + (size_t)PX * (128 + 8) * 2;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void*)pcl_kernel<6, PX, SL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    // (the attribute names the instantiation that is launched)
+    const void* kern = C == 6 ? (const void*)pcl_kernel<6, PX, SL> : (const void*)pcl_kernel<7, PX, SL>;
+    if (lds > 64 * 1024 && hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return RGDA_ERR_LAUNCH;
     dim3 grid(cdiv(h * w, PX), b);
-    pcl_kernel<6, PX, SL><<<grid, PX * SL, lds, st>>>(feat, labels, pn, count, lacc, (bf16_t*)dfeat, lddf, accumulate, K, h * w,
-                                                      ignore_label, 1.f / temperature, weight);
+    if (C == 6)
+        pcl_kernel<6, PX, SL><<<grid, PX * SL, lds, st>>>(feat, labels, pn, count, lacc, (bf16_t*)dfeat, lddf, accumulate, K, h * w,
+                                                          ignore_label, 1.f / temperature, weight);
+    else
+        pcl_kernel<7, PX, SL><<<grid, PX * SL, lds, st>>>(feat, labels, pn, count, lacc, (bf16_t*)dfeat, lddf, accumulate, K, h * w,
+                                                          ignore_label, 1.f / temperature, weight);
     RGDA_CHECK_LAUNCH();
     pcl_loss_finish_kernel<<<1, 1, 0, st>>>(lacc, count, loss);
     RGDA_CHECK_LAUNCH();

@@ -91,6 +91,8 @@ extern "C" int rgda_pseudo_select(const float* soft, int64_t* out, int b, int c,
     dim3 grid(min(cdiv(hw, 256), 1024), b);
     if (c == 6)
         pseudo_pick_kernel<6><<<grid, 256, 0, st>>>(soft, classmax, out, hw, cutoff_top, cutoff_low, ignore_label, c);
+    else if (c == 7)
+        pseudo_pick_kernel<7><<<grid, 256, 0, st>>>(soft, classmax, out, hw, cutoff_top, cutoff_low, ignore_label, c);
     else
         pseudo_pick_kernel<0><<<grid, 256, 0, st>>>(soft, classmax, out, hw, cutoff_top, cutoff_low, ignore_label, c);
     RGDA_CHECK_LAUNCH();
@@ -452,7 +454,7 @@ extern "C" int rgda_pseudo_lrh(const float* soft, const float* classmax, const i
                                int max_regions, void* ws, size_t ws_bytes, rgda_stream_t stream) {
     if (!soft || !classmax || !regions || !out || !ws || b <= 0 || hw < 0 || max_regions <= 0 || max_regions > 65535)
         return RGDA_ERR_ARG;
-    if (class_num != 6 || (hw & 3)) return RGDA_ERR_UNSUPPORTED;       // (the two-call route serves everything else)
+    if ((class_num != 6 && class_num != 7) || (hw & 3)) return RGDA_ERR_UNSUPPORTED;   // (the two-call route serves everything else)
     if (((uintptr_t)ws & 15) || ws_bytes < rgda_pseudo_lrh_workspace(b, hw, max_regions, class_num)) return RGDA_ERR_WORKSPACE;
     if (hw == 0) return RGDA_OK;
     hipStream_t st = to_stream(stream);
@@ -472,9 +474,15 @@ extern "C" int rgda_pseudo_lrh(const float* soft, const float* classmax, const i
     if (const char* e = TUNE_ENV("RGDA_LRH_WG")) min_wg = atoi(e);                        // tuning experiments only
     while (chunk > 1024 && (long long)cdiv(hw, chunk) * b < min_wg) chunk >>= 1;
     dim3 g1(cdiv(hw, chunk), b);
-    pick_hist_kernel<6><<<g1, 256, (size_t)lds_regions * C * 4, st>>>(soft, classmax, regions, lab8, reg16, hist, ids, flag, counters,
-                                                                       hw, chunk, cutoff_top, cutoff_low, ignore_label, percent, R,
-                                                                       lds_regions);
+    // lab8 holds the selected class 0..C-1 or 0xff (ignore): one byte serves both class counts
+    if (C == 6)
+        pick_hist_kernel<6><<<g1, 256, (size_t)lds_regions * C * 4, st>>>(soft, classmax, regions, lab8, reg16, hist, ids, flag, counters,
+                                                                           hw, chunk, cutoff_top, cutoff_low, ignore_label, percent, R,
+                                                                           lds_regions);
+    else
+        pick_hist_kernel<7><<<g1, 256, (size_t)lds_regions * C * 4, st>>>(soft, classmax, regions, lab8, reg16, hist, ids, flag, counters,
+                                                                           hw, chunk, cutoff_top, cutoff_low, ignore_label, percent, R,
+                                                                           lds_regions);
     RGDA_CHECK_LAUNCH();
     dim3 g3(min(cdiv(hw, 1024), 512), b);
     lrh_gather8_kernel<<<g3, 256, 0, st>>>(lab8, reg16, ids, out, hw, R, ignore_label);
@@ -812,44 +820,32 @@ extern "C" int rgda_label_refine_sup(const float* feat, const float* protos, con
                       ws_bytes, stream);
 }
 
-static int refine_run(const float* feat, const float* protos, const float* p1, const float* p2, const float* soft,
-                      const long long* sup, int max_regions, float* out, int b, int k, int c, int h, int w, int H, int W,
-                      float temp, int views, void* ws, size_t ws_bytes, rgda_stream_t stream) {
-    if (!soft || !out || !ws) return RGDA_ERR_ARG;
-    const bool pview = views & 1, lview = views & 2;
-    if ((pview && (!feat || !protos)) || (lview && (!p1 || !p2))) return RGDA_ERR_ARG;
-    if (c != 6) return RGDA_ERR_UNSUPPORTED;   // ISPRS: 6 classes (regda/datasets/isprsda.py:18-26)
-    if (b <= 0 || (pview && (k < 2 || k > 4096 || (k & 3))) || h <= 0 || w <= 0 || H <= 0 || W <= 0 || !(temp > 0.f))
-        return RGDA_ERR_ARG;
-    if (ws_bytes < (sup ? rgda_label_refine_sup_workspace(b, c, h, w, max_regions) : rgda_label_refine_workspace(b, c, h, w)))
-        return RGDA_ERR_WORKSPACE;
+// the launches of refine_run for one class count (the workspace is laid out and cleared by the caller)
+template <int C>
+static int refine_launch(const float* feat, const float* protos, const float* p1, const float* p2, const float* soft,
+                         const long long* sup, int max_regions, float* out, int b, int k, int h, int w, int H, int W,
+                         float temp, int views, char* base, float* sim, float* classmax, float* pstd, float* pc,
+                         rgda_stream_t stream) {
     hipStream_t st = to_stream(stream);
-    char* base = (char*)ws;
-    float* sim = (float*)base;
-    size_t off = rgda_label_refine_classmax_offset(b, c, h, w);
-    float* classmax = (float*)(base + off);
-    off += align256((size_t)b * c * 4 + 16);
-    float* pstd = (float*)(base + off);
-    off += align256((size_t)c * 4);
-    float* pc = (float*)(base + off);
-    if (zero_bytes(classmax, (size_t)b * c * 4 + 16, stream) != RGDA_OK) return RGDA_ERR_LAUNCH;
+    const bool pview = views & 1;
+    const int c = C;
     const int hw = h * w;
     if (pview) {
     proto_center_kernel<<<c, 256, 0, st>>>(protos, pc, pstd, k);
     RGDA_CHECK_LAUNCH();
     constexpr int PX = 32, SL = 16;
-    size_t lds = ((size_t)6 * k + SL * PX * 7) * 4;
+    size_t lds = ((size_t)C * k + SL * PX * (C + 1)) * 4;       // pc[C][k] then red[SL][PX][C+1]
     dim3 g1(cdiv(hw, PX), b);
     if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void*)pearson_sim_kernel<6, PX, SL>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        hipFuncSetAttribute((const void*)pearson_sim_kernel<C, PX, SL>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)lds) != hipSuccess)
         return RGDA_ERR_LAUNCH;
-    pearson_sim_kernel<6, PX, SL><<<g1, PX * SL, lds, st>>>(feat, pc, pstd, sim, k, hw);
+    pearson_sim_kernel<C, PX, SL><<<g1, PX * SL, lds, st>>>(feat, pc, pstd, sim, k, hw);
     RGDA_CHECK_LAUNCH();
     }
     dim3 g2(cdiv(W, 256), cdiv(H, REFINE_ROWS), b);
     if (!sup) {
-        refine_apply_kernel<6><<<g2, 256, 0, st>>>(sim, p1, p2, soft, out, classmax, h, w, H, W, temp, views);
+        refine_apply_kernel<C><<<g2, 256, 0, st>>>(sim, p1, p2, soft, out, classmax, h, w, H, W, temp, views);
         RGDA_CHECK_LAUNCH();
         return RGDA_OK;
     }
@@ -861,11 +857,38 @@ static int refine_run(const float* feat, const float* protos, const float* p1, c
     sv.cnt = (int*)((char*)sv.tbl + tbl_bytes);
     if (zero_bytes(sv.tbl, tbl_bytes + 256, stream) != RGDA_OK) return RGDA_ERR_LAUNCH;     // key 0 = below every float
     const size_t HW = (size_t)H * W;
-    sup_max_kernel<6><<<dim3(cdiv(HW, (size_t)256), b), 256, 0, st>>>(soft, sv, HW);
+    sup_max_kernel<C><<<dim3(cdiv(HW, (size_t)256), b), 256, 0, st>>>(soft, sv, HW);
     RGDA_CHECK_LAUNCH();
-    refine_apply_kernel<6, true><<<g2, 256, 0, st>>>(sim, p1, p2, soft, out, classmax, h, w, H, W, temp, views, sv);
+    refine_apply_kernel<C, true><<<g2, 256, 0, st>>>(sim, p1, p2, soft, out, classmax, h, w, H, W, temp, views, sv);
     RGDA_CHECK_LAUNCH();
     return RGDA_OK;
+}
+
+static int refine_run(const float* feat, const float* protos, const float* p1, const float* p2, const float* soft,
+                      const long long* sup, int max_regions, float* out, int b, int k, int c, int h, int w, int H, int W,
+                      float temp, int views, void* ws, size_t ws_bytes, rgda_stream_t stream) {
+    if (!soft || !out || !ws) return RGDA_ERR_ARG;
+    const bool pview = views & 1, lview = views & 2;
+    if ((pview && (!feat || !protos)) || (lview && (!p1 || !p2))) return RGDA_ERR_ARG;
+    if (c != 6 && c != 7) return RGDA_ERR_UNSUPPORTED;   // ISPRS: 6 classes (regda/datasets/isprsda.py:18-26), LoveDA: 7
+    if (b <= 0 || (pview && (k < 2 || k > 4096 || (k & 3))) || h <= 0 || w <= 0 || H <= 0 || W <= 0 || !(temp > 0.f))
+        return RGDA_ERR_ARG;
+    if (ws_bytes < (sup ? rgda_label_refine_sup_workspace(b, c, h, w, max_regions) : rgda_label_refine_workspace(b, c, h, w)))
+        return RGDA_ERR_WORKSPACE;
+    char* base = (char*)ws;
+    float* sim = (float*)base;
+    size_t off = rgda_label_refine_classmax_offset(b, c, h, w);
+    float* classmax = (float*)(base + off);
+    off += align256((size_t)b * c * 4 + 16);
+    float* pstd = (float*)(base + off);
+    off += align256((size_t)c * 4);
+    float* pc = (float*)(base + off);
+    if (zero_bytes(classmax, (size_t)b * c * 4 + 16, stream) != RGDA_OK) return RGDA_ERR_LAUNCH;
+    if (c == 6)
+        return refine_launch<6>(feat, protos, p1, p2, soft, sup, max_regions, out, b, k, h, w, H, W, temp, views, base, sim, classmax,
+                                pstd, pc, stream);
+    return refine_launch<7>(feat, protos, p1, p2, soft, sup, max_regions, out, b, k, h, w, H, W, temp, views, base, sim, classmax, pstd,
+                            pc, stream);
 }
 
 // --------------------------------------------------------------------------------------
@@ -954,14 +977,20 @@ __global__ void __launch_bounds__(256) downscale_label_kernel(const int64_t* __r
     }
 }
 
-// Fast form for scale 16 and C <= 6 (the RegDA configuration: 512 -> 32, six classes + ignore): one workgroup per ROW of
-// low-res cells.  A thread owns two label columns of the 16-row band (16-byte loads, fully coalesced 4 KB rows) and
-// counts its 32 labels in seven 9-bit fields of one 64-bit word; the eight threads of a cell add their words with DPP
-// row shifts (no LDS, no atomics), the first of them picks the class.  (The one-workgroup-per-cell kernel above spends
-// 94 us on 8192 tiny workgroups with LDS atomics and a single-thread tail; this is ~8 us for the same 17 MB.)
+// Fast form for scale 16 and C in {6, 7} (the RegDA configurations: 512 -> 32, six ISPRS or seven LoveDA classes +
+// ignore): one workgroup per ROW of low-res cells.  A thread owns two label columns of the 16-row band (16-byte loads,
+// fully coalesced 4 KB rows) and counts its 32 labels in 9-bit fields of one 64-bit word; the eight threads of a cell add
+// their words with DPP row shifts (no LDS, no atomics), the first of them picks the class.  (The one-workgroup-per-cell
+// kernel above spends 94 us on 8192 tiny workgroups with LDS atomics and a single-thread tail; this is ~8 us for the
+// same 17 MB.)  Six classes: seven fields, the last one counts "ignore".  Seven classes: the seven fields are the
+// classes (63 bits) and the ignore count is 256 - their sum, exact because every cell holds exactly 16 * 16 labels
+// (a label outside [-1, C) raises the flag and, not being a class, lands in that remainder).
+template <int C>
 __global__ void __launch_bounds__(256) downscale_label16_kernel(const int64_t* __restrict__ label, int64_t* label_ds,
-                                                                float* cnt, int* flag, int h, int w, int C,
+                                                                float* cnt, int* flag, int h, int w,
                                                                 int ignore_label, float min_ratio) {
+    static_assert(C >= 1 && C <= 7, "C class fields (+ an ignore field below 7) of 9 bits in 64");
+    constexpr bool IGN_FIELD = C < 7;            // ignore counted in field C, or derived from the others
     const int W = w * 16;
     const int b = blockIdx.y / h, y = blockIdx.y % h;
     const int col = (blockIdx.x * 256 + threadIdx.x) * 2;           // first of this thread's two columns
@@ -978,9 +1007,14 @@ __global__ void __launch_bounds__(256) downscale_label16_kernel(const int64_t* _
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
                 long long l = k ? v.y : v.x;
-                if (l == ignore_label) l = C;
-                if (l < 0 || l > C) bad = 1;
-                else packed += 1ull << (9 * (int)l);
+                if (IGN_FIELD) {
+                    if (l == ignore_label) l = C;
+                    if (l < 0 || l > C) bad = 1;
+                    else packed += 1ull << (9 * (int)l);
+                } else if (l != ignore_label) {
+                    if (l < 0 || l >= C) bad = 1;
+                    else packed += 1ull << (9 * (int)l);
+                }
             }
         }
     }
@@ -999,11 +1033,17 @@ __global__ void __launch_bounds__(256) downscale_label16_kernel(const int64_t* _
     if ((threadIdx.x & 7) == 0 && col < W) {
         const int x = col / 16;
         // avg_pool2d of the one-hot: count / 256 in fp32; torch.max keeps the first maximum
+        int n_ign = 256;
+        if (!IGN_FIELD) {
+#pragma unroll
+            for (int c = 0; c < C; ++c) n_ign -= (int)((packed >> (9 * c)) & 511u);
+        }
         float best = __fdiv_rn((float)(packed & 511u), 256.f);
         int arg = 0;
         for (int c = 1; c <= C; ++c) {
-            float r = __fdiv_rn((float)((packed >> (9 * c)) & 511u), 256.f);
-            if (r > best) { best = r; arg = c; }
+            const unsigned n = (IGN_FIELD || c < C) ? (unsigned)((packed >> (9 * c)) & 511u) : (unsigned)n_ign;
+            float r = __fdiv_rn((float)n, 256.f);
+            if (r > best) { best = r; arg = c; }        // strict >: the first maximum, a class tied with ignore wins
         }
         long long o = arg;
         if (arg == C) o = ignore_label;
@@ -1071,7 +1111,7 @@ extern "C" int rgda_proto_stats(const float* feat, const int64_t* label, int64_t
                                 int scale, int ignore_label, float min_ratio, void* stats, size_t stats_bytes,
                                 rgda_stream_t stream) {
     if (!feat || !label || !label_ds || !stats) return RGDA_ERR_ARG;
-    if (c != 6) return RGDA_ERR_UNSUPPORTED;
+    if (c != 6 && c != 7) return RGDA_ERR_UNSUPPORTED;            // ISPRS (6) and LoveDA (7)
     if (b <= 0 || k <= 0 || h <= 0 || w <= 0 || scale <= 1) return RGDA_ERR_ARG;
     if (stats_bytes < rgda_proto_update_workspace(c, k)) return RGDA_ERR_WORKSPACE;
     hipStream_t st = to_stream(stream);
@@ -1079,12 +1119,18 @@ extern "C" int rgda_proto_stats(const float* feat, const int64_t* label, int64_t
     float* cnt = sums + (size_t)c * k;
     int* flag = (int*)(cnt + c);
     if (zero_bytes(stats, rgda_proto_update_workspace(c, k), stream) != RGDA_OK) return RGDA_ERR_LAUNCH;
-    if (scale == 16 && c <= 6 && !(w & 1))
-        downscale_label16_kernel<<<dim3(cdiv(w * 8, 256), b * h), 256, 0, st>>>(label, label_ds, cnt, flag, h, w, c, ignore_label, min_ratio);
+    const dim3 g16(cdiv(w * 8, 256), b * h);
+    if (scale == 16 && !(w & 1) && c == 6)
+        downscale_label16_kernel<6><<<g16, 256, 0, st>>>(label, label_ds, cnt, flag, h, w, ignore_label, min_ratio);
+    else if (scale == 16 && !(w & 1))
+        downscale_label16_kernel<7><<<g16, 256, 0, st>>>(label, label_ds, cnt, flag, h, w, ignore_label, min_ratio);
     else
         downscale_label_kernel<<<b * h * w, 256, 0, st>>>(label, label_ds, cnt, flag, h, w, scale, c, ignore_label, min_ratio);
     RGDA_CHECK_LAUNCH();
-    proto_accum_kernel<6><<<k, 256, 0, st>>>(feat, label_ds, sums, k, h * w, b);
+    if (c == 6)
+        proto_accum_kernel<6><<<k, 256, 0, st>>>(feat, label_ds, sums, k, h * w, b);
+    else
+        proto_accum_kernel<7><<<k, 256, 0, st>>>(feat, label_ds, sums, k, h * w, b);
     RGDA_CHECK_LAUNCH();
     return RGDA_OK;
 }
@@ -1140,9 +1186,12 @@ __global__ void __launch_bounds__(256) teacher_probs_kernel(const float* __restr
 extern "C" int rgda_teacher_probs(const float* p1, const float* p2, float* probs, int b, int c, int h, int w, int H,
                                   int W, rgda_stream_t stream) {
     if (!p1 || !p2 || !probs || b <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return RGDA_ERR_ARG;
-    if (c != 6) return RGDA_ERR_UNSUPPORTED;
+    if (c != 6 && c != 7) return RGDA_ERR_UNSUPPORTED;            // ISPRS (6) and LoveDA (7)
     dim3 g(cdiv(W, 256), H, b);
-    teacher_probs_kernel<6><<<g, 256, 0, to_stream(stream)>>>(p1, p2, probs, h, w, H, W);
+    if (c == 6)
+        teacher_probs_kernel<6><<<g, 256, 0, to_stream(stream)>>>(p1, p2, probs, h, w, H, W);
+    else
+        teacher_probs_kernel<7><<<g, 256, 0, to_stream(stream)>>>(p1, p2, probs, h, w, H, W);
     RGDA_CHECK_LAUNCH();
     return RGDA_OK;
 }

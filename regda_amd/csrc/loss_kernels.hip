@@ -21,7 +21,6 @@
 
 namespace {
 
-constexpr int LC = 6;                    // class count (rgda_upsample_ce's restriction)
 constexpr int KIND_CE = 0;               // rgda_upsample_ce: a kind of this file only, not an rgda_loss_kind
 constexpr size_t MAX_ROW_LDS = 150 * 1024;   // dynamic LDS of the grad pass: the widest row served
 constexpr int GHM_BINS = 30;
@@ -149,13 +148,12 @@ __device__ __forceinline__ int ghm_bucket(float g, const float* edges) {
 }
 
 // ---------------------------------------------------------------------------------------------------- stat pass
-template <int KIND>
+template <int KIND, int C>
 __global__ void __launch_bounds__(256) loss_stat_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
                                                         const int64_t* __restrict__ label, const float* __restrict__ soft,
                                                         const float* __restrict__ class_weight, LossHdr* hdr,
                                                         void* scratch, int h, int w, int H, int W, int ignore_label,
                                                         LossParams prm) {
-    constexpr int C = LC;
     extern __shared__ float rows[];
     __shared__ int s_cnt[3], s_kept[2], s_hist[2][32];
     __shared__ float s_edges[GHM_BINS + 1];
@@ -373,19 +371,18 @@ __device__ __forceinline__ void contract_row(const float* G, const int* lxi, con
     }
 }
 
-// dynamic LDS: rows[2 heads][C][2][w] | G[2][C][W] (with gradients) | lxi[W] | lxl[W]
-static size_t grad_lds(int w, int W, bool want) {
-    return ((size_t)2 * LC * 2 * w + (want ? (size_t)2 * LC * W : 0) + (size_t)2 * W) * 4;
+// dynamic LDS: rows[2 heads][c][2][w] | G[2][c][W] (with gradients) | lxi[W] | lxl[W]
+static size_t grad_lds(int c, int w, int W, bool want) {
+    return ((size_t)2 * c * 2 * w + (want ? (size_t)2 * c * W : 0) + (size_t)2 * W) * 4;
 }
 
-template <int KIND>
+template <int KIND, int C>
 __global__ void __launch_bounds__(256) loss_grad_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
                                                         const int64_t* __restrict__ label,
                                                         const float* __restrict__ class_weight,
                                                         const LossHdr* __restrict__ hdr, const void* __restrict__ scratch,
                                                         float* partial, float* T, int h, int w, int H, int W,
                                                         int ignore_label, LossParams prm, int want_grad) {
-    constexpr int C = LC;
     extern __shared__ float lds[];
     float* rows = lds;
     float* G = lds + 2 * C * 2 * w;
@@ -475,9 +472,9 @@ __global__ void __launch_bounds__(256) loss_grad_kernel(const float* __restrict_
 }
 
 // vertical contraction T -> g[head][b][c][y][x]
+template <int C>
 __global__ void __launch_bounds__(256) loss_col_kernel(const float* __restrict__ T, float* g1, float* g2, int b_n, int h,
                                                        int w, int H) {
-    constexpr int C = LC;
     int i = blockIdx.x * 256 + threadIdx.x;
     int total = 2 * b_n * C * h * w;
     if (i >= total) return;
@@ -539,7 +536,7 @@ struct LossCall {
 };
 
 // the passes of one call, in stream order
-template <int KIND>
+template <int KIND, int C>
 static int run_passes(const LossCall& a, rgda_stream_t stream) {
     hipStream_t st = to_stream(stream);
     const int want = a.g1 != nullptr;
@@ -550,9 +547,9 @@ static int run_passes(const LossCall& a, rgda_stream_t stream) {
             constexpr bool uv = KIND == RGDA_LOSS_UPS || KIND == RGDA_LOSS_UVEM;
             const size_t zero = KIND == RGDA_LOSS_OHEM ? offsetof(LossHdr, cut) : offsetof(LossHdr, sel_arrived);
             if (zero_bytes(a.hdr, zero, stream) != RGDA_OK) return RGDA_ERR_LAUNCH;
-            const size_t lds = uv ? 0 : (size_t)2 * LC * 2 * a.w * 4;
-            if (lds_attr((const void*)loss_stat_kernel<KIND>, lds) != RGDA_OK) return RGDA_ERR_LAUNCH;
-            loss_stat_kernel<KIND><<<rows_grid, 256, lds, st>>>(a.p1, a.p2, a.label, a.soft, a.class_weight, a.hdr,
+            const size_t lds = uv ? 0 : (size_t)2 * C * 2 * a.w * 4;
+            if (lds_attr((const void*)loss_stat_kernel<KIND, C>, lds) != RGDA_OK) return RGDA_ERR_LAUNCH;
+            loss_stat_kernel<KIND, C><<<rows_grid, 256, lds, st>>>(a.p1, a.p2, a.label, a.soft, a.class_weight, a.hdr,
                                                                 a.scratch, a.h, a.w, a.H, a.W, a.ignore_label, a.prm);
             RGDA_CHECK_LAUNCH();
         }
@@ -566,13 +563,13 @@ static int run_passes(const LossCall& a, rgda_stream_t stream) {
             }
         }
     }
-    const size_t lds = grad_lds(a.w, a.W, want);
-    if (lds_attr((const void*)loss_grad_kernel<KIND>, lds) != RGDA_OK) return RGDA_ERR_LAUNCH;
-    loss_grad_kernel<KIND><<<rows_grid, 256, lds, st>>>(a.p1, a.p2, a.label, a.class_weight, a.hdr, a.scratch,
+    const size_t lds = grad_lds(C, a.w, a.W, want);
+    if (lds_attr((const void*)loss_grad_kernel<KIND, C>, lds) != RGDA_OK) return RGDA_ERR_LAUNCH;
+    loss_grad_kernel<KIND, C><<<rows_grid, 256, lds, st>>>(a.p1, a.p2, a.label, a.class_weight, a.hdr, a.scratch,
                                                         a.partial, a.T, a.h, a.w, a.H, a.W, a.ignore_label, a.prm, want);
     RGDA_CHECK_LAUNCH();
     if (want) {
-        loss_col_kernel<<<cdiv((long long)2 * a.b * LC * a.h * a.w, 256), 256, 0, st>>>(a.T, a.g1, a.g2, a.b, a.h, a.w,
+        loss_col_kernel<C><<<cdiv((long long)2 * a.b * C * a.h * a.w, 256), 256, 0, st>>>(a.T, a.g1, a.g2, a.b, a.h, a.w,
                                                                                        a.H);
         RGDA_CHECK_LAUNCH();
     }
@@ -581,16 +578,24 @@ static int run_passes(const LossCall& a, rgda_stream_t stream) {
     return RGDA_OK;
 }
 
+template <int C>
 static int run_kind(int kind, const LossCall& a, rgda_stream_t stream) {
     switch (kind) {
-        case KIND_CE: return run_passes<KIND_CE>(a, stream);
-        case RGDA_LOSS_OHEM: return run_passes<RGDA_LOSS_OHEM>(a, stream);
-        case RGDA_LOSS_FOCAL: return run_passes<RGDA_LOSS_FOCAL>(a, stream);
-        case RGDA_LOSS_GHM: return run_passes<RGDA_LOSS_GHM>(a, stream);
-        case RGDA_LOSS_UPS: return run_passes<RGDA_LOSS_UPS>(a, stream);
-        case RGDA_LOSS_UVEM: return run_passes<RGDA_LOSS_UVEM>(a, stream);
+        case KIND_CE: return run_passes<KIND_CE, C>(a, stream);
+        case RGDA_LOSS_OHEM: return run_passes<RGDA_LOSS_OHEM, C>(a, stream);
+        case RGDA_LOSS_FOCAL: return run_passes<RGDA_LOSS_FOCAL, C>(a, stream);
+        case RGDA_LOSS_GHM: return run_passes<RGDA_LOSS_GHM, C>(a, stream);
+        case RGDA_LOSS_UPS: return run_passes<RGDA_LOSS_UPS, C>(a, stream);
+        case RGDA_LOSS_UVEM: return run_passes<RGDA_LOSS_UVEM, C>(a, stream);
         default: return RGDA_ERR_ARG;
     }
+}
+
+// the class counts served: ISPRS (6) and LoveDA (7)
+static bool class_count_ok(int c) { return c == 6 || c == 7; }
+
+static int run_kind(int kind, int c, const LossCall& a, rgda_stream_t stream) {
+    return c == 6 ? run_kind<6>(kind, a, stream) : run_kind<7>(kind, a, stream);
 }
 
 }  // namespace
@@ -604,10 +609,10 @@ extern "C" int rgda_upsample_ce(const float* p1, const float* p2, const int64_t*
                                 float* loss, float* g1, float* g2, int b, int c, int h, int w, int H, int W,
                                 int ignore_label, void* ws, size_t ws_bytes, rgda_stream_t stream) {
     if (!p1 || !p2 || !label || !loss || !ws || ((g1 == nullptr) != (g2 == nullptr))) return RGDA_ERR_ARG;
-    if (c != LC) return RGDA_ERR_UNSUPPORTED;
+    if (!class_count_ok(c)) return RGDA_ERR_UNSUPPORTED;
     if (b <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return RGDA_ERR_ARG;
     if (ws_bytes < rgda_upsample_ce_workspace(b, c, h, w, H, W)) return RGDA_ERR_WORKSPACE;
-    if (grad_lds(w, W, g1 != nullptr) > MAX_ROW_LDS) return RGDA_ERR_UNSUPPORTED;
+    if (grad_lds(c, w, W, g1 != nullptr) > MAX_ROW_LDS) return RGDA_ERR_UNSUPPORTED;
     LossCall a{};
     a.p1 = p1, a.p2 = p2, a.label = label, a.class_weight = class_weight;
     a.loss = loss, a.g1 = g1, a.g2 = g2;
@@ -615,7 +620,7 @@ extern "C" int rgda_upsample_ce(const float* p1, const float* p2, const int64_t*
     a.T = (float*)((char*)ws + align256_((size_t)b * H * 2 * 4));
     a.heads = 2, a.b = b, a.h = h, a.w = w, a.H = H, a.W = W, a.ignore_label = ignore_label;
     a.prm.gscale = (float)(0.5 / ((double)b * H * W));
-    return run_kind(KIND_CE, a, stream);
+    return run_kind(KIND_CE, c, a, stream);
 }
 
 extern "C" size_t rgda_upsample_loss_workspace(int kind, int b, int c, int h, int w, int H, int W) {
@@ -643,9 +648,9 @@ extern "C" int rgda_upsample_loss(int kind, int heads, const float* p1, const fl
     if (kind == RGDA_LOSS_OHEM && !(thresh >= 0.f)) return RGDA_ERR_ARG;
     // the reference's FocalLoss / GHMLoss take no class balancer
     if ((kind == RGDA_LOSS_FOCAL || kind == RGDA_LOSS_GHM) && class_weight) return RGDA_ERR_ARG;
-    if (c != LC) return RGDA_ERR_UNSUPPORTED;
+    if (!class_count_ok(c)) return RGDA_ERR_UNSUPPORTED;
     if (ws_bytes < rgda_upsample_loss_workspace(kind, b, c, h, w, H, W)) return RGDA_ERR_WORKSPACE;
-    if (grad_lds(w, W, g1 != nullptr) > MAX_ROW_LDS) return RGDA_ERR_UNSUPPORTED;
+    if (grad_lds(c, w, W, g1 != nullptr) > MAX_ROW_LDS) return RGDA_ERR_UNSUPPORTED;
     LossCall a{};
     a.p1 = p1, a.p2 = p2, a.soft = soft, a.class_weight = class_weight, a.label = label;
     a.acc_sum = acc_sum, a.loss = loss, a.g1 = g1, a.g2 = g2;
@@ -668,5 +673,5 @@ extern "C" int rgda_upsample_loss(int kind, int heads, const float* p1, const fl
     prm.gamma = (float)gamma;
     prm.mom = (float)momentum;
     prm.omm = (float)(1.0 - momentum);
-    return run_kind(kind, a, stream);
+    return run_kind(kind, c, a, stream);
 }

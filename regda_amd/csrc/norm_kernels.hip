@@ -1737,9 +1737,12 @@ __global__ void __launch_bounds__(256) classifier_bwd_reduce_kernel(const float*
 extern "C" int rgda_classifier_fwd(const void* hidden, int ldh, const float* w, const float* bias, float* logits,
                                    int N, int HW, int C, int ncls, rgda_stream_t stream) {
     if (!hidden || !w || !bias || !logits || N <= 0 || HW <= 0 || C <= 0 || (C & 7) || (ldh & 7)) return RGDA_ERR_ARG;
-    if (ncls != 6) return RGDA_ERR_UNSUPPORTED;
+    if (ncls != 6 && ncls != 7) return RGDA_ERR_UNSUPPORTED;     // ISPRS (6) and LoveDA (7)
     long long M = (long long)N * HW;
-    classifier_fwd_kernel<6><<<cdiv(M, 4), 256, 0, to_stream(stream)>>>((const bf16_t*)hidden, ldh, w, bias, logits, N, HW, C);
+    if (ncls == 6)
+        classifier_fwd_kernel<6><<<cdiv(M, 4), 256, 0, to_stream(stream)>>>((const bf16_t*)hidden, ldh, w, bias, logits, N, HW, C);
+    else
+        classifier_fwd_kernel<7><<<cdiv(M, 4), 256, 0, to_stream(stream)>>>((const bf16_t*)hidden, ldh, w, bias, logits, N, HW, C);
     RGDA_CHECK_LAUNCH();
     return RGDA_OK;
 }
@@ -1748,27 +1751,23 @@ extern "C" size_t rgda_classifier_bwd_workspace(int64_t M, int C, int ncls) {
     return (size_t)cdiv(M, 64) * ((size_t)ncls * C + 64) * 4;
 }
 
-extern "C" int rgda_classifier_bwd(const void* hidden, int ldh, const float* w, const float* glogits, void* dhidden,
-                                   int lddh, float* dw, float* db, int N, int HW, int C, int ncls, void* ws,
-                                   size_t ws_bytes, rgda_stream_t stream) {
-    if (!hidden || !w || !glogits || !dhidden || !dw || !db || N <= 0 || HW <= 0 || C <= 0 || (C & 7) || (ldh & 7) ||
-        (lddh & 7))
-        return RGDA_ERR_ARG;
-    if (ncls != 6) return RGDA_ERR_UNSUPPORTED;
+template <int NC>
+static int classifier_bwd_run(const void* hidden, int ldh, const float* w, const float* glogits, void* dhidden, int lddh,
+                              float* dw, float* db, int N, int HW, int C, void* ws, size_t ws_bytes, hipStream_t st) {
+    const size_t lds = (size_t)256 * 8 * NC * 4;         // [rpb][vpb*8][NC] floats, rpb * vpb = 256
     long long M = (long long)N * HW;
     RowLayout L = row_layout(C);
-    hipStream_t st = to_stream(stream);
     if (ws) {
         // 64 rows per workgroup (the whole chip), per-workgroup partial dW / db in the workspace, then one small
         // deterministic reduction: ncls*C atomics per workgroup onto the SAME addresses forced few, long workgroups
         // (64 of them at M = 16384: a quarter of the CUs, 70 us)
-        if (ws_bytes < rgda_classifier_bwd_workspace(M, C, ncls)) return RGDA_ERR_WORKSPACE;
+        if (ws_bytes < rgda_classifier_bwd_workspace(M, C, NC)) return RGDA_ERR_WORKSPACE;
         const int blocks = cdiv(M, 64);
         dim3 grid(blocks, cdiv(L.vpr, L.vpb));
-        classifier_bwd_kernel<6><<<grid, 256, (size_t)256 * 8 * 6 * 4, st>>>(
+        classifier_bwd_kernel<NC><<<grid, 256, lds, st>>>(
             (const bf16_t*)hidden, ldh, w, glogits, (bf16_t*)dhidden, lddh, dw, db, N, HW, C, 64, (float*)ws);
         RGDA_CHECK_LAUNCH();
-        classifier_bwd_reduce_kernel<6><<<cdiv(6 * C + 6, 32), 256, 0, st>>>((const float*)ws, blocks, dw, db, C);
+        classifier_bwd_reduce_kernel<NC><<<cdiv(NC * C + NC, 32), 256, 0, st>>>((const float*)ws, blocks, dw, db, C);
         RGDA_CHECK_LAUNCH();
         return RGDA_OK;
     }
@@ -1777,8 +1776,20 @@ extern "C" int rgda_classifier_bwd(const void* hidden, int ldh, const float* w, 
     if (const char* e = TUNE_ENV("RGDA_CLS_ROWS")) rows_per_block = atoi(e);     // tuning experiments only
     while ((long long)cdiv(M, rows_per_block) * cdiv(L.vpr, L.vpb) > 1024) rows_per_block *= 2;
     dim3 grid(cdiv(M, rows_per_block), cdiv(L.vpr, L.vpb));
-    classifier_bwd_kernel<6><<<grid, 256, (size_t)256 * 8 * 6 * 4, st>>>(
+    classifier_bwd_kernel<NC><<<grid, 256, lds, st>>>(
         (const bf16_t*)hidden, ldh, w, glogits, (bf16_t*)dhidden, lddh, dw, db, N, HW, C, rows_per_block, nullptr);
     RGDA_CHECK_LAUNCH();
     return RGDA_OK;
+}
+
+extern "C" int rgda_classifier_bwd(const void* hidden, int ldh, const float* w, const float* glogits, void* dhidden,
+                                   int lddh, float* dw, float* db, int N, int HW, int C, int ncls, void* ws,
+                                   size_t ws_bytes, rgda_stream_t stream) {
+    if (!hidden || !w || !glogits || !dhidden || !dw || !db || N <= 0 || HW <= 0 || C <= 0 || (C & 7) || (ldh & 7) ||
+        (lddh & 7))
+        return RGDA_ERR_ARG;
+    hipStream_t st = to_stream(stream);
+    if (ncls == 6) return classifier_bwd_run<6>(hidden, ldh, w, glogits, dhidden, lddh, dw, db, N, HW, C, ws, ws_bytes, st);
+    if (ncls == 7) return classifier_bwd_run<7>(hidden, ldh, w, glogits, dhidden, lddh, dw, db, N, HW, C, ws, ws_bytes, st);
+    return RGDA_ERR_UNSUPPORTED;
 }

@@ -294,7 +294,7 @@ class SSLStep:
         # written as an int64 tensor and read back) where the chain is the default one; tests that look at the selected
         # labels (keep_debug) and the other configurations take the two calls
         regs = (regs_t.squeeze(1) if regs_t.dim() == 4 else regs_t) if self.sam_refine else None
-        fuse_lrh = (self.refine_label and self.sam_refine and not self.keep_debug and self.C == 6 and self.max_regions <= 65535
+        fuse_lrh = (self.refine_label and self.sam_refine and not self.keep_debug and self.max_regions <= 65535
                     and (soft_t.shape[-1] * soft_t.shape[-2]) % 4 == 0)
         hard = None
         if self.refine_label:
