@@ -58,6 +58,13 @@ enum rgda_status {
 };
 
 int rgda_abi_version(void);
+/* The LDS a class-specific launch needs and the most its entry point accepts (beyond it: RGDA_ERR_UNSUPPORTED), so that
+ * a caller can refuse a shape before it launches anything.  which: RGDA_LDS_LOSS_ROW = the row pass of rgda_upsample_ce /
+ * rgda_upsample_loss with gradients (n = logits width w, W = label width), RGDA_LDS_PCL = rgda_pcl_loss (n = K),
+ * RGDA_LDS_REFINE = the prototype view of rgda_label_refine* (n = k).  c: the class count.  0 for an unknown `which`. */
+enum { RGDA_LDS_LOSS_ROW = 0, RGDA_LDS_PCL = 1, RGDA_LDS_REFINE = 2 };
+size_t rgda_class_lds(int which, int c, int n, int W);
+size_t rgda_class_lds_limit(int which);
 const char* rgda_strerror(int status);
 
 /* ------------------------------------------------------------------ labels */
@@ -90,7 +97,7 @@ int rgda_lrh(const int64_t* labels, const int64_t* regions, int64_t* out, int b,
 /* pseudo_selection followed by Homogenizer.forward in one pass over the soft labels -- the chain of the SSL step
  * (tools/train_ssl_reg.py:224-228): out = LRH(pseudo_selection(soft), regions) exactly as the two calls above give it
  * (bit-exact), without the intermediate int64 label tensor.  classmax: f32 [b][c] per-image per-class maxima of `soft`
- * (what rgda_label_refine leaves in its workspace, or rgda_pseudo_select's ws[0 .. b*c)).  class_num in {6, 7}, hw % 4 == 0,
+ * (what rgda_label_refine leaves in its workspace, or rgda_pseudo_select's ws[0 .. b*c)).  6 <= class_num <= 16, hw % 4 == 0,
  * max_regions <= 65535 (RGDA_ERR_UNSUPPORTED otherwise: use the two calls).  ws: rgda_pseudo_lrh_workspace bytes,
  * 16-byte aligned: int32 hist[b][R][C], int32 ids[b][R], int32 flag (bit0: a region id outside [0, R)), then scratch. */
 size_t rgda_pseudo_lrh_workspace(int b, int hw, int max_regions, int class_num);
@@ -111,7 +118,8 @@ int rgda_masks_to_regions(const uint8_t* masks, const int64_t* areas, int32_t* r
  * feat: NCHW f32 (b,k,h,w); protos (c,k) f32; p1,p2: NCHW f32 (b,c,h,w);
  * soft/out: NCHW f32 (b,c,H,W) (out may alias soft).  ws >= workspace bytes:
  * f32 sim[b][c][h*w] then f32 classmax[b][c] (+ int32 flag) laid out so that
- * `classmax` can be handed to rgda_pseudo_select (returned offset).  c in {6, 7} (all three label_refine entries). */
+ * `classmax` can be handed to rgda_pseudo_select (returned offset).  6 <= c <= 16 (all three label_refine entries); with the prototype view the centred
+ * prototypes sit in LDS: c * k floats plus the partial sums within 160 KB (c = 16: k = 2048 fits, 4096 does not; beyond it RGDA_ERR_UNSUPPORTED). */
 size_t rgda_label_refine_workspace(int b, int c, int h, int w);
 size_t rgda_label_refine_classmax_offset(int b, int c, int h, int w);
 int rgda_label_refine(const float* feat, const float* protos, const float* p1, const float* p2,
@@ -146,7 +154,7 @@ int rgda_label_refine_sup(const float* feat, const float* protos, const float* p
 /* Aligner.update_prototype(feat, label)  regda/gast/alignment.py:86-90,300-327,456-481.
  * feat NCHW f32 (b,k,h,w); label (b,H,W) int64 with H = 16h, W = 16w;
  * protos (c,k) f32 updated in place; label_ds (b,h*w) int64 out.
- * ws: f32 sums[c][k], f32 cnt[c].  c in {6, 7} (rgda_proto_stats too). */
+ * ws: f32 sums[c][k], f32 cnt[c].  6 <= c <= 16 (rgda_proto_stats too). */
 size_t rgda_proto_update_workspace(int c, int k);
 int rgda_proto_update(const float* feat, const int64_t* label, float* protos, int64_t* label_ds,
                       int b, int k, int c, int h, int w, int scale, int ignore_label,
@@ -170,7 +178,7 @@ int rgda_proto_apply(float* protos, const void* stats, int c, int k, float decay
  * p1,p2: NCHW f32 (b,c,h,w) logits; label (b,H,W) int64; class_weight: NULL or
  * f32[2][c] per-head per-class weights (ClassBalance, balance.py:27-43).
  * loss: f32[1] (mean over ALL pixels, mean over heads).  g1,g2: NULL or
- * NCHW f32 (b,c,h,w) gradients of `loss` w.r.t. p1,p2.  c in {6, 7}. */
+ * NCHW f32 (b,c,h,w) gradients of `loss` w.r.t. p1,p2.  6 <= c <= 16. */
 size_t rgda_upsample_ce_workspace(int b, int c, int h, int w, int H, int W);
 int rgda_upsample_ce(const float* p1, const float* p2, const int64_t* label,
                      const float* class_weight, float* loss, float* g1, float* g2, int b, int c,
@@ -194,7 +202,7 @@ int rgda_upsample_ce(const float* p1, const float* p2, const int64_t* label,
  * are averaged (regda/utils/tools.py:240-254, balance.py:438-460).  heads 1: one loss_fn call on one prediction (p2 == p1;
  * the loss is that call's, g1 + g2 its gradient, GHM's acc_sum is updated once).  class_weight: NULL or f32[2][c] (per head, the
  * ClassBalance state of that head's call); must be NULL for FOCAL and GHM.  Parameters a kind does not use are ignored.
- * loss: f32[1].  g1, g2: NULL or NCHW f32 (b,c,h,w).  c in {6, 7}; b * H * W < 2^31.  ws: rgda_upsample_loss_workspace
+ * loss: f32[1].  g1, g2: NULL or NCHW f32 (b,c,h,w).  6 <= c <= 16; b * H * W < 2^31.  ws: rgda_upsample_loss_workspace
  * bytes (0 = bad arguments); the per-pixel scratch is 8 (OHEM), 2 (GHM), 4 (UPS / UVEM) or 0 (focal) bytes per pixel.
  * Deterministic: integer atomics for counts and histograms, fixed-order reductions, no float atomics. */
 enum rgda_loss_kind {
@@ -211,7 +219,7 @@ int rgda_upsample_loss(int kind, int heads, const float* p1, const float* p2, co
                        int W, int ignore_label, void* ws, size_t ws_bytes, rgda_stream_t stream);
 
 /* Deeplabv2 eval-branch output  regda/models/Encoder.py:152-155:
- * (softmax(up(x1)) + softmax(up(x2))) / 2, up = bilinear align_corners=True.  c in {6, 7}. */
+ * (softmax(up(x1)) + softmax(up(x2))) / 2, up = bilinear align_corners=True.  6 <= c <= 16. */
 int rgda_teacher_probs(const float* p1, const float* p2, float* probs, int b, int c, int h, int w,
                        int H, int W, rgda_stream_t stream);
 
@@ -484,7 +492,7 @@ int rgda_spatial_mix_multi(int nsrc, const void* const* ins, const int* ldins, c
                            const int* Js, void* out, int ldout, int N, int I, int C, rgda_stream_t stream);
 
 /* 1x1 classifier with bias (regda/models/Encoder.py:40): hidden [M][ldh] bf16 ->
- * logits NCHW f32 (N,ncls,HW); backward gives dhidden (bf16), dW f32[ncls][C] +=, db +=.  ncls in {6, 7}.
+ * logits NCHW f32 (N,ncls,HW); backward gives dhidden (bf16), dW f32[ncls][C] +=, db +=.  6 <= ncls <= 16.
  * ws (optional, rgda_classifier_bwd_workspace bytes): per-workgroup partial sums + a deterministic reduction instead of
  * atomics (NULL: atomics). */
 int rgda_classifier_fwd(const void* hidden, int ldh, const float* w, const float* bias,
@@ -644,7 +652,9 @@ int rgda_confusion_accumulate(const int64_t* y_true, const int64_t* y_pred, int6
 /* ------------------------------------------------------------- stage 2, "align"  */
 
 /* PrototypeContrastiveLoss (regda/loss.py:10-47), forward + gradient w.r.t. the features in one pass:
- *   feat f32 NCHW (b,K,h,w); labels int64 (b,h,w), `ignore_label` pixels are removed; protos f32 (C,K), C in {6, 7}.
+ *   feat f32 NCHW (b,K,h,w); labels int64 (b,h,w), `ignore_label` pixels are removed; protos f32 (C,K), 6 <= C <= 16;
+ *   the normalised prototypes sit in LDS: C * K floats plus the partial sums within 160 KB (C = 16: K = 2048 fits, 4096 does
+ *   not; beyond it RGDA_ERR_UNSUPPORTED).
  *   logits = normalize(feat_p) . normalize(protos)^T / temperature   (tnf.normalize: x / max(||x||, 1e-12))
  *   loss[0] += weight * mean over the kept pixels of cross_entropy(logits, label)      (NaN-free only if one is kept)
  *   dfeat (optional) bf16 [b*h*w][lddf], pixel-major -- the layout rgda_instnorm_bwd consumes: (+)= weight * dloss/dfeat

@@ -33,6 +33,7 @@ class AlignStep(SSLStep):
 
     def step(self, images_s, label_s, images_t, regs_t, lr):
         """One stage-2 iteration.  Returns device tensors (loss_seg, loss_align, grad_norm_sq)."""
+        self._check_shape(images_s, images_t)
         self.lr_dev.fill_(float(lr))
         with ops.use_stream(torch.cuda.current_stream()):
             return self._step(images_s, label_s, images_t, None, regs_t)

@@ -164,6 +164,17 @@ __global__ void pcl_loss_finish_kernel(const rgda_stat_t* acc, const int* count,
 
 static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// pcl_kernel's layout: PX = 32 pixels x SL k-slices.  SL = 16, and 8 from 15 classes on: at K = 2048 the prototypes
+// (C * 8 KB) and red[16][32][C+1] pass the 160 KB of LDS from C = 15 (C = 16: 177 KB; with 8 slices 156 KB).  Halving the
+// slices halves the partial-sum buffer, not the prototypes, and keeps every product and sum in fp32.
+constexpr int PX = 32;
+static constexpr int pcl_slices(int C) { return C <= 14 ? 16 : 8; }
+static size_t pcl_lds(int C, int K) {
+    return ((size_t)C * K + (size_t)pcl_slices(C) * PX * (C + 1) + PX * (C + 1)) * 4 + (size_t)PX * (128 + 8) * 2;
+}
+
+size_t pcl_lds_bytes(int C, int K) { return pcl_lds(C, K); }
+
 extern "C" size_t rgda_pcl_loss_workspace(int C, int K) {
     return align256((size_t)C * K * 4) + 256;
 }
@@ -172,9 +183,10 @@ extern "C" int rgda_pcl_loss(const float* feat, const int64_t* labels, const flo
                              int lddf, int accumulate, int b, int K, int C, int h, int w, int ignore_label,
                              float temperature, float weight, void* ws, size_t ws_bytes, rgda_stream_t stream) {
     if (!feat || !labels || !protos || !loss || !ws) return RGDA_ERR_ARG;
-    if (C != 6 && C != 7) return RGDA_ERR_UNSUPPORTED;   // ISPRS: 6 classes (regda/datasets/isprsda.py:18-26), LoveDA: 7
+    if (!class_count_ok(C)) return RGDA_ERR_UNSUPPORTED;
     if (b <= 0 || K < 8 || K > 4096 || (K & 7) || h <= 0 || w <= 0 || !(temperature > 0.f)) return RGDA_ERR_ARG;
     if (dfeat && ((lddf & 7) || lddf < K)) return RGDA_ERR_ARG;
+    if (pcl_lds(C, K) > RGDA_LDS_MAX) return RGDA_ERR_UNSUPPORTED;          // the prototypes do not fit in LDS
     if (ws_bytes < rgda_pcl_loss_workspace(C, K)) return RGDA_ERR_WORKSPACE;
     hipStream_t st = to_stream(stream);
     float* pn = (float*)ws;
@@ -188,20 +200,19 @@ extern "C" int rgda_pcl_loss(const float* feat, const int64_t* labels, const flo
     long long g = (n + 255) / 256;
     pcl_count_kernel<<<(int)(g > 1024 ? 1024 : g), 256, 0, st>>>(labels, n, ignore_label, C, count, flag);
     RGDA_CHECK_LAUNCH();
-    constexpr int PX = 32, SL = 16;
-    const size_t lds = ((size_t)C * K + SL * PX * (C + 1) + PX * (C + 1)) * 4 + (size_t)PX * (128 + 8) * 2;
-    // (the attribute names the instantiation that is launched)
-    const void* kern = C == 6 ? (const void*)pcl_kernel<6, PX, SL> : (const void*)pcl_kernel<7, PX, SL>;
-    if (lds > 64 * 1024 && hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return RGDA_ERR_LAUNCH;
+    const size_t lds = pcl_lds(C, K);
     dim3 grid(cdiv(h * w, PX), b);
-    if (C == 6)
-        pcl_kernel<6, PX, SL><<<grid, PX * SL, lds, st>>>(feat, labels, pn, count, lacc, (bf16_t*)dfeat, lddf, accumulate, K, h * w,
+    const int rc = with_classes(C, [&](auto cc) {
+        constexpr int C = decltype(cc)::value, SL = pcl_slices(C);
+        if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)pcl_kernel<C, PX, SL>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                   (int)lds) != hipSuccess)
+            return RGDA_ERR_LAUNCH;
+        pcl_kernel<C, PX, SL><<<grid, PX * SL, lds, st>>>(feat, labels, pn, count, lacc, (bf16_t*)dfeat, lddf, accumulate, K, h * w,
                                                           ignore_label, 1.f / temperature, weight);
-    else
-        pcl_kernel<7, PX, SL><<<grid, PX * SL, lds, st>>>(feat, labels, pn, count, lacc, (bf16_t*)dfeat, lddf, accumulate, K, h * w,
-                                                          ignore_label, 1.f / temperature, weight);
-    RGDA_CHECK_LAUNCH();
+        RGDA_CHECK_LAUNCH();
+        return RGDA_OK;
+    });
+    if (rc != RGDA_OK) return rc;
     pcl_loss_finish_kernel<<<1, 1, 0, st>>>(lacc, count, loss);
     RGDA_CHECK_LAUNCH();
     return RGDA_OK;

@@ -204,3 +204,28 @@ static inline int zero_bytes(void* p, size_t bytes, rgda_stream_t stream) {
     return hipMemsetAsync(p, 0, bytes, (hipStream_t)stream) == hipSuccess ? RGDA_OK : RGDA_ERR_LAUNCH;
 }
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// ---- class-count dispatch.  Every class-specific entry point serves RGDA_MIN_CLASSES <= c <= RGDA_MAX_CLASSES through a
+// compile-time instantiation: per-class arrays indexed by a run-time count would live in scratch.  `f` is called with
+// std::integral_constant<int, c> (read it as `constexpr int C = decltype(cc)::value`); any other count returns
+// RGDA_ERR_UNSUPPORTED without calling it, so an entry point that dispatches first checks the count before it touches
+// memory or launches.  Up to 16 classes a selected label still fits lab8's byte and the register and LDS budgets close.
+#include <type_traits>
+#define RGDA_MIN_CLASSES 6
+#define RGDA_MAX_CLASSES 16
+static inline bool class_count_ok(int c) { return c >= RGDA_MIN_CLASSES && c <= RGDA_MAX_CLASSES; }
+// the LDS bytes of the class-dependent layouts (defined next to their kernels; rgda_class_lds reports them)
+size_t loss_row_lds_bytes(int c, int w, int W, bool want);     // loss_kernels.hip
+size_t pcl_lds_bytes(int C, int K);                            // align_kernels.hip
+size_t refine_lds_bytes(int C, int k);                         // label_kernels.hip
+#define RGDA_LOSS_ROW_LDS_MAX ((size_t)150 * 1024)              // the widest row the fused upsample + loss pass serves
+#define RGDA_LDS_MAX ((size_t)160 * 1024)                       // LDS of one gfx950 workgroup
+template <int LO = RGDA_MIN_CLASSES, int HI = RGDA_MAX_CLASSES, class F>
+static inline int with_classes(int c, F&& f) {
+    if constexpr (LO > HI) {
+        return RGDA_ERR_UNSUPPORTED;
+    } else {
+        if (c == LO) return f(std::integral_constant<int, LO>{});
+        return with_classes<LO + 1, HI>(c, f);
+    }
+}

@@ -52,8 +52,9 @@ __global__ void __launch_bounds__(256) pseudo_pick_kernel(const float* __restric
                                                           int64_t* __restrict__ out, int hw, float top,
                                                           float low, int ignore_label, int c_rt) {
     const int b = blockIdx.y;
-    const int c = C > 0 ? C : c_rt;
-    float thr[C > 0 ? C : 16];
+    static_assert(C >= 1 && C <= 16, "a compile-time class count (thr[] stays in registers)");
+    const int c = C;
+    float thr[C];
     for (int k = 0; k < c; ++k) thr[k] = fmaxf(__fmul_rn(classmax[b * c + k], top), low);
     const float* base = soft + (size_t)b * c * hw;
     int64_t* o = out + (size_t)b * hw;
@@ -89,14 +90,13 @@ extern "C" int rgda_pseudo_select(const float* soft, int64_t* out, int b, int c,
         RGDA_CHECK_LAUNCH();
     }
     dim3 grid(min(cdiv(hw, 256), 1024), b);
-    if (c == 6)
-        pseudo_pick_kernel<6><<<grid, 256, 0, st>>>(soft, classmax, out, hw, cutoff_top, cutoff_low, ignore_label, c);
-    else if (c == 7)
-        pseudo_pick_kernel<7><<<grid, 256, 0, st>>>(soft, classmax, out, hw, cutoff_top, cutoff_low, ignore_label, c);
-    else
-        pseudo_pick_kernel<0><<<grid, 256, 0, st>>>(soft, classmax, out, hw, cutoff_top, cutoff_low, ignore_label, c);
-    RGDA_CHECK_LAUNCH();
-    return RGDA_OK;
+    // (this entry point has always served 1..16 classes; below 6 it is the only class-count-specific one that does)
+    return with_classes<1, RGDA_MAX_CLASSES>(c, [&](auto cc) {
+        pseudo_pick_kernel<decltype(cc)::value><<<grid, 256, 0, st>>>(soft, classmax, out, hw, cutoff_top, cutoff_low,
+                                                                      ignore_label, c);
+        RGDA_CHECK_LAUNCH();
+        return RGDA_OK;
+    });
 }
 
 // --------------------------------------------------------------------------------------
@@ -454,7 +454,7 @@ extern "C" int rgda_pseudo_lrh(const float* soft, const float* classmax, const i
                                int max_regions, void* ws, size_t ws_bytes, rgda_stream_t stream) {
     if (!soft || !classmax || !regions || !out || !ws || b <= 0 || hw < 0 || max_regions <= 0 || max_regions > 65535)
         return RGDA_ERR_ARG;
-    if ((class_num != 6 && class_num != 7) || (hw & 3)) return RGDA_ERR_UNSUPPORTED;   // (the two-call route serves everything else)
+    if (!class_count_ok(class_num) || (hw & 3)) return RGDA_ERR_UNSUPPORTED;   // (the two-call route serves everything else)
     if (((uintptr_t)ws & 15) || ws_bytes < rgda_pseudo_lrh_workspace(b, hw, max_regions, class_num)) return RGDA_ERR_WORKSPACE;
     if (hw == 0) return RGDA_OK;
     hipStream_t st = to_stream(stream);
@@ -474,16 +474,15 @@ extern "C" int rgda_pseudo_lrh(const float* soft, const float* classmax, const i
     if (const char* e = TUNE_ENV("RGDA_LRH_WG")) min_wg = atoi(e);                        // tuning experiments only
     while (chunk > 1024 && (long long)cdiv(hw, chunk) * b < min_wg) chunk >>= 1;
     dim3 g1(cdiv(hw, chunk), b);
-    // lab8 holds the selected class 0..C-1 or 0xff (ignore): one byte serves both class counts
-    if (C == 6)
-        pick_hist_kernel<6><<<g1, 256, (size_t)lds_regions * C * 4, st>>>(soft, classmax, regions, lab8, reg16, hist, ids, flag, counters,
-                                                                           hw, chunk, cutoff_top, cutoff_low, ignore_label, percent, R,
-                                                                           lds_regions);
-    else
-        pick_hist_kernel<7><<<g1, 256, (size_t)lds_regions * C * 4, st>>>(soft, classmax, regions, lab8, reg16, hist, ids, flag, counters,
-                                                                           hw, chunk, cutoff_top, cutoff_low, ignore_label, percent, R,
-                                                                           lds_regions);
-    RGDA_CHECK_LAUNCH();
+    // lab8 holds the selected class 0..C-1 or 0xff (ignore): one byte serves every class count
+    const int rc = with_classes(C, [&](auto cc) {
+        pick_hist_kernel<decltype(cc)::value><<<g1, 256, (size_t)lds_regions * C * 4, st>>>(
+            soft, classmax, regions, lab8, reg16, hist, ids, flag, counters, hw, chunk, cutoff_top, cutoff_low, ignore_label,
+            percent, R, lds_regions);
+        RGDA_CHECK_LAUNCH();
+        return RGDA_OK;
+    });
+    if (rc != RGDA_OK) return rc;
     dim3 g3(min(cdiv(hw, 1024), 512), b);
     lrh_gather8_kernel<<<g3, 256, 0, st>>>(lab8, reg16, ids, out, hw, R, ignore_label);
     RGDA_CHECK_LAUNCH();
@@ -820,6 +819,12 @@ extern "C" int rgda_label_refine_sup(const float* feat, const float* protos, con
                       ws_bytes, stream);
 }
 
+// pearson_sim_kernel's k-slices: 16, and 8 from 15 classes on, where pc[C][k] + red[16][32][C+1] passes the 160 KB of LDS
+// at k = 2048 (C = 16: 162 KB; with 8 slices 145 KB)
+static constexpr int refine_slices(int C) { return C <= 14 ? 16 : 8; }
+static size_t refine_lds(int C, int k) { return ((size_t)C * k + (size_t)refine_slices(C) * 32 * (C + 1)) * 4; }   // pc | red
+size_t refine_lds_bytes(int C, int k) { return refine_lds(C, k); }
+
 // the launches of refine_run for one class count (the workspace is laid out and cleared by the caller)
 template <int C>
 static int refine_launch(const float* feat, const float* protos, const float* p1, const float* p2, const float* soft,
@@ -833,8 +838,8 @@ static int refine_launch(const float* feat, const float* protos, const float* p1
     if (pview) {
     proto_center_kernel<<<c, 256, 0, st>>>(protos, pc, pstd, k);
     RGDA_CHECK_LAUNCH();
-    constexpr int PX = 32, SL = 16;
-    size_t lds = ((size_t)C * k + SL * PX * (C + 1)) * 4;       // pc[C][k] then red[SL][PX][C+1]
+    constexpr int PX = 32, SL = refine_slices(C);
+    const size_t lds = refine_lds(C, k);
     dim3 g1(cdiv(hw, PX), b);
     if (lds > 64 * 1024 &&
         hipFuncSetAttribute((const void*)pearson_sim_kernel<C, PX, SL>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -870,9 +875,10 @@ static int refine_run(const float* feat, const float* protos, const float* p1, c
     if (!soft || !out || !ws) return RGDA_ERR_ARG;
     const bool pview = views & 1, lview = views & 2;
     if ((pview && (!feat || !protos)) || (lview && (!p1 || !p2))) return RGDA_ERR_ARG;
-    if (c != 6 && c != 7) return RGDA_ERR_UNSUPPORTED;   // ISPRS: 6 classes (regda/datasets/isprsda.py:18-26), LoveDA: 7
+    if (!class_count_ok(c)) return RGDA_ERR_UNSUPPORTED;   // ISPRS: 6 classes (regda/datasets/isprsda.py:18-26), LoveDA: 7
     if (b <= 0 || (pview && (k < 2 || k > 4096 || (k & 3))) || h <= 0 || w <= 0 || H <= 0 || W <= 0 || !(temp > 0.f))
         return RGDA_ERR_ARG;
+    if (pview && refine_lds(c, k) > RGDA_LDS_MAX) return RGDA_ERR_UNSUPPORTED;          // the prototypes do not fit in LDS
     if (ws_bytes < (sup ? rgda_label_refine_sup_workspace(b, c, h, w, max_regions) : rgda_label_refine_workspace(b, c, h, w)))
         return RGDA_ERR_WORKSPACE;
     char* base = (char*)ws;
@@ -884,11 +890,10 @@ static int refine_run(const float* feat, const float* protos, const float* p1, c
     off += align256((size_t)c * 4);
     float* pc = (float*)(base + off);
     if (zero_bytes(classmax, (size_t)b * c * 4 + 16, stream) != RGDA_OK) return RGDA_ERR_LAUNCH;
-    if (c == 6)
-        return refine_launch<6>(feat, protos, p1, p2, soft, sup, max_regions, out, b, k, h, w, H, W, temp, views, base, sim, classmax,
-                                pstd, pc, stream);
-    return refine_launch<7>(feat, protos, p1, p2, soft, sup, max_regions, out, b, k, h, w, H, W, temp, views, base, sim, classmax, pstd,
-                            pc, stream);
+    return with_classes(c, [&](auto cc) {
+        return refine_launch<decltype(cc)::value>(feat, protos, p1, p2, soft, sup, max_regions, out, b, k, h, w, H, W, temp, views,
+                                                  base, sim, classmax, pstd, pc, stream);
+    });
 }
 
 // --------------------------------------------------------------------------------------
@@ -977,7 +982,7 @@ __global__ void __launch_bounds__(256) downscale_label_kernel(const int64_t* __r
     }
 }
 
-// Fast form for scale 16 and C in {6, 7} (the RegDA configurations: 512 -> 32, six ISPRS or seven LoveDA classes +
+// Fast form for scale 16 and C <= 7 (the RegDA configurations: 512 -> 32, six ISPRS or seven LoveDA classes +
 // ignore): one workgroup per ROW of low-res cells.  A thread owns two label columns of the 16-row band (16-byte loads,
 // fully coalesced 4 KB rows) and counts its 32 labels in 9-bit fields of one 64-bit word; the eight threads of a cell add
 // their words with DPP row shifts (no LDS, no atomics), the first of them picks the class.  (The one-workgroup-per-cell
@@ -1057,6 +1062,84 @@ __global__ void __launch_bounds__(256) downscale_label16_kernel(const int64_t* _
     if (threadIdx.x < C && wg_cnt[threadIdx.x]) atomicAdd(&cnt[threadIdx.x], (float)wg_cnt[threadIdx.x]);
 }
 
+// The same pass for 8..16 classes, where C fields of 9 bits no longer fit one word: NW = ceil(C / 7) 64-bit words of seven
+// fields, class l in field l % 7 of word l / 7 (eight classes: 2 words, 15 and 16: 3), the ignore count again 256 minus
+// the class sum.  A label adds to each word through a select on its word index, never an index into `packed` (a
+// run-time index would put the words in scratch); the eight threads of a cell add word by word.  The decision is the
+// one above: ratios count / 256 in fp32, strict > in class order with ignore last (the first maximum wins, a class tied
+// with ignore wins), a best ratio below min_ratio is ignore (exactly 0.75 is kept).
+template <int C>
+__global__ void __launch_bounds__(256) downscale_label16_wide_kernel(const int64_t* __restrict__ label, int64_t* label_ds,
+                                                                     float* cnt, int* flag, int h, int w,
+                                                                     int ignore_label, float min_ratio) {
+    static_assert(C >= 8 && C <= 16, "2 or 3 words of seven 9-bit class fields");
+    constexpr int NW = (C + 6) / 7;
+    const int W = w * 16;
+    const int b = blockIdx.y / h, y = blockIdx.y % h;
+    const int col = (blockIdx.x * 256 + threadIdx.x) * 2;           // first of this thread's two columns
+    unsigned long long packed[NW];
+#pragma unroll
+    for (int q = 0; q < NW; ++q) packed[q] = 0;
+    int bad = 0;
+    if (col < W) {
+        const int64_t* src = label + ((size_t)b * h * 16 + (size_t)y * 16) * W + col;
+        longlong2 rows[16];                                          // the whole band in flight at once
+#pragma unroll
+        for (int r = 0; r < 16; ++r) rows[r] = *(const longlong2*)(src + (size_t)r * W);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const longlong2 v = rows[r];
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const long long l = k ? v.y : v.x;
+                if (l == ignore_label) continue;
+                if (l < 0 || l >= C) { bad = 1; continue; }
+                const int q = (int)l / 7;
+                const unsigned long long inc = 1ull << (9 * ((int)l - 7 * q));
+#pragma unroll
+                for (int u = 0; u < NW; ++u) packed[u] += (q == u) ? inc : 0ull;
+            }
+        }
+    }
+    if (bad) atomicOr(flag, 2);
+    // sum over the 8 threads (16 columns) of a cell: lanes 8k .. 8k+7 of a wave
+#pragma unroll
+    for (int u = 0; u < NW; ++u) {
+#pragma unroll
+        for (int o = 1; o < 8; o <<= 1) {
+            const unsigned lo = (unsigned)packed[u], hi = (unsigned)(packed[u] >> 32);
+            packed[u] += ((unsigned long long)(unsigned)__shfl_xor((int)hi, o, 64) << 32) | (unsigned)__shfl_xor((int)lo, o, 64);
+        }
+    }
+    __shared__ int wg_cnt[C];                                        // cells of this workgroup per class
+    if (threadIdx.x < C) wg_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    if ((threadIdx.x & 7) == 0 && col < W) {
+        const int x = col / 16;
+        int n[C + 1];
+        n[C] = 256;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            n[c] = (int)((packed[c / 7] >> (9 * (c % 7))) & 511u);
+            n[C] -= n[c];
+        }
+        float best = __fdiv_rn((float)n[0], 256.f);
+        int arg = 0;
+#pragma unroll
+        for (int c = 1; c <= C; ++c) {
+            const float r = __fdiv_rn((float)n[c], 256.f);
+            if (r > best) { best = r; arg = c; }        // strict >: the first maximum, a class tied with ignore wins
+        }
+        long long o = arg;
+        if (arg == C) o = ignore_label;
+        if (best < min_ratio) o = ignore_label;
+        label_ds[((size_t)b * h + y) * w + x] = o;
+        if (o != ignore_label) atomicAdd(&wg_cnt[(int)o], 1);
+    }
+    __syncthreads();
+    if (threadIdx.x < C && wg_cnt[threadIdx.x]) atomicAdd(&cnt[threadIdx.x], (float)wg_cnt[threadIdx.x]);
+}
+
 // one workgroup per feature channel k: its 256 threads walk that channel's hw values of every image (image after
 // image), the six per-class sums are reduced wave -> LDS -> thread in a fixed order and leave with plain stores -- no
 // atomics, bit-reproducible prototypes
@@ -1111,7 +1194,7 @@ extern "C" int rgda_proto_stats(const float* feat, const int64_t* label, int64_t
                                 int scale, int ignore_label, float min_ratio, void* stats, size_t stats_bytes,
                                 rgda_stream_t stream) {
     if (!feat || !label || !label_ds || !stats) return RGDA_ERR_ARG;
-    if (c != 6 && c != 7) return RGDA_ERR_UNSUPPORTED;            // ISPRS (6) and LoveDA (7)
+    if (!class_count_ok(c)) return RGDA_ERR_UNSUPPORTED;
     if (b <= 0 || k <= 0 || h <= 0 || w <= 0 || scale <= 1) return RGDA_ERR_ARG;
     if (stats_bytes < rgda_proto_update_workspace(c, k)) return RGDA_ERR_WORKSPACE;
     hipStream_t st = to_stream(stream);
@@ -1120,19 +1203,21 @@ extern "C" int rgda_proto_stats(const float* feat, const int64_t* label, int64_t
     int* flag = (int*)(cnt + c);
     if (zero_bytes(stats, rgda_proto_update_workspace(c, k), stream) != RGDA_OK) return RGDA_ERR_LAUNCH;
     const dim3 g16(cdiv(w * 8, 256), b * h);
-    if (scale == 16 && !(w & 1) && c == 6)
-        downscale_label16_kernel<6><<<g16, 256, 0, st>>>(label, label_ds, cnt, flag, h, w, ignore_label, min_ratio);
-    else if (scale == 16 && !(w & 1))
-        downscale_label16_kernel<7><<<g16, 256, 0, st>>>(label, label_ds, cnt, flag, h, w, ignore_label, min_ratio);
-    else
-        downscale_label_kernel<<<b * h * w, 256, 0, st>>>(label, label_ds, cnt, flag, h, w, scale, c, ignore_label, min_ratio);
-    RGDA_CHECK_LAUNCH();
-    if (c == 6)
-        proto_accum_kernel<6><<<k, 256, 0, st>>>(feat, label_ds, sums, k, h * w, b);
-    else
-        proto_accum_kernel<7><<<k, 256, 0, st>>>(feat, label_ds, sums, k, h * w, b);
-    RGDA_CHECK_LAUNCH();
-    return RGDA_OK;
+    return with_classes(c, [&](auto cc) {
+        constexpr int C = decltype(cc)::value;
+        if (scale == 16 && !(w & 1)) {
+            if constexpr (C <= 7)
+                downscale_label16_kernel<C><<<g16, 256, 0, st>>>(label, label_ds, cnt, flag, h, w, ignore_label, min_ratio);
+            else
+                downscale_label16_wide_kernel<C><<<g16, 256, 0, st>>>(label, label_ds, cnt, flag, h, w, ignore_label, min_ratio);
+        } else {
+            downscale_label_kernel<<<b * h * w, 256, 0, st>>>(label, label_ds, cnt, flag, h, w, scale, c, ignore_label, min_ratio);
+        }
+        RGDA_CHECK_LAUNCH();
+        proto_accum_kernel<C><<<k, 256, 0, st>>>(feat, label_ds, sums, k, h * w, b);
+        RGDA_CHECK_LAUNCH();
+        return RGDA_OK;
+    });
 }
 
 // local = sums / (cnt + 1e-7), the old prototype where cnt < 1 (alignment.py:318-321), then the EMA (:435-438)
@@ -1186,14 +1271,12 @@ __global__ void __launch_bounds__(256) teacher_probs_kernel(const float* __restr
 extern "C" int rgda_teacher_probs(const float* p1, const float* p2, float* probs, int b, int c, int h, int w, int H,
                                   int W, rgda_stream_t stream) {
     if (!p1 || !p2 || !probs || b <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return RGDA_ERR_ARG;
-    if (c != 6 && c != 7) return RGDA_ERR_UNSUPPORTED;            // ISPRS (6) and LoveDA (7)
     dim3 g(cdiv(W, 256), H, b);
-    if (c == 6)
-        teacher_probs_kernel<6><<<g, 256, 0, to_stream(stream)>>>(p1, p2, probs, h, w, H, W);
-    else
-        teacher_probs_kernel<7><<<g, 256, 0, to_stream(stream)>>>(p1, p2, probs, h, w, H, W);
-    RGDA_CHECK_LAUNCH();
-    return RGDA_OK;
+    return with_classes(c, [&](auto cc) {
+        teacher_probs_kernel<decltype(cc)::value><<<g, 256, 0, to_stream(stream)>>>(p1, p2, probs, h, w, H, W);
+        RGDA_CHECK_LAUNCH();
+        return RGDA_OK;
+    });
 }
 
 // --------------------------------------------------------------------------------------

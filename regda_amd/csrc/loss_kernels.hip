@@ -22,7 +22,7 @@
 namespace {
 
 constexpr int KIND_CE = 0;               // rgda_upsample_ce: a kind of this file only, not an rgda_loss_kind
-constexpr size_t MAX_ROW_LDS = 150 * 1024;   // dynamic LDS of the grad pass: the widest row served
+constexpr size_t MAX_ROW_LDS = RGDA_LOSS_ROW_LDS_MAX;   // dynamic LDS of the grad pass: the widest row served
 constexpr int GHM_BINS = 30;
 constexpr int SEL_PASSES = 6;
 constexpr int SEL_BINS = 2048;
@@ -591,14 +591,14 @@ static int run_kind(int kind, const LossCall& a, rgda_stream_t stream) {
     }
 }
 
-// the class counts served: ISPRS (6) and LoveDA (7)
-static bool class_count_ok(int c) { return c == 6 || c == 7; }
-
+// the class counts served: common.h, class_count_ok
 static int run_kind(int kind, int c, const LossCall& a, rgda_stream_t stream) {
-    return c == 6 ? run_kind<6>(kind, a, stream) : run_kind<7>(kind, a, stream);
+    return with_classes(c, [&](auto cc) { return run_kind<decltype(cc)::value>(kind, a, stream); });
 }
 
 }  // namespace
+
+size_t loss_row_lds_bytes(int c, int w, int W, bool want) { return grad_lds(c, w, W, want); }
 
 extern "C" size_t rgda_upsample_ce_workspace(int b, int c, int h, int w, int H, int W) {
     (void)W;

@@ -1737,14 +1737,13 @@ __global__ void __launch_bounds__(256) classifier_bwd_reduce_kernel(const float*
 extern "C" int rgda_classifier_fwd(const void* hidden, int ldh, const float* w, const float* bias, float* logits,
                                    int N, int HW, int C, int ncls, rgda_stream_t stream) {
     if (!hidden || !w || !bias || !logits || N <= 0 || HW <= 0 || C <= 0 || (C & 7) || (ldh & 7)) return RGDA_ERR_ARG;
-    if (ncls != 6 && ncls != 7) return RGDA_ERR_UNSUPPORTED;     // ISPRS (6) and LoveDA (7)
     long long M = (long long)N * HW;
-    if (ncls == 6)
-        classifier_fwd_kernel<6><<<cdiv(M, 4), 256, 0, to_stream(stream)>>>((const bf16_t*)hidden, ldh, w, bias, logits, N, HW, C);
-    else
-        classifier_fwd_kernel<7><<<cdiv(M, 4), 256, 0, to_stream(stream)>>>((const bf16_t*)hidden, ldh, w, bias, logits, N, HW, C);
-    RGDA_CHECK_LAUNCH();
-    return RGDA_OK;
+    return with_classes(ncls, [&](auto cc) {
+        classifier_fwd_kernel<decltype(cc)::value><<<cdiv(M, 4), 256, 0, to_stream(stream)>>>((const bf16_t*)hidden, ldh, w, bias,
+                                                                                              logits, N, HW, C);
+        RGDA_CHECK_LAUNCH();
+        return RGDA_OK;
+    });
 }
 
 extern "C" size_t rgda_classifier_bwd_workspace(int64_t M, int C, int ncls) {
@@ -1757,6 +1756,10 @@ static int classifier_bwd_run(const void* hidden, int ldh, const float* w, const
     const size_t lds = (size_t)256 * 8 * NC * 4;         // [rpb][vpb*8][NC] floats, rpb * vpb = 256
     long long M = (long long)N * HW;
     RowLayout L = row_layout(C);
+    // (from 9 classes on the dW reduction needs more than the default 64 KB of dynamic LDS: 128 KB at 16)
+    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)classifier_bwd_kernel<NC>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int)lds) != hipSuccess)
+        return RGDA_ERR_LAUNCH;
     if (ws) {
         // 64 rows per workgroup (the whole chip), per-workgroup partial dW / db in the workspace, then one small
         // deterministic reduction: ncls*C atomics per workgroup onto the SAME addresses forced few, long workgroups
@@ -1789,7 +1792,7 @@ extern "C" int rgda_classifier_bwd(const void* hidden, int ldh, const float* w, 
         (lddh & 7))
         return RGDA_ERR_ARG;
     hipStream_t st = to_stream(stream);
-    if (ncls == 6) return classifier_bwd_run<6>(hidden, ldh, w, glogits, dhidden, lddh, dw, db, N, HW, C, ws, ws_bytes, st);
-    if (ncls == 7) return classifier_bwd_run<7>(hidden, ldh, w, glogits, dhidden, lddh, dw, db, N, HW, C, ws, ws_bytes, st);
-    return RGDA_ERR_UNSUPPORTED;
+    return with_classes(ncls, [&](auto cc) {
+        return classifier_bwd_run<decltype(cc)::value>(hidden, ldh, w, glogits, dhidden, lddh, dw, db, N, HW, C, ws, ws_bytes, st);
+    });
 }

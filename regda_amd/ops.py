@@ -11,6 +11,38 @@ import torch
 from ._lib import lib
 
 
+# The class counts every class-specific kernel serves (regda_amd/csrc/common.h: with_classes); other counts return
+# RGDA_ERR_UNSUPPORTED, raised here as ValueError.
+MIN_CLASSES, MAX_CLASSES = 6, 16
+
+
+def check_class_count(c, who='class_num'):
+    """ValueError unless MIN_CLASSES <= c <= MAX_CLASSES."""
+    if not MIN_CLASSES <= int(c) <= MAX_CLASSES:
+        raise ValueError(f'{who}: {c} classes; the kernels serve {MIN_CLASSES} <= class_num <= {MAX_CLASSES}')
+
+
+_LDS_LOSS_ROW, _LDS_PCL, _LDS_REFINE = 0, 1, 2      # rgda_class_lds `which` (include/rgda_hip.h)
+
+
+def check_step_shape(c, k, H, W, who='step'):
+    """ValueError where a training step at c classes, k prototype channels and H x W tiles (logits at output stride 16)
+    would reach a kernel that cannot serve it -- so that a step refuses before its first launch, never halfway.  The
+    LDS needs and limits are the library's own (rgda_class_lds)."""
+    check_class_count(c, who)
+    L = lib()
+    w = (int(W) + 15) // 16
+    row, lim = L.size('rgda_class_lds', _LDS_LOSS_ROW, c, w, W), L.size('rgda_class_lds_limit', _LDS_LOSS_ROW)
+    if row > lim:
+        raise ValueError(f'{who}: {c} classes at {W}-pixel rows need {row} B of LDS in the fused upsample + loss row pass, '
+                         f'above its limit of {lim} B (16 classes: W <= 1008; 1024 x 1024 tiles serve up to 15)')
+    for which, name in ((_LDS_PCL, 'PrototypeContrastiveLoss'), (_LDS_REFINE, 'label_refine')):
+        need, lim = L.size('rgda_class_lds', which, c, k, 0), L.size('rgda_class_lds_limit', which)
+        if need > lim:
+            raise ValueError(f'{who}: {c} prototypes of {k} channels need {need} B of LDS in {name}, above the {lim} B '
+                             f'of gfx950 (16 classes serve k = 2048)')
+
+
 _STREAM = None      # cached raw hipStream_t of the stream selected with use_stream() (saves ~8 us per launch)
 
 

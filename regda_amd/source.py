@@ -36,6 +36,7 @@ class SourceStep(SSLStep):
         without align_domain.  images_t may be None when align_domain is off (no target forward then)."""
         if self.align_domain and images_t is None:
             raise ValueError('SourceStep(align_domain=True) needs the target images')
+        self._check_shape(images_s, images_t if self.align_domain else None)
         ops.set_f32(self.lr_dev, lr)
         with ops.use_stream(torch.cuda.current_stream()):
             return self._step(images_s, label_s, images_t)

@@ -24,8 +24,10 @@ class SSLStep:
                  process_group=None, overlap_wgrad=True, overlap_comm=True, class_balancer_s=None,
                  class_balancer_t=None, grad_payload='fp32', comm=None, loss_s='CrossEntropy', loss_t='none',
                  uvem_m=0.2, uvem_t=0.7, uvem_g=4.0):
+        ops.check_class_count(class_num, type(self).__name__)
         self.model = model
         self.C, self.ig = class_num, ignore_label
+        self._shape_ok = None
         self.momentum, self.wd, self.max_norm = momentum, weight_decay, max_norm
         self.top, self.low, self.percent = cutoff_top, cutoff_low, percent
         self.pdecay, self.temp = proto_decay, refine_temp
@@ -79,6 +81,7 @@ class SSLStep:
     def step(self, images_s, label_s, images_t, soft_t, regs_t, lr):
         """One SSL iteration.  Returns device tensors (loss_source, loss_target, grad_norm_sq): nothing here
         synchronises with the host."""
+        self._check_shape(images_s, images_t)
         if self._graph is not None:
             return self._replay(images_s, label_s, images_t, soft_t, regs_t, lr)
         if self._plan is not None:
@@ -87,10 +90,19 @@ class SSLStep:
         with ops.use_stream(torch.cuda.current_stream()):
             return self._step(images_s, label_s, images_t, soft_t, regs_t)
 
+    def _check_shape(self, *images):
+        """ValueError before the first launch where a kernel of the step cannot serve these tiles (ops.check_step_shape)."""
+        for x in images:
+            if x is None or tuple(x.shape[-2:]) == self._shape_ok:
+                continue
+            ops.check_step_shape(self.C, self.prototypes.shape[-1], x.shape[-2], x.shape[-1], type(self).__name__)
+            self._shape_ok = tuple(x.shape[-2:])
+
     def capture(self, images_s, label_s, images_t, soft_t, regs_t):
         """Capture one whole step (both streams) into a hipGraph; later `step()` calls replay it.  The step is a
         static launch sequence over fixed shapes, so replay removes the ~20 ms of per-step host launch work.
         Call after at least one eager step (momentum initialisation is a different kernel variant)."""
+        self._check_shape(images_s, images_t)
         assert not self.first, 'run one eager step before capture()'
         if self.world > 1:
             raise RuntimeError('whole-step graphs are single-GPU; the multi-GPU path stays eager')
@@ -139,6 +151,7 @@ class SSLStep:
         streams, same results as the eager step, a fraction of the host time.  Call after at least one eager step
         (the first step initialises the momentum with another kernel variant).  Inputs are copied into static
         buffers at every replay; the returned tensors (losses, `last_hard`, ...) are overwritten by the next step."""
+        self._check_shape(images_s, images_t)
         assert not self.first, 'run one eager step before record_plan()'
         assert self._graph is None and self._plan is None
         self._static = self._static_inputs(images_s, label_s, images_t, soft_t, regs_t)
