@@ -239,8 +239,10 @@ int rgda_class_count(const int64_t* label, int32_t* cnt, int64_t n, int c, rgda_
  *   res_relu_mask : NULL or uint8 [N*Ho*Wo][Cout/8] sign bits (rgda_bn_train_apply): res is added only where its
  *          bit is set -- the gradient of a residual connection gated by the ReLU it passed through, so that gated
  *          copy never has to be written to memory
- *   stats: NULL or rgda_stat_t[RGDA_STAT_REPLICAS][2][Cout] (FRAC_FWD); per-channel sum and sum of squares of the
- *          (bf16-rounded) outputs are accumulated order-independently (BatchNorm batch stats)
+ *   stats: NULL or rgda_stat_t[stat_groups][RGDA_STAT_REPLICAS][2][Cout] (FRAC_FWD); per-channel sum and sum of squares of
+ *          the (bf16-rounded) outputs are accumulated order-independently (BatchNorm batch stats)
+ *   stat_groups: the statistics groups, equal blocks of WHOLE images: N % stat_groups != 0 is RGDA_ERR_ARG (here and in
+ *          rgda_conv2d_grouped, rgda_conv2d_bnbwd's `groups` and rgda_conv2d_bnin's, as in rgda_stem_conv)
  *   mode 0: y[n,ho,wo] = sum x[n, ho*stride-pad+kh*dil, wo*stride-pad+kw*dil] * w
  *   mode 1: y[n,ho,wo] = sum x[n, (ho+pad-kh*dil)/stride, (wo+pad-kw*dil)/stride] * w
  *           (terms with a non-integer or out-of-range source are zero)

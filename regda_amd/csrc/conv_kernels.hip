@@ -1307,8 +1307,10 @@ static int conv_use_halo(long long M, int Cout, int Cin, int kh, int kw, int str
     if (const char* e = TUNE_ENV("RGDA_HALO_MIN")) min_tiles = atoi(e);                 // tuning experiments only
     int min8 = 100;
     if (const char* e = TUNE_ENV("RGDA_HALO_MIN8")) min8 = atoi(e);                     // tuning experiments only
-    if ((long long)9 * Cin >= 4096 && !(H & 7) && !(rows_per_group % 256) && (M / 256) * cdiv(Cout, 128) >= min8) return 8;
-    if ((long long)9 * Cin >= 2048 && dil == 1 && !(H & 3) && !(rows_per_group % 128) && (M / 128) * cdiv(Cout, 128) >= min_tiles) return 4;
+    // (a tile is TR image rows x 32 columns: TR * W memory rows, inside one statistics group -- always so for the whole-image
+    // groups conv2d_launch accepts)
+    if ((long long)9 * Cin >= 4096 && !(H & 7) && !(rows_per_group % (8 * W)) && (M / 256) * cdiv(Cout, 128) >= min8) return 8;
+    if ((long long)9 * Cin >= 2048 && dil == 1 && !(H & 3) && !(rows_per_group % (4 * W)) && (M / 128) * cdiv(Cout, 128) >= min_tiles) return 4;
     return 0;
 }
 
@@ -1346,7 +1348,10 @@ struct BnEvalFuse { const float* rm; const float* rv; const float* gamma; const 
 // activation with rgda_bn_train_apply and runs the plain convolution)
 static int conv_bnin_kind(long long M, int Cout, int Cin, int kh, int kw, int stride, int pad, int dil, int H, int W, int Ho,
                           int Wo, int groups) {
-    if (groups < 1 || (M % groups) || Cin > RGDA_BNIN_MAX_C || (Cin & 63)) return 0;
+    // (statistics groups are whole images, as conv2d_launch requires: N = M / (Ho * Wo) images)
+    if (groups < 1 || Ho <= 0 || Wo <= 0 || (M % ((long long)Ho * Wo)) || (M / ((long long)Ho * Wo)) % groups ||
+        Cin > RGDA_BNIN_MAX_C || (Cin & 63))
+        return 0;
     const int rpg = (int)(M / groups);
     if (const int tr = conv_use_halo(M, Cout, Cin, kh, kw, stride, pad, dil, H, W, Ho, Wo, rpg))
         return (tr == 4) ? 1 : (dil == 1 ? 2 : 0);          // (dilation 2: its 160 KB of LDS leave no room for the table)
@@ -1403,7 +1408,9 @@ static int conv2d_launch(const void* x, int ldx, const void* wgt, void* y, int l
     hipStream_t st = to_stream(stream);
     // tile choice: fill 256 CUs (2 workgroups each); prefer the big tile when it still gives >= 512 groups
     if (stat_groups < 1) stat_groups = 1;
-    if (M % stat_groups) return RGDA_ERR_ARG;
+    // a statistics group is a whole number of images: a tile of the halo kernels (TR image rows of one 32-column band)
+    // or of the operand-path BatchNorm (whose halo rows come from neighbouring image rows) then never spans two groups
+    if (N % stat_groups || M % stat_groups) return RGDA_ERR_ARG;
     a.rows_per_group = (int)(M / stat_groups);
     a.bn_y = a.bn_x = nullptr; a.bn_mask = nullptr; a.bn_mi = a.bn_nscale = nullptr; a.bn_ldy = a.bn_ldx = a.bn_rpi = a.bn_relu = 0;
     a.bn_gamma = a.bn_beta = nullptr;
