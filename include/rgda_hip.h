@@ -609,6 +609,34 @@ int rgda_window_accumulate(const float* tile, float* full, float* count, int N, 
                            int x1, int h, int w, int Th, int Tw, rgda_stream_t stream);
 int rgda_window_normalise(float* full, const float* count, int N, int C, int Hf, int Wf, rgda_stream_t stream);
 
+/* Batched sliding-window inference: the window loop of pre_slide with K windows per network forward.  A window is a row
+ * (image, y1, x1) of the int32 [K][3] DEVICE table `windows`; every window has the full tile size Th x Tw and lies inside
+ * its image (H >= Th, W >= Tw).  V = `views` is 1, or 8 (tta_predict's views (flip, k) = (v >> 2, v & 3), Th == Tw).
+ * A table row outside the images is not read: it sets *flag (optional, device int) to 1 and contributes zeros / nothing.
+ *
+ * rgda_window_gather: out f32 [K*V][C][Th][Tw], row w*V + v = view v of window w, bit for bit rgda_window_crop followed
+ * by rgda_dihedral_nchw(flip_first = 1).  The source is src_f32 (f32 [n][C][H][W]) or src_u8 (uint8 [n][H][W][3], HWC as
+ * imread returns it, C = 3) through lut (f32 [3][256], device: the rgda_augment_tiles normalisation table); exactly one.
+ *
+ * rgda_window_scatter: adds pred f32 [K*V][C][Th][Tw] into full f32 [n][C][H][W] and count f32 [n][1][H][W], bit for bit
+ * the sequential rgda_window_accumulate calls of the K windows in table order (with V = 8 each window's value is first
+ * the mean of its de-augmented views, scale 1/8 fused into the sum, in view order, as tta_predict forms it).  One thread
+ * per pixel of the flattened image rows [row0, row0 + rows) of the n*H rows, which must cover the K windows; no atomics.
+ * K <= 1024.
+ *
+ * rgda_window_finish: full /= count (rgda_window_normalise), then the first maximum over C into labels_u8 (uint8
+ * [n][H][W], C <= 256) and / or labels_i64 (int64 [n][H][W]) (rgda_argmax_nchw), and with y_true (int64 [n][H][W]) the
+ * confusion matrix cm int64 [C][C] += counts of the pixels with y_true >= 0 (rgda_confusion_accumulate; flag |= 1 on a
+ * label >= C; C <= 64).  Each output is optional; y_true and cm go together and need flag.
+ * Errors before any launch: null pointers, sizes outside the above (RGDA_ERR_ARG). */
+int rgda_window_gather(const float* src_f32, const uint8_t* src_u8, const float* lut, const int32_t* windows, int K,
+                       int views, int n, int C, int H, int W, int Th, int Tw, float* out, int* flag,
+                       rgda_stream_t stream);
+int rgda_window_scatter(const float* pred, const int32_t* windows, int K, int views, int n, int C, int H, int W, int Th,
+                        int Tw, int row0, int rows, float* full, float* count, int* flag, rgda_stream_t stream);
+int rgda_window_finish(float* full, const float* count, int n, int C, int H, int W, uint8_t* labels_u8,
+                       int64_t* labels_i64, const int64_t* y_true, int64_t* cm, int* flag, rgda_stream_t stream);
+
 /* tnf.interpolate(mode='bilinear', align_corners=True) of the soft labels to the dataset size
  * (regda/gast/pseudo_generation.py:135). */
 int rgda_resize_bilinear_ac(const float* src, float* dst, int N, int C, int h, int w, int H, int W,

@@ -880,6 +880,73 @@ def window_normalise(full, count):
     lib().call('rgda_window_normalise', full.data_ptr(), count.data_ptr(), n, c, Hf, Wf, _stream())
 
 
+def window_gather(src, windows, tile, views=1, lut=None, out=None, flag=None):
+    """rgda_window_gather: the network input of K windows, [K*views][C][Th][Tw] f32.  src: f32 [n][C][H][W], or uint8
+    [n][H][W][3] with `lut` (f32 [3][256] device table); windows: device int32 [K][3] rows (image, y1, x1); tile =
+    (Th, Tw); views 1 or 8 (tta_predict's order)."""
+    _need_cuda(src, windows, lut, out, flag)
+    th, tw = tile
+    if src.dtype == torch.uint8:
+        n, H, W, c = src.shape
+        if c != 3 or lut is None:
+            raise ValueError('window_gather: a uint8 source is [n][H][W][3] and needs lut')
+        f32, u8 = None, src.contiguous()
+    else:
+        if src.dtype != torch.float32 or src.dim() != 4:
+            raise ValueError('window_gather: the source is f32 [n][C][H][W] or uint8 [n][H][W][3]')
+        n, c, H, W = src.shape
+        f32, u8 = src.contiguous(), None
+    if windows.dtype != torch.int32 or windows.dim() != 2 or windows.shape[1] != 3 or not windows.is_contiguous():
+        raise ValueError('window_gather: windows must be a contiguous int32 [K][3] table')
+    k = windows.shape[0]
+    if out is None:
+        out = torch.empty(k * views, c, th, tw, device=src.device)
+    assert tuple(out.shape) == (k * views, c, th, tw) and out.dtype == torch.float32 and out.is_contiguous()
+    lib().call('rgda_window_gather', _p(f32), _p(u8), _p(lut), windows.data_ptr(), k, views, n, c, H, W, th, tw,
+               out.data_ptr(), _p(flag), _stream())
+    return out
+
+
+def window_scatter(pred, windows, full, count, rows, views=1, flag=None):
+    """rgda_window_scatter: full [n][C][H][W] / count [n][1][H][W] += the K windows of pred [K*views][C][Th][Tw], in table
+    order.  rows = (row0, nrows): the span of the flattened n*H image rows the windows cover."""
+    _need_cuda(pred, windows, full, count, flag)
+    n, c, H, W = full.shape
+    kv, cp, th, tw = pred.shape
+    k = windows.shape[0]
+    if kv != k * views or cp != c or tuple(count.shape) != (n, 1, H, W):
+        raise ValueError('window_scatter: pred %s, %d windows x %d views, full %s, count %s' %
+                         (tuple(pred.shape), k, views, tuple(full.shape), tuple(count.shape)))
+    assert pred.dtype == full.dtype == count.dtype == torch.float32 and windows.dtype == torch.int32
+    assert full.is_contiguous() and count.is_contiguous() and windows.is_contiguous()
+    lib().call('rgda_window_scatter', pred.contiguous().data_ptr(), windows.data_ptr(), k, views, n, c, H, W, th, tw,
+               int(rows[0]), int(rows[1]), full.data_ptr(), count.data_ptr(), _p(flag), _stream())
+
+
+def window_finish(full, count, labels=None, y_true=None, cm=None, flag=None):
+    """rgda_window_finish: full /= count in place, then (optionally) the argmax into `labels` (uint8 or int64 [n][H][W],
+    written in place) and the confusion matrix cm int64 [C][C] of the pixels with y_true >= 0 (int64 [n][H][W])."""
+    _need_cuda(full, count, labels, y_true, cm, flag)
+    n, c, H, W = full.shape
+    assert full.is_contiguous() and count.is_contiguous() and tuple(count.shape) == (n, 1, H, W)
+    u8 = i64 = None
+    if labels is not None:
+        assert tuple(labels.shape) == (n, H, W) and labels.is_contiguous()
+        if labels.dtype == torch.uint8:
+            u8 = labels
+        elif labels.dtype == torch.int64:
+            i64 = labels
+        else:
+            raise ValueError('window_finish: labels are uint8 or int64')
+    yt = None
+    if y_true is not None:
+        yt = y_true.to(full.device, torch.int64).contiguous()
+        assert yt.numel() == n * H * W and cm is not None and cm.dtype == torch.int64 and tuple(cm.shape) == (c, c)
+    lib().call('rgda_window_finish', full.data_ptr(), count.data_ptr(), n, c, H, W, _p(u8), _p(i64), _p(yt), _p(cm),
+               _p(flag), _stream())
+    return labels
+
+
 def resize_bilinear_ac(src, size):
     n, c, h, w = src.shape
     dst = torch.empty(n, c, size[0], size[1], device=src.device)

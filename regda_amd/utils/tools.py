@@ -111,24 +111,118 @@ def tta_predict(model, img):
     return out
 
 
-def pre_slide(model, image, num_classes=7, tile_size=(512, 512), tta=False):
-    """Sliding-window inference with overlap 1/2 (tools.py:61-97); returns the visit-count average (n, C, H, W)."""
-    image = image.contiguous().float()
-    n, c, H, W = image.shape
+def window_list(H, W, tile_size=(512, 512)):
+    """The windows pre_slide visits on an H x W image, in its order: a list of (y1, x1, h, w) -- exactly the arithmetic
+    of tools.py:61-97 (stride ceil(tile[0] / 2) on both axes; edge windows shifted back inside the image; none at all
+    when the image is much smaller than the tile)."""
     stride = ceil(tile_size[0] * (1 - 1 / 2))
     tile_rows = int(ceil((H - tile_size[0]) / stride) + 1)
     tile_cols = int(ceil((W - tile_size[1]) / stride) + 1)
-    full_probs = torch.zeros(n, num_classes, H, W, device=image.device)
-    count = torch.zeros(n, 1, H, W, device=image.device)
+    out = []
     for row in range(tile_rows):
         for col in range(tile_cols):
             x1, y1 = int(col * stride), int(row * stride)
             x2, y2 = min(x1 + tile_size[1], W), min(y1 + tile_size[0], H)
             x1, y1 = max(int(x2 - tile_size[1]), 0), max(int(y2 - tile_size[0]), 0)
-            h, w = y2 - y1, x2 - x1
-            img = image if (h, w) == (H, W) else ops.window_crop(image, y1, x1, h, w, h, w)
-            padded_img = pad_image(img, tile_size)
-            padded = tta_predict(model, padded_img) if tta else model(padded_img)
-            ops.window_accumulate(padded.contiguous(), full_probs, count, y1, x1, h, w)
+            out.append((y1, x1, y2 - y1, x2 - x1))
+    return out
+
+
+# one forward of the batched route stays below 2^27 input pixels: the widest activations (the stem's and layer 1's
+# outputs, the upsampled probabilities) hold at most 16 values per input pixel, so their offsets stay below 2^31
+MAX_WINDOW_PIXELS = 1 << 27
+
+
+def batched_slide_supported(shape, tile_size=(512, 512), tta=False):
+    """True where pre_slide(window_batch=K) runs the batched route for an image batch of `shape` (n, c, H, W) or (H, W):
+    the image is at least the tile in both dimensions (so every window is a whole tile) and, with TTA, the tile is
+    square (rot90 keeps its shape).  Otherwise pre_slide takes the per-window path."""
+    H, W = shape[-2:]
+    th, tw = tile_size
+    return H >= th and W >= tw and (not tta or th == tw)
+
+
+def check_window_batch(window_batch, tile_size=(512, 512), tta=False):
+    k = int(window_batch)
+    if k != window_batch or k < 1:
+        raise ValueError('window_batch must be a positive int, got %r' % (window_batch,))
+    if k * (8 if tta else 1) * tile_size[0] * tile_size[1] > MAX_WINDOW_PIXELS:
+        raise ValueError('window_batch=%d: %d windows x %d views of %dx%d pixels per forward exceed %d pixels' %
+                         (k, k, 8 if tta else 1, tile_size[0], tile_size[1], MAX_WINDOW_PIXELS))
+    return k
+
+
+def slide_accumulate(model, image, num_classes, tile_size=(512, 512), tta=False, window_batch=16, lut=None):
+    """The batched window loop without the final division: -> (full (n, C, H, W), count (n, 1, H, W)) as pre_slide holds
+    them before rgda_window_normalise.  image: f32 (n, c, H, W), or uint8 (n, H, W, 3) with `lut` (f32 [3][256] device
+    table), on the GPU; batched_slide_supported must hold.  Windows are taken image by image in pre_slide's order,
+    `window_batch` of them (x 8 views with tta) per forward."""
+    K = check_window_batch(window_batch, tile_size, tta)
+    if image.dtype == torch.uint8:
+        n, H, W, _ = image.shape
+    else:
+        n, _, H, W = image.shape
+    th, tw = tile_size
+    assert batched_slide_supported((H, W), tile_size, tta)
+    views = 8 if tta else 1
+    rows = [(i, y1, x1) for i in range(n) for (y1, x1, _, _) in window_list(H, W, tile_size)]
+    table = torch.tensor(rows, dtype=torch.int32).to(image.device, non_blocking=True)
+    full = torch.zeros(n, num_classes, H, W, device=image.device)
+    count = torch.zeros(n, 1, H, W, device=image.device)
+    for s in range(0, len(rows), K):
+        chunk = rows[s:s + K]
+        wins = table[s:s + len(chunk)]
+        batch = ops.window_gather(image, wins, tile_size, views, lut=lut)
+        pred = model(batch)
+        r0 = min(i * H + y1 for i, y1, _ in chunk)
+        r1 = max(i * H + y1 + th for i, y1, _ in chunk)
+        ops.window_scatter(pred.contiguous(), wins, full, count, (r0, r1 - r0), views)
+    return full, count
+
+
+def pre_slide(model, image, num_classes=7, tile_size=(512, 512), tta=False, window_batch=None):
+    """Sliding-window inference with overlap 1/2 (tools.py:61-97); returns the visit-count average (n, C, H, W).
+    window_batch=K: the windows of all n images go through the model K at a time (K x 8 views with tta), gathered and
+    scattered by one launch each (rgda_window_gather / _scatter); every value is placed and summed as the per-window
+    loop places and sums it.  Images smaller than the tile (and non-square tiles with tta) take the per-window path."""
+    image = image.contiguous().float()
+    if window_batch is not None:
+        check_window_batch(window_batch, tile_size, tta)
+        if batched_slide_supported(image.shape, tile_size, tta):
+            full, count = slide_accumulate(model, image, num_classes, tile_size, tta, window_batch)
+            ops.window_finish(full, count)
+            return full
+    n, c, H, W = image.shape
+    full_probs = torch.zeros(n, num_classes, H, W, device=image.device)
+    count = torch.zeros(n, 1, H, W, device=image.device)
+    for y1, x1, h, w in window_list(H, W, tile_size):
+        img = image if (h, w) == (H, W) else ops.window_crop(image, y1, x1, h, w, h, w)
+        padded_img = pad_image(img, tile_size)
+        padded = tta_predict(model, padded_img) if tta else model(padded_img)
+        ops.window_accumulate(padded.contiguous(), full_probs, count, y1, x1, h, w)
     ops.window_normalise(full_probs, count)
     return full_probs
+
+
+def window_groups(loader, tile_size=(512, 512), tta=False, window_batch=16):
+    """Consecutive loader items (image (b, c, H, W), meta) in groups for the batched route: items of one shape are
+    collected until they hold at least `window_batch` windows (the last group of a shape may hold fewer).  An item the
+    batched route does not serve (batched_slide_supported) comes as a group of its own.  Yields lists of items, in
+    loader order."""
+    group, shape, nwin = [], None, 0
+    for item in loader:
+        shp = tuple(item[0].shape)
+        if group and shp != shape:
+            yield group
+            group, nwin = [], 0
+        if not batched_slide_supported(shp, tile_size, tta):
+            yield [item]
+            continue
+        group.append(item)
+        shape = shp
+        nwin += shp[0] * len(window_list(shp[2], shp[3], tile_size))
+        if nwin >= window_batch:
+            yield group
+            group, nwin = [], 0
+    if group:
+        yield group

@@ -1,0 +1,176 @@
+"""Sliding-window inference: the per-window path against window_batch = K.
+
+    python scripts/dev/infer_bench.py [--models resnet101,resnet50] [--ks 4,8,16,32] [--tiles 64] [--eval-items 200]
+                                      [--scene 6000] [--sections invariance,tiles,image,scene,eval]
+
+Random-init Deeplabv2 (6 classes, confident classifiers as in bench.py), eval mode, synthetic inputs.  Prints one JSON
+line per measurement:
+  invariance  the eval forward of one sample at batch 1 against the same sample inside a batch of K: bitwise equal?
+              (max |diff| and the argmax disagreement rate where not), 512^2 and 1024^2
+  tiles       512^2 items, n = 1 each, grouped as evaluate groups them: tiles/s and host ms per tile, tta off / on
+  image       one 1024^2 (LoveDA-sized) image
+  scene       a uint8 scene through predict_scene (per-window: window_batch=None)
+  eval        one evaluate() call over `--eval-items` 512^2 items, wall time and peak device memory
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+
+
+def build(rt, ncls=6, seed=0):
+    from regda_amd.models.Encoder import Deeplabv2
+    torch.manual_seed(seed)
+    m = Deeplabv2(dict(backbone=dict(resnet_type=rt, output_stride=16, pretrained=False), multi_layer=True,
+                       cascade=False, use_ppm=True, ppm=dict(num_classes=ncls, use_aux=False, fc_dim=2048),
+                       inchannels=2048, num_classes=ncls, is_ins_norm=True))
+    with torch.no_grad():
+        for head in ('layer5', 'layer6'):
+            m.convs[f'{head}.conv_last.4'].w.mul_(40.0)
+    m.sync_weights()
+    m.eval()
+    return m
+
+
+def emit(**kw):
+    print(json.dumps(kw), flush=True)
+
+
+def timed(fn, reps=1):
+    """-> (wall s, host s): host = until the last launch is issued, wall = until the device is done."""
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    t1 = time.perf_counter()
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    return (t2 - t0) / reps, (t1 - t0) / reps
+
+
+def invariance(m, rt, ks):
+    g = torch.Generator().manual_seed(1)
+    for size in (512, 1024):
+        x = torch.randn(max(ks), 3, size, size, generator=g).cuda()
+        one = m(x[:1].contiguous())
+        for k in ks:
+            if k * size * size > (1 << 27):
+                continue
+            got = m(x[:k].contiguous())[:1]
+            d = (got - one).abs()
+            emit(section='invariance', model=rt, size=size, batch=k, bitwise=bool(torch.equal(got, one)),
+                 max_abs=float(d.max()), argmax_disagree=float((got.argmax(1) != one.argmax(1)).float().mean()))
+
+
+def tiles(m, rt, ks, n_items, size=512):
+    from regda_amd.utils.tools import pre_slide, window_groups
+    g = torch.Generator().manual_seed(2)
+    items = [(torch.randn(1, 3, size, size, generator=g).cuda(), None) for _ in range(n_items)]
+    for tta in (False, True):
+        for k in [None] + ks:
+            def run():
+                if k is None:
+                    for x, _ in items:
+                        pre_slide(m, x, num_classes=6, tta=tta)
+                else:
+                    for grp in window_groups(items, tta=tta, window_batch=k):
+                        pre_slide(m, torch.cat([x for x, _ in grp]), num_classes=6, tta=tta, window_batch=k)
+            try:
+                run()
+                wall, host = timed(run)
+            except (RuntimeError, ValueError) as e:
+                emit(section='tiles', model=rt, size=size, tta=tta, window_batch=k, error=str(e)[:200])
+                continue
+            emit(section='tiles', model=rt, size=size, tta=tta, window_batch=k, tiles_per_s=round(n_items / wall, 2),
+                 host_ms_per_tile=round(1e3 * host / n_items, 3), wall_ms_per_tile=round(1e3 * wall / n_items, 3))
+
+
+def image(m, rt, ks, size=1024):
+    from regda_amd.utils.tools import pre_slide, window_list
+    x = torch.randn(1, 3, size, size, generator=torch.Generator().manual_seed(3)).cuda()
+    nw = len(window_list(size, size))
+    for tta in (False, True):
+        for k in [None] + ks:
+            fn = lambda: pre_slide(m, x, num_classes=6, tta=tta, window_batch=k)     # noqa: E731
+            fn()
+            wall, host = timed(fn, 3)
+            emit(section='image', model=rt, size=size, windows=nw, tta=tta, window_batch=k, ms=round(1e3 * wall, 2),
+                 host_ms=round(1e3 * host, 2), tiles_per_s=round(nw / wall, 2))
+
+
+def scene(m, rt, ks, size):
+    import numpy as np
+    from configs import ToPotsdam
+    from regda_amd.utils.infer import predict_scene
+    from regda_amd.utils.tools import window_list
+    s = torch.from_numpy(np.random.default_rng(4).integers(0, 256, (size, size, 3), dtype=np.uint8))
+    nw = len(window_list(size, size))
+    runs = [(None, False)] + [(k, False) for k in ks] + [(16, True)]
+    for k, tta in runs:
+        torch.cuda.reset_peak_memory_stats()
+        fn = lambda: predict_scene(m, s, ToPotsdam, 6, tta=tta, window_batch=k)     # noqa: E731
+        fn()
+        wall, host = timed(fn)
+        emit(section='scene', model=rt, size=size, windows=nw, tta=tta, window_batch=k, s=round(wall, 3),
+             host_s=round(host, 3), tiles_per_s=round(nw / wall, 2),
+             peak_gib=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))
+
+
+def evaluation(m, rt, ks, n_items):
+    from regda_amd.utils.eval import evaluate
+    g = torch.Generator().manual_seed(5)
+    loader = [(torch.randn(1, 3, 512, 512, generator=g), {'cls': torch.randint(-1, 6, (1, 512, 512), generator=g)})
+              for _ in range(n_items)]
+
+    class Cfg:
+        DATASETS = 'IsprsDA'
+        NUM_CLASSES = 6
+        SNAPSHOT_DIR = None
+    ref = None
+    for k in [None] + ks:
+        torch.cuda.reset_peak_memory_stats()
+        fn = lambda: evaluate(m, Cfg, is_training=True, dataloader=loader, window_batch=k)     # noqa: E731
+        out = fn()
+        wall, host = timed(fn)
+        ref = out if ref is None else ref
+        emit(section='eval', model=rt, items=n_items, window_batch=k, s=round(wall, 3), host_s=round(host, 3),
+             items_per_s=round(n_items / wall, 2), miou=float(out[1]), same_table=out == ref,
+             peak_gib=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--models', default='resnet101,resnet50')
+    ap.add_argument('--ks', default='4,8,16,32')
+    ap.add_argument('--tiles', type=int, default=64)
+    ap.add_argument('--eval-items', type=int, default=200)
+    ap.add_argument('--scene', type=int, default=6000)
+    ap.add_argument('--sections', default='invariance,tiles,image,scene,eval')
+    a = ap.parse_args()
+    ks = [int(k) for k in a.ks.split(',') if k]
+    sections = a.sections.split(',')
+    emit(device=torch.cuda.get_device_name(0), date=time.strftime('%Y-%m-%d'), ks=ks)
+    for rt in a.models.split(','):
+        m = build(rt)
+        if 'invariance' in sections:
+            invariance(m, rt, [2, 4, 8, 16])
+        if 'tiles' in sections:
+            tiles(m, rt, ks, a.tiles)
+        if 'image' in sections:
+            image(m, rt, ks)
+        if 'scene' in sections:
+            scene(m, rt, ks, a.scene)
+        if 'eval' in sections:
+            evaluation(m, rt, ks, a.eval_items)
+        del m
+        torch.cuda.empty_cache()
+
+
+if __name__ == '__main__':
+    main()
