@@ -37,10 +37,15 @@ extern "C" {
  * depend on the order in which workgroups retire: two runs of the same step are bit-identical (fp32 atomics made the
  * batch statistics differ in the last bits from run to run, which moved thresholded pseudo labels).
  *   forward  (sum y, sum y^2 of conv outputs):  FRAC = 26 -> resolution 1.5e-8 per partial (below BatchNorm's eps by
- *            three orders of magnitude after the division by the row count), |total| < 1.4e11 (a partial is clamped at 2^61 fixed-point units)
- *   backward (sum g', sum g' xhat):             FRAC = 40 -> resolution 9e-13 per partial, |total| < 8.4e6
- * Partials outside the range are clamped, non-finite partials add nothing (the non-finite ELEMENTS still propagate
- * through the element-wise passes and the loss). */
+ *            three orders of magnitude after the division by the row count), range |partial|, |total| < 2^33 = 8.6e9
+ *   backward (sum g', sum g' xhat):             FRAC = 40 -> resolution 9e-13 per partial, range 2^19 = 5.2e5
+ * Beyond the range: a workgroup partial that is out of range or not finite adds a poison value (3 * 2^60 units); the
+ * consumers add the copies without wrapping (128-bit) and read a total of 2^59 units or more as NaN.  That channel's
+ * (mean, invstd), BatchNorm outputs, running statistics and gradients are then NaN; the other channels are unaffected.
+ * Not guaranteed in two cases: a first sum (sum y, sum g') whose poisons are offset by in-range partials of the opposite
+ * sign that add up to about -3 * 2^60 units per poison can land back in range (sums of squares cannot: their partials are
+ * never negative); and once one copy's own 64-bit accumulator has received 2^63 units (16 x the range) it wraps, and a
+ * total can then read finite where it lands within 2^59 units of a nonzero multiple of 2^64. */
 #define RGDA_STAT_REPLICAS 8
 #define RGDA_STAT_FRAC_FWD 26
 #define RGDA_STAT_FRAC_BWD 40

@@ -78,12 +78,17 @@ static __device__ __forceinline__ float wave_max(float v) {
 
 // ---- order-independent per-channel accumulators (include/rgda_hip.h: rgda_stat_t, 64-bit fixed point).
 // A workgroup's partial sum (reduced in a fixed order inside the workgroup) -> round(v * 2^frac) -> integer atomic.
-// A partial that is out of range (|v * 2^frac| >= 2^59) or not finite adds RGDA_STAT_POISON = 3 * 2^60 instead, and
-// stat_total() reads a total of magnitude >= 2^59 as +inf: with in-range totals below 2^59, k poisons move the 64-bit sum
-// by (3 k mod 16) * 2^60, i.e. out of range for every k that is not a multiple of 16 -- a diverging run shows inf / NaN in
-// its BatchNorm outputs instead of silently wrapped (sign-flipped) statistics.  ONE comparison on the total: a check per
-// replica cost 0.14 ms per step in the BatchNorm preambles.  In-range totals: |sum| < 2^59 / 2^frac = 8.6e9 forward,
-// 5.2e5 backward.
+// A partial that is out of range (|v * 2^frac| >= 2^59) or not finite adds RGDA_STAT_POISON = 3 * 2^60 instead.
+// stat_total() adds the replicas in 128 bits (eight in-range replicas of up to 2^61 each reach 2^64: in 64 bits that sum
+// wrapped to a finite, wrong total) and reads a total of magnitude >= 2^59 as NaN -- not +inf: a +inf sum of squares alone
+// gave var = inf, invstd = 0 and a finite y = beta.  So a diverging run shows NaN in that channel's (mean, invstd), outputs,
+// running statistics and gradients.  Not guaranteed: (a) a signed sum (sum y, sum g') whose poisons are offset by in-range
+// partials of the opposite sign adding up to about -3 * 2^60 each can land back in range (sums of squares cannot: their
+// partials are never negative); (b) once the partials and poisons added to one replica pass 2^63 (16 x the range) its
+// 64-bit accumulator wraps, and a total can then read finite where it lands within 2^59 of a nonzero multiple of 2^64
+// (k poisons in one replica still read out of range for every k that is not a multiple of 16).  ONE comparison on the
+// total: a check per replica cost 0.14 ms per step in the BatchNorm preambles.  In-range totals: |sum| < 2^59 / 2^frac =
+// 8.6e9 forward, 5.2e5 backward.
 #define RGDA_STAT_POISON (3ll << 60)
 static __device__ __forceinline__ long long stat_fix(float v, int frac) {
     // round(v * 2^frac) as a 64-bit integer without fp64 or the software float -> int64 routine (40+ instructions at the
@@ -101,11 +106,11 @@ static __device__ __forceinline__ void stat_add(rgda_stat_t* p, float v, int fra
 }
 // total of statistic `which` (0: first sum, 1: second) of channel c over the replicas of one row group, as a double
 static __device__ __forceinline__ double stat_total(const rgda_stat_t* __restrict__ st, int C, int c, int which, int frac) {
-    long long t = 0;
+    __int128 t = 0;
 #pragma unroll
     for (int r = 0; r < NREP; ++r) t += st[(size_t)(2 * r + which) * C + c];
-    if (t >= (1ll << 59) || t <= -(1ll << 59)) return (double)__builtin_inff();      // poisoned or out of range
-    return (double)t * (1.0 / (double)(1ll << frac));
+    if (t >= (__int128)(1ll << 59) || t <= -(__int128)(1ll << 59)) return (double)__builtin_nan("");  // poisoned or out of range
+    return (double)(long long)t * (1.0 / (double)(1ll << frac));
 }
 
 // mean, biased variance and 1 / sqrt(var + eps) of channel c from one row group's accumulators: fp64 from the exact

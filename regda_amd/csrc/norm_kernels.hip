@@ -1686,15 +1686,17 @@ __global__ void __launch_bounds__(256) classifier_bwd_kernel(const bf16_t* __res
         }
     }
     if (part && blockIdx.y == 0) {
-        __shared__ float dbl2[64][NC];
+        // db over the row lanes through the dW buffer, [rpb][NC] (rpb is up to 256: below 32 channels a fixed [64][NC]
+        // table overflowed into the dW partials other threads were still reading)
+        __syncthreads();                                // the dW reduction above has read lds
         if (cvl == 0) {
 #pragma unroll
-            for (int c = 0; c < NC; ++c) dbl2[rl][c] = dbacc[c];
+            for (int c = 0; c < NC; ++c) lds[rl * NC + c] = dbacc[c];
         }
         __syncthreads();
         if (threadIdx.x < NC) {
             float a = 0.f;
-            for (int r = 0; r < rpb; ++r) a += dbl2[r][threadIdx.x];
+            for (int r = 0; r < rpb; ++r) a += lds[r * NC + threadIdx.x];
             part[(size_t)blockIdx.x * (NC * C + 64) + NC * C + threadIdx.x] = a;
         }
     }

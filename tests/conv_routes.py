@@ -219,11 +219,11 @@ def group_sums(rows, groups, weight=None):
     return torch.stack([v.sum(1), (v * w).sum(1)], 1), torch.stack([v.abs().sum(1), (v * w).abs().sum(1)], 1)
 
 
-def stat_violations(got, ref, absref, rows_per_group, frac):
-    """Fused statistics [groups][2][C] against fp64 sums of the stored values: fp32 partials of at most PARTIAL_ROWS rows
+def stat_violations(got, ref, absref, rows_per_group, frac, partial_rows=PARTIAL_ROWS):
+    """Fused statistics [groups][2][C] against fp64 sums of the stored values: fp32 partials of at most `partial_rows` rows
     (a sum of n terms errs by at most (n - 1) 2^-24 times the sum of their magnitudes), then each partial rounded to the
     2^-frac fixed-point step.  -> number of violating (group, sum, channel) entries."""
-    n = min(rows_per_group, PARTIAL_ROWS) + 8
+    n = min(rows_per_group, partial_rows) + 8
     bound = U32 * n * absref + rows_per_group * 2.0 ** -frac
     return int(((got.double() - ref).abs() > bound).sum())
 

@@ -345,7 +345,7 @@ def test_batchnorm_fwd_bwd(ops, N, C, H, W):
     assert int(nbt) == 1
     y = torch.empty(M, C, dtype=BF, device='cuda')
     ops.bn_apply(xg, mi, gamma.cuda(), beta.cuda(), y, M, C, True, to_pxc(res))
-    assert relerr(from_pxc(y, N, H, W), yr.detach()) < 1e-2
+    assert relerr(from_pxc(y, N, H, W), yr.detach()) < 6e-3
     sums = ops.new_stats(8, 2, C)
     gg = to_pxc(go)
     ops.bn_bwd_reduce(gg, y, xg, mi, sums, M, C, True)
@@ -353,10 +353,10 @@ def test_batchnorm_fwd_bwd(ops, N, C, H, W):
     gm = torch.empty(M, C, dtype=BF, device='cuda')
     dgam, dbet = torch.zeros(C, device='cuda'), torch.zeros(C, device='cuda')
     ops.bn_bwd_apply(gg, y, xg, mi, gamma.cuda(), sums, dx, M, C, True, gm, dgam, dbet)
-    assert relerr(from_pxc(dx, N, H, W), xr.grad) < 2e-2
-    assert relerr(dgam.cpu(), gr.grad) < 1e-2 and relerr(dbet.cpu(), br.grad) < 1e-2
+    assert relerr(from_pxc(dx, N, H, W), xr.grad) < 1.2e-2
+    assert relerr(dgam.cpu(), gr.grad) < 6e-3 and relerr(dbet.cpu(), br.grad) < 6e-3
     # gmask = gradient reaching the residual branch
-    assert relerr(from_pxc(gm, N, H, W), go * (yr.detach() > 0)) < 1e-2
+    assert relerr(from_pxc(gm, N, H, W), go * (yr.detach() > 0)) < 4e-3
     # eval-mode finalize
     mi2 = torch.empty(2, C, device='cuda')
     ops.bn_finalize(None, mi2, rmg, rvg, None, M, C)
@@ -433,7 +433,7 @@ def test_bn_dropout_scale(ops):
     one, zero = torch.ones(C, device='cuda'), torch.zeros(C, device='cuda')
     ops.bn_apply(x.to(BF).cuda(), mi, one, zero, y, M, C, True, None, ns.cuda(), HW)
     ref = F.relu(x).reshape(N, HW, C) * ns[:, None, :]
-    assert relerr(y.float().cpu().reshape(N, HW, C), ref) < 1e-2
+    assert relerr(y.float().cpu().reshape(N, HW, C), ref) < 6e-3
 
 
 def test_maxpool(ops):
@@ -452,7 +452,7 @@ def test_maxpool(ops):
     assert torch.equal(from_pxc(y, N, Ho, Wo), yr.detach())
     gx = torch.empty(N * H * W, C, dtype=BF, device='cuda')
     ops.maxpool_bwd(to_pxc(go), idx, gx, N, H, W, C, Ho, Wo)
-    assert relerr(from_pxc(gx, N, H, W), xr.grad) < 1e-2
+    assert relerr(from_pxc(gx, N, H, W), xr.grad) < 4e-3      # one bf16 rounding of an fp32 sum of <= 4 values
 
 
 def test_instnorm(ops):
@@ -470,11 +470,11 @@ def test_instnorm(ops):
     mi = torch.empty(N, 2, C, device='cuda')
     ops.instnorm_fwd(to_pxc(x), cat[:, :C], None, feat, mi, N, HW, C)
     torch.testing.assert_close(feat.cpu(), yr.detach(), rtol=1e-4, atol=1e-4)
-    assert relerr(from_pxc(cat[:, :C], N, H, W), yr.detach()) < 1e-2
+    assert relerr(from_pxc(cat[:, :C], N, H, W), yr.detach()) < 6e-3
     dx = torch.empty(N * HW, C, dtype=BF, device='cuda')
     gc = rbf(gc)
     ops.instnorm_bwd(to_pxc(ga), to_pxc(gb), to_pxc(gc), to_pxc(x), mi, dx, N, HW, C)
-    assert relerr(from_pxc(dx, N, H, W), xr.grad) < 2e-2
+    assert relerr(from_pxc(dx, N, H, W), xr.grad) < 1.2e-2
 
 
 def test_spatial_mix_pool_and_upsample(ops):
@@ -488,12 +488,12 @@ def test_spatial_mix_pool_and_upsample(ops):
         q = torch.empty(N * s * s, C, dtype=BF, device='cuda')
         ops.spatial_mix(xg, P.cuda(), q, N, s * s, H * W, C)
         refq = F.adaptive_avg_pool2d(x, s)
-        assert relerr(from_pxc(q, N, s, s), refq) < 1e-2, s
+        assert relerr(from_pxc(q, N, s, s), refq) < 6e-3, s
         U = upsample_matrix(s, s, H, W)
         up = torch.empty(N * H * W, C, dtype=BF, device='cuda')
         ops.spatial_mix(q, U.cuda(), up, N, H * W, s * s, C)
         refu = F.interpolate(from_pxc(q, N, s, s), (H, W), mode='bilinear', align_corners=False)
-        assert relerr(from_pxc(up, N, H, W), refu) < 1e-2, s
+        assert relerr(from_pxc(up, N, H, W), refu) < 6e-3, s
 
 
 def test_spatial_mix_multi(ops):
@@ -509,7 +509,7 @@ def test_spatial_mix_multi(ops):
         ref = ref + torch.einsum('ij,njc->nic', Pt, t)
     out = torch.empty(N * H * W, C, dtype=BF, device='cuda')
     ops.spatial_mix_multi(ins, mats, out, N, H * W, C)
-    assert relerr(out.float().cpu().reshape(N, H * W, C), ref) < 1e-2
+    assert relerr(out.float().cpu().reshape(N, H * W, C), ref) < 6e-3
 
 
 def test_classifier(ops):
@@ -528,7 +528,7 @@ def test_classifier(ops):
     dh = torch.empty(N * H * W, C, dtype=BF, device='cuda')
     dw, db = torch.zeros(6, C, device='cuda'), torch.zeros(6, device='cuda')
     ops.classifier_bwd(hg, w.cuda(), gl.cuda(), dh, dw, db, N, H * W, C, 6)
-    assert relerr(from_pxc(dh, N, H, W), hr.grad) < 1e-2
+    assert relerr(from_pxc(dh, N, H, W), hr.grad) < 6e-3
     torch.testing.assert_close(dw.cpu(), wr.grad, rtol=1e-4, atol=1e-4)
     torch.testing.assert_close(db.cpu(), br_.grad, rtol=1e-4, atol=1e-4)
 
@@ -585,15 +585,15 @@ def test_batchnorm_bwd_with_dropout_scale(ops, C, N, HW):
     y = torch.empty(M, C, dtype=BF, device='cuda')
     ops.bn_apply(xg, mi, gamma.cuda(), beta.cuda(), y, M, C, True, None, ns.cuda(), HW)
     ref_y = yr.detach().permute(0, 2, 1).reshape(M, C)
-    assert relerr(y.float().cpu(), ref_y) < 1e-2
+    assert relerr(y.float().cpu(), ref_y) < 6e-3
     gg = go.permute(0, 2, 1).reshape(M, C).to(BF).cuda().contiguous()
     sums = ops.new_stats(8, 2, C)
     ops.bn_bwd_reduce(gg, y, xg, mi, sums, M, C, True, ns.cuda(), HW)
     dx = torch.empty(M, C, dtype=BF, device='cuda')
     dgam, dbet = torch.zeros(C, device='cuda'), torch.zeros(C, device='cuda')
     ops.bn_bwd_apply(gg, y, xg, mi, gamma.cuda(), sums, dx, M, C, True, None, dgam, dbet, ns.cuda(), HW)
-    assert relerr(dx.float().cpu(), xr.grad) < 2e-2
-    assert relerr(dgam.cpu(), gr.grad) < 1e-2 and relerr(dbet.cpu(), br.grad) < 1e-2
+    assert relerr(dx.float().cpu(), xr.grad) < 1.2e-2
+    assert relerr(dgam.cpu(), gr.grad) < 6e-3 and relerr(dbet.cpu(), br.grad) < 6e-3
 
 
 @pytest.mark.parametrize('groups', [1, 2])
@@ -1275,7 +1275,7 @@ def test_small_map_batchnorm_several_layers_per_launch(ops):
         outs = [F.relu(F.batch_norm(xr[gi].t().reshape(1, C, Mg), rm2, rv2, gr, br, True, 0.1, 1e-5)) for gi in range(G)]
         yref = torch.cat([o.reshape(C, Mg).t() for o in outs], 0)
         yref.backward(go.float().cpu())
-        assert relerr(y.float().cpu(), yref.detach()) < 1e-2, li
+        assert relerr(y.float().cpu(), yref.detach()) < 6e-3, li
         torch.testing.assert_close(rm.cpu(), rm2, rtol=2e-4, atol=2e-5)
         torch.testing.assert_close(rv.cpu(), rv2, rtol=2e-4, atol=2e-5)
         assert int(nbt) == G
@@ -1283,8 +1283,8 @@ def test_small_map_batchnorm_several_layers_per_launch(ops):
         if mask is not None:
             assert torch.equal(unpack_mask(mask, C), (y > 0).cpu())
         # the gradient: tolerance of the general kernels' test (bf16 output, fp32 sums in another order)
-        assert relerr(dx.float().cpu(), xr.grad.reshape(M, C)) < 2e-2, li
-        assert relerr(dgam.cpu(), gr.grad) < 1e-2 and relerr(dbet.cpu(), br.grad) < 1e-2
+        assert relerr(dx.float().cpu(), xr.grad.reshape(M, C)) < 1.2e-2, li
+        assert relerr(dgam.cpu(), gr.grad) < 6e-3 and relerr(dbet.cpu(), br.grad) < 6e-3
         # ... and against the general kernels on the same tensors
         st = ops.new_stats(G, 8, 2, C)
         xc = x.contiguous()
