@@ -4,13 +4,18 @@ compute with fp32 accumulate, online EMA teacher) on N MI355X GPUs, one process 
 
     python bench.py --gpus 1 --steps 10 --warmup 3
     python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR     (+ the last timed step's outputs, DIR/*.npy)
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full                 (+ every other measurement, below)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Prints ONE JSON line (rank 0).  A step = model(src), model(tgt), EMA-teacher forward on tgt, label_refine,
 pseudo_selection, LRH, update_prototype, 2x loss, backward of both passes, grad all-reduce, clip + SGD +
-EMA: nothing is skipped inside the timed region.  `roofline` is measured live with HIP events around
-every conv launch of one extra (untimed) step; `cpu_baseline` times the CPU oracle (stock PyTorch fp32)
-on a bounded sample on rank 0 at N=1.
+EMA: nothing is skipped inside the timed region.
+
+A plain run does what the headline figure needs and nothing else: set-up, warm-up, ONE timed window of --steps steps,
+the --dump-outputs files, the line.  `--full` adds, behind that window and without touching it: further timed windows
+(--repeats), the same steps with per-step host -> device staging, the idle-queue host enqueue probe, `roofline`
+(measured live with HIP events around every conv launch of one extra, untimed step), `cpu_baseline` (the CPU oracle,
+stock PyTorch fp32, on a bounded sample on rank 0 at N=1) and the full record file.
 """
 import argparse
 import json
@@ -35,23 +40,28 @@ def parse():
     ap.add_argument('--gpus', type=int, default=None, help='number of ranks (one per GPU); without a launcher environment and N > 1 the script re-executes itself under torch.distributed.run')
     ap.add_argument('--backend', default='nccl', choices=['nccl', 'gloo'], help="'gloo' = launcher self-test without GPUs (rendezvous + one all-reduce, no step)")
     ap.add_argument('--steps', type=int, default=40)
-    ap.add_argument('--repeats', type=int, default=2, help='further timed windows of --steps steps after the reported one (spread of a short window on a fresh box): ms_per_step_windows in the line')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beside the headline figure, behind its timed window: further windows '
+                         '(--repeats), per-step host -> device staging, the host enqueue probe, the roofline probe, the CPU '
+                         'baseline; and write the full record (--full-json).  Off: one timed window, the line, nothing else')
+    ap.add_argument('--repeats', type=int, default=2, help='with --full: further timed windows of --steps steps after the reported one (the spread of a short window): ms_per_step_windows in the full record')
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--batch', type=int, default=8, help='source (= target) images per GPU')
     ap.add_argument('--size', type=int, default=512)
     ap.add_argument('--model', default='resnet101')
     ap.add_argument('--no-teacher', action='store_true', help='offline soft labels (the reference\'s mode) instead of the online EMA teacher')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true')
-    ap.add_argument('--full-json', default=os.path.join(ROOT, 'gpurun_out', 'bench_full.json'),
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: leave the CPU baseline out')
+    ap.add_argument('--no-roofline', action='store_true', help='with --full: leave the roofline probe out')
+    ap.add_argument('--full-json', default=None,
                     help='where the FULL record goes (per-kernel roofline table, timing windows, host probes, CPU-baseline '
-                         'phases); stdout carries one short line with the contract keys, roofline and cpu_baseline')
+                         'phases); stdout carries one short line with the contract keys, roofline and cpu_baseline.  Default: '
+                         'bench_out/bench_full.json next to this script with --full, no file without it')
     ap.add_argument('--serial', action='store_true', help='one stream only (clean per-kernel profiles)')
     ap.add_argument('--grad-payload', default='fp32', choices=['fp32', 'bf16'], help="gradient exchange: 'fp32' bucketed all-reduce (default), 'bf16' all-to-all + fp32 accumulation + all-gather of bf16 payloads (half the bytes per link)")
     ap.add_argument('--comm', default='torch', choices=['torch', 'abi'], help="who issues the collectives: 'torch' = torch.distributed (backend nccl = RCCL; default), 'abi' = the library's own RCCL entry points (rgda_comm_*; the communicator id travels through the process group's store)")
     ap.add_argument('--no-comm-overlap', action='store_true', help='all-reduce the whole gradient after backward instead of bucket by bucket during it')
     ap.add_argument('--eager', action='store_true', help='one Python -> ctypes call per launch instead of the recorded launch plan (regda_amd/plan.py, the default)')
-    ap.add_argument('--no-h2d', action='store_true', help='reuse one device-resident batch instead of staging a fresh pinned host batch per step over a copy stream')
+    ap.add_argument('--no-h2d', action='store_true', help='with --full: leave out the window that stages a fresh pinned host batch per step over a copy stream')
     ap.add_argument('--graph', action='store_true', help='replay the step as one captured hipGraph (measured slower than the recorded plan on ROCm 7.2: 22.4 vs 21.0 ms/step)')
     ap.add_argument('--bn-operand', default=None, help="tuning: which BatchNorm units run on their consumer's operand path, e.g. 'stem+bn1+bn2' (model default), 'none'; ':1' appended = wherever served, not only where it pays")
     ap.add_argument('--relu-mask', type=int, default=None, help='tuning: keep ReLU sign bits for units with at least this many channels (model default: all units)')
@@ -70,6 +80,8 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error('--steps must be at least 1')
+    if args.full and args.full_json is None:
+        args.full_json = os.path.join(ROOT, 'bench_out', 'bench_full.json')
     return args
 
 
@@ -571,12 +583,12 @@ def main():
         return d, th, o
 
     # `value`: inputs resident in HBM when the timed region starts (the bench contract): the FIRST window of exactly K steps;
-    # further windows of the same K steps only report the spread (a 0.4 - 0.8 s window on a freshly leased box moves by +-1 %)
+    # further windows of the same K steps (--full) only report the spread (a 0.4 - 0.8 s window moves by +-1 % from run to run)
     dt, t_host, out = timed_steps()
     dumped = snapshot_outputs(step, out) if args.dump_outputs and rank == 0 else None
-    windows = [dt / args.steps * 1e3] + [timed_steps()[0] / args.steps * 1e3 for _ in range(max(0, args.repeats))]
+    windows = [dt / args.steps * 1e3] + [timed_steps()[0] / args.steps * 1e3 for _ in range(max(0, args.repeats) if args.full else 0)]
     dt_h2d = None
-    if not args.no_h2d:
+    if args.full and not args.no_h2d:
         # input path (tools/train_ssl_reg.py:200-206 moves every batch to the GPU inside the iteration): two distinct
         # synthetic batches in pinned host memory, copied per step by a copy stream -- straight into the recorded step's
         # static input buffers once the running step has read them, or into double-buffered slots in eager mode
@@ -635,7 +647,7 @@ def main():
     # host cost of enqueueing ONE step, measured from an idle queue (in the timed loop above the GPU is the bottleneck and
     # the launch queue pushes back on the host, so that loop's host time mostly shows the back-pressure)
     t_iso = []
-    for _ in range(3):
+    for _ in range(3 if args.full else 0):
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         one()
@@ -680,10 +692,11 @@ def main():
         'step_mfma_frac': value / world * gflop_pair / (MFMA_PEAK_TFLOPS * 1e3),
         'step_mfma_frac_basis': 'reference conv FLOPs (BASELINE.md section 2), label path / BN / optimizer time included',
         'loss_source': losses[0], 'loss_target': losses[1], 'hip_graph': graphed, 'plan_replay': planned,
-        'host_enqueue_ms_per_step': sorted(t_iso)[1] * 1e3,         # one step enqueued into an idle queue (median of 3)
         'host_loop_ms_per_step': t_host / args.steps * 1e3,         # the timed loop's host side (includes queue back-pressure)
     }
-    if rank == 0 and world == 1 and not args.no_roofline:
+    if t_iso:
+        res['host_enqueue_ms_per_step'] = sorted(t_iso)[1] * 1e3    # one step enqueued into an idle queue (median of 3)
+    if rank == 0 and world == 1 and args.full and not args.no_roofline:
         step._graph = step._plan = None          # the per-launch HIP-event probe needs the eager path ...
         side, step.wgrad_stream = step.wgrad_stream, None     # ... and one stream, so a launch's events bracket only itself
         kern = conv_flops_probe(one)
@@ -766,7 +779,7 @@ def main():
                                   'what': f'pre_slide(tta=True) of one {args.size}x{args.size} tile: 8 dihedral views '
                                           'through the eval network as one batch, de-augmented and averaged'}
         model.train()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         res['cpu_baseline'] = cpu_baseline(args)
     if dist.is_initialized():
         dist.destroy_process_group()
@@ -775,9 +788,10 @@ def main():
         # (< 1.8 KB: whoever keeps only the tail of stdout still holds every contract key, `roofline` and `cpu_baseline` whole).
         full_path = args.full_json
         try:
-            os.makedirs(os.path.dirname(os.path.abspath(full_path)), exist_ok=True)
-            with open(full_path, 'w') as f:
-                json.dump(res, f)
+            if full_path is not None:
+                os.makedirs(os.path.dirname(os.path.abspath(full_path)), exist_ok=True)
+                with open(full_path, 'w') as f:
+                    json.dump(res, f)
         except OSError as e:
             print(f'bench.py: could not write {full_path}: {e}', file=sys.stderr)
             full_path = None

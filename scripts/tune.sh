@@ -12,7 +12,10 @@
 #                                              the library for that arm); default arms ".ab_base ."
 #     bash scripts/tune.sh kstep [bench args]  kernel time of ONE serial step by kernel name (+ per-launch list)
 #     bash scripts/tune.sh klist [bench args]  every launch of one overlapped step in start order (gaps, streams)
-#     bash scripts/tune.sh profiles rNN        regenerate everything profiles/ holds for a round into gpurun_out/
+#     [OUT=dir] bash scripts/tune.sh profiles rNN
+#                                              regenerate everything profiles/ holds for a round: the profiler summaries
+#                                              next to the other logs, the bench lines (`bench.py --full`), step phases
+#                                              and provenance into $OUT (default: profiles/ itself)
 #     bash scripts/tune.sh dev <script> [args] a scripts/dev/ probe with the tuning library copied over the product one
 #                                              (conv_phases.py, kbench.py, one_conv.py, conv_ablate.sh, mfma_ceiling.py,
 #                                               gemm_calib.py, wgrad_calib.py, coresidency.py, grid_barrier.py)
@@ -47,7 +50,7 @@ ab)
     [ -f $dir/regda_amd/csrc/librgda_hip.so.arm0 ] || cp $dir/regda_amd/csrc/librgda_hip.so $dir/regda_amd/csrc/librgda_hip.so.arm0
     lib=$dir/regda_amd/csrc/librgda_hip.so.arm0; for e in $envs; do case $e in LIB=*) lib=${e#LIB=} ;; esac; done
     cp $lib $dir/regda_amd/csrc/librgda_hip.so
-    ( cd $dir; env $envs python bench.py --steps 10 --repeats 0 --warmup 3 --no-cpu-baseline --no-roofline --no-h2d ${BARGS:-} 2>/dev/null | last_json "$arm" )
+    ( cd $dir; env $envs python bench.py --full --steps 10 --repeats 0 --warmup 3 --no-cpu-baseline --no-roofline --no-h2d ${BARGS:-} 2>/dev/null | last_json "$arm" )
   done; done ;;
 kstep)
   on_box; rm -rf gpurun_out/ks
@@ -94,10 +97,11 @@ profiles)
   python scripts/lib/prof_summary.py gpurun_out/prof_o/r_results.db 5 > gpurun_out/${tag}_kernel_stats_overlapped.txt
   grep '"metric"' gpurun_out/prof_o.log >> gpurun_out/${tag}_kernel_stats_overlapped.txt; rm -rf gpurun_out/prof_o
   # ---- the bench lines
-  timeout 900 python bench.py --phases --full-json gpurun_out/${tag}_bench_1gpu_full.json > gpurun_out/${tag}_bench_1gpu.json 2> gpurun_out/${tag}_bench_1gpu.err
-  grep ' ms  ' gpurun_out/${tag}_bench_1gpu.err > gpurun_out/${tag}_step_phases.txt
-  { echo "box: $(hostname)  date: $(date -u +%FT%TZ)  commit: ${GRAFT_COMMIT:-see profiles/README.md}"; rocm-smi --showproductname 2>/dev/null | grep -i "card series" | head -1; } > gpurun_out/${tag}_provenance.txt
-  cut -c1-900 gpurun_out/${tag}_bench_1gpu.json; cat gpurun_out/${tag}_step_phases.txt ;;
+  OUT=${OUT:-profiles}; mkdir -p "$OUT"
+  timeout 900 python bench.py --full --phases --full-json "$OUT/${tag}_bench_1gpu_full.json" > "$OUT/${tag}_bench_1gpu.json" 2> "$OUT/${tag}_bench_1gpu.err"
+  grep ' ms  ' "$OUT/${tag}_bench_1gpu.err" > "$OUT/${tag}_step_phases.txt"
+  { echo "box: $(hostname)  date: $(date -u +%FT%TZ)  commit: $(git rev-parse --short HEAD 2>/dev/null || echo see profiles/README.md)"; rocm-smi --showproductname 2>/dev/null | grep -i "card series" | head -1; } > "$OUT/${tag}_provenance.txt"
+  cut -c1-900 "$OUT/${tag}_bench_1gpu.json"; cat "$OUT/${tag}_step_phases.txt" ;;
 *)
   sed -n 2,22p "$0" ;;
 esac

@@ -1,5 +1,6 @@
-"""bench.py's harness: `--steps` validation and `--dump-outputs` (what the last timed step computed, as .npy files).
-The snapshot logic runs on the CPU with a stand-in step; the end-to-end run needs the GPU."""
+"""bench.py's harness: `--steps` validation, `--dump-outputs` (what the last timed step computed, as .npy files) and
+`--full` (everything beside the headline figure).  The snapshot logic runs on the CPU with a stand-in step; the
+end-to-end runs need the GPU."""
 import json
 import os
 import subprocess
@@ -51,6 +52,61 @@ def test_steps_below_one_is_an_error():
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '0'], capture_output=True, text=True,
                        timeout=120)
     assert r.returncode != 0 and '--steps' in r.stderr
+
+
+def test_full_is_off_by_default_and_names_the_record(monkeypatch):
+    """A plain command line leaves `--full` off and writes no full record; `--full` sends the record to
+    bench_out/bench_full.json next to the script unless `--full-json` names another place (which also holds without
+    `--full`)."""
+    bench = _bench()
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '5', '--warmup', '2'])
+    a = bench.parse()
+    assert a.full is False and a.full_json is None and (a.steps, a.warmup, a.gpus) == (5, 2, 1)
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full'])
+    a = bench.parse()
+    assert a.full is True and a.full_json == os.path.join(ROOT, 'bench_out', 'bench_full.json')
+    for extra in ([], ['--full']):
+        monkeypatch.setattr(sys, 'argv', ['bench.py', '--full-json', 'x.json'] + extra)
+        assert bench.parse().full_json == 'x.json'
+
+
+def test_plain_line_holds_the_contract_keys_only():
+    """The line of a plain run: every contract key, none of the figures that `--full` measures, no record file."""
+    bench = _bench()
+    res = {'metric': 'm', 'value': 450.123456, 'unit': 'pairs/s', 'n_gpus': 1, 'steps': 10, 'warmup': 3,
+           'ms_per_step': 17.7654321, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'bf16',
+           'with_h2d_staging': None, 'comm_exposed_ms': None, 'replicas': None, 'ms_per_step_windows': [17.7654321]}
+    line = bench.compact_line(res, None)
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'steps', 'warmup'):
+        assert k in line
+    assert line['value'] == 450.1 and line['ms_per_step'] == 17.77 and line['full_record'] is None
+    for k in ('roofline', 'cpu_baseline', 'with_h2d_staging_pairs_per_s', 'host_enqueue_ms_per_step'):
+        assert k not in line
+
+
+@pytest.mark.gpu
+def test_bench_plain_and_full(tmp_path):
+    """The same command line without and with `--full`.  Plain: the contract keys, no roofline / CPU baseline / staging /
+    enqueue figures, and nothing written.  `--full`: all of those, and the record file with the further windows."""
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1']
+    lines = {}
+    for name, extra in (('plain', []), ('full', ['--full', '--full-json', str(tmp_path / 'full.json')])):
+        r = subprocess.run(cmd + extra, cwd=tmp_path, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines[name] = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
+        if name == 'plain':
+            assert not list(tmp_path.iterdir())
+    moved = ('roofline', 'cpu_baseline', 'with_h2d_staging_pairs_per_s', 'host_enqueue_ms_per_step')
+    for name, line in lines.items():
+        assert line['metric'] == 'src+tgt 512x512 image-pairs/sec (SSL step)' and line['unit'] == 'pairs/s'
+        assert line['higher_is_better'] is True and line['dtype'] == 'bf16' and line['steps'] == 2 and line['warmup'] == 1
+        assert line['ms_per_step'] > 0 and line['plan_replay']
+        assert abs(line['value'] * line['ms_per_step'] / 8e3 - 1) < 2e-3      # both rounded to 4 digits in the line
+        assert all((k in line) == (name == 'full') for k in moved), (name, sorted(line))
+    assert lines['plain']['full_record'] is None
+    full = json.load(open(tmp_path / 'full.json'))
+    assert len(full['ms_per_step_windows']) == 3 and full['ms_per_step_windows'][0] == full['ms_per_step']
+    assert full['roofline']['by_kernel'] and full['cpu_baseline']['value'] > 0
 
 
 @pytest.mark.gpu
