@@ -343,7 +343,8 @@ const char* rgda_conv2d_kernel(int variant, int N, int H, int W, int Cin, int Ho
 /* Which conv_igemm_kernel<BC, BP, STAGES, ...> instantiation rgda_conv2d picks for a problem: returns
  * BC | BP << 10 | STAGES << 20 (STAGES 82 / 83 = 8-wave workgroups with a 2 / 3 stage ring), or a negative
  * status.  rows_per_group = rows of one BatchNorm group when fused statistics with groups > 1 are requested, else 0.
- * (bench.py labels its per-launch timings with it so they can be matched against rocprof kernel names.) */
+ * (Nothing in this repository calls it: bench.py and the tests take the instantiation's full name from
+ * rgda_conv2d_kernel.  It stays for hosts built against the ABI.) */
 int rgda_conv2d_tile(int64_t M, int Cout, int kh, int kw, int Cin, int rows_per_group);
 
 /* Weight gradient: dw[co][tap][ci] (f32, row stride taps*Cin) +=

@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include <type_traits>
+#include <vector>
 
 struct ConvArgs {
     const bf16_t* x;
@@ -1286,11 +1287,83 @@ __global__ void __launch_bounds__(512) conv3x3_c64_kernel(ConvArgs a) {
 #endif
 }
 
+// Host dispatch of the forward / data-gradient convolutions: the route table (one row per kernel instantiation), conv_select
+// (which row serves a call, with which argument block and grid) and conv_launch (one switch over the table).  A new kernel
+// is one row here, one condition in conv_select and one entry in tests/conv_routes.py.
+#ifdef RGDA_TUNING      // rows that only the RGDA_* environment hooks reach: not instantiated in the product library
+#define TUNING_ONLY(...) __VA_ARGS__
+#else
+#define TUNING_ONLY(...)
+#endif
+// conv_igemm_kernel's rows, T(BC, BP, STAGES, WC, WP, PIPE, XF): what pick_tile and the operand-path BatchNorm yield,
+// then what RGDA_TILE / RGDA_NO_PIPE reach
+#define CONV_IGEMM_ROUTES(T)                                                                                         \
+    T(64, 64, 2, 2, 2, false, false) T(128, 64, 3, 2, 2, true, false) T(128, 128, 2, 2, 4, false, false)             \
+    T(128, 128, 3, 2, 4, true, false) T(128, 256, 3, 2, 4, true, false) T(128, 128, 2, 2, 4, false, true)            \
+    TUNING_ONLY(T(128, 128, 3, 2, 4, false, false) T(128, 256, 3, 2, 4, false, false) T(128, 64, 3, 2, 2, false, false) \
+                T(128, 256, 3, 2, 2, false, false) T(256, 128, 3, 2, 2, false, false) T(128, 128, 2, 2, 2, false, false) \
+                T(128, 128, 4, 2, 2, false, false) T(128, 128, 3, 2, 2, false, false) T(128, 64, 2, 2, 2, false, false) \
+                T(128, 64, 4, 2, 2, false, false) T(64, 128, 3, 2, 2, false, false) T(64, 64, 4, 2, 2, false, false) \
+                T(64, 64, 3, 2, 2, false, false))
+#define IGEMM_ID(BC, BP, ST, WC, WP, PIPE, XF) R_IGEMM_##BC##x##BP##_##ST##_##WC##x##WP##_##PIPE##_##XF
+#define IGEMM_ROUTE(BC, BP, ST, WC, WP, PIPE, XF)                                                                    \
+    ROUTE(IGEMM_ID(BC, BP, ST, WC, WP, PIPE, XF), 64 * WC * WP, conv_igemm_kernel, BC, BP, ST, WC, WP, PIPE, XF)
+// conv3x3_c64_kernel, conv1x1_stream_kernel: one instantiation per fused epilogue (EPI_*, the last argument), ids ID##0 + kind
+#define PER_EPI_ROUTES(ID, KERNEL, ...)                                                                              \
+    ROUTE(ID##0, 512, KERNEL, __VA_ARGS__, 0) ROUTE(ID##1, 512, KERNEL, __VA_ARGS__, 1)                              \
+    ROUTE(ID##2, 512, KERNEL, __VA_ARGS__, 2) ROUTE(ID##3, 512, KERNEL, __VA_ARGS__, 3)                              \
+    ROUTE(ID##4, 512, KERNEL, __VA_ARGS__, 4) ROUTE(ID##5, 512, KERNEL, __VA_ARGS__, 5)                              \
+    ROUTE(ID##6, 512, KERNEL, __VA_ARGS__, 6)
+// ROUTE(route id, block size, kernel template, its full template argument list): the launch expression and the name
+// rgda_conv2d_kernel reports (the one rocprofv3 prints) are both generated from a row.
+// conv3x3_halo_kernel<D, TR, XF, NS, PF>, conv3x3_halo_wide_kernel<D, TR, NS, PF, XF>: dilation, image rows per tile,
+// operand transform, weight stages, pipelined across the barriers.  (The pipelined form of the 8-row variant with the
+// transform spills 80 registers: it keeps the plain loop.  Dilation 2: 3 stages, 160 KB.)  _PLAIN: what RGDA_HALO_NS reaches.
+#define CONV_ROUTES                                                                                                  \
+    CONV_IGEMM_ROUTES(IGEMM_ROUTE)                                                                                   \
+    ROUTE(R_HALO_1_4, 512, conv3x3_halo_kernel, 1, 4, false, 4, true)                                                \
+    ROUTE(R_HALO_1_8, 512, conv3x3_halo_kernel, 1, 8, false, 4, true)                                                \
+    ROUTE(R_HALO_2_8, 512, conv3x3_halo_kernel, 2, 8, false, 3, true)                                                \
+    ROUTE(R_HALO_1_4_XF, 512, conv3x3_halo_kernel, 1, 4, true, 4, true)                                              \
+    ROUTE(R_HALO_1_8_XF, 512, conv3x3_halo_kernel, 1, 8, true, 3, false)                                             \
+    TUNING_ONLY(ROUTE(R_HALO_1_4_PLAIN, 512, conv3x3_halo_kernel, 1, 4, false, 3, false)                             \
+                ROUTE(R_HALO_1_8_PLAIN, 512, conv3x3_halo_kernel, 1, 8, false, 3, false)                             \
+                ROUTE(R_HALO_2_8_PLAIN, 512, conv3x3_halo_kernel, 2, 8, false, 3, false)                             \
+                ROUTE(R_HALO_1_4_XF_PLAIN, 512, conv3x3_halo_kernel, 1, 4, true, 3, false))                          \
+    ROUTE(R_HALOW_1_4, 512, conv3x3_halo_wide_kernel, 1, 4, 4, true, false)                                          \
+    ROUTE(R_HALOW_1_8, 512, conv3x3_halo_wide_kernel, 1, 8, 4, true, false)                                          \
+    ROUTE(R_HALOW_2_8, 512, conv3x3_halo_wide_kernel, 2, 8, 3, true, false)                                          \
+    ROUTE(R_HALOW_1_4_XF, 512, conv3x3_halo_wide_kernel, 1, 4, 4, true, true)                                        \
+    ROUTE(R_HALOW_1_8_XF, 512, conv3x3_halo_wide_kernel, 1, 8, 3, false, true)                                       \
+    PER_EPI_ROUTES(R_C64_, conv3x3_c64_kernel, 128)                                                                  \
+    PER_EPI_ROUTES(R_STREAM1_, conv1x1_stream_kernel, 1, 128, 2, 4)                                                  \
+    PER_EPI_ROUTES(R_STREAM2_, conv1x1_stream_kernel, 2, 128, 2, 4)
+#define ROUTE(ID, BLOCK, KERNEL, ...) ID,
+enum { CONV_ROUTES CONV_ROUTE_COUNT };
+#undef ROUTE
+#define ROUTE(ID, BLOCK, KERNEL, ...) #KERNEL "<" #__VA_ARGS__ ">",
+static const char* const CONV_ROUTE_NAMES[CONV_ROUTE_COUNT] = {CONV_ROUTES};
+#undef ROUTE
+constexpr int R_GROUPED = IGEMM_ID(128, 64, 3, 2, 2, true, false);   // its problems share launches (rgda_conv2d_grouped)
+
+static int conv_launch(int route, const ConvArgs& a, int grid, hipStream_t st) {
+    switch (route) {
+#define ROUTE(ID, BLOCK, KERNEL, ...) case ID: KERNEL<__VA_ARGS__><<<grid, BLOCK, 0, st>>>(a); break;
+        CONV_ROUTES
+#undef ROUTE
+    }
+    RGDA_CHECK_LAUNCH();
+    return RGDA_OK;
+}
+
+// an integer tuning hook: `dflt` in the product library (TUNE_ENV is a null constant there), the environment's value in a tuning build
+static inline int tune_int(const char* name, int dflt) { const char* e = TUNE_ENV(name); return e ? atoi(e) : dflt; }
+
 // tile choice (measured on MI355X, scripts/dev/dev_conv_bench.py): the L2 -> LDS path sustains <= ~80 GB/s per CU, so the
 // long-K head convolutions want the largest tile that still gives every CU a workgroup (128 x 256, 85 FLOP per
 // byte, 8 waves); large-M layers run 128 x 128 tiles with 8 waves and a 2-stage ring (64 KiB: two workgroups =
-// 16 waves per CU); everything else 128 x 64 tiles with 4 waves, two workgroups per CU.  `stages` 82 / 83 mean
-// 8-wave workgroups with 2 / 3 stages.  rows_per_group != 0: a tile may not straddle two statistics groups.
+// 16 waves per CU); everything else 128 x 64 tiles with 4 waves, two workgroups per CU.
+// rows_per_group != 0: a tile may not straddle two statistics groups.
 // the cases conv3x3_halo_kernel serves: 3x3 / stride 1 / pad = dilation on 32-wide maps, tiles inside one statistics group
 // -> image rows per tile (0 = not served):
 //   8 (128 x 256 tiles): K >= 4096, dilation 1 or 2 (the heads, layer 4) -- where the 128 x 256 implicit-GEMM tile would be picked;
@@ -1303,61 +1376,79 @@ static int conv_use_halo(long long M, int Cout, int Cin, int kh, int kw, int str
     if (const char* e = TUNE_ENV("RGDA_HALO")) { if (!atoi(e)) return 0; }              // tuning experiments only
     if (kh != 3 || kw != 3 || stride != 1 || pad != dil || (dil != 1 && dil != 2)) return 0;
     if ((W & 31) || Wo != W || Ho != H || (Cin & 63)) return 0;        // (W > 32: conv3x3_halo_wide_kernel, 32-column bands)
-    int min_tiles = 100;
-    if (const char* e = TUNE_ENV("RGDA_HALO_MIN")) min_tiles = atoi(e);                 // tuning experiments only
-    int min8 = 100;
-    if (const char* e = TUNE_ENV("RGDA_HALO_MIN8")) min8 = atoi(e);                     // tuning experiments only
+    const int min_tiles = tune_int("RGDA_HALO_MIN", 100), min8 = tune_int("RGDA_HALO_MIN8", 100);     // tuning experiments only
     // (a tile is TR image rows x 32 columns: TR * W memory rows, inside one statistics group -- always so for the whole-image
-    // groups conv2d_launch accepts)
+    // groups conv_select accepts)
     if ((long long)9 * Cin >= 4096 && !(H & 7) && !(rows_per_group % (8 * W)) && (M / 256) * cdiv(Cout, 128) >= min8) return 8;
     if ((long long)9 * Cin >= 2048 && dil == 1 && !(H & 3) && !(rows_per_group % (4 * W)) && (M / 128) * cdiv(Cout, 128) >= min_tiles) return 4;
     return 0;
 }
 
-static int pick_tile(long long M, int Cout, long long ktot, int rows_per_group, int& bc, int& bp, int& stages) {
-    bc = (Cout <= 64) ? 64 : 128;
-    bp = 64;
-    int waves = 4;
-    int t82 = 512, t83 = 256;
-    if (const char* e = TUNE_ENV("RGDA_T82")) t82 = atoi(e);     // tuning experiments only
-    if (const char* e = TUNE_ENV("RGDA_T83")) t83 = atoi(e);     // tuning experiments only
-    if (bc == 128 && ktot >= 4096 && (long long)cdiv(M, 256) * cdiv(Cout, bc) >= 240) { bp = 256; waves = 8; }
-    else if (bc == 128 && (long long)cdiv(M, 128) * cdiv(Cout, bc) >= t82) { bp = 128; waves = 8; }
-    else if (bc == 128 && (long long)cdiv(M, 128) * cdiv(Cout, bc) >= t83) { bp = 128; waves = 9; }
+// the generic tile of a problem: conv_igemm_kernel<bc, bp, stages, wc, wp, pipe, false>
+struct ConvTile { int bc, bp, stages, wc, wp; bool pipe; };
+
+static int pick_tile(long long M, int Cout, long long ktot, int rows_per_group, ConvTile& t) {
+    t.bc = (Cout <= 64) ? 64 : 128;
+    t.bp = 64;
+    t.wc = 2;
+    bool waves8 = false, ring3 = false;       // 2 x 4 waves; 128 x 128 tiles with the 3-stage ring
+    const int t82 = tune_int("RGDA_T82", 512), t83 = tune_int("RGDA_T83", 256);     // tuning experiments only
+    if (t.bc == 128 && ktot >= 4096 && (long long)cdiv(M, 256) * cdiv(Cout, t.bc) >= 240) { t.bp = 256; waves8 = true; }
+    else if (t.bc == 128 && (long long)cdiv(M, 128) * cdiv(Cout, t.bc) >= t82) { t.bp = 128; waves8 = true; }
+    else if (t.bc == 128 && (long long)cdiv(M, 128) * cdiv(Cout, t.bc) >= t83) { t.bp = 128; waves8 = ring3 = true; }
     if (rows_per_group) {
-        while (bp > 64 && (rows_per_group % bp)) bp >>= 1;
-        if (rows_per_group % bp) return 1;
+        while (t.bp > 64 && (rows_per_group % t.bp)) t.bp >>= 1;
+        if (rows_per_group % t.bp) return 1;
     }
-    stages = (bc == 64) ? 2 : 3;
-    if (waves >= 8 && bp >= 128) stages = (bp == 256 || waves == 9) ? 83 : 82;
+    t.wp = (waves8 && t.bp >= 128) ? 4 : 2;
+    t.stages = (t.wp == 4) ? ((t.bp == 256 || ring3) ? 3 : 2) : ((t.bc == 64) ? 2 : 3);
+    t.pipe = t.stages == 3 && !TUNE_ENV("RGDA_NO_PIPE");       // (off switch: tuning experiments only)
     return 0;
 }
 
-extern "C" int rgda_conv2d_tile(int64_t M, int Cout, int kh, int kw, int Cin, int rows_per_group) {
-    int bc, bp, stages;
-    if (pick_tile(M, Cout, (long long)kh * kw * Cin, rows_per_group, bc, bp, stages)) return RGDA_ERR_UNSUPPORTED;
-    return bc | (bp << 10) | (stages << 20);
+// the route whose template arguments are the tile's fields (-1: no such instantiation)
+static int igemm_route(const ConvTile& t) {
+#define TILE(BC, BP, ST, WC, WP, PIPE, XF)                                                                           \
+    if (!XF && t.bc == BC && t.bp == BP && t.stages == ST && t.wc == WC && t.wp == WP && t.pipe == PIPE)             \
+        return IGEMM_ID(BC, BP, ST, WC, WP, PIPE, XF);
+    CONV_IGEMM_ROUTES(TILE)
+#undef TILE
+    return -1;
 }
 
-static int ilog2_exact(int v);
+// (ABI: 8-wave workgroups are reported as STAGES 82 / 83 = a 2 / 3 stage ring; the only place this encoding exists)
+extern "C" int rgda_conv2d_tile(int64_t M, int Cout, int kh, int kw, int Cin, int rows_per_group) {
+    ConvTile t;
+    if (pick_tile(M, Cout, (long long)kh * kw * Cin, rows_per_group, t)) return RGDA_ERR_UNSUPPORTED;
+    return t.bc | (t.bp << 10) | ((t.wp == 4 ? 80 + t.stages : t.stages) << 20);
+}
+
+static int ilog2_exact(int v) {
+    if (v <= 0 || (v & (v - 1))) return -1;
+    int s = 0;
+    while ((1 << s) < v) ++s;
+    return s;
+}
 struct BnBwdFuse { const void* y; int ldy; const unsigned char* mask; const void* x; int ldx; const float* mi; const float* nscale; int rpi; int relu; const float* gamma; const float* beta; };
 struct BnEvalFuse { const float* rm; const float* rv; const float* gamma; const float* beta; float eps; int relu; };
+// the optional fused parts of a convolution call (each may be null)
+struct ConvFuse { const BnBwdFuse* bnb; const BnEvalFuse* bne; const rgda_bn_operand* bnin; };
 
-// which kernel serves a convolution whose operand is a BatchNorm (+ ReLU) on the operand path: 1 = conv3x3_halo_kernel
-// <1, 4>, 2 = <1, 8>, 3 = conv_igemm_kernel<128, 128, 2, 2, 4, false, true>; 0 = none (the caller materialises the
-// activation with rgda_bn_train_apply and runs the plain convolution)
+// which kernel serves a convolution whose operand is a BatchNorm (+ ReLU) on the operand path: 1 = the halo kernels with
+// 4 image rows per tile, 2 = with 8, 3 = conv_igemm_kernel<128, 128, 2, 2, 4, false, true>; 0 = none (the caller
+// materialises the activation with rgda_bn_train_apply and runs the plain convolution)
 static int conv_bnin_kind(long long M, int Cout, int Cin, int kh, int kw, int stride, int pad, int dil, int H, int W, int Ho,
                           int Wo, int groups) {
-    // (statistics groups are whole images, as conv2d_launch requires: N = M / (Ho * Wo) images)
+    // (statistics groups are whole images, as conv_select requires: N = M / (Ho * Wo) images)
     if (groups < 1 || Ho <= 0 || Wo <= 0 || (M % ((long long)Ho * Wo)) || (M / ((long long)Ho * Wo)) % groups ||
         Cin > RGDA_BNIN_MAX_C || (Cin & 63))
         return 0;
     const int rpg = (int)(M / groups);
     if (const int tr = conv_use_halo(M, Cout, Cin, kh, kw, stride, pad, dil, H, W, Ho, Wo, rpg))
         return (tr == 4) ? 1 : (dil == 1 ? 2 : 0);          // (dilation 2: its 160 KB of LDS leave no room for the table)
-    int bc, bp, stages;
-    if (pick_tile(M, Cout, (long long)kh * kw * Cin, rpg, bc, bp, stages)) return 0;
-    return (bc == 128 && bp == 128 && stages == 82) ? 3 : 0;
+    ConvTile t;
+    if (pick_tile(M, Cout, (long long)kh * kw * Cin, rpg, t)) return 0;
+    return (t.bc == 128 && t.bp == 128 && t.wp == 4 && t.stages == 2) ? 3 : 0;
 }
 
 // 0 = not served, 1 = served, 2 = served and faster than the apply pass it replaces.  Where the transform pays
@@ -1371,33 +1462,32 @@ extern "C" int rgda_conv2d_bnin_supported(int64_t M, int Cout, int Cin, int kh, 
     return (Cin > 256 || (kh == 1 && Cin < 128)) ? 1 : 2;
 }
 
-static int conv2d_launch(const void* x, int ldx, const void* wgt, void* y, int ldy, const void* res, int ldres,
-                         const unsigned char* res_mask, rgda_stat_t* stats, int stat_groups, int N, int H, int W, int Cin, int Ho, int Wo, int Cout,
-                         int kh, int kw, int stride, int pad, int dil, int mode, const BnBwdFuse* bnb,
-                         rgda_stream_t stream, const BnEvalFuse* bne = nullptr, const rgda_bn_operand* bnin = nullptr,
-                         const char** sel = nullptr, ConvArgs* out_args = nullptr) {
-    // sel != nullptr: dry run -- *sel = the kernel instantiation that would serve the call (the name rocprofv3 reports),
-    // nothing is launched (rgda_conv2d_kernel; bench.py labels its per-launch timings with it); out_args: the argument
-    // block that launch would carry (rgda_conv2d_grouped packs several into one launch)
-#define RGDA_LAUNCH(NAME, ...)                                                     \
-    do {                                                                           \
-        if (sel) { *sel = NAME; if (out_args) *out_args = a; return RGDA_OK; }     \
-        __VA_ARGS__;                                                               \
-    } while (0)
-#define RGDA_IGEMM(BC, BP, ST, WC, WP, PIPE, XF)                                                                  \
-    RGDA_LAUNCH("conv_igemm_kernel<" #BC ", " #BP ", " #ST ", " #WC ", " #WP ", " #PIPE ", " #XF ">",              \
-                conv_igemm_kernel<BC, BP, ST, WC, WP, PIPE, XF><<<grid, 64 * WC * WP, 0, st>>>(a))
-    if (!x || !wgt || !y) return RGDA_ERR_ARG;
+// the fused epilogue conv_epilogue runs for an argument block (the c64 and stream kernels have one instantiation each)
+static int conv_epi_kind(const ConvArgs& a) {
+    return a.ev_rm ? EPI_EV : a.bn_x ? (a.bn_relu == 2 ? EPI_BNX2 : EPI_BNX)
+         : a.res ? (a.stats ? EPI_RES_STATS : EPI_RES) : (a.stats ? EPI_STATS : EPI_PLAIN);
+}
+
+// What serves a convolution call: validates it, fills the argument block and picks the route and its grid, in this
+// order of precedence: operand-path BatchNorm, c64, halo / halo-wide, stream, generic tile.  Launches nothing.
+struct ConvPlan { ConvArgs a; int route, grid; };
+static int conv_select(const rgda_conv2d_desc& d, const ConvFuse& f, ConvPlan& p) {
+    const int N = d.N, H = d.H, W = d.W, Cin = d.Cin, Ho = d.Ho, Wo = d.Wo, Cout = d.Cout, kh = d.kh, kw = d.kw,
+              stride = d.stride, pad = d.pad, dil = d.dil, mode = d.mode;
+    const BnBwdFuse* bnb = f.bnb;
+    const BnEvalFuse* bne = f.bne;
+    const rgda_bn_operand* bnin = f.bnin;
+    if (!d.x || !d.wgt || !d.y) return RGDA_ERR_ARG;
     if (N <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0 || Cin <= 0 || Cout <= 0 || kh <= 0 || kw <= 0 ||
         stride <= 0 || dil <= 0 || pad < 0 || (mode != 0 && mode != 1))
         return RGDA_ERR_ARG;
-    if ((Cin & 63) || (Cout & 7) || (ldx & 7) || (ldy & 7) || (res && (ldres & 7)) || ldx < Cin || ldy < Cout)
+    if ((Cin & 63) || (Cout & 7) || (d.ldx & 7) || (d.ldy & 7) || (d.res && (d.ldres & 7)) || d.ldx < Cin || d.ldy < Cout)
         return RGDA_ERR_ARG;
-    ConvArgs a;
-    a.x = (const bf16_t*)x; a.w = (const bf16_t*)wgt; a.y = (bf16_t*)y; a.res = (const bf16_t*)res; a.stats = stats;
-    if (res_mask && (!res || bne)) return RGDA_ERR_ARG;
-    a.res_mask = res_mask;
-    a.ldx = ldx; a.ldy = ldy; a.ldres = ldres;
+    ConvArgs& a = p.a = ConvArgs{};        // every optional part off
+    a.x = (const bf16_t*)d.x; a.w = (const bf16_t*)d.wgt; a.y = (bf16_t*)d.y; a.res = (const bf16_t*)d.res; a.stats = d.stats;
+    if (d.res_relu_mask && (!d.res || bne)) return RGDA_ERR_ARG;
+    a.res_mask = d.res_relu_mask;
+    a.ldx = d.ldx; a.ldy = d.ldy; a.ldres = d.ldres;
     a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.Ho = Ho; a.Wo = Wo; a.Cout = Cout; a.KH = kh; a.KW = kw;
     a.stride = stride; a.pad = pad; a.dil = dil; a.mode = mode;
     long long M = (long long)N * Ho * Wo;
@@ -1405,17 +1495,13 @@ static int conv2d_launch(const void* x, int ldx, const void* wgt, void* y, int l
     a.M = (int)M;
     a.howo_shift = ilog2_exact(Ho * Wo);
     a.wo_shift = ilog2_exact(Wo);
-    hipStream_t st = to_stream(stream);
-    // tile choice: fill 256 CUs (2 workgroups each); prefer the big tile when it still gives >= 512 groups
-    if (stat_groups < 1) stat_groups = 1;
+    const int stat_groups = d.stat_groups < 1 ? 1 : d.stat_groups;
     // a statistics group is a whole number of images: a tile of the halo kernels (TR image rows of one 32-column band)
     // or of the operand-path BatchNorm (whose halo rows come from neighbouring image rows) then never spans two groups
     if (N % stat_groups || M % stat_groups) return RGDA_ERR_ARG;
     a.rows_per_group = (int)(M / stat_groups);
-    a.bn_y = a.bn_x = nullptr; a.bn_mask = nullptr; a.bn_mi = a.bn_nscale = nullptr; a.bn_ldy = a.bn_ldx = a.bn_rpi = a.bn_relu = 0;
-    a.bn_gamma = a.bn_beta = nullptr;
     if (bnb) {
-        if (!stats || !bnb->x || !bnb->mi || (bnb->relu == 1 && !bnb->y && !bnb->mask) || (bnb->ldx & 7) ||
+        if (!a.stats || !bnb->x || !bnb->mi || (bnb->relu == 1 && !bnb->y && !bnb->mask) || (bnb->ldx & 7) ||
             (bnb->relu == 1 && bnb->y && (bnb->ldy & 7)) || (bnb->nscale && bnb->rpi <= 0) || bnb->relu < 0 || bnb->relu > 2)
             return RGDA_ERR_ARG;
         a.bn_mask = bnb->relu == 1 ? bnb->mask : nullptr;
@@ -1424,16 +1510,13 @@ static int conv2d_launch(const void* x, int ldx, const void* wgt, void* y, int l
         if (bnb->relu == 2 && (!bnb->gamma || !bnb->beta)) return RGDA_ERR_ARG;
         a.bn_gamma = bnb->gamma; a.bn_beta = bnb->beta;
     }
-    a.ev_rm = a.ev_rv = a.ev_gamma = a.ev_beta = nullptr; a.ev_eps = 0.f; a.ev_relu = 0;
     if (bne) {
-        if (!bne->rm || !bne->rv || !bne->gamma || !bne->beta || stats) return RGDA_ERR_ARG;
+        if (!bne->rm || !bne->rv || !bne->gamma || !bne->beta || a.stats) return RGDA_ERR_ARG;
         a.ev_rm = bne->rm; a.ev_rv = bne->rv; a.ev_gamma = bne->gamma; a.ev_beta = bne->beta; a.ev_eps = bne->eps;
         a.ev_relu = bne->relu;
     }
-    a.dbg = nullptr; a.skip = 0;
     if (const char* e = TUNE_ENV("RGDA_CONV_DBG")) a.dbg = (unsigned long long*)strtoull(e, nullptr, 0);   // tuning only
-    if (const char* e = TUNE_ENV("RGDA_CONV_SKIP")) a.skip = atoi(e);                                      // tuning only
-    a.xf.stats = nullptr;
+    a.skip = tune_int("RGDA_CONV_SKIP", 0);                                                                // tuning only
     if (bnin) {
         // BatchNorm (+ ReLU) of the producer on this convolution's operand path: forward only, statistics groups = the
         // operand's groups (whole images), a kernel that carries the transform
@@ -1447,140 +1530,89 @@ static int conv2d_launch(const void* x, int ldx, const void* wgt, void* y, int l
         a.xf.rm = bnin->running_mean; a.xf.rv = bnin->running_var; a.xf.nbt = (long long*)bnin->num_batches_tracked;
         a.xf.eps = bnin->eps; a.xf.mom = bnin->momentum; a.xf.groups = bnin->groups; a.xf.relu = bnin->relu; a.xf.C = Cin;
         a.xf.rows_per_group = (int)((long long)N * H * W / bnin->groups);
+        a.tiles_c = cdiv(Cout, 128);
         if (kind == 3) {
-            a.tiles_c = cdiv(Cout, 128); a.tiles_p = cdiv(M, 128);
-            const int grid = a.tiles_c * a.tiles_p;
-            RGDA_IGEMM(128, 128, 2, 2, 4, false, true);
+            a.tiles_p = cdiv(M, 128);
+            p.route = IGEMM_ID(128, 128, 2, 2, 4, false, true);
         } else {
-            const int tr = kind == 1 ? 4 : 8;
-            a.tiles_c = cdiv(Cout, 128); a.tiles_p = (int)(M / (tr * 32));
-            const int grid = a.tiles_c * a.tiles_p;
-            int ns = 4;
-            if (const char* e = TUNE_ENV("RGDA_HALO_NS")) ns = atoi(e);                     // tuning experiments only
-            if (W != 32 && kind == 1) RGDA_LAUNCH("conv3x3_halo_wide_kernel<1, 4, 4, true, true>", conv3x3_halo_wide_kernel<1, 4, 4, true, true><<<grid, 512, 0, st>>>(a));
-            else if (W != 32) RGDA_LAUNCH("conv3x3_halo_wide_kernel<1, 8, 3, false, true>", conv3x3_halo_wide_kernel<1, 8, 3, false, true><<<grid, 512, 0, st>>>(a));
-            else if (kind == 1 && ns == 4) RGDA_LAUNCH("conv3x3_halo_kernel<1, 4, true, 4, true>", conv3x3_halo_kernel<1, 4, true, 4><<<grid, 512, 0, st>>>(a));
-            else if (kind == 1) RGDA_LAUNCH("conv3x3_halo_kernel<1, 4, true, 3, false>", conv3x3_halo_kernel<1, 4, true><<<grid, 512, 0, st>>>(a));
-            // (the pipelined form of the 8-row variant with the transform spills 80 registers: it keeps the plain loop)
-            else RGDA_LAUNCH("conv3x3_halo_kernel<1, 8, true, 3, false>", conv3x3_halo_kernel<1, 8, true><<<grid, 512, 0, st>>>(a));
+            a.tiles_p = (int)(M / ((kind == 1 ? 4 : 8) * 32));
+            if (W != 32) p.route = kind == 1 ? R_HALOW_1_4_XF : R_HALOW_1_8_XF;
+            else p.route = kind == 1 ? R_HALO_1_4_XF : R_HALO_1_8_XF;
+#ifdef RGDA_TUNING      // RGDA_HALO_NS != 4: the plain loop
+            if (const char* e = TUNE_ENV("RGDA_HALO_NS")) { if (atoi(e) != 4 && W == 32 && kind == 1) p.route = R_HALO_1_4_XF_PLAIN; }
+#endif
         }
-        RGDA_CHECK_LAUNCH();
+        p.grid = a.tiles_c * a.tiles_p;
         return RGDA_OK;
     }
     // layer1's 64 -> 64 3x3 on 128-wide maps: weights-resident rolling-window kernel, one workgroup per CU
-    {
-        int c64_on = 1;
-        if (const char* e = TUNE_ENV("RGDA_C64")) c64_on = atoi(e);                         // tuning experiments only
-        if (c64_on && kh == 3 && kw == 3 && stride == 1 && pad == 1 && dil == 1 && Cin == 64 && Cout == 64 && W == 128 &&
-            Wo == W && Ho == H && !(a.rows_per_group % (H * W))) {
-            int rpw = (int)((long long)N * H / 256);
-            while (rpw > 1 && (H % rpw)) --rpw;
-            if (rpw >= 2) {
-                a.tpw = rpw;
-                a.tiles_c = 1;
-                a.tiles_p = N * H;
-                const int kind = a.ev_rm ? EPI_EV : a.bn_x ? (a.bn_relu == 2 ? EPI_BNX2 : EPI_BNX)
-                               : a.res ? (a.stats ? EPI_RES_STATS : EPI_RES) : (a.stats ? EPI_STATS : EPI_PLAIN);
-                const int grid = N * H / rpw;
-#define RGDA_C64(KIND) case KIND: RGDA_LAUNCH("conv3x3_c64_kernel<128, " #KIND ">", conv3x3_c64_kernel<128, KIND><<<grid, 512, 0, st>>>(a)); break
-                switch (kind) { RGDA_C64(0); RGDA_C64(1); RGDA_C64(2); RGDA_C64(3); RGDA_C64(4); RGDA_C64(5); RGDA_C64(6); }
-#undef RGDA_C64
-                RGDA_CHECK_LAUNCH();
-                return RGDA_OK;
-            }
+    if (tune_int("RGDA_C64", 1) && kh == 3 && kw == 3 && stride == 1 && pad == 1 && dil == 1 && Cin == 64 && Cout == 64 && W == 128 &&
+        Wo == W && Ho == H && !(a.rows_per_group % (H * W))) {
+        int rpw = (int)((long long)N * H / 256);
+        while (rpw > 1 && (H % rpw)) --rpw;
+        if (rpw >= 2) {
+            a.tpw = rpw;
+            a.tiles_c = 1;
+            a.tiles_p = N * H;
+            p.route = R_C64_0 + conv_epi_kind(a);
+            p.grid = N * H / rpw;
+            return RGDA_OK;
         }
     }
     // long-K 3x3 convolutions on 32-wide maps (heads, layer 4): the halo kernel (tiles of 8 image rows = 256 pixels)
     if (const int tr = conv_use_halo(M, Cout, Cin, kh, kw, stride, pad, dil, H, W, Ho, Wo, a.rows_per_group)) {
         a.tiles_c = cdiv(Cout, 128);
         a.tiles_p = (int)(M / (tr * 32));
-        const int grid = a.tiles_c * a.tiles_p;
-        int ns = 4;                                                                        // (dilation 2: 3 stages, 160 KB)
-        if (const char* e = TUNE_ENV("RGDA_HALO_NS")) ns = atoi(e);                         // tuning experiments only
-        if (W != 32) {
-            if (tr == 4) RGDA_LAUNCH("conv3x3_halo_wide_kernel<1, 4, 4, true, false>", conv3x3_halo_wide_kernel<1, 4, 4><<<grid, 512, 0, st>>>(a));
-            else if (dil == 1) RGDA_LAUNCH("conv3x3_halo_wide_kernel<1, 8, 4, true, false>", conv3x3_halo_wide_kernel<1, 8, 4><<<grid, 512, 0, st>>>(a));
-            else RGDA_LAUNCH("conv3x3_halo_wide_kernel<2, 8, 3, true, false>", conv3x3_halo_wide_kernel<2, 8, 3, true><<<grid, 512, 0, st>>>(a));
+        if (W != 32) p.route = tr == 4 ? R_HALOW_1_4 : dil == 1 ? R_HALOW_1_8 : R_HALOW_2_8;
+        else p.route = tr == 4 ? R_HALO_1_4 : dil == 1 ? R_HALO_1_8 : R_HALO_2_8;
+#ifdef RGDA_TUNING      // RGDA_HALO_NS != 4: the plain loop
+        if (const char* e = TUNE_ENV("RGDA_HALO_NS")) {
+            if (atoi(e) != 4 && W == 32) p.route = tr == 4 ? R_HALO_1_4_PLAIN : dil == 1 ? R_HALO_1_8_PLAIN : R_HALO_2_8_PLAIN;
         }
-        else if (tr == 4 && ns == 4) RGDA_LAUNCH("conv3x3_halo_kernel<1, 4, false, 4, true>", conv3x3_halo_kernel<1, 4, false, 4><<<grid, 512, 0, st>>>(a));
-        else if (tr == 4) RGDA_LAUNCH("conv3x3_halo_kernel<1, 4, false, 3, false>", conv3x3_halo_kernel<1, 4><<<grid, 512, 0, st>>>(a));
-        else if (dil == 1 && ns == 4) RGDA_LAUNCH("conv3x3_halo_kernel<1, 8, false, 4, true>", conv3x3_halo_kernel<1, 8, false, 4><<<grid, 512, 0, st>>>(a));
-        else if (dil == 1) RGDA_LAUNCH("conv3x3_halo_kernel<1, 8, false, 3, false>", conv3x3_halo_kernel<1, 8><<<grid, 512, 0, st>>>(a));
-        else if (ns == 4) RGDA_LAUNCH("conv3x3_halo_kernel<2, 8, false, 3, true>", conv3x3_halo_kernel<2, 8, false, 3, true><<<grid, 512, 0, st>>>(a));
-        else RGDA_LAUNCH("conv3x3_halo_kernel<2, 8, false, 3, false>", conv3x3_halo_kernel<2, 8><<<grid, 512, 0, st>>>(a));
-        RGDA_CHECK_LAUNCH();
+#endif
+        p.grid = a.tiles_c * a.tiles_p;
         return RGDA_OK;
     }
     // short-K 1x1 convolutions on large maps: the persistent streaming kernel, `wgs` workgroups of T pixel tiles each
-    {
-        int stream_on = 1, wpc = 1;
-        if (const char* e = TUNE_ENV("RGDA_STREAM")) stream_on = atoi(e);                   // tuning experiments only
-        if (const char* e = TUNE_ENV("RGDA_STREAM_WPC")) wpc = atoi(e);                     // tuning experiments only
-        if (stream_on && kh == 1 && kw == 1 && stride == 1 && pad == 0 && Ho == H && Wo == W &&
-            (Cin == 64 || Cin == 128) && !(Cout & 127) && M >= 4 * 128 && !(M & 127) &&
-            (long long)M * ldx * 2 < (1ll << 31)) {            // (32-bit byte offsets into the pixel operand)
-            const int bp = 128;
-            const int tiles_c = Cout / 128;
-            const long long tiles_p = M / bp;
-            int chunks = (256 * wpc) / tiles_c;
-            while (chunks > 1 && ((tiles_p % chunks) || (a.rows_per_group % (int)(tiles_p / chunks * bp)))) chunks >>= 1;
-            const long long T = chunks >= 1 ? tiles_p / chunks : 0;
-            if (!(M % bp) && chunks >= 1 && T >= 4 && T <= 4096 && !(tiles_p % chunks) && !(a.rows_per_group % (int)(T * bp))) {
-                a.tiles_c = tiles_c; a.tiles_p = (int)tiles_p; a.tpw = (int)T;
-                const int grid = tiles_c * chunks;
-                // one instantiation per fused epilogue (the choice conv_epilogue makes from the arguments)
-                const int kind = a.ev_rm ? EPI_EV : a.bn_x ? (a.bn_relu == 2 ? EPI_BNX2 : EPI_BNX)
-                               : a.res ? (a.stats ? EPI_RES_STATS : EPI_RES) : (a.stats ? EPI_STATS : EPI_PLAIN);
-#define RGDA_STREAM(KC, BP, WC, WP, KIND)                                                                      \
-    case KIND: RGDA_LAUNCH("conv1x1_stream_kernel<" #KC ", " #BP ", " #WC ", " #WP ", " #KIND ">",              \
-                           conv1x1_stream_kernel<KC, BP, WC, WP, KIND><<<grid, 512, 0, st>>>(a)); break
-#define RGDA_STREAM_ALL(KC, BP, WC, WP)                                                                        \
-    switch (kind) {                                                                                            \
-        RGDA_STREAM(KC, BP, WC, WP, 0); RGDA_STREAM(KC, BP, WC, WP, 1); RGDA_STREAM(KC, BP, WC, WP, 2);         \
-        RGDA_STREAM(KC, BP, WC, WP, 3); RGDA_STREAM(KC, BP, WC, WP, 4); RGDA_STREAM(KC, BP, WC, WP, 5);         \
-        RGDA_STREAM(KC, BP, WC, WP, 6);                                                                         \
-    }
-                if (Cin == 64) { RGDA_STREAM_ALL(1, 128, 2, 4) }
-                else { RGDA_STREAM_ALL(2, 128, 2, 4) }
-#undef RGDA_STREAM_ALL
-#undef RGDA_STREAM
-                RGDA_CHECK_LAUNCH();
-                return RGDA_OK;
-            }
+    const int wpc = tune_int("RGDA_STREAM_WPC", 1);                                      // tuning experiments only
+    if (tune_int("RGDA_STREAM", 1) && kh == 1 && kw == 1 && stride == 1 && pad == 0 && Ho == H && Wo == W &&
+        (Cin == 64 || Cin == 128) && !(Cout & 127) && M >= 4 * 128 && !(M & 127) &&
+        (long long)M * d.ldx * 2 < (1ll << 31)) {            // (32-bit byte offsets into the pixel operand)
+        const int bp = 128;
+        const int tiles_c = Cout / 128;
+        const long long tiles_p = M / bp;
+        int chunks = (256 * wpc) / tiles_c;
+        while (chunks > 1 && ((tiles_p % chunks) || (a.rows_per_group % (int)(tiles_p / chunks * bp)))) chunks >>= 1;
+        const long long T = chunks >= 1 ? tiles_p / chunks : 0;
+        if (!(M % bp) && chunks >= 1 && T >= 4 && T <= 4096 && !(tiles_p % chunks) && !(a.rows_per_group % (int)(T * bp))) {
+            a.tiles_c = tiles_c; a.tiles_p = (int)tiles_p; a.tpw = (int)T;
+            p.route = (Cin == 64 ? R_STREAM1_0 : R_STREAM2_0) + conv_epi_kind(a);
+            p.grid = tiles_c * chunks;
+            return RGDA_OK;
         }
     }
-    int bc, bp, stages;
-    if (pick_tile(M, Cout, (long long)kh * kw * Cin, (stats && stat_groups > 1) ? a.rows_per_group : 0, bc, bp, stages))
+    // the generic tile: fill 256 CUs (2 workgroups each); prefer the big tile when it still gives >= 512 groups
+    ConvTile t;
+    if (pick_tile(M, Cout, (long long)kh * kw * Cin, (a.stats && stat_groups > 1) ? a.rows_per_group : 0, t))
         return RGDA_ERR_UNSUPPORTED;
-    if (const char* e = TUNE_ENV("RGDA_TILE")) sscanf(e, "%d,%d,%d", &bc, &bp, &stages);   // tuning experiments only
-    a.tiles_c = cdiv(Cout, bc);
-    a.tiles_p = cdiv(M, bp);
-    int grid = a.tiles_c * a.tiles_p;
-    static const bool pipe = TUNE_ENV("RGDA_NO_PIPE") == nullptr;                           // (off switch: tuning experiments only)
-    if (pipe && bc == 128 && bp == 128 && stages == 83) RGDA_IGEMM(128, 128, 3, 2, 4, true, false);
-    else if (pipe && bc == 128 && bp == 256 && stages == 83) RGDA_IGEMM(128, 256, 3, 2, 4, true, false);
-    else if (pipe && bc == 128 && bp == 64 && stages == 3) RGDA_IGEMM(128, 64, 3, 2, 2, true, false);
-    else if (bc == 128 && bp == 128 && stages == 83) RGDA_IGEMM(128, 128, 3, 2, 4, false, false);
-    else if (bc == 128 && bp == 128 && stages == 82) RGDA_IGEMM(128, 128, 2, 2, 4, false, false);
-    else if (bc == 128 && bp == 256 && stages == 83) RGDA_IGEMM(128, 256, 3, 2, 4, false, false);
-    else if (bc == 128 && bp == 256) RGDA_IGEMM(128, 256, 3, 2, 2, false, false);
-    else if (bc == 256 && bp == 128) RGDA_IGEMM(256, 128, 3, 2, 2, false, false);
-    else if (bc == 128 && bp == 128 && stages == 2) RGDA_IGEMM(128, 128, 2, 2, 2, false, false);
-    else if (bc == 128 && bp == 128 && stages == 4) RGDA_IGEMM(128, 128, 4, 2, 2, false, false);
-    else if (bc == 128 && bp == 128) RGDA_IGEMM(128, 128, 3, 2, 2, false, false);
-    else if (bc == 128 && bp == 64 && stages == 2) RGDA_IGEMM(128, 64, 2, 2, 2, false, false);
-    else if (bc == 128 && bp == 64 && stages == 4) RGDA_IGEMM(128, 64, 4, 2, 2, false, false);
-    else if (bc == 128 && bp == 64) RGDA_IGEMM(128, 64, 3, 2, 2, false, false);
-    else if (bc == 64 && bp == 128) RGDA_IGEMM(64, 128, 3, 2, 2, false, false);
-    else if (stages == 4) RGDA_IGEMM(64, 64, 4, 2, 2, false, false);
-    else if (stages == 2) RGDA_IGEMM(64, 64, 2, 2, 2, false, false);
-    else RGDA_IGEMM(64, 64, 3, 2, 2, false, false);
-    RGDA_CHECK_LAUNCH();
-    return RGDA_OK;
+    if (const char* e = TUNE_ENV("RGDA_TILE")) {       // tuning experiments only: bc,bp,stages[,wp], pipelined where such a row exists
+        t.wp = 2;
+        sscanf(e, "%d,%d,%d,%d", &t.bc, &t.bp, &t.stages, &t.wp);
+        t.pipe = !TUNE_ENV("RGDA_NO_PIPE");
+        if (igemm_route(t) < 0) t.pipe = false;
+    }
+    a.tiles_c = cdiv(Cout, t.bc);
+    a.tiles_p = cdiv(M, t.bp);
+    p.route = igemm_route(t);
+    p.grid = a.tiles_c * a.tiles_p;
+    return p.route < 0 ? RGDA_ERR_UNSUPPORTED : RGDA_OK;
 }
 
-#undef RGDA_IGEMM
-#undef RGDA_LAUNCH
+static int conv_run(const rgda_conv2d_desc& d, const ConvFuse& f, rgda_stream_t stream) {
+    ConvPlan p;
+    if (const int rc = conv_select(d, f, p)) return rc;
+    return conv_launch(p.route, p.a, p.grid, to_stream(stream));
+}
 
 // The kernel instantiation that serves a convolution call, as rocprofv3 names it (no launch): `variant` 0 = rgda_conv2d
 // (fused statistics with `stat_groups` groups when has_stats), 1 = rgda_conv2d_bneval, 2 = rgda_conv2d_bnbwd,
@@ -1589,106 +1621,88 @@ extern "C" const char* rgda_conv2d_kernel(int variant, int N, int H, int W, int 
                                           int stride, int pad, int dil, int mode, int has_stats, int stat_groups) {
     static rgda_stat_t dummy_stats;
     static const float dummy_f = 0.f;
-    const char* name = nullptr;
-    void* const p = (void*)&dummy_stats;           // never dereferenced: a dry run stops before any launch
+    void* const ptr = (void*)&dummy_stats;         // never dereferenced: nothing is launched
     rgda_stat_t* st = (has_stats || variant >= 2) ? &dummy_stats : nullptr;
     BnEvalFuse e = {&dummy_f, &dummy_f, &dummy_f, &dummy_f, 1e-5f, 1};
-    BnBwdFuse b = {nullptr, 0, (const unsigned char*)p, p, (Cout + 7) & ~7, &dummy_f, nullptr, 0, 1, nullptr, nullptr};
+    BnBwdFuse b = {nullptr, 0, (const unsigned char*)ptr, ptr, (Cout + 7) & ~7, &dummy_f, nullptr, 0, 1, nullptr, nullptr};
     rgda_bn_operand o = {&dummy_stats, &dummy_f, &dummy_f, nullptr, nullptr, nullptr, nullptr, 1e-5f, 0.1f, stat_groups < 1 ? 1 : stat_groups, 1};
-    const int ld_in = (Cin + 7) & ~7, ld_out = (Cout + 7) & ~7;
-    const int rc = conv2d_launch(p, ld_in, p, p, ld_out, nullptr, 0, nullptr, variant == 1 ? nullptr : st, stat_groups, N, H, W, Cin, Ho,
-                                 Wo, Cout, kh, kw, stride, pad, dil, variant == 3 ? 0 : mode, variant == 2 ? &b : nullptr, nullptr,
-                                 variant == 1 ? &e : nullptr, variant == 3 ? &o : nullptr, &name);
-    return rc == RGDA_OK ? name : nullptr;
+    const rgda_conv2d_desc d = {ptr, ptr, ptr, nullptr, nullptr, variant == 1 ? nullptr : st, (Cin + 7) & ~7, (Cout + 7) & ~7, 0,
+                                stat_groups, N, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil, variant == 3 ? 0 : mode};
+    ConvPlan p;
+    return conv_select(d, {variant == 2 ? &b : nullptr, variant == 1 ? &e : nullptr, variant == 3 ? &o : nullptr}, p) == RGDA_OK ? CONV_ROUTE_NAMES[p.route] : nullptr;
 }
 
-static const char* const GROUPED_KERNEL = "conv_igemm_kernel<128, 64, 3, 2, 2, true, false>";
+// selects every descriptor of a list (before anything is launched: a list with a wrong entry launches nothing)
+static int conv_select_list(const rgda_conv2d_desc* descs, int n, std::vector<ConvPlan>& plans) {
+    if (!descs || n < 0) return RGDA_ERR_ARG;
+    plans.resize(n);
+    for (int i = 0; i < n; ++i)
+        if (const int rc = conv_select(descs[i], ConvFuse{}, plans[i])) return rc;
+    return RGDA_OK;
+}
+static thread_local std::vector<ConvPlan> conv_plans;
 
 extern "C" int rgda_conv2d_grouped(const rgda_conv2d_desc* descs, int n, rgda_stream_t stream) {
-    if (!descs || n < 0) return RGDA_ERR_ARG;
+    if (const int rc = conv_select_list(descs, n, conv_plans)) return rc;
     hipStream_t st = to_stream(stream);
     ConvGroup g;
     g.n = 0; g.start[0] = 0;
     auto flush = [&]() -> int {
+        int rc = RGDA_OK;
         if (g.n == 1) {          // alone: the ordinary launch (same kernel, same argument block)
-            conv_igemm_kernel<128, 64, 3, 2, 2, true, false><<<g.start[1], 256, 0, st>>>(g.a[0]);
+            rc = conv_launch(R_GROUPED, g.a[0], g.start[1], st);
         } else if (g.n > 1) {
             for (int i = g.n + 1; i <= CONV_GROUP_MAX; ++i) g.start[i] = g.start[g.n];
             conv_igemm_grouped_kernel<128, 64, 3, 2, 2, true><<<g.start[g.n], 256, 0, st>>>(g);
+            RGDA_CHECK_LAUNCH();
         }
         g.n = 0;
-        RGDA_CHECK_LAUNCH();
-        return RGDA_OK;
+        return rc;
     };
-    // validate everything first: nothing is launched when one descriptor is wrong
     for (int i = 0; i < n; ++i) {
-        const rgda_conv2d_desc& d = descs[i];
-        const char* name = nullptr;
-        const int rc = conv2d_launch(d.x, d.ldx, d.wgt, d.y, d.ldy, d.res, d.ldres, d.res_relu_mask, (rgda_stat_t*)d.stats,
-                                     d.stat_groups, d.N, d.H, d.W, d.Cin, d.Ho, d.Wo, d.Cout, d.kh, d.kw, d.stride, d.pad, d.dil,
-                                     d.mode, nullptr, stream, nullptr, nullptr, &name);
-        if (rc != RGDA_OK) return rc;
-    }
-    for (int i = 0; i < n; ++i) {
-        const rgda_conv2d_desc& d = descs[i];
-        const char* name = nullptr;
-        ConvArgs a;
-        conv2d_launch(d.x, d.ldx, d.wgt, d.y, d.ldy, d.res, d.ldres, d.res_relu_mask, (rgda_stat_t*)d.stats, d.stat_groups, d.N, d.H,
-                      d.W, d.Cin, d.Ho, d.Wo, d.Cout, d.kh, d.kw, d.stride, d.pad, d.dil, d.mode, nullptr, stream, nullptr, nullptr,
-                      &name, &a);
-        if (name && !strcmp(name, GROUPED_KERNEL)) {
-            g.a[g.n] = a;
-            g.start[g.n + 1] = g.start[g.n] + a.tiles_c * a.tiles_p;
+        const ConvPlan& p = conv_plans[i];
+        if (p.route == R_GROUPED) {
+            g.a[g.n] = p.a;
+            g.start[g.n + 1] = g.start[g.n] + p.grid;
             if (++g.n == CONV_GROUP_MAX) { if (int rc = flush()) return rc; }
         } else {                 // another kernel serves it: its own launch
-            const int rc = conv2d_launch(d.x, d.ldx, d.wgt, d.y, d.ldy, d.res, d.ldres, d.res_relu_mask, (rgda_stat_t*)d.stats,
-                                         d.stat_groups, d.N, d.H, d.W, d.Cin, d.Ho, d.Wo, d.Cout, d.kh, d.kw, d.stride, d.pad, d.dil,
-                                         d.mode, nullptr, stream);
-            if (rc != RGDA_OK) return rc;
+            if (const int rc = conv_launch(p.route, p.a, p.grid, st)) return rc;
         }
     }
     return flush();
 }
 
-// how many kernel launches rgda_conv2d_grouped makes of a list, and (name != NULL) whether they all share the grouped kernel
+// how many kernel launches rgda_conv2d_grouped makes of a list (negative: the status it would fail with)
 extern "C" int rgda_conv2d_grouped_launches(const rgda_conv2d_desc* descs, int n) {
-    if (!descs || n < 0) return RGDA_ERR_ARG;
-    int grouped = 0, single = 0;
-    for (int i = 0; i < n; ++i) {
-        const rgda_conv2d_desc& d = descs[i];
-        const char* name = nullptr;
-        const int rc = conv2d_launch(d.x, d.ldx, d.wgt, d.y, d.ldy, d.res, d.ldres, d.res_relu_mask, (rgda_stat_t*)d.stats,
-                                     d.stat_groups, d.N, d.H, d.W, d.Cin, d.Ho, d.Wo, d.Cout, d.kh, d.kw, d.stride, d.pad, d.dil,
-                                     d.mode, nullptr, nullptr, nullptr, nullptr, &name);
-        if (rc != RGDA_OK) return rc;
-        if (!strcmp(name, GROUPED_KERNEL)) ++grouped; else ++single;
-    }
-    return single + (grouped + CONV_GROUP_MAX - 1) / CONV_GROUP_MAX;
+    if (const int rc = conv_select_list(descs, n, conv_plans)) return rc;
+    int grouped = 0;
+    for (const ConvPlan& p : conv_plans) grouped += p.route == R_GROUPED;
+    return n - grouped + (grouped + CONV_GROUP_MAX - 1) / CONV_GROUP_MAX;
 }
 
 extern "C" int rgda_conv2d(const void* x, int ldx, const void* wgt, void* y, int ldy, const void* res, int ldres,
                            const uint8_t* res_relu_mask, rgda_stat_t* stats, int stat_groups, int N, int H, int W, int Cin,
                            int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int dil, int mode,
                            rgda_stream_t stream) {
-    return conv2d_launch(x, ldx, wgt, y, ldy, res, ldres, res_relu_mask, stats, stat_groups, N, H, W, Cin, Ho, Wo, Cout, kh, kw, stride,
-                         pad, dil, mode, nullptr, stream);
+    return conv_run({x, wgt, y, res, res_relu_mask, stats, ldx, ldy, ldres, stat_groups, N, H, W, Cin, Ho, Wo, Cout, kh, kw,
+                     stride, pad, dil, mode}, ConvFuse{}, stream);
 }
 
 extern "C" int rgda_conv2d_bneval(const void* x, int ldx, const void* wgt, void* y, int ldy, const void* res, int ldres,
                                   const float* running_mean, const float* running_var, const float* gamma,
                                   const float* beta, float eps, int relu, int N, int H, int W, int Cin, int Ho, int Wo,
                                   int Cout, int kh, int kw, int stride, int pad, int dil, rgda_stream_t stream) {
-    BnEvalFuse e = {running_mean, running_var, gamma, beta, eps, relu};
-    return conv2d_launch(x, ldx, wgt, y, ldy, res, ldres, nullptr, nullptr, 1, N, H, W, Cin, Ho, Wo, Cout, kh, kw, stride,
-                         pad, dil, 0, nullptr, stream, &e);
+    const BnEvalFuse e = {running_mean, running_var, gamma, beta, eps, relu};
+    return conv_run({x, wgt, y, res, nullptr, nullptr, ldx, ldy, ldres, 1, N, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil, 0},
+                    ConvFuse{nullptr, &e, nullptr}, stream);
 }
 
 extern "C" int rgda_conv2d_bnin(const rgda_bn_operand* bn_in, const void* x, int ldx, const void* wgt, void* y, int ldy,
                                 const void* res, int ldres, rgda_stat_t* stats, int stat_groups, int N, int H, int W, int Cin,
                                 int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int dil, rgda_stream_t stream) {
     if (!bn_in) return RGDA_ERR_ARG;
-    return conv2d_launch(x, ldx, wgt, y, ldy, res, ldres, nullptr, stats, stat_groups, N, H, W, Cin, Ho, Wo, Cout, kh, kw, stride,
-                         pad, dil, 0, nullptr, stream, nullptr, bn_in);
+    return conv_run({x, wgt, y, res, nullptr, stats, ldx, ldy, ldres, stat_groups, N, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad,
+                     dil, 0}, ConvFuse{nullptr, nullptr, bn_in}, stream);
 }
 
 extern "C" int rgda_conv2d_bnbwd(const void* x, int ldx, const void* wgt, void* y, int ldy, const void* res, int ldres,
@@ -1698,9 +1712,9 @@ extern "C" int rgda_conv2d_bnbwd(const void* x, int ldx, const void* wgt, void* 
                                  const float* bn_gamma, const float* bn_beta, int N,
                                  int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad,
                                  int dil, int mode, rgda_stream_t stream) {
-    BnBwdFuse b = {bn_y, bn_ldy, bn_relu_mask, bn_x, bn_ldx, bn_mi, bn_nscale, rows_per_image, relu, bn_gamma, bn_beta};
-    return conv2d_launch(x, ldx, wgt, y, ldy, res, ldres, res_relu_mask, sums, groups, N, H, W, Cin, Ho, Wo, Cout, kh, kw,
-                         stride, pad, dil, mode, &b, stream);
+    const BnBwdFuse b = {bn_y, bn_ldy, bn_relu_mask, bn_x, bn_ldx, bn_mi, bn_nscale, rows_per_image, relu, bn_gamma, bn_beta};
+    return conv_run({x, wgt, y, res, res_relu_mask, sums, ldx, ldy, ldres, groups, N, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad,
+                     dil, mode}, ConvFuse{&b, nullptr, nullptr}, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -2670,15 +2684,42 @@ __global__ void __launch_bounds__(256) conv_wgrad3x3_wide_kernel(WgradGroup g) {
     conv_wgrad3x3_body<WT, D, STAGES>(g);
 }
 
-static int ilog2_exact(int v) {
-    if (v <= 0 || (v & (v - 1))) return -1;
-    int s = 0;
-    while ((1 << s) < v) ++s;
-    return s;
-}
-
-// kernel families: 0..4 generic <128,128> <128,64> <64,128> <64,64> <256,128>; 5..10 tap-fused 3x3 <WT,D>
-enum { WK_G128_128 = 0, WK_G128_64, WK_G64_128, WK_G64_64, WK_G256_128, WK_F64_1, WK_F64_2, WK_F32_1, WK_F32_2, WK_F16_1, WK_F16_2, WK_COUNT };
+// The weight-gradient kernel families (generic tiles <BCO, BCI, ..>, tap-fused 3x3 <WT, D, ..>), one row each:
+// WGRAD(id, block size, slice, capacity, remap, kernel template, its full template argument list).
+//   slice: floats a workgroup leaves in the workspace per split (its accumulators; tap-fused: nine 64 x 64 taps).
+//   capacity: workgroups the chip holds at once: one per CU for the 144 KB generic tile and the dilated 64-wide tap-fused
+//   kernel, two per CU for everything else (the tap-fused kernels run 2-stage rings of 48-72 KB).
+//   remap: keeping a layer's work items on one XCD (one L2) pays where the items of a layer re-read the same rows many
+//   times (the taps of the small-channel 3x3 layers in the 64x64 kernel: 297 -> 220 us; tap-fused: 2 %); the
+//   grouped 1x1 layers of the 128x128 kernel measured 9 % SLOWER with it (207 -> 225 us), so they keep b -> item b.
+//   (Round 5, measured and not kept: a finer mapping for those -- the result tiles of one (layer, K split), which stream the
+//   same pixel rows, in consecutive slots of ONE XCD, the units round-robin over the XCDs, so that the 1.5 x over-fetch of
+//   b -> item b (FETCH_SIZE 1.0 GB against 0.67 GB unique per 16-layer launch) would hit one L2: conv_wgrad_kernel<256, 128>
+//   194 -> 226 us, step +0.28 ms (interleaved A/B).  32 workgroups x 3 stages x 48 KB in flight per XCD exceed its 4 MB
+//   L2; the launches run at 5.2 TB/s of fabric reads either way and spreading a unit over four L2s is what reaches it.)
+// The wide tap-fused forms <64, 1>, <64, 2> (52 KB per stage: one per CU either way) and <32, 2> spill when capped at 256
+// registers; <32, 1> takes 50 KB, <16, 1> 72 KB, <16, 2> 56 KB.
+// (round 5: with the compact halo tile THREE stages of <32, 1> fit a CU twice (75 KB); measured 296 against 294 us per launch
+// and +0.2 ms on the step: the loop does not wait for its DMA -- the other workgroup of the CU covers it -- and the
+// larger footprint costs the neighbouring streams' kernels their place)
+#define WGRAD_ROUTES                                                                           \
+    WGRAD(WK_G128_128, 512, 128 * 128, 512, 0, conv_wgrad_kernel, 128, 128, 2, 4, 3)           \
+    WGRAD(WK_G128_64, 512, 128 * 64, 512, 1, conv_wgrad_kernel, 128, 64, 4, 2, 3)              \
+    WGRAD(WK_G64_128, 512, 64 * 128, 512, 1, conv_wgrad_kernel, 64, 128, 2, 4, 3)              \
+    WGRAD(WK_G64_64, 256, 64 * 64, 512, 1, conv_wgrad_kernel, 64, 64, 2, 2, 3)                 \
+    WGRAD(WK_G256_128, 512, 256 * 128, 256, 0, conv_wgrad_kernel, 256, 128, 4, 2, 3)           \
+    WGRAD(WK_F64_1, 256, 9 * 64 * 64, 256, 1, conv_wgrad3x3_wide_kernel, 64, 1, 3)             \
+    WGRAD(WK_F64_2, 256, 9 * 64 * 64, 256, 1, conv_wgrad3x3_wide_kernel, 64, 2, 3)             \
+    WGRAD(WK_F32_1, 256, 9 * 64 * 64, 512, 1, conv_wgrad3x3_kernel, 32, 1, 2)                  \
+    WGRAD(WK_F32_2, 256, 9 * 64 * 64, 256, 1, conv_wgrad3x3_wide_kernel, 32, 2, 3)             \
+    WGRAD(WK_F16_1, 256, 9 * 64 * 64, 512, 1, conv_wgrad3x3_kernel, 16, 1, 3)                  \
+    WGRAD(WK_F16_2, 256, 9 * 64 * 64, 512, 1, conv_wgrad3x3_kernel, 16, 2, 2)
+#define WGRAD(ID, BLOCK, SLICE, CAPACITY, REMAP, KERNEL, ...) ID,
+enum { WGRAD_ROUTES WK_COUNT };
+#undef WGRAD
+#define WGRAD(ID, BLOCK, SLICE, CAPACITY, REMAP, KERNEL, ...) {#KERNEL "<" #__VA_ARGS__ ">", SLICE, CAPACITY, REMAP},
+static const struct { const char* name; size_t slice_floats; int capacity, remap; } WGRAD_KINDS[WK_COUNT] = {WGRAD_ROUTES};
+#undef WGRAD
 
 #ifndef RGDA_TAPFUSED_MIN_TILES
 #define RGDA_TAPFUSED_MIN_TILES 1
@@ -2718,14 +2759,14 @@ static int wgrad_prepare(const rgda_wgrad_desc& d, WgradArgs& a) {
             a.tap_fused = 1;
             a.tiles_co = cdiv(d.Cout, 64);
             a.tiles_ci = cdiv(d.Cin, 64);
-            return (wt == 64 ? WK_F64_1 : wt == 32 ? WK_F32_1 : WK_F16_1) + (d.dil == 2 ? 1 : 0);
+            if (d.dil == 2) return wt == 64 ? WK_F64_2 : wt == 32 ? WK_F32_2 : WK_F16_2;
+            return wt == 64 ? WK_F64_1 : wt == 32 ? WK_F32_1 : WK_F16_1;
         }
     }
     int bco = (d.Cout <= 64) ? 64 : 128, bci = (d.Cin <= 64) ? 64 : 128;
     // wide layers: 256 x 128 result tiles (8 waves of 64 x 64): 1.0 LDS fragment read per MFMA instead of 1.5 and
     // 48 KB instead of 64 KB of operands through LDS per 4.2 MFLOP -- the 128 x 128 loop is bound by LDS cycles
-    int big = 1;
-    if (const char* e = TUNE_ENV("RGDA_WGRAD_BIG")) big = atoi(e);                        // tuning experiments only
+    const int big = tune_int("RGDA_WGRAD_BIG", 1);                                        // tuning experiments only
     // (a 2-stage 256 x 256 tile, MFMA-bound on paper, measured the same step time: 21.71 vs 21.72 ms)
     if (big && bci == 128 && d.Cout >= 256 && (d.Cout % 256) == 0) bco = 256;
     a.tiles_co = cdiv(d.Cout, bco);
@@ -2743,17 +2784,6 @@ static inline int wgrad_ktiles(const WgradArgs& a) {
     return a.N * (a.H / (64 / wt)) * (a.W / wt);
 }
 
-// floats a workgroup of kernel family `kind` leaves in the workspace per split (its accumulators)
-static inline size_t wgrad_slice_floats(int kind) {
-    switch (kind) {
-        case WK_G128_128: return 128 * 128;
-        case WK_G128_64: return 128 * 64;
-        case WK_G64_128: return 64 * 128;
-        case WK_G64_64: return 64 * 64;
-        case WK_G256_128: return 256 * 128;
-        default: return 9 * 64 * 64;            // tap-fused: nine 64 x 64 taps
-    }
-}
 #define RGDA_WGRAD_WS_COUNTERS (64 * 1024)      // bytes of tile counters at the head of the workspace (16 K tiles per launch)
 
 // K splits of the layers of one launch (g.a[0..n)); 1 without a workspace.  One split count S for the launch (a layer
@@ -2765,14 +2795,9 @@ static inline size_t wgrad_slice_floats(int kind) {
 // 336 workgroups out of 112 tiles: two rounds of 86 steps where S = 2 gives one round of 128.)
 // Returns the bytes of partial tiles the launch needs behind the counters.
 static size_t wgrad_plan_splits(int kind, WgradGroup& g, bool have_ws) {
-    // workgroups the chip holds at once: one per CU for the 144 KB generic tile and the dilated 64-wide tap-fused kernel,
-    // two per CU for everything else (the tap-fused kernels run 2-stage rings of 48-72 KB)
-    const int capacity = (kind == WK_G256_128 || kind == WK_F64_1 || kind == WK_F64_2 || kind == WK_F32_2) ? 256 : 512;
-    int minkt = 16;
-    if (const char* e = TUNE_ENV("RGDA_WGRAD_MINKT")) minkt = atoi(e);                     // tuning experiments only
+    const int capacity = WGRAD_KINDS[kind].capacity;
+    const int minkt = tune_int("RGDA_WGRAD_MINKT", 16), rule = tune_int("RGDA_WGRAD_RULE", 1);     // tuning experiments only
     int best = 1;
-    int rule = 1;
-    if (const char* e = TUNE_ENV("RGDA_WGRAD_RULE")) rule = atoi(e);                       // tuning experiments only
     if (have_ws && rule == 0) {            // the pre-ABI-4 rule: split until the launch fills the chip
         int total = 0;
         for (int l = 0; l < g.n; ++l) total += wgrad_tiles(g.a[l]);
@@ -2795,7 +2820,7 @@ static size_t wgrad_plan_splits(int kind, WgradGroup& g, bool have_ws) {
             if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = S; }
         }
     }
-    if (const char* e = TUNE_ENV("RGDA_WGRAD_SPLITS")) best = atoi(e);                     // tuning experiments only
+    best = tune_int("RGDA_WGRAD_SPLITS", best);                                            // tuning experiments only
     size_t floats = 0;
     int items = 0, tiles_before = 0;
     for (int l = 0; l < g.n; ++l) {
@@ -2812,7 +2837,7 @@ static size_t wgrad_plan_splits(int kind, WgradGroup& g, bool have_ws) {
         a.ws_part = (float*)(uintptr_t)floats;
         a.ws_cnt = (int*)(uintptr_t)tiles_before;
         if (a.splits > 1) {
-            floats += (size_t)wgrad_tiles(a) * split_slots(a.splits) * wgrad_slice_floats(kind);
+            floats += (size_t)wgrad_tiles(a) * split_slots(a.splits) * WGRAD_KINDS[kind].slice_floats;
             tiles_before += wgrad_tiles(a) * (split_groups(a.splits) + 1);      // counters of this layer
         }
     }
@@ -2838,31 +2863,11 @@ static int wgrad_launch(int kind, WgradGroup& g, void* ws, size_t ws_bytes, hipS
         if (TUNE_ENV("RGDA_WGRAD_ATOMIC")) a.ws_part = nullptr;    // tuning only: every split adds to dW itself (not reproducible)
     }
     const int items = g.first[RGDA_WGRAD_MAXG];
-    // keeping a layer's work items on one XCD (one L2) pays where the items of a layer re-read the same rows many
-    // times (the taps of the small-channel 3x3 layers in the 64x64 kernel: 297 -> 220 us; tap-fused: 2 %); the
-    // grouped 1x1 layers of the 128x128 kernel measured 9 % SLOWER with it (207 -> 225 us), so they keep b -> item b.
-    // (Round 5, measured and not kept: a finer mapping for those -- the result tiles of one (layer, K split), which stream the
-    // same pixel rows, in consecutive slots of ONE XCD, the units round-robin over the XCDs, so that the 1.5 x over-fetch of
-    // b -> item b (FETCH_SIZE 1.0 GB against 0.67 GB unique per 16-layer launch) would hit one L2: conv_wgrad_kernel<256, 128>
-    // 194 -> 226 us, step +0.28 ms (interleaved A/B).  32 workgroups x 3 stages x 48 KB in flight per XCD exceed its 4 MB
-    // L2; the launches run at 5.2 TB/s of fabric reads either way and spreading a unit over four L2s is what reaches it.)
-    g.remap = (kind != WK_G128_128 && kind != WK_G256_128);
-    if (const char* e = TUNE_ENV("RGDA_WGRAD_REMAP")) g.remap = atoi(e);                   // tuning experiments only
+    g.remap = tune_int("RGDA_WGRAD_REMAP", WGRAD_KINDS[kind].remap);                       // tuning experiments only
     switch (kind) {
-        case WK_G128_128: conv_wgrad_kernel<128, 128, 2, 4><<<items, 512, 0, st>>>(g); break;
-        case WK_G128_64: conv_wgrad_kernel<128, 64, 4, 2><<<items, 512, 0, st>>>(g); break;
-        case WK_G64_128: conv_wgrad_kernel<64, 128, 2, 4><<<items, 512, 0, st>>>(g); break;
-        case WK_G64_64: conv_wgrad_kernel<64, 64><<<items, 256, 0, st>>>(g); break;
-        case WK_G256_128: conv_wgrad_kernel<256, 128, 4, 2><<<items, 512, 0, st>>>(g); break;
-        case WK_F64_1: conv_wgrad3x3_wide_kernel<64, 1, 3><<<items, 256, 0, st>>>(g); break;  // (capped at 256 registers it spills)
-        case WK_F64_2: conv_wgrad3x3_wide_kernel<64, 2, 3><<<items, 256, 0, st>>>(g); break;  // 52 KB per stage: one per CU either way
-        // (round 5: with the compact halo tile THREE stages fit a CU twice (75 KB); measured 296 against 294 us per launch and
-        // +0.2 ms on the step: the loop does not wait for its DMA -- the other workgroup of the CU covers it -- and the
-        // larger footprint costs the neighbouring streams' kernels their place)
-        case WK_F32_1: conv_wgrad3x3_kernel<32, 1, 2><<<items, 256, 0, st>>>(g); break;       // 50 KB
-        case WK_F32_2: conv_wgrad3x3_wide_kernel<32, 2, 3><<<items, 256, 0, st>>>(g); break;  // (capped at 256 registers it spills)
-        case WK_F16_1: conv_wgrad3x3_kernel<16, 1, 3><<<items, 256, 0, st>>>(g); break;       // 72 KB
-        default: conv_wgrad3x3_kernel<16, 2, 2><<<items, 256, 0, st>>>(g); break;              // 56 KB
+#define WGRAD(ID, BLOCK, SLICE, CAPACITY, REMAP, KERNEL, ...) case ID: KERNEL<__VA_ARGS__><<<items, BLOCK, 0, st>>>(g); break;
+        WGRAD_ROUTES
+#undef WGRAD
     }
     RGDA_CHECK_LAUNCH();
     return RGDA_OK;
@@ -2901,15 +2906,10 @@ static int wgrad_for_each_launch(const rgda_wgrad_desc* descs, int n, F fn) {
 
 // the kernel instantiation (as rocprofv3 names it) a layer's weight gradient maps to; layers with the same name share launches
 extern "C" const char* rgda_conv2d_wgrad_kernel(const rgda_wgrad_desc* d) {
-    static const char* const names[WK_COUNT] = {
-        "conv_wgrad_kernel<128, 128, 2, 4, 3>", "conv_wgrad_kernel<128, 64, 4, 2, 3>", "conv_wgrad_kernel<64, 128, 2, 4, 3>",
-        "conv_wgrad_kernel<64, 64, 2, 2, 3>", "conv_wgrad_kernel<256, 128, 4, 2, 3>",
-        "conv_wgrad3x3_wide_kernel<64, 1, 3>", "conv_wgrad3x3_wide_kernel<64, 2, 3>", "conv_wgrad3x3_kernel<32, 1, 2>",
-        "conv_wgrad3x3_wide_kernel<32, 2, 3>", "conv_wgrad3x3_kernel<16, 1, 3>", "conv_wgrad3x3_kernel<16, 2, 2>"};
     if (!d) return nullptr;
     WgradArgs a;
     const int kind = wgrad_prepare(*d, a);
-    return (kind >= 0 && kind < WK_COUNT) ? names[kind] : nullptr;
+    return (kind >= 0 && kind < WK_COUNT) ? WGRAD_KINDS[kind].name : nullptr;
 }
 
 extern "C" size_t rgda_conv2d_wgrad_workspace(const rgda_wgrad_desc* descs, int n) {
@@ -2937,9 +2937,6 @@ extern "C" int rgda_conv2d_wgrad_grouped(const rgda_wgrad_desc* descs, int n, vo
 extern "C" int rgda_conv2d_wgrad(const void* x, int ldx, const void* dy, int lddy, float* dw, int N, int H, int W,
                                  int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int dil,
                                  void* ws, size_t ws_bytes, rgda_stream_t stream) {
-    rgda_wgrad_desc d;
-    d.x = x; d.dy = dy; d.dw = dw; d.ldx = ldx; d.lddy = lddy; d.lddw = 0; d.co_split = 0;
-    d.N = N; d.H = H; d.W = W; d.Cin = Cin; d.Ho = Ho; d.Wo = Wo; d.Cout = Cout; d.kh = kh; d.kw = kw;
-    d.stride = stride; d.pad = pad; d.dil = dil;
+    const rgda_wgrad_desc d = {x, dy, dw, ldx, lddy, N, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, dil, 0, 0};
     return rgda_conv2d_wgrad_grouped(&d, 1, ws, ws_bytes, stream);
 }
