@@ -720,6 +720,34 @@ int rgda_coral_loss(const float* feat_s, int bs, int hws, int64_t ldcs, int64_t 
                     void* dfeat_s, int ldds, void* dfeat_t, int lddt, int accumulate, float weight, void* ws,
                     size_t ws_bytes, rgda_stream_t stream);
 
+/* ClassWareWhitening(class_ids = range(C), groups) (regda/gast/class_ware_whiten.py:14-65) of
+ * Aligner.whiten_class_ware (regda/gast/alignment.py:165-170), forward + gradient w.r.t. the feature map in one call:
+ *   feat f32 (b, k, hw): element (image i, channel c, pixel p) at feat[i * ldb + c * ldc + p] (NCHW: ldc = h*w,
+ *   ldb = k*h*w); labels int64 (b, hw), already at feature resolution; `ignore_label` pixels belong to no class.
+ *   s = k / groups.  For every class c < C with n_c >= 2 pixels and every group g of s consecutive channels:
+ *     mu = mean of the class's rows (fp32, fixed order);  Xc = bf16(X - mu), rounded once
+ *     S = Xc^T Xc / (n_c - 1)   (bf16 products, fp32 sums);  D = S - I (fp32);  term = sum(D * D) / s^2
+ *   a class with n_c <= 1 contributes 0 (the reference substitutes the identity).  loss[0] += weight * sum of the terms
+ *   dfeat (optional) bf16 [b*hw][lddf], pixel-major -- the layout rgda_instnorm_bwd consumes: the g block of the row
+ *     of a pixel of class c  (+)= 4 weight / (s^2 (n_c - 1)) * Xc[pixel][g block] . bf16(D_cg)
+ *     accumulate != 0: added in fp32, rounded once; the rows of ignored pixels and of classes with n_c <= 1 are left.
+ *     accumulate == 0: every row is written, those rows as zeros.
+ * (D is symmetric and the centred rows sum to zero, so the mean term of the backward vanishes.)
+ * 6 <= C <= 16 (a runtime value) and s in {32, 64, 96, 128}: RGDA_ERR_UNSUPPORTED otherwise.  Null pointers,
+ * k % groups != 0, lddf % 8 != 0 or lddf < k, dfeat not 16-byte aligned, ws not 256-byte aligned, b * hw > 2^24:
+ * RGDA_ERR_ARG.  Every check comes before any launch.  Deterministic: no floating-point atomics; the pixels are
+ * sorted by class in image order and every sum over them (means, the four row shares of a covariance block) is
+ * reduced in a fixed order.  The sort is one workgroup, serial in b * hw: meant for feature maps of some 10^4 pixels.
+ * ws: rgda_whiten_loss_workspace(n = b * hw, k, C, groups) bytes (0 for arguments the entry point rejects) =
+ *   256 + a(4 NP) + a(4 NP / 64) + a(4 C k) + 2 a(2 k NP) + a(2 C k s) + a(4 C groups),
+ *   NP = 64 * ceil(n / 64) + 64 * C,  a(x) = x rounded up to a multiple of 256.
+ * Its first int32 is a flag: bit 2 is set when a label outside [0, C) that is not ignore_label was seen (such a pixel
+ * is treated as ignored); the next 16 are the per-class pixel counts. */
+size_t rgda_whiten_loss_workspace(int n, int k, int C, int groups);
+int rgda_whiten_loss(const float* feat, int b, int hw, int64_t ldc, int64_t ldb, const int64_t* labels, int k,
+                     int C, int groups, int ignore_label, float* loss, void* dfeat, int lddf, int accumulate,
+                     float weight, void* ws, size_t ws_bytes, rgda_stream_t stream);
+
 /* Factored form of the PPM heads' tap-shifted bilinear maps (regda/models/Encoder.py:30-51: Upsample(bilinear,
  * align_corners=False) of the s x s branches into the 3x3 / pad 1 conv_last): the map V[(y,x)][(jy,jx),(ky,kx)] =
  * Uy[y+ky-1][jy] * Ux[x+kx-1][jx] is separable, so V and V^T are applied as two short maps (csrc/mix_kernels.hip).

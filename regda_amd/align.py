@@ -5,13 +5,16 @@ rank 2), on the same kernel plans as the SSL step (regda_amd/ssl.py):
     labels -> label_refine -> pseudo_selection -> Homogenizer (LRH) -> DownscaleLabel
     loss = loss_calc(src) + 0.5 * (PrototypeContrastiveLoss(src) + PrototypeContrastiveLoss(tgt))
            [+ CoralLoss(feat_s, feat_t)  with align_domain=True, --align-domain 1]
+           [+ whiten_weight * 0.5 * (ClassWareWhitening(feat_s, label_s_down) + ClassWareWhitening(feat_t, label_t))
+              with whiten_weight > 0: an extension, tools/train_align_reg.py never calls the whitener]
     -> backward -> clip_grad_norm_(32) -> SGD
 
 Differences to the SSL step that matter for the kernels: there is no CE on the target logits (their gradient is
 zero) and the loss reaches the network through the third forward output, the instance-normalised features
 (rgda_pcl_loss writes d loss / d feat pixel-major, `Deeplabv2._backward_plan(gfeat=...)` adds it in the
 instance-norm backward; with align_domain rgda_coral_loss then adds the CORAL gradient of both halves onto it).
-Data-parallel ranks compute CORAL on their local batch (regda_amd/source.py)."""
+Data-parallel ranks compute CORAL on their local batch (regda_amd/source.py), and so the whitening term
+(rgda_whiten_loss, added onto the same gradient rows after PCL and CORAL)."""
 import torch
 
 from . import ops
@@ -22,7 +25,7 @@ BF = torch.bfloat16
 
 
 class AlignStep(SSLStep):
-    def __init__(self, model, prototypes, pcl_temperature=8.0, align_domain=False, **kw):
+    def __init__(self, model, prototypes, pcl_temperature=8.0, align_domain=False, whiten_weight=0.0, **kw):
         kw.setdefault('proto_decay', 0.999)        # Aligner(decay=0.999), train_align_reg.py:112-113
         kw['ema_decay'] = None
         super().__init__(model, prototypes, **kw)
@@ -30,6 +33,15 @@ class AlignStep(SSLStep):
         self.loss_align = torch.zeros(1, device=model.device)
         self.align_domain = bool(align_domain)     # --align-domain 1: + aligner.align_domain(feat_s, feat_t), :188
         self.loss_domain = torch.zeros(1, device=model.device)
+        # > 0: + whiten_weight * Aligner.whiten_class_ware(feat_s, label_s, feat_t, label_t) (32 groups, alignment.py:71)
+        self.whiten_weight = float(whiten_weight)
+        if self.whiten_weight < 0.0:
+            raise ValueError('AlignStep: whiten_weight must be >= 0')
+        k = self.prototypes.shape[-1]
+        if self.whiten_weight > 0.0 and (k % 32 or k // 32 not in ops.WHITEN_BLOCKS):
+            raise NotImplementedError(f'AlignStep(whiten_weight > 0): {k} feature channels in 32 groups; served are '
+                                      f'{ops.WHITEN_BLOCKS} channels per group')
+        self.loss_white = torch.zeros(1, device=model.device)
 
     def step(self, images_s, label_s, images_t, regs_t, lr):
         """One stage-2 iteration.  Returns device tensors (loss_seg, loss_align, grad_norm_sq)."""
@@ -98,6 +110,11 @@ class AlignStep(SSLStep):
             self.loss_domain.zero_()
             ops.coral_loss(feat_s, feat_t, 1.0, loss=self.loss_domain, dfeat_s=gfeat[:nb * h * w],
                            dfeat_t=gfeat[nb * h * w:], accumulate=True)
+        if self.whiten_weight > 0.0:
+            self.loss_white.zero_()
+            for f, lab, rows in ((feat_s, label_s_down, gfeat[:nb * h * w]), (feat_t, label_t, gfeat[nb * h * w:])):
+                ops.whiten_loss(f, lab, self.C, 32, self.ig, 0.5 * self.whiten_weight, loss=self.loss_white, dfeat=rows,
+                                accumulate=True)
         self._backward_and_update(T, main, g1, g2, gfeat=gfeat)
         self.last_hard, self.last_label_t, self.last_label_s_down = hard, label_t, label_s_down
         return loss_seg, self.loss_align, self.gn

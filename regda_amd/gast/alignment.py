@@ -1,12 +1,15 @@
 """Aligner (prototype EMA + online soft-label re-weighting + domain alignment) -- mirror of the parts of
 regda/gast/alignment.py that the authors' recipe (runs/regda/run_2potsdam.sh) uses: label_refine (:194-265,
 with and without the superpixel view; every `mode`), update_prototype (:86-90), align_domain (CORAL, :79-84),
-update_avg / init_avg (the prototype initialisation of tools/init_prototypes.py, :107-126), DownscaleLabel (:456-481).
-The other alignment losses (align_class, whitening, MMD) are not provided.
+whiten_class_ware (ClassWareWhitening, :165-170), update_avg / init_avg (the prototype initialisation of
+tools/init_prototypes.py, :107-126), DownscaleLabel (:456-481).
+The other alignment losses (align_class, align_instance, MMD) are not provided: their distances are detached in the
+reference, so they carry no gradient.
 """
 import torch
 
 from .. import ops
+from .class_ware_whiten import ClassWareWhitening
 from .coral import CoralLoss
 
 
@@ -46,6 +49,7 @@ class Aligner:
                                            min_ratio=0.75)
         self._classmax_ws = None
         self.coral = CoralLoss()
+        self.whitener = ClassWareWhitening(class_ids=range(class_num), groups=32, ignore_label=ignore_label)
         self._avg_stats = None          # update_avg: f32 sums[c][k] then cnt[c], summed over the batches seen
 
     def align_domain(self, feat_s, feat_t):
@@ -55,6 +59,14 @@ class Aligner:
         assert len(feat_s.shape) == 4, 'tensor "feat_s" and "feat_t" must have 4 dimensions'
         assert feat_s.shape[1] == self.feat_channels
         return self.coral(feat_s, feat_t)
+
+    def whiten_class_ware(self, feat_s, label_s, feat_t=None, label_t=None):
+        """Class-aware whitening of the source features against the downscaled full-size labels, averaged with the
+        target's when both target arguments are given (alignment.py:165-170).  Gradients reach the features."""
+        loss_white = self.whitener(feat_s, self.downscale_gt(label_s))
+        if feat_t is not None and label_t is not None:
+            loss_white = 0.5 * (loss_white + self.whitener(feat_t, self.downscale_gt(label_t)))
+        return loss_white
 
     def update_avg(self, feat, label):
         """Add a batch's per-class feature sums and pixel counts (of the downscaled label) to the running totals

@@ -1091,6 +1091,44 @@ def coral_loss(feat_s, feat_t, weight=1.0, loss=None, dfeat_s=None, dfeat_t=None
     return loss
 
 
+WHITEN_BLOCKS = (32, 64, 96, 128)      # channels per group rgda_whiten_loss serves
+
+
+def whiten_loss(feat, labels, class_num, groups, ignore_label=-1, weight=1.0, loss=None, dfeat=None, accumulate=False,
+                check=False, return_ws=False):
+    """ClassWareWhitening(range(class_num), groups)(feat, labels) (regda/gast/class_ware_whiten.py): feat f32
+    (b, k, h, w), read in place through its channel and image strides when the pixels of an image are contiguous (NCHW,
+    channel slices, batch slices), copied otherwise (another dtype, channels-last); labels int64 (b, h, w) or
+    (b, 1, h, w) at feature resolution.  loss (f32[1]) += weight * L; dfeat
+    (optional) bf16 [b*h*w, >= k] pixel-major rows: (+)= weight * dL / dfeat (rgda_whiten_loss; accumulate=False
+    writes every row).  check=True reads the label-range flag back (one host sync) and raises ValueError on a label
+    outside [0, class_num) that is not ignore_label.  Returns the (accumulating) fp32 loss tensor (and the workspace
+    with return_ws: int32 word 0 is the flag, words 1..16 the per-class pixel counts)."""
+    _need_cuda(feat, labels, dfeat)
+    assert feat.dim() == 4, 'whiten_loss: NCHW (b, k, h, w) features'
+    feat = feat.float()
+    b, k, h, w = feat.shape
+    ldb, ldc = feat.stride(0), feat.stride(1)
+    if not ((w == 1 or feat.stride(3) == 1) and (h == 1 or feat.stride(2) == w) and ldc >= h * w and
+            (b == 1 or ldb >= ldc * k)):
+        feat = feat.contiguous()
+        ldb, ldc = k * h * w, h * w
+    assert labels.dtype == torch.int64 and labels.numel() == b * h * w, (labels.dtype, labels.shape, feat.shape)
+    labels = labels.contiguous().view(b, h, w)
+    if dfeat is not None:
+        assert dfeat.dtype == torch.bfloat16 and dfeat.dim() == 2 and dfeat.shape[0] == b * h * w and dfeat.stride(1) == 1
+    if loss is None:
+        loss = torch.zeros(1, device=feat.device)
+    L = lib()
+    ws = _ws(L.size('rgda_whiten_loss_workspace', b * h * w, k, int(class_num), int(groups)), feat.device)
+    L.call('rgda_whiten_loss', feat.data_ptr(), b, h * w, ldc, ldb, labels.data_ptr(), k, int(class_num),
+           int(groups), int(ignore_label), loss.data_ptr(), _p(dfeat), _ld(dfeat) if dfeat is not None else 0,
+           int(bool(accumulate)), float(weight), ws.data_ptr(), ws.numel(), _stream())
+    if check and int(ws[:4].view(torch.int32).item()) & 4:
+        raise ValueError('whiten_loss: a label is outside [0, class_num) and is not ignore_label')
+    return (loss, ws) if return_ws else loss
+
+
 # ---------------------------------------------------------------- ASPP head (Classifier_Module)
 def _ptr_array(tensors):
     import ctypes
