@@ -675,6 +675,45 @@ int rgda_augment_tiles(const uint8_t* img, const uint8_t* label, const float* so
                        const int32_t* label_lut, float* img_out, int64_t* label_out, float* soft_out, int64_t* regs_out,
                        int* flag, rgda_stream_t stream);
 
+/* ------------------------------------------------------------- region maps without SAM */
+
+/* The region maps rgda_lrh and rgda_label_refine_sup read, generated from the raw tile.
+ * NOT pinned: the superpixel algorithm.  The reference gets its superpixels from cv2.ximgproc.createSuperpixelLSC
+ * (regda/gast/superpixels.py:49-83) and skimage.segmentation.slic (regda/gast/slic/superpixel.py:66-90), both third
+ * party.  rgda_superpixels stands in for them and reproduces neither: it is this library's own integer SLIC, specified
+ * here, restated in numpy in tests/superpixel_ref.py and bit-exact against that restatement.
+ *   img uint8 [N][H][W][3] (HWC, the raw tile rgda_augment_tiles takes; 4-byte aligned); region size 4 <= S <= 64 with
+ *   H % S == 0, W % S == 0, H, W <= 16384; compactness 1 <= m <= 64; iters >= 1; min_area >= 1; N <= 65535.
+ *   Cell k = gy * (W / S) + gx owns one centre (cy, cx, cr, cg, cb), all int32.
+ *   Update(labels): per centre the int32 sums of (y, x, r, g, b) and the count n of its pixels; each component becomes
+ *     (2 * sum + n) / (2 * n) (integer division: round half up); a centre with n == 0 keeps its value.
+ *   Initial centres: Update of the grid labelling (every pixel labelled with its own cell).
+ *   Assign(centres): a pixel of cell (gy, gx) takes, among the existing cells (gy + a, gx + b), a, b in {-1, 0, 1}, the
+ *     centre of least d = ((r-cr)^2 + (g-cg)^2 + (b-cb)^2) * S^2 + m^2 * ((y-cy)^2 + (x-cx)^2); equal d: the smaller k.
+ *     d < 2^31 within the limits above (a centre stays inside the 3 x 3 cells around its own, so |y - cy| < 3 S).
+ *   for it = 1..iters: labels = Assign(centres); if it < iters: centres = Update(labels).
+ *   Components: the 4-connected components of equal labels inside one image; a component's root is its smallest
+ *     pixel index y * W + x; components of fewer than min_area pixels become region 0 ("no region", which LRH leaves
+ *     as it is: local_region_homog.py:149) -- they are NOT merged into a neighbour; the others are numbered 1..R in
+ *     increasing root order.
+ *   regs_out int32 [N][H][W]; count_out int32 [N] = R per image.  R <= H * W / min_area.
+ * ws: rgda_superpixels_workspace bytes (0 for a shape that is not served), 16-byte aligned, cleared inside the call where
+ * it has to be.  It begins with int32 centres[2][N][cells][5]; copy (iters & 1) holds the centres of the last Assign.
+ * 2 + iters + 7 launches, no host synchronisation.  Errors before any launch: null pointer, N / H / W < 1, H % S or
+ * W % S != 0, iters < 1, min_area < 1, misalignment (RGDA_ERR_ARG); S, m, H, W or N outside the limits
+ * (RGDA_ERR_UNSUPPORTED); a short workspace (RGDA_ERR_WORKSPACE). */
+size_t rgda_superpixels_workspace(int N, int H, int W, int S);
+int rgda_superpixels(const uint8_t* img, int N, int H, int W, int S, int m, int iters, int min_area, int32_t* regs_out,
+                     int32_t* count_out, void* ws, size_t ws_bytes, rgda_stream_t stream);
+
+/* edge_shrinking(label_supixl, win_size)   regda/gast/superpixels.py:129-152.  PINNED: the reference's own loop,
+ * bit-exact against a golden minted from it (tests/golden/edge_shrink.npz).
+ * regs, out: int32 [N][H][W] (not the same buffer).  out = regs where every pixel of the (2 * win + 1)^2 window that lies
+ * inside the image holds the same id, `fill` elsewhere.  The reference calls it with win = 3 and
+ * fill = int(h / region_size * w / region_size); fill = 0 ("no region") is the useful value in front of LRH.
+ * 0 <= win <= 8 (beyond: RGDA_ERR_UNSUPPORTED).  One launch. */
+int rgda_region_shrink(const int32_t* regs, int N, int H, int W, int win, int fill, int32_t* out, rgda_stream_t stream);
+
 /* ------------------------------------------------------------- evaluation path */
 
 /* cls.argmax(dim=1) of the (N,C,H,W) probabilities (regda/utils/eval.py:43): int64 (N,H,W), first maximum wins. */

@@ -1020,6 +1020,61 @@ def augment_tiles(img, params, lut, size, label=None, label_lut=None, soft=None,
     return res
 
 
+# ----------------------------------------------------------------------------- region maps without SAM
+def superpixels_max_regions(h, w, min_area):
+    """The exclusive bound on the region ids rgda_superpixels writes for an h x w image: R <= h * w // min_area, so
+    ids lie in [0, that + 1) -- the `max_regions` a Homogenizer / SSLStep is given."""
+    return int(h) * int(w) // int(min_area) + 1
+
+
+def superpixels(img, region_size=16, compactness=10, iters=10, min_area=None, out=None, ws=None):
+    """rgda_superpixels: img uint8 [N][H][W][3] on the GPU -> (regs int32 [N][H][W], count int32 [N]).  The integer SLIC
+    of include/rgda_hip.h (this library's own specification: it stands in for the reference's third-party LSC / SLIC
+    generators and reproduces neither), 4-connected components, components below `min_area` (default S * S // 4)
+    dropped to region 0, the others numbered 1..count.  out: (regs, count) tensors to write into; ws: a workspace of
+    at least rgda_superpixels_workspace bytes to reuse.  No host synchronisation."""
+    _need_cuda(img)
+    if img.dim() != 4 or img.shape[3] != 3 or img.dtype != torch.uint8:
+        raise ValueError('superpixels: img must be uint8 [N][H][W][3], got %s %s' % (img.dtype, tuple(img.shape)))
+    n, h, w, _ = img.shape
+    s = int(region_size)
+    min_area = s * s // 4 if min_area is None else int(min_area)
+    img = img.contiguous()
+    if img.data_ptr() % 4:
+        img = img.clone()
+    L = lib()
+    need = L.size('rgda_superpixels_workspace', n, h, w, s)
+    if need == 0:
+        raise ValueError(f'superpixels: {n} x {h} x {w} tiles at region_size {s} are not served: 4 <= region_size <= 64, '
+                         f'H and W multiples of it and at most 16384, N <= 65535')
+    if ws is None or ws.numel() < need or ws.data_ptr() % 16:
+        ws = _ws(need, img.device)
+    regs, count = out if out is not None else (None, None)
+    if regs is None:
+        regs = torch.empty((n, h, w), dtype=torch.int32, device=img.device)
+    if count is None:
+        count = torch.empty((n,), dtype=torch.int32, device=img.device)
+    assert tuple(regs.shape) == (n, h, w) and regs.dtype == torch.int32 and regs.is_contiguous()
+    assert tuple(count.shape) == (n,) and count.dtype == torch.int32 and count.is_contiguous()
+    L.call('rgda_superpixels', img.data_ptr(), n, h, w, s, int(compactness), int(iters), min_area, regs.data_ptr(),
+           count.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    return regs, count
+
+
+def region_shrink(regs, win=3, fill=0):
+    """rgda_region_shrink (the reference's edge_shrinking, superpixels.py:129-152, bit-exact): regs int32 [N][H][W] or
+    [H][W] -> a new map that keeps an id where the (2 * win + 1)^2 window inside the image holds only that id and is
+    `fill` elsewhere."""
+    _need_cuda(regs)
+    if regs.dtype != torch.int32 or regs.dim() not in (2, 3):
+        raise ValueError('region_shrink: regs must be int32 [N][H][W] or [H][W], got %s %s' % (regs.dtype, tuple(regs.shape)))
+    src = regs.contiguous()
+    out = torch.empty_like(src)
+    n, h, w = (1,) + tuple(src.shape) if src.dim() == 2 else tuple(src.shape)
+    lib().call('rgda_region_shrink', src.data_ptr(), n, h, w, int(win), int(fill), out.data_ptr(), _stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- evaluation path
 def argmax_nchw(probs):
     n, c, h, w = probs.shape

@@ -9,14 +9,18 @@ waits for an event.  The tensors keep the reference's dtypes and shapes (the int
 With `augment`, the host batches are RAW tiles (uint8 HWC images, uint8 labels, f32 soft labels, int32 region maps): they
 are copied into device staging buffers on the copy stream and the training augmentation (regda_amd.aug) writes the
 step's tensors from them on the same stream, one launch per domain, with each sample's parameters drawn on the host
-when the batch is staged, in batch order."""
+when the batch is staged, in batch order.
+
+With `regions` as well, a domain whose roles name a 'mask_sup' tensor that the host batches do not carry gets its region
+map from the raw uint8 tile itself (regda_amd.gast.superpixels.SuperPixelsSLIC, rgda_superpixels) on the copy stream; the
+map is the augmentation's `regs` input, so it goes through the same crop and dihedral element as the image."""
 import torch
 
 from .. import ops
 
 
 class DevicePrefetcher:
-    def __init__(self, host_batches, device=None, depth=2, into=None, augment=None):
+    def __init__(self, host_batches, device=None, depth=2, into=None, augment=None, regions=None):
         """host_batches: list of {name: CPU tensor or None} with identical shapes; cycled through in order.
         into: {name: device tensor} -- stage every batch straight into THESE tensors (one slot: the static input
         buffers of a recorded step, SSLStep.static_inputs()); `release()` must then be given the event after which the
@@ -25,13 +29,21 @@ class DevicePrefetcher:
         'image' (uint8 [N][H][W][3]), 'mask' (uint8 [N][H][W] class labels), 'soft' (f32 [N][C][H][W]) and 'mask_sup'
         (int32 [N][H][W] region ids); the named host tensors are raw and their slot tensors hold the pipeline's outputs
         (f32 [N][3][Ho][Wo], int64 [N][Ho][Wo], f32 [N][C][Ho][Wo], int64 [N][1][Ho][Wo]).  Names in no role are
-        copied as they are."""
+        copied as they are.
+        regions: a SuperPixelsSLIC (needs `augment`).  Where a domain's roles name 'mask_sup' and the host batches have
+        no tensor of that name (absent or None), the int32 region map is generated from the staged raw image and
+        delivered under that name as the pipeline's int64 [N][1][Ho][Wo] output.  A batch that carries its 'mask_sup' is
+        staged as without `regions`."""
+        if regions is not None and not augment:
+            raise ValueError('DevicePrefetcher: regions= generates the region maps from the RAW uint8 tiles, which only '
+                             'the augment= path stages; give augment=[(pipeline, roles), ...] as well')
         assert host_batches and (into is not None or depth >= 2)
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self.host = [{k: (None if v is None else v.contiguous().pin_memory()) for k, v in b.items()} for b in host_batches]
         self.augment = []
         shapes = {k: (None if v is None else (tuple(v.shape), v.dtype)) for k, v in self.host[0].items()}
         for pipe, roles in (augment or ()):
+            gen = roles.get('mask_sup') if regions is not None and self.host[0].get(roles.get('mask_sup')) is None else None
             roles = {r: k for r, k in roles.items() if self.host[0].get(k) is not None}
             img = self.host[0][roles['image']]
             n, h, w, _ = img.shape
@@ -45,18 +57,25 @@ class DevicePrefetcher:
             # device staging of the raw batch (one set: written and read in copy-stream order), the device tables and
             # the per-batch parameter table
             raw = {r: torch.empty_like(self.host[0][k], device=self.device) for r, k in roles.items()}
+            if gen is not None:
+                # generated on the device: no host tensor, but a slot tensor like any other mask_sup
+                shapes[gen] = out['mask_sup']
+                raw['mask_sup'] = torch.empty((n, h, w), dtype=torch.int32, device=self.device)
+                raw['sup_count'] = torch.empty((n,), dtype=torch.int32, device=self.device)
+                regions.reserve(n, h, w, self.device)
             tables = pipe.device_tables(self.device)
             prm = torch.empty(n, 4, dtype=torch.int32, device=self.device)
-            self.augment.append((pipe, roles, raw, tables, prm))
+            self.augment.append((pipe, roles, raw, tables, prm, gen))
         if into is not None:
             depth = 1
-            self.slots = [{k: into.get(k) for k in self.host[0]}]
+            self.slots = [{k: into.get(k) for k in shapes}]
             for k, v in shapes.items():
                 t = self.slots[0][k]
                 assert (v is None) == (t is None) and (v is None or (tuple(t.shape) == v[0] and t.dtype == v[1])), k
         else:
             self.slots = [{k: (None if v is None else torch.empty(v[0], dtype=v[1], device=self.device))
                            for k, v in shapes.items()} for _ in range(depth)]
+        self.regions = regions
         self.single = into is not None
         self.copy_stream = torch.cuda.Stream(device=self.device)
         if self.augment:
@@ -90,10 +109,13 @@ class DevicePrefetcher:
         # writes into the slot wait for the step that reads it
         with ops.use_stream(self.copy_stream):
             done = set()
-            for pipe, roles, raw, _, prm in self.augment:
+            for pipe, roles, raw, _, prm, gen in self.augment:
                 for r, k in roles.items():
                     raw[r].copy_(src[k], non_blocking=True)
                     done.add(k)
+                if gen is not None:
+                    self.regions(raw['image'], out=(raw['mask_sup'], raw['sup_count']))
+                    done.add(gen)
                 n, h, w, _ = raw['image'].shape
                 p = pipe.params(n, h, w)
                 ops.check_augment_params(p, h, w, *pipe.out_size(h, w))
@@ -104,9 +126,9 @@ class DevicePrefetcher:
             for k, t in dst.items():
                 if t is not None and k not in done:
                     t.copy_(src[k], non_blocking=True)
-            for pipe, roles, raw, (lut, llut), prm in self.augment:
+            for pipe, roles, raw, (lut, llut), prm, gen in self.augment:
                 out = {'image': dst[roles['image']], 'label': dst.get(roles.get('mask')), 'soft': dst.get(roles.get('soft')),
-                       'regs': dst.get(roles.get('mask_sup'))}
+                       'regs': dst.get(roles.get('mask_sup', gen))}
                 ops.augment_tiles(raw['image'], prm, lut, tuple(out['image'].shape[2:]), label=raw.get('mask'),
                                   label_lut=llut, soft=raw.get('soft'), regs=raw.get('mask_sup'), out=out)
             self.copied[slot] = self.copy_stream.record_event()
