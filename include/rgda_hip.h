@@ -675,6 +675,32 @@ int rgda_augment_tiles(const uint8_t* img, const uint8_t* label, const float* so
                        const int32_t* label_lut, float* img_out, int64_t* label_out, float* soft_out, int64_t* regs_out,
                        int* flag, rgda_stream_t stream);
 
+/* ------------------------------------------------------------- cross-domain mixing */
+
+/* ClassMix and CutMix across the domains (regda/utils/classmix.py:17-53, regda/utils/cutmix.py:15-31): the pixels of the
+ * source batch that a predicate selects are pasted over the target batch, in place, one launch for the whole batch.
+ * Sample n of the source pairs with sample n of the target, as in the reference.
+ *   img_s f32 [N][3][H][W], label_s int64 [N][H][W]: the source (read only)
+ *   img_t f32 [N][3][H][W]; label_t int64 [N][H][W], soft_t f32 [N][C][H][W], regs_t int64 [N][H][W], each or NULL
+ * Per pixel (n, y, x) with l = label_s[n][y][x]:
+ *   RGDA_MIX_CLASS: cond = 0 <= l < C && (class_bits >> l) & 1        (classmix.py:42-50 with class_ids as a bit set)
+ *   RGDA_MIX_BOX:   cond = y0 <= y < y1 && x0 <= x < x1               (cutmix.py:29-30)
+ * Where cond holds: img_t[n][:][y][x] = img_s[n][:][y][x]; label_t = l; soft_t[n][c] = (l == c) ? 1 : 0 for every c (so
+ * a box pixel whose source label is ignore_label gets all-zero planes); regs_t = 0, the id LRH leaves alone
+ * (local_region_homog.py:149-151).  Where it does not hold nothing is written.  The reference knows hard labels only;
+ * soft_t and regs_t are this library's extension to the inputs its SSL step takes.
+ * A label that is neither in [0, C) nor ignore_label sets *flag (optional, device int) to 1: it is not pasted in class
+ * mode and is pasted as it is, with all-zero soft planes, in box mode (where only the labels inside the box are read).
+ * 16-byte accesses when W % 4 == 0 and every given pointer is 16-byte aligned, element accesses otherwise.  No
+ * arithmetic, no atomics: two runs are bit-identical.
+ * Errors before any launch (RGDA_ERR_ARG): null img_s / label_s / img_t; N, H or W < 1; C outside 1..32; an unknown
+ * mode; in class mode a bit of class_bits at or above C; in box mode a box outside 0 <= y0 <= y1 <= H,
+ * 0 <= x0 <= x1 <= W.  An empty class set or an empty box returns RGDA_OK without a launch. */
+enum rgda_mix_mode { RGDA_MIX_CLASS = 0, RGDA_MIX_BOX = 1 };
+int rgda_domain_mix(const float* img_s, const int64_t* label_s, float* img_t, int64_t* label_t, float* soft_t,
+                    int64_t* regs_t, int N, int C, int H, int W, int mode, uint32_t class_bits, int y0, int y1, int x0,
+                    int x1, int ignore_label, int* flag, rgda_stream_t stream);
+
 /* ------------------------------------------------------------- region maps without SAM */
 
 /* The region maps rgda_lrh and rgda_label_refine_sup read, generated from the raw tile.

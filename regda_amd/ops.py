@@ -1020,6 +1020,72 @@ def augment_tiles(img, params, lut, size, label=None, label_lut=None, soft=None,
     return res
 
 
+# ----------------------------------------------------------------------------- cross-domain mixing
+MIX_CLASS, MIX_BOX = 0, 1       # rgda_mix_mode (include/rgda_hip.h)
+MIX_MAX_CLASSES = 32            # one bit of class_bits per class
+
+
+def mix_class_bits(classes, class_num):
+    """The class set of rgda_domain_mix as its bit mask; ValueError for an id outside [0, class_num)."""
+    bits = 0
+    for c in classes:
+        c = int(c)
+        if not 0 <= c < class_num:
+            raise ValueError('domain_mix: class id %d outside [0, %d)' % (c, class_num))
+        bits |= 1 << c
+    return bits
+
+
+def domain_mix(images_s, label_s, images_t, label_t=None, soft_t=None, regs_t=None, classes=None, box=None,
+               ignore_label=-1, check=False, class_num=None, flag=None):
+    """rgda_domain_mix: paste the source pixels a predicate selects over the target tensors IN PLACE, one launch.
+    images_s, images_t f32 (N,3,H,W); label_s int64 (N,H,W) or (N,1,H,W); optional targets label_t int64 (N,H,W) or
+    (N,1,H,W), soft_t f32 (N,C,H,W), regs_t int64 (N,H,W) or (N,1,H,W).  Exactly one of
+      classes: an iterable of class ids -- the pixels whose source label is one of them (ClassMix), or
+      box = (y0, y1, x0, x1) -- the pixels of rows [y0, y1) and columns [x0, x1) (CutMix).
+    A pasted pixel takes the source image and label, a one-hot soft label and region id 0.  class_num: the class count
+    the labels are checked against (default: soft_t's C, else 32, the most the kernel serves).  flag: optional device
+    int32 tensor, set to 1 by a source label that is neither a class nor ignore_label; check=True reads it back (one
+    host synchronisation, as pseudo_select does) and raises ValueError.  The target tensors must be contiguous (they
+    are written in place); anything but f32 images and int64 labels is a ValueError.
+    -> (images_t, label_t, soft_t, regs_t)."""
+    _need_cuda(images_s, label_s, images_t, label_t, soft_t, regs_t, flag)
+    if (classes is None) == (box is None):
+        raise ValueError('domain_mix: give exactly one of classes= and box=')
+    if images_t.dim() != 4 or images_t.shape[1] != 3 or tuple(images_s.shape) != tuple(images_t.shape):
+        raise ValueError('domain_mix: images must both be (N,3,H,W), got %s and %s'
+                         % (tuple(images_s.shape), tuple(images_t.shape)))
+    n, _, h, w = images_t.shape
+    maps = ((n, h, w), (n, 1, h, w))
+    c = int(class_num) if class_num is not None else (soft_t.shape[1] if soft_t is not None else MIX_MAX_CLASSES)
+    want = (('images_s', images_s, torch.float32, None), ('images_t', images_t, torch.float32, None),
+            ('label_s', label_s, torch.int64, maps), ('label_t', label_t, torch.int64, maps),
+            ('soft_t', soft_t, torch.float32, ((n, c, h, w),)), ('regs_t', regs_t, torch.int64, maps))
+    for name, t, dt, shapes in want:
+        if t is None:
+            continue
+        if t.dtype != dt or (shapes is not None and tuple(t.shape) not in shapes):
+            raise ValueError('domain_mix: %s must be %s %s, got %s %s' % (name, dt, shapes, t.dtype, tuple(t.shape)))
+        if not name.endswith('_s') and not t.is_contiguous():
+            raise ValueError('domain_mix: %s is written in place and must be contiguous' % name)
+    if not 1 <= c <= MIX_MAX_CLASSES:
+        raise ValueError('domain_mix: %d classes; the kernel serves 1..%d' % (c, MIX_MAX_CLASSES))
+    if classes is not None:
+        mode, bits, (y0, y1, x0, x1) = MIX_CLASS, mix_class_bits(classes, c), (0, 0, 0, 0)
+    else:
+        mode, bits, (y0, y1, x0, x1) = MIX_BOX, 0, (int(v) for v in box)
+    if n * h * w == 0:
+        return images_t, label_t, soft_t, regs_t
+    if check and flag is None:
+        flag = torch.zeros(1, dtype=torch.int32, device=images_t.device)
+    lib().call('rgda_domain_mix', images_s.contiguous().data_ptr(), label_s.contiguous().data_ptr(), images_t.data_ptr(),
+               _p(label_t) or None, _p(soft_t) or None, _p(regs_t) or None, n, c, h, w, mode, bits, y0, y1, x0, x1,
+               int(ignore_label), _p(flag) or None, _stream())
+    if check and int(flag.item()) != 0:
+        raise ValueError('domain_mix: a source label is neither in [0, %d) nor ignore_label %d' % (c, ignore_label))
+    return images_t, label_t, soft_t, regs_t
+
+
 # ----------------------------------------------------------------------------- region maps without SAM
 def superpixels_max_regions(h, w, min_area):
     """The exclusive bound on the region ids rgda_superpixels writes for an h x w image: R <= h * w // min_area, so

@@ -13,14 +13,18 @@ when the batch is staged, in batch order.
 
 With `regions` as well, a domain whose roles name a 'mask_sup' tensor that the host batches do not carry gets its region
 map from the raw uint8 tile itself (regda_amd.gast.superpixels.SuperPixelsSLIC, rgda_superpixels) on the copy stream; the
-map is the augmentation's `regs` input, so it goes through the same crop and dihedral element as the image."""
+map is the augmentation's `regs` input, so it goes through the same crop and dihedral element as the image.
+
+With `mix`, one more launch on the copy stream (rgda_domain_mix) pastes part of the source slot over the target slot
+after everything else has been written there: cross-domain ClassMix / CutMix, drawn per batch on the host when the batch
+is staged (regda_amd.aug.mix.DomainMix)."""
 import torch
 
 from .. import ops
 
 
 class DevicePrefetcher:
-    def __init__(self, host_batches, device=None, depth=2, into=None, augment=None, regions=None):
+    def __init__(self, host_batches, device=None, depth=2, into=None, augment=None, regions=None, mix=None):
         """host_batches: list of {name: CPU tensor or None} with identical shapes; cycled through in order.
         into: {name: device tensor} -- stage every batch straight into THESE tensors (one slot: the static input
         buffers of a recorded step, SSLStep.static_inputs()); `release()` must then be given the event after which the
@@ -33,7 +37,13 @@ class DevicePrefetcher:
         regions: a SuperPixelsSLIC (needs `augment`).  Where a domain's roles name 'mask_sup' and the host batches have
         no tensor of that name (absent or None), the int32 region map is generated from the staged raw image and
         delivered under that name as the pipeline's int64 [N][1][Ho][Wo] output.  A batch that carries its 'mask_sup' is
-        staged as without `regions`."""
+        staged as without `regions`.
+        mix: (domain_mix, roles_s, roles_t) -- a regda_amd.aug.mix.DomainMix and the {role: name} of the source
+        ('image', 'mask') and target ('image' and any of 'mask', 'soft', 'mask_sup') slot tensors (f32 [N][3][H][W],
+        int64 [N][H][W], f32 [N][C][H][W], int64 [N][1][H][W]: the augmentation's outputs, or what the host batches
+        carry; the int64 maps with or without the unit axis).  The target tensors of a slot are rewritten in place where the batch's draw pastes; a pasted pixel gets
+        the source image and label, a one-hot soft label and region 0.  `mix_flag` (device int32) is set to 1 by a source
+        label that is neither a class nor the ignore label."""
         if regions is not None and not augment:
             raise ValueError('DevicePrefetcher: regions= generates the region maps from the RAW uint8 tiles, which only '
                              'the augment= path stages; give augment=[(pipeline, roles), ...] as well')
@@ -76,9 +86,33 @@ class DevicePrefetcher:
             self.slots = [{k: (None if v is None else torch.empty(v[0], dtype=v[1], device=self.device))
                            for k, v in shapes.items()} for _ in range(depth)]
         self.regions = regions
+        self.mix = None
+        if mix is not None:
+            dmix, roles_s, roles_t = mix
+            if 'image' not in roles_s or 'mask' not in roles_s or 'image' not in roles_t:
+                raise ValueError("DevicePrefetcher: mix= needs the source's 'image' and 'mask' and the target's 'image'")
+            if 'mask' not in roles_t and 'soft' not in roles_t:
+                raise ValueError("DevicePrefetcher: mix= needs a target 'mask' or 'soft' role: without either the "
+                                 'target has no supervision to mix (the online-teacher batch labels it inside the step)')
+            unknown = (set(roles_s) - {'image', 'mask'}) | (set(roles_t) - {'image', 'mask', 'soft', 'mask_sup'})
+            missing = [k for k in list(roles_s.values()) + list(roles_t.values()) if shapes.get(k) is None]
+            if unknown or missing:
+                raise ValueError('DevicePrefetcher: mix= roles %s unknown, tensors %s not in the batches'
+                                 % (sorted(unknown), missing))
+            (n, _, h, w), c = shapes[roles_t['image']][0], dmix.class_num
+            maps = [((n, h, w), torch.int64), ((n, 1, h, w), torch.int64)]
+            want = {'image': [((n, 3, h, w), torch.float32)], 'mask': maps, 'soft': [((n, c, h, w), torch.float32)],
+                    'mask_sup': maps}
+            for roles in (roles_s, roles_t):
+                for r, k in roles.items():
+                    if shapes[k] not in want[r]:
+                        raise ValueError('DevicePrefetcher: mix= pairs the source and target slots pixel by pixel at %d '
+                                         'classes: %r (%s) must be %s, got %s' % (c, k, r, want[r], shapes[k]))
+            self.mix = (dmix, dict(roles_s), dict(roles_t), (h, w))
+            self.mix_flag = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.single = into is not None
         self.copy_stream = torch.cuda.Stream(device=self.device)
-        if self.augment:
+        if self.augment or self.mix:
             self.copy_stream.wait_stream(torch.cuda.current_stream())     # the staging buffers and tables made above
         self.copied = [None] * depth        # event: the slot holds its batch
         self.consumed = [None] * depth      # event: the step that read the slot has been enqueued and finished with it
@@ -102,6 +136,7 @@ class DevicePrefetcher:
             for k, dst in self.slots[slot].items():
                 if dst is not None:
                     dst.copy_(src[k], non_blocking=True)
+            self._mix(slot)
             self.copied[slot] = self.copy_stream.record_event()
 
     def _stage_augmented(self, slot, src):
@@ -131,7 +166,23 @@ class DevicePrefetcher:
                        'regs': dst.get(roles.get('mask_sup', gen))}
                 ops.augment_tiles(raw['image'], prm, lut, tuple(out['image'].shape[2:]), label=raw.get('mask'),
                                   label_lut=llut, soft=raw.get('soft'), regs=raw.get('mask_sup'), out=out)
+            self._mix(slot)
             self.copied[slot] = self.copy_stream.record_event()
+
+    def _mix(self, slot):
+        # the last writer of the slot, on the copy stream: the source slot tensors are only read
+        if self.mix is None:
+            return
+        dmix, roles_s, roles_t, (h, w) = self.mix
+        drawn = dmix.draw(h, w)
+        if drawn is None:
+            return
+        dst = self.slots[slot]
+        with ops.use_stream(self.copy_stream):
+            ops.domain_mix(dst[roles_s['image']], dst[roles_s['mask']], dst[roles_t['image']],
+                           label_t=dst.get(roles_t.get('mask')), soft_t=dst.get(roles_t.get('soft')),
+                           regs_t=dst.get(roles_t.get('mask_sup')), ignore_label=dmix.ignore_label,
+                           class_num=dmix.class_num, flag=self.mix_flag, **{drawn[0]: drawn[1]})
 
     def next(self):
         """-> the device batch for this step (valid until `release()` + `depth - 1` further `next()` calls); the copy of
