@@ -785,6 +785,45 @@ int rgda_coral_loss(const float* feat_s, int bs, int hws, int64_t ldcs, int64_t 
                     void* dfeat_s, int ldds, void* dfeat_t, int lddt, int accumulate, float weight, void* ws,
                     size_t ws_bytes, rgda_stream_t stream);
 
+/* MMDLoss (regda/gast/mmd.py:15-58; the commented `self.mmd = MMDLoss(kernel_type='linear')` of
+ * regda/gast/alignment.py:68), forward + gradient w.r.t. both feature maps in one call.  Features are addressed as in
+ * rgda_coral_loss (strided NCHW or (n, d) rows, no permuted copy); `total` = the ns source rows followed by the nt target
+ * rows (mmd.py:27), n = ns + nt.
+ * kernel_type RGDA_MMD_RBF (guassian_kernel, mmd.py:25-38, and the four block means of mmd.py:53-57):
+ *   mu = column means of total (fp32, fixed order);  Xc = bf16(total - mu), rounded once (distances do not see the shift;
+ *   centring first keeps r_i + r_j - 2 g accurate on post-ReLU features);  r_i = sum of squares of the rounded row (fp32)
+ *   bw = fix_sigma when fix_sigma > 0, else the mean pairwise squared distance sum(l2) / (n^2 - n) of mmd.py:34 in closed
+ *        form, (2 n sum_i r_i - 2 |sum_i Xc_i|^2) / (n^2 - n);  bw /= kernel_mul^(kernel_num / 2);  bw_q = bw kernel_mul^q,
+ *        q < kernel_num.  Computed on the device (no read-back); a constant of the backward, as in the reference (`.data`).
+ *   per upper 128 x 128 tile of the n x n matrix: g = Xc Xc^T (bf16 products, fp32 sums),
+ *        l2_ij = max(r_i + r_j - 2 g_ij, 0), exactly 0 for i = j;  kappa_ij = sum_q exp(-l2_ij / bw_q)
+ *        s_ij = a_i a_j with a = 1 / ns for a source row, -1 / nt for a target row
+ *        L = sum_ij s_ij kappa_ij (tiles off the diagonal count twice; tile partials reduced in a fixed order)
+ *        W_ij = bf16(s_ij sum_q exp(-l2_ij / bw_q) / bw_q), W_ii = 0, stored to both triangles;  rho_i = sum_j W_ij (fp32, of
+ *        the rounded values, per-tile partial row sums reduced in a fixed order)
+ *   loss[0] += weight * L
+ *   dfeat_s (optional) bf16 [ns][ldds], pixel-major -- the layout rgda_instnorm_bwd consumes: row i
+ *        (+)= -4 weight (rho_i Xc_i - sum_j W_ij Xc_j)            (accumulate != 0: added in fp32, rounded once)
+ *   dfeat_t (optional) bf16 [nt][lddt]: the same for rows ns .. n of total.
+ * kernel_type RGDA_MMD_LINEAR (forward_linear, mmd.py:41-44): loss[0] += weight * |mean_s - mean_t|^2 / d; source rows
+ *   (+)= 2 weight (mean_s - mean_t) / (d ns), target rows (+)= -2 weight (mean_s - mean_t) / (d nt).
+ * Before any launch: null feat / loss / ws, ws not 256-byte aligned, d % 32 != 0, ns < 2, nt < 2, kernel_num < 1,
+ * kernel_mul <= 0, an unknown kernel_type, ldd % 8 != 0 or ldd < d: RGDA_ERR_ARG; kernel_num > 8 or n > 32768:
+ * RGDA_ERR_UNSUPPORTED; a short workspace: RGDA_ERR_WORKSPACE.  Deterministic: no atomics.
+ * ws: rgda_mmd_loss_workspace(ns, nt, d) bytes (0 for arguments the entry point rejects) =
+ *   a(12 d) + 2 a(2 NP d) + 2 a(4 NP) + a(4 d) + 256 + a(4 T NP) + a(4 U) + a(2 NP^2),
+ *   NP = 128 * ceil(n / 128), T = NP / 128, U = T (T + 1) / 2, a(x) = x rounded up to a multiple of 256
+ * (the last term is W: 512 MB at n = 16384, 2 GB at the limit).  RGDA_MMD_LINEAR uses the means only and accepts a
+ * workspace of the first term, a(12 d) bytes. */
+#define RGDA_MMD_RBF 0
+#define RGDA_MMD_LINEAR 1
+size_t rgda_mmd_loss_workspace(int ns, int nt, int d);
+int rgda_mmd_loss(const float* feat_s, int bs, int hws, int64_t ldcs, int64_t ldbs,
+                  const float* feat_t, int bt, int hwt, int64_t ldct, int64_t ldbt, int d, int kernel_type,
+                  float kernel_mul, int kernel_num, float fix_sigma, float* loss, void* dfeat_s, int ldds,
+                  void* dfeat_t, int lddt, int accumulate, float weight, void* ws, size_t ws_bytes,
+                  rgda_stream_t stream);
+
 /* ClassWareWhitening(class_ids = range(C), groups) (regda/gast/class_ware_whiten.py:14-65) of
  * Aligner.whiten_class_ware (regda/gast/alignment.py:165-170), forward + gradient w.r.t. the feature map in one call:
  *   feat f32 (b, k, hw): element (image i, channel c, pixel p) at feat[i * ldb + c * ldc + p] (NCHW: ldc = h*w,

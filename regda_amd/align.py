@@ -4,7 +4,8 @@ rank 2), on the same kernel plans as the SSL step (regda_amd/ssl.py):
     model(src) -> update_prototype -> model(tgt) -> the student's own (softmax(up x1) + softmax(up x2)) / 2 as soft
     labels -> label_refine -> pseudo_selection -> Homogenizer (LRH) -> DownscaleLabel
     loss = loss_calc(src) + 0.5 * (PrototypeContrastiveLoss(src) + PrototypeContrastiveLoss(tgt))
-           [+ CoralLoss(feat_s, feat_t)  with align_domain=True, --align-domain 1]
+           [+ domain_weight * CoralLoss(feat_s, feat_t)  with align_domain=True, --align-domain 1; align_domain='mmd' /
+              'mmd_linear': the MMDLoss of regda/gast/mmd.py in its place (regda_amd/source.py)]
            [+ whiten_weight * 0.5 * (ClassWareWhitening(feat_s, label_s_down) + ClassWareWhitening(feat_t, label_t))
               with whiten_weight > 0: an extension, tools/train_align_reg.py never calls the whitener]
     -> backward -> clip_grad_norm_(32) -> SGD
@@ -19,19 +20,23 @@ import torch
 
 from . import ops
 from .ddp import all_reduce_prototype_statistics
+from .source import domain_kind, domain_loss
 from .ssl import SSLStep
 
 BF = torch.bfloat16
 
 
 class AlignStep(SSLStep):
-    def __init__(self, model, prototypes, pcl_temperature=8.0, align_domain=False, whiten_weight=0.0, **kw):
+    def __init__(self, model, prototypes, pcl_temperature=8.0, align_domain=False, whiten_weight=0.0, mmd=None,
+                 domain_weight=1.0, **kw):
+        self.domain_kind, self.mmd = domain_kind(align_domain, mmd)
         kw.setdefault('proto_decay', 0.999)        # Aligner(decay=0.999), train_align_reg.py:112-113
         kw['ema_decay'] = None
         super().__init__(model, prototypes, **kw)
         self.pcl_temp = pcl_temperature
         self.loss_align = torch.zeros(1, device=model.device)
         self.align_domain = bool(align_domain)     # --align-domain 1: + aligner.align_domain(feat_s, feat_t), :188
+        self.domain_weight = float(domain_weight)
         self.loss_domain = torch.zeros(1, device=model.device)
         # > 0: + whiten_weight * Aligner.whiten_class_ware(feat_s, label_s, feat_t, label_t) (32 groups, alignment.py:71)
         self.whiten_weight = float(whiten_weight)
@@ -108,8 +113,8 @@ class AlignStep(SSLStep):
                      dfeat=gfeat[nb * h * w:])
         if self.align_domain:
             self.loss_domain.zero_()
-            ops.coral_loss(feat_s, feat_t, 1.0, loss=self.loss_domain, dfeat_s=gfeat[:nb * h * w],
-                           dfeat_t=gfeat[nb * h * w:], accumulate=True)
+            domain_loss(self.domain_kind, self.mmd, feat_s, feat_t, self.domain_weight, loss=self.loss_domain,
+                        dfeat_s=gfeat[:nb * h * w], dfeat_t=gfeat[nb * h * w:], accumulate=True)
         if self.whiten_weight > 0.0:
             self.loss_white.zero_()
             for f, lab, rows in ((feat_s, label_s_down, gfeat[:nb * h * w]), (feat_t, label_t, gfeat[nb * h * w:])):

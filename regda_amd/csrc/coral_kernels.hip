@@ -11,19 +11,14 @@
 //   loss   : loss[0] += weight * sum(D^2) / (4 d^2), one thread, fixed order            coral_loss_kernel
 //   grad   : dX^T = D . Xc^T  ->  dfeat = (+/-) weight / (d^2 (n - 1)) * dX (+ dfeat)      coral_grad_kernel
 //
-// Both products are C[m][n] = sum_k P[m][k] Q[n][k] with P and Q row-major bf16 and K contiguous, so the MFMA
-// fragments are plain 16-byte loads from global memory (no LDS): a 128 x 128 tile per wavefront, 4 x 4
-// v_mfma_f32_32x32x16_bf16 accumulators, the next 32-wide K group loaded while the current one is multiplied.
-// Inside a K group the lane half h and element j of k-step s take k = 16h + 8s + j: A and B use the same
-// permutation, so the sum is unchanged, and the two lanes of a row read 64 contiguous bytes per group.
+// Both products are C[m][n] = sum_k P[m][k] Q[n][k] with P and Q row-major bf16 and K contiguous: the tile routine of
+// gram_tile.h (a 128 x 128 tile per wavefront, fragments loaded straight from global memory, no LDS).
 #include "common.h"
+#include "gram_tile.h"
 
 namespace {
 
-constexpr int CT = 128;          // tile edge (rows of P and of Q per job)
-constexpr int KG = 32;           // K per loop iteration (two k-steps of 16)
 constexpr int TILE_FLOATS = CT * CT;
-constexpr int GN = 64;           // pixels per wavefront of the gradient product (128 x 64 tiles)
 
 size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
 int round32(int x) { return (x + 31) & ~31; }
@@ -120,62 +115,6 @@ __global__ void __launch_bounds__(256) coral_center_kernel(Feat fs, Feat ft, con
         const int c = c0 + tx;
         if (g0 + gg < f.n && c < d) xp[(size_t)(g0 + gg) * d + c] = tile[gg][tx];
     }
-}
-
-// acc[i][j] += P[prow0 + 32i .. +32][k0:k1] . Q[qrow0 + 32j .. +32][k0:k1]^T  (rows clamped to pmax / qmax: the
-// clamped rows compute values nobody stores); k1 - k0 a multiple of KG
-template <int NJ>
-static __device__ __forceinline__ void tile_nt(const bf16_t* __restrict__ P, size_t ldp, int prow0, int pmax,
-                                               const bf16_t* __restrict__ Q, size_t ldq, int qrow0, int qmax,
-                                               int k0, int k1, f32x16 (&acc)[4][NJ]) {
-    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
-    const bf16_t* pp[4];
-    const bf16_t* qp[NJ];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        pp[i] = P + (size_t)min(prow0 + 32 * i + r, pmax) * ldp + 16 * h;
-    }
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) qp[j] = Q + (size_t)min(qrow0 + 32 * j + r, qmax) * ldq + 16 * h;
-    uint4 a[2][4], b[2][NJ], na[2][4], nb[2][NJ];
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) a[s][i] = *(const uint4*)(pp[i] + k0 + 8 * s);
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) b[s][j] = *(const uint4*)(qp[j] + k0 + 8 * s);
-    }
-    for (int k = k0; k < k1; k += KG) {
-        const int kn = (k + KG < k1) ? k + KG : k;      // the last iteration re-reads its own group (cached)
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) na[s][i] = *(const uint4*)(pp[i] + kn + 8 * s);
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) nb[s][j] = *(const uint4*)(qp[j] + kn + 8 * s);
-        }
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < NJ; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[s][i]),
-                                                                        __builtin_bit_cast(bf16x8, b[s][j]), acc[i][j], 0, 0, 0);
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) a[s][i] = na[s][i];
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) b[s][j] = nb[s][j];
-        }
-    }
-}
-
-static __device__ __forceinline__ void upper_tile(int u, int T, int& I, int& J) {
-    I = 0;
-    while (u >= T - I) { u -= T - I; ++I; }
-    J = I + u;
 }
 
 // job = u * (Ss + St) + q: upper tile u, K chunk q (q < Ss: source, else target).  Partials in the accumulator's own

@@ -1,16 +1,17 @@
 """Aligner (prototype EMA + online soft-label re-weighting + domain alignment) -- mirror of the parts of
 regda/gast/alignment.py that the authors' recipe (runs/regda/run_2potsdam.sh) uses: label_refine (:194-265,
-with and without the superpixel view; every `mode`), update_prototype (:86-90), align_domain (CORAL, :79-84),
-whiten_class_ware (ClassWareWhitening, :165-170), update_avg / init_avg (the prototype initialisation of
-tools/init_prototypes.py, :107-126), DownscaleLabel (:456-481).
-The other alignment losses (align_class, align_instance, MMD) are not provided: their distances are detached in the
-reference, so they carry no gradient.
+with and without the superpixel view; every `mode`), update_prototype (:86-90), align_domain (CORAL, :79-84, or
+the MMD of the reference's commented `self.mmd`, :68), whiten_class_ware (ClassWareWhitening, :165-170),
+update_avg / init_avg (the prototype initialisation of tools/init_prototypes.py, :107-126), DownscaleLabel (:456-481).
+MMD carries a gradient (only its bandwidth is detached, regda/gast/mmd.py:34) and is provided.  align_class and
+align_instance are not: their distances end in `.detach()` in the reference, so they carry no gradient.
 """
 import torch
 
 from .. import ops
 from .class_ware_whiten import ClassWareWhitening
 from .coral import CoralLoss
+from .mmd import MMDLoss
 
 
 class DownscaleLabel(torch.nn.Module):
@@ -49,16 +50,21 @@ class Aligner:
                                            min_ratio=0.75)
         self._classmax_ws = None
         self.coral = CoralLoss()
+        self.mmd = MMDLoss(kernel_type='linear')        # the reference's commented line, alignment.py:68
+        self.mmd_rbf = MMDLoss()                        # kind='mmd': the reference's rbf defaults
         self.whitener = ClassWareWhitening(class_ids=range(class_num), groups=32, ignore_label=ignore_label)
         self._avg_stats = None          # update_avg: f32 sums[c][k] then cnt[c], summed over the batches seen
 
-    def align_domain(self, feat_s, feat_t):
-        """CORAL between the pixel rows of two (b, k, h, w) feature maps (alignment.py:79-84).  The NCHW maps go to
-        rgda_coral_loss as they are (no permuted copy); gradients reach both inputs."""
+    def align_domain(self, feat_s, feat_t, kind='coral'):
+        """CORAL between the pixel rows of two (b, k, h, w) feature maps (alignment.py:79-84); kind='mmd': the
+        multi-kernel RBF MMD of regda/gast/mmd.py with its defaults, 'mmd_linear': its linear form (self.mmd).  The
+        NCHW maps go to rgda_coral_loss / rgda_mmd_loss as they are (no permuted copy); gradients reach both inputs."""
+        if kind not in ('coral', 'mmd', 'mmd_linear'):
+            raise ValueError(f"align_domain: kind {kind!r}; served are 'coral', 'mmd' and 'mmd_linear'")
         assert feat_s.shape == feat_t.shape, 'tensor "feat_s" has the same shape as tensor "feat_t"'
         assert len(feat_s.shape) == 4, 'tensor "feat_s" and "feat_t" must have 4 dimensions'
         assert feat_s.shape[1] == self.feat_channels
-        return self.coral(feat_s, feat_t)
+        return {'coral': self.coral, 'mmd': self.mmd_rbf, 'mmd_linear': self.mmd}[kind](feat_s, feat_t)
 
     def whiten_class_ware(self, feat_s, label_s, feat_t=None, label_t=None):
         """Class-aware whitening of the source features against the downscaled full-size labels, averaged with the

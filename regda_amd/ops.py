@@ -1212,6 +1212,40 @@ def coral_loss(feat_s, feat_t, weight=1.0, loss=None, dfeat_s=None, dfeat_t=None
     return loss
 
 
+MMD_KERNEL_TYPES = {'rbf': 0, 'linear': 1}      # RGDA_MMD_RBF, RGDA_MMD_LINEAR
+
+
+def mmd_loss(feat_s, feat_t, weight=1.0, kernel_type='rbf', kernel_mul=2.0, kernel_num=5, fix_sigma=None, loss=None,
+             dfeat_s=None, dfeat_t=None, accumulate=False):
+    """MMDLoss(kernel_type, kernel_mul, kernel_num, fix_sigma)(feat_s rows, feat_t rows) (regda/gast/mmd.py):
+    feat_s / feat_t f32 NCHW (b, d, h, w) (the pixels are the rows; batch slices of one map are read in place) or (n, d).
+    loss (f32[1]) += weight * MMD; dfeat_s / dfeat_t (optional) bf16 [n, >= d] pixel-major rows:
+    (+)= weight * d MMD / d feat (rgda_mmd_loss).  fix_sigma None or 0: the bandwidth is the mean pairwise squared
+    distance, computed on the device.  Returns the (accumulating) fp32 loss tensor."""
+    if kernel_type not in MMD_KERNEL_TYPES:
+        raise ValueError(f"mmd_loss: kernel_type {kernel_type!r}; served are 'rbf' and 'linear'")
+    _need_cuda(feat_s, feat_t, dfeat_s, dfeat_t)
+    xs, bs, hws, lcs, lbs, d = _coral_side(feat_s)
+    xt, bt, hwt, lct, lbt, dt = _coral_side(feat_t)
+    if d != dt:
+        raise ValueError(f'mmd_loss: feature dimensions differ ({d} vs {dt})')
+    for g, n in ((dfeat_s, bs * hws), (dfeat_t, bt * hwt)):
+        if g is not None:
+            assert g.dtype == torch.bfloat16 and g.dim() == 2 and g.shape[0] == n and g.stride(1) == 1, (g.shape, n)
+    if loss is None:
+        loss = torch.zeros(1, device=xs.device)
+    L = lib()
+    nbytes = L.size('rgda_mmd_loss_workspace', bs * hws, bt * hwt, d)
+    if kernel_type == 'linear' and nbytes:
+        nbytes = (12 * d + 255) // 256 * 256          # the linear form needs the means only (include/rgda_hip.h)
+    ws = _ws(nbytes, xs.device)
+    L.call('rgda_mmd_loss', xs.data_ptr(), bs, hws, lcs, lbs, xt.data_ptr(), bt, hwt, lct, lbt, d,
+           MMD_KERNEL_TYPES[kernel_type], float(kernel_mul), int(kernel_num), float(fix_sigma or 0.0), loss.data_ptr(),
+           _p(dfeat_s), _ld(dfeat_s) if dfeat_s is not None else 0, _p(dfeat_t), _ld(dfeat_t) if dfeat_t is not None else 0,
+           int(bool(accumulate)), float(weight), ws.data_ptr(), ws.numel(), _stream())
+    return loss
+
+
 WHITEN_BLOCKS = (32, 64, 96, 128)      # channels per group rgda_whiten_loss serves
 
 

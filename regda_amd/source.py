@@ -10,7 +10,11 @@ a zero gradient (train_src.py discards the target logits) and CORAL reaches the 
 features: rgda_coral_loss writes d CORAL / d feat for both halves pixel-major, `Deeplabv2._backward_plan(gfeat=...)`
 adds it in the instance-norm backward.
 
-Data-parallel ranks compute CORAL on their local batch (the covariances of the rank's own source and target pixels),
+align_domain='mmd' / 'mmd_linear' puts the MMD of regda/gast/mmd.py (rgda_mmd_loss; the reference's commented
+`self.mmd`, alignment.py:68) in CORAL's place, on the same gradient rows; `mmd=dict(kernel_mul=, kernel_num=, fix_sigma=)`
+sets its kernel parameters and `domain_weight` scales either domain term.
+
+Data-parallel ranks compute CORAL / MMD on their local batch (the rank's own source and target pixels),
 the same per-rank semantics as the per-GPU BatchNorm statistics: there is no extra collective."""
 import torch
 
@@ -19,15 +23,38 @@ from .ssl import SSLStep
 
 BF = torch.bfloat16
 
+MMD_OPTIONS = ('kernel_mul', 'kernel_num', 'fix_sigma')
+
+
+def domain_kind(align_domain, mmd=None):
+    """align_domain False / True / 'coral' / 'mmd' / 'mmd_linear' -> (kind or None, the MMD keyword arguments)"""
+    kinds = {False: None, True: 'coral', 'coral': 'coral', 'mmd': 'mmd', 'mmd_linear': 'mmd_linear'}
+    if not isinstance(align_domain, (bool, int, str)) or align_domain not in kinds:       # 0 / 1 as False / True
+        raise ValueError(f"align_domain {align_domain!r}; served are False, True, 'coral', 'mmd' and 'mmd_linear'")
+    mmd = dict(mmd or {})
+    if set(mmd) - set(MMD_OPTIONS):
+        raise ValueError(f'mmd: unknown options {sorted(set(mmd) - set(MMD_OPTIONS))}; served are {MMD_OPTIONS}')
+    return kinds[align_domain], mmd
+
+
+def domain_loss(kind, mmd, feat_s, feat_t, weight, **kw):
+    """the domain term of a fused step: CORAL or MMD of the two halves of the feature map, onto the gradient rows"""
+    if kind == 'coral':
+        return ops.coral_loss(feat_s, feat_t, weight, **kw)
+    return ops.mmd_loss(feat_s, feat_t, weight, 'linear' if kind == 'mmd_linear' else 'rbf', **mmd, **kw)
+
 
 class SourceStep(SSLStep):
-    def __init__(self, model, class_balancer_s=None, align_domain=False, class_num=6, loss_s='CrossEntropy', **kw):
+    def __init__(self, model, class_balancer_s=None, align_domain=False, class_num=6, loss_s='CrossEntropy', mmd=None,
+                 domain_weight=1.0, **kw):
+        self.domain_kind, self.mmd = domain_kind(align_domain, mmd)
         kw['ema_decay'] = None
         kw.setdefault('sam_refine', False)
         kw.setdefault('refine_label', False)
         super().__init__(model, torch.zeros(class_num, 2048), class_num=class_num, class_balancer_s=class_balancer_s,
                          loss_s=loss_s, **kw)
         self.align_domain = bool(align_domain)
+        self.domain_weight = float(domain_weight)
         self.loss_domain = torch.zeros(1, device=model.device)
 
     @torch.no_grad()
@@ -69,7 +96,7 @@ class SourceStep(SSLStep):
         if self.align_domain:
             n, k, h, w = feat.shape
             gfeat = torch.empty(n * h * w, k, dtype=BF, device=m.device)
-            ops.coral_loss(feat[:nb], feat[nb:], 1.0, loss=self.loss_domain, dfeat_s=gfeat[:nb * h * w],
-                           dfeat_t=gfeat[nb * h * w:])
+            domain_loss(self.domain_kind, self.mmd, feat[:nb], feat[nb:], self.domain_weight, loss=self.loss_domain,
+                        dfeat_s=gfeat[:nb * h * w], dfeat_t=gfeat[nb * h * w:])
         self._backward_and_update(T, main, g1, g2, gfeat=gfeat)
         return loss_seg, self.loss_domain, self.gn
