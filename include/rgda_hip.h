@@ -852,6 +852,59 @@ int rgda_whiten_loss(const float* feat, int b, int hw, int64_t ldc, int64_t ldb,
                      int C, int groups, int ignore_label, float* loss, void* dfeat, int lddf, int accumulate,
                      float weight, void* ws, size_t ws_bytes, rgda_stream_t stream);
 
+/* PixelContrastLoss (regda/gast/contrastive.py:27-162: the pixel-wise supervised contrast of Wang et al., ICCV 2021,
+ * with hard-anchor sampling) in two entry points.  The host takes the reference's random draws between them
+ * (regda_amd/gast/contrastive.py::plan_anchors); the device does the rest.
+ *
+ * rgda_pixel_contrast_select: labels int64 (b, H, W) are read at (y * H / h, x * W / w) -- what
+ *   interpolate(mode='nearest') reads for integer ratios; H % h != 0 or W % w != 0: RGDA_ERR_UNSUPPORTED.
+ *   predict: RGDA_PREDICT_LABELS int64 (b, h, w), or RGDA_PREDICT_LOGITS f32 (b, C, h, w) whose argmax is taken (the
+ *   lowest index on ties).  A pixel with 0 <= label < C has key 2 * label + easy, easy = (predict == label); an ignored
+ *   pixel and one with a label outside [0, C) have key 2 C (the latter also sets bit 2 of flag[0]).
+ *   counts int32 [b][C][2]: the pixels per (class, hard / easy);  order int32 [b][h * w]: per image the pixel indices
+ *   stably sorted by key, so each of the 2 C lists is in ascending pixel order and the ignored pixels come last.
+ *   One workgroup per image, no atomics that could change the output.  2 <= C <= 16 and h * w <= 16384:
+ *   RGDA_ERR_UNSUPPORTED otherwise; null pointers, sizes < 1, an unknown predict_kind: RGDA_ERR_ARG; before any launch.
+ *
+ * rgda_pixel_contrast_loss: forward + gradient w.r.t. the feature map in one call.  feat f32 (b, k, hw) is addressed as
+ *   in rgda_whiten_loss (ldc, ldb, read in place).  anchors int32 [A][3] = (image, class, hard_keep), ranks int32
+ *   [A][n_view]: the first hard_keep ranks of an anchor index its hard list (key 2 class of `order`), the rest its easy
+ *   list.  Row r = v * A + a (view-major, contrastive.py:114) is view v of anchor a, N = A * n_view.
+ *     X = bf16(feat rows), rounded once;  dot_rq = sum_c X_rc X_qc (bf16 products, fp32 sums, by upper 128 x 128 tiles;
+ *     K is split into up to 8 runs of whole 32-channel groups whose partials are added in order)
+ *     G_rq = dot_rq / temperature (fp32 division), stored symmetric;  m_r = max_q G_rq over all N columns
+ *     l_rq = G_rq - m_r;  neg_r = sum over q of another class of exp(l_rq)
+ *     for q of the same class, q != r:  d_rq = exp(l_rq) + neg_r + eps;  lp_rq = l_rq - log(d_rq)
+ *     L = -(temperature / base_temperature) / N * sum_r [ sum_q lp_rq / (P_r + eps) ],  P_r = the number of such q
+ *     (every row sum: 64 lane-strided fp32 partials, then a butterfly; the sum over r: 256 strided partials, a
+ *     butterfly per wavefront, then (w0 + w1) + (w2 + w3));   loss[0] += weight * L
+ *     c_r = -(temperature / base_temperature) / (N (P_r + eps));  W_rq = c_r (1 - exp(l_rq) / d_rq) for a positive q,
+ *     -c_r exp(l_rq) sum_p 1 / d_rp for a negative q, 0 for q = r (m_r is a constant of the backward, as in the
+ *     reference: `.detach()`);  M = bf16(W + W^T), rounded once
+ *   dfeat (optional) bf16 [b * hw][lddf], pixel-major -- the layout rgda_instnorm_bwd consumes: the row of the pixel of
+ *     r  (+)= weight / temperature * sum_q M_rq X_q  (bf16 products, fp32 sums).
+ *     accumulate != 0: added in fp32 to the selected rows only, rounded once; every other row is left.
+ *     accumulate == 0: every row is written (its first k columns), the unselected ones as zeros.
+ *   The selected rows are distinct (ranks of one list are distinct), so there are no atomics: deterministic.
+ * Before any launch: null feat / order / counts / anchors / ranks / loss / ws, ws not 256-byte aligned, k % 32 != 0,
+ * temperature or base_temperature <= 0, eps < 0, b * hw > 2^24, dfeat not 16-byte aligned, lddf % 8 != 0 or lddf < k: RGDA_ERR_ARG;
+ * N < 1, N > 4096 or C outside 2..16: RGDA_ERR_UNSUPPORTED; a short workspace: RGDA_ERR_WORKSPACE.
+ * ws: rgda_pixel_contrast_loss_workspace(N, k) bytes (0 for arguments the entry point rejects) =
+ *   2 a(4 NP) + 2 a(2 NP k) + a(20 NP) + a(4 NP^2) + a(65536 U S) + a(2 NP^2),
+ *   NP = 128 * ceil(N / 128), T = NP / 128, U = T (T + 1) / 2, g = k / 32, S0 = min(g, clamp(256 / U, 1, 8)),
+ *   S = ceil(g / ceil(g / S0)), a(x) = x rounded up to a multiple of 256  (fp32 G: 4 MB at N = 1024). */
+#define RGDA_PREDICT_LABELS 0
+#define RGDA_PREDICT_LOGITS 1
+int rgda_pixel_contrast_select(const int64_t* labels, const void* predict, int predict_kind, int b, int C, int H,
+                               int W, int h, int w, int ignore_label, int32_t* counts, int32_t* order, int* flag,
+                               rgda_stream_t stream);
+size_t rgda_pixel_contrast_loss_workspace(int N, int k);
+int rgda_pixel_contrast_loss(const float* feat, int b, int hw, int64_t ldc, int64_t ldb, int k, int C,
+                             const int32_t* order, const int32_t* counts, const int32_t* anchors, int A,
+                             const int32_t* ranks, int n_view, float temperature, float base_temperature, float eps,
+                             float* loss, void* dfeat, int lddf, int accumulate, float weight, void* ws,
+                             size_t ws_bytes, rgda_stream_t stream);
+
 /* Factored form of the PPM heads' tap-shifted bilinear maps (regda/models/Encoder.py:30-51: Upsample(bilinear,
  * align_corners=False) of the s x s branches into the 3x3 / pad 1 conv_last): the map V[(y,x)][(jy,jx),(ky,kx)] =
  * Uy[y+ky-1][jy] * Ux[x+kx-1][jx] is separable, so V and V^T are applied as two short maps (csrc/mix_kernels.hip).

@@ -8,6 +8,8 @@ rank 2), on the same kernel plans as the SSL step (regda_amd/ssl.py):
               'mmd_linear': the MMDLoss of regda/gast/mmd.py in its place (regda_amd/source.py)]
            [+ whiten_weight * 0.5 * (ClassWareWhitening(feat_s, label_s_down) + ClassWareWhitening(feat_t, label_t))
               with whiten_weight > 0: an extension, tools/train_align_reg.py never calls the whitener]
+           [+ contrast_weight * 0.5 * (PixelContrastLoss(feat_s, label_s, argmax x2_s) + PixelContrastLoss(feat_t, label_t,
+              argmax x2_t)) with contrast_weight > 0: an extension, tools/train_align_reg.py never constructs that loss]
     -> backward -> clip_grad_norm_(32) -> SGD
 
 Differences to the SSL step that matter for the kernels: there is no CE on the target logits (their gradient is
@@ -15,11 +17,19 @@ zero) and the loss reaches the network through the third forward output, the ins
 (rgda_pcl_loss writes d loss / d feat pixel-major, `Deeplabv2._backward_plan(gfeat=...)` adds it in the
 instance-norm backward; with align_domain rgda_coral_loss then adds the CORAL gradient of both halves onto it).
 Data-parallel ranks compute CORAL on their local batch (regda_amd/source.py), and so the whitening term
-(rgda_whiten_loss, added onto the same gradient rows after PCL and CORAL)."""
+(rgda_whiten_loss, added onto the same gradient rows after PCL and CORAL), and so the pixel contrast
+(rgda_pixel_contrast_loss, added after those; the predictions are the argmax of the head-2 logits at feature
+resolution, taken inside rgda_pixel_contrast_select; its random draws come from the global CPU generator, which costs
+one host sync per domain and step; a domain without a class of more than max_views labelled pixels contributes 0.  Its
+parameters are the reference's defaults, kept in `step.contrast` (a dict: temperature, base_temperature, max_samples,
+max_views, eps) and read at every step, so assigning `step.contrast['max_views'] = ...` changes them.  The head logits and
+the features of the fused model are f32, so the `.float()` below copies nothing.  `step.last_contrast` holds, per domain,
+the (order, counts, anchors, ranks) the term used, or None)."""
 import torch
 
 from . import ops
 from .ddp import all_reduce_prototype_statistics
+from .gast.contrastive import select_and_plan
 from .source import domain_kind, domain_loss
 from .ssl import SSLStep
 
@@ -28,7 +38,12 @@ BF = torch.bfloat16
 
 class AlignStep(SSLStep):
     def __init__(self, model, prototypes, pcl_temperature=8.0, align_domain=False, whiten_weight=0.0, mmd=None,
-                 domain_weight=1.0, **kw):
+                 domain_weight=1.0, contrast_weight=0.0, **kw):
+        # > 0: + contrast_weight * 0.5 * (PixelContrastLoss(source) + PixelContrastLoss(target)), the reference's defaults
+        self.contrast_weight = float(contrast_weight)
+        if self.contrast_weight < 0.0:
+            raise ValueError('AlignStep: contrast_weight must be >= 0')
+        self.contrast = dict(temperature=0.1, base_temperature=0.07, max_samples=1024, max_views=100, eps=1e-5)
         self.domain_kind, self.mmd = domain_kind(align_domain, mmd)
         kw.setdefault('proto_decay', 0.999)        # Aligner(decay=0.999), train_align_reg.py:112-113
         kw['ema_decay'] = None
@@ -47,6 +62,8 @@ class AlignStep(SSLStep):
             raise NotImplementedError(f'AlignStep(whiten_weight > 0): {k} feature channels in 32 groups; served are '
                                       f'{ops.WHITEN_BLOCKS} channels per group')
         self.loss_white = torch.zeros(1, device=model.device)
+        self.loss_contrast = torch.zeros(1, device=model.device)
+        self.last_contrast = [None, None]
 
     def step(self, images_s, label_s, images_t, regs_t, lr):
         """One stage-2 iteration.  Returns device tensors (loss_seg, loss_align, grad_norm_sq)."""
@@ -120,6 +137,19 @@ class AlignStep(SSLStep):
             for f, lab, rows in ((feat_s, label_s_down, gfeat[:nb * h * w]), (feat_t, label_t, gfeat[nb * h * w:])):
                 ops.whiten_loss(f, lab, self.C, 32, self.ig, 0.5 * self.whiten_weight, loss=self.loss_white, dfeat=rows,
                                 accumulate=True)
+        if self.contrast_weight > 0.0:
+            self.loss_contrast.zero_()
+            pc = self.contrast
+            sides = ((feat_s, label_s, s2, gfeat[:nb * h * w]), (feat_t, label_t, t2, gfeat[nb * h * w:]))
+            for side, (f, lab, logits, rows) in enumerate(sides):
+                lab = lab.reshape(lab.shape[0], *lab.shape[-2:])
+                order, counts, anchors, ranks, _ = select_and_plan(lab, logits.float(), self.C, (h, w), self.ig,
+                                                                   pc['max_samples'], pc['max_views'], None)
+                self.last_contrast[side] = None if anchors is None else (order, counts, anchors, ranks)
+                if anchors is None:        # no class of this domain's batch has more than max_views pixels: the term is 0
+                    continue
+                ops.pixel_contrast_loss(f, order, counts, anchors, ranks, pc['temperature'], pc['base_temperature'], pc['eps'],
+                                        0.5 * self.contrast_weight, loss=self.loss_contrast, dfeat=rows, accumulate=True)
         self._backward_and_update(T, main, g1, g2, gfeat=gfeat)
         self.last_hard, self.last_label_t, self.last_label_s_down = hard, label_t, label_s_down
         return loss_seg, self.loss_align, self.gn

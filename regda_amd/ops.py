@@ -1284,6 +1284,81 @@ def whiten_loss(feat, labels, class_num, groups, ignore_label=-1, weight=1.0, lo
     return (loss, ws) if return_ws else loss
 
 
+PIXEL_CONTRAST_MAX_ROWS = 4096      # N = anchors * views rgda_pixel_contrast_loss serves
+
+
+def _feat_in_place(feat):
+    """-> (f32 tensor, image stride, channel stride): read in place when the pixels of an image are contiguous"""
+    feat = feat.float()
+    b, k, h, w = feat.shape
+    ldb, ldc = feat.stride(0), feat.stride(1)
+    if not ((w == 1 or feat.stride(3) == 1) and (h == 1 or feat.stride(2) == w) and ldc >= h * w and
+            (b == 1 or ldb >= ldc * k)):
+        feat = feat.contiguous()
+        ldb, ldc = k * h * w, h * w
+    return feat, ldb, ldc
+
+
+def pixel_contrast_select(labels, predict, class_num, size, ignore_label=-1, check=False):
+    """The selection tables of PixelContrastLoss (regda/gast/contrastive.py): labels int64 (b, H, W), read at the
+    nearest-downscaled positions of the (h, w) = size grid (H % h == 0 and W % w == 0); predict int64 (b, h, w), or f32
+    logits (b, class_num, h, w) whose argmax is taken (the lowest index on ties).
+    -> counts int32 [b, class_num, 2] (hard: predict != label, easy), order int32 [b, h*w] (per image the pixel indices
+    stably sorted by (class, easy), ignored pixels last), flag int32 [1] (bit 2: a label outside [0, class_num) that is
+    not ignore_label; check=True reads it back -- one host sync -- and raises ValueError)."""
+    _need_cuda(labels, predict)
+    h, w = int(size[0]), int(size[1])
+    assert labels.dtype == torch.int64 and labels.dim() == 3, (labels.dtype, labels.shape)
+    labels = labels.contiguous()
+    b, H, W = labels.shape
+    C = int(class_num)
+    if predict.dtype == torch.int64:
+        kind = 0
+        assert predict.numel() == b * h * w, (predict.shape, (b, h, w))
+    else:
+        kind = 1
+        assert predict.dtype == torch.float32 and tuple(predict.shape) == (b, C, h, w), (predict.dtype, predict.shape)
+    predict = predict.contiguous()
+    counts = torch.empty(b, C, 2, dtype=torch.int32, device=labels.device)
+    order = torch.empty(b, h * w, dtype=torch.int32, device=labels.device)
+    flag = torch.zeros(1, dtype=torch.int32, device=labels.device)
+    lib().call('rgda_pixel_contrast_select', labels.data_ptr(), predict.data_ptr(), kind, b, C, H, W, h, w,
+               int(ignore_label), counts.data_ptr(), order.data_ptr(), flag.data_ptr(), _stream())
+    if check and int(flag.item()) & 4:
+        raise ValueError('pixel_contrast_select: a label is outside [0, class_num) and is not ignore_label')
+    return counts, order, flag
+
+
+def pixel_contrast_loss(feat, order, counts, anchors, ranks, temperature=0.1, base_temperature=0.07, eps=1e-5, weight=1.0,
+                        loss=None, dfeat=None, accumulate=False):
+    """PixelContrastLoss._contrastive on the rows the tables select (rgda_pixel_contrast_loss): feat f32 (b, k, h, w),
+    read in place through its channel and image strides; order / counts from pixel_contrast_select; anchors int32
+    [A, 3] (image, class, hard_keep) and ranks int32 [A, n_view] from gast.contrastive.plan_anchors, on the device.
+    loss (f32[1]) += weight * L; dfeat (optional) bf16 [b*h*w, >= k] pixel-major rows: (+)= weight * dL / dfeat
+    (accumulate=False writes every row, the unselected ones as zeros).  Returns the (accumulating) fp32 loss tensor."""
+    _need_cuda(feat, order, counts, anchors, ranks, dfeat)
+    assert feat.dim() == 4, 'pixel_contrast_loss: NCHW (b, k, h, w) features'
+    feat, ldb, ldc = _feat_in_place(feat)
+    b, k, h, w = feat.shape
+    C = counts.shape[1]
+    for t in (order, counts, anchors, ranks):
+        assert t.dtype == torch.int32 and t.is_contiguous(), (t.dtype, t.shape)
+    assert tuple(order.shape) == (b, h * w) and tuple(counts.shape) == (b, C, 2), (order.shape, counts.shape)
+    A, n_view = ranks.shape
+    assert tuple(anchors.shape) == (A, 3), anchors.shape
+    if dfeat is not None:
+        assert dfeat.dtype == torch.bfloat16 and dfeat.dim() == 2 and dfeat.shape[0] == b * h * w and dfeat.stride(1) == 1
+    if loss is None:
+        loss = torch.zeros(1, device=feat.device)
+    L = lib()
+    ws = _ws(L.size('rgda_pixel_contrast_loss_workspace', A * n_view, k), feat.device)
+    L.call('rgda_pixel_contrast_loss', feat.data_ptr(), b, h * w, ldc, ldb, k, C, order.data_ptr(), counts.data_ptr(),
+           anchors.data_ptr(), A, ranks.data_ptr(), n_view, float(temperature), float(base_temperature), float(eps),
+           loss.data_ptr(), _p(dfeat), _ld(dfeat) if dfeat is not None else 0, int(bool(accumulate)), float(weight),
+           ws.data_ptr(), ws.numel(), _stream())
+    return loss
+
+
 # ---------------------------------------------------------------- ASPP head (Classifier_Module)
 def _ptr_array(tensors):
     import ctypes
