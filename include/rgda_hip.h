@@ -168,7 +168,7 @@ int rgda_proto_update(const float* feat, const int64_t* label, float* protos, in
 /* The two halves of rgda_proto_update, for data-parallel ranks (ABI 9).  rgda_proto_stats leaves the
  * sufficient statistics of _compute_local_prototypes (alignment.py:300-327) in `stats` (rgda_proto_update_workspace
  * bytes): f32 sums[c][k] = sum of feat over the pixels whose downscaled label is class c, f32 cnt[c] = their number,
- * then a flag word.  Both add over batches: the ranks all-reduce (sum) the first c * k + c floats and each calls
+ * then an int32 flag word (bit 2: a label outside [0, c) that is not ignore_label).  Both add over batches: the ranks all-reduce (sum) the first c * k + c floats and each calls
  * rgda_proto_apply -- local = sums / (cnt + 1e-7), the old prototype where cnt < 1 (:318-321), EMA (:435-438) -- which
  * gives the prototypes of the concatenated global batch on every rank.  rgda_proto_update == stats + apply.
  * rgda_proto_apply takes 0 <= decay < 1: decay 0 on zero prototypes is Aligner.init_avg (alignment.py:121-122) over

@@ -21,15 +21,19 @@ __global__ void __launch_bounds__(256) pseudo_max_kernel(const float* __restrict
             float4 v = p4[i];
             mx = fmaxf(mx, fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));
             mn = fminf(mn, fminf(fminf(v.x, v.y), fminf(v.z, v.w)));
+            bad |= (v.x != v.x) | (v.y != v.y) | (v.z != v.z) | (v.w != v.w);
         }
     } else {
         for (int i = beg + threadIdx.x; i < end; i += 256) {
             float v = p[i];
             mx = fmaxf(mx, v);
             mn = fminf(mn, v);
+            bad |= v != v;
         }
     }
-    bad = (mx > 1.f) || (mn < 0.f);
+    // fmaxf / fminf drop a NaN operand, so NaN is looked for on its own: the reference's range assert
+    // (pseudo_generation.py:71) fails on one
+    bad |= (mx > 1.f) || (mn < 0.f);
     mx = wave_max(mx);
     __shared__ float smx[4];
     __shared__ int sbad;
@@ -959,8 +963,9 @@ __global__ void __launch_bounds__(256) downscale_label_kernel(const int64_t* __r
     int bad = 0;
     for (int i = threadIdx.x; i < s * s; i += 256) {
         long long l = src[(size_t)(i / s) * W + (i % s)];
+        if (l != ignore_label && (l < 0 || l >= C)) bad = 1;      // (the label C is no class: flagged, counted as ignore)
         if (l == ignore_label) l = C;
-        if (l < 0 || l > C) { bad = 1; continue; }
+        if (l < 0 || l > C) continue;
         atomicAdd(&hist[(int)l], 1);
     }
     if (bad) atomicOr(flag, 2);
@@ -1013,9 +1018,9 @@ __global__ void __launch_bounds__(256) downscale_label16_kernel(const int64_t* _
             for (int k = 0; k < 2; ++k) {
                 long long l = k ? v.y : v.x;
                 if (IGN_FIELD) {
+                    if (l != ignore_label && (l < 0 || l >= C)) bad = 1;    // (the label C is no class: flagged, counted as ignore)
                     if (l == ignore_label) l = C;
-                    if (l < 0 || l > C) bad = 1;
-                    else packed += 1ull << (9 * (int)l);
+                    if (l >= 0 && l <= C) packed += 1ull << (9 * (int)l);
                 } else if (l != ignore_label) {
                     if (l < 0 || l >= C) bad = 1;
                     else packed += 1ull << (9 * (int)l);

@@ -269,8 +269,23 @@ def label_refine_sup(feat, protos, p1, p2, soft, label_t_sup, temp=2.0, views=3,
     return out
 
 
-def proto_update(feat, label, protos, scale=16, ignore_label=-1, min_ratio=0.75, decay=0.996):
-    """In-place EMA update of `protos`; returns the downscaled label (b,1,h,w) int64."""
+def proto_flag_index(class_num, k):
+    """Index (in float32 elements) of the int32 flag word behind sums[c][k] and cnt[c] in the statistics buffer of
+    rgda_proto_stats / the workspace of rgda_proto_update: bit 2 is set by a label outside [0, class_num) that is not
+    ignore_label."""
+    return int(class_num) * int(k) + int(class_num)
+
+
+def _proto_check(buf, class_num, k):
+    i = proto_flag_index(class_num, k)
+    if int(buf.view(torch.int32)[i].item()) & 2:
+        raise ValueError('update_prototype: a label is outside [0, class_num) and is not ignore_label')
+
+
+def proto_update(feat, label, protos, scale=16, ignore_label=-1, min_ratio=0.75, decay=0.996, check=False):
+    """In-place EMA update of `protos`; returns the downscaled label (b,1,h,w) int64.  check=True reads the range flag
+    back (one host sync) and raises ValueError for a label outside [0, class_num) that is not ignore_label, like
+    ops.lrh; the default leaves the call enqueue-only."""
     _need_cuda(feat, label, protos)
     feat = feat.contiguous().float()
     label = label.contiguous()
@@ -285,13 +300,16 @@ def proto_update(feat, label, protos, scale=16, ignore_label=-1, min_ratio=0.75,
     ws = _ws(L.size('rgda_proto_update_workspace', c, k), feat.device)
     L.call('rgda_proto_update', feat.data_ptr(), label.data_ptr(), protos.data_ptr(), ds.data_ptr(), b, k, c, h, w,
            scale, ignore_label, float(min_ratio), float(decay), ws.data_ptr(), ws.numel(), _stream())
+    if check:
+        _proto_check(ws[:(proto_flag_index(c, k) + 1) * 4].view(torch.float32), c, k)
     return ds
 
 
-def proto_stats(feat, label, scale=16, ignore_label=-1, min_ratio=0.75, class_num=6, stats=None):
+def proto_stats(feat, label, scale=16, ignore_label=-1, min_ratio=0.75, class_num=6, stats=None, check=False):
     """The sufficient statistics of update_prototype for data-parallel ranks (rgda_proto_stats): returns (stats, ds) --
     `stats` a float32 buffer whose first class_num * k + class_num elements are sums[c][k] and cnt[c] (what the ranks
-    all-reduce), ds the downscaled label (b,1,h,w) int64."""
+    all-reduce), ds the downscaled label (b,1,h,w) int64.  The int32 flag word sits at element proto_flag_index(class_num,
+    k); check=True reads it back (one host sync) and raises ValueError for an out-of-range label."""
     _need_cuda(feat, label)
     feat = feat.contiguous().float()
     label = label.contiguous()
@@ -308,6 +326,8 @@ def proto_stats(feat, label, scale=16, ignore_label=-1, min_ratio=0.75, class_nu
     assert stats.is_contiguous() and stats.dtype == torch.float32 and stats.numel() * 4 >= nbytes
     L.call('rgda_proto_stats', feat.data_ptr(), label.data_ptr(), ds.data_ptr(), b, k, class_num, h, w, scale, ignore_label,
            float(min_ratio), stats.data_ptr(), stats.numel() * 4, _stream())
+    if check:
+        _proto_check(stats, class_num, k)
     return stats, ds
 
 

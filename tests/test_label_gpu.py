@@ -1,6 +1,7 @@
 """GPU parity of the label path (pseudo_selection, LRH, label_refine, update_prototype, loss, teacher)
 through the C ABI, against the golden vectors of the reference and against the oracle on seeded
-inputs.  Integer results must be bit-identical; float tolerances are stated per test."""
+inputs.  Integer results must be bit-identical; float tolerances are stated per test.
+Per element at edge shapes and on every route: tests/label_cases.py, test_label_cases_cpu.py, test_label_passes_gpu.py."""
 import numpy as np
 import pytest
 import torch
