@@ -905,6 +905,51 @@ int rgda_pixel_contrast_loss(const float* feat, int b, int hw, int64_t ldc, int6
                              float* loss, void* dfeat, int lddf, int accumulate, float weight, void* ws,
                              size_t ws_bytes, rgda_stream_t stream);
 
+/* TripletLoss (regda/gast/triple.py:13-55: batch-hard mining, Hermans et al., arXiv:1703.07737), forward + gradient
+ * w.r.t. the feature map in one call.  feat f32 (b, k, hw) is addressed as in rgda_whiten_loss (ldc, ldb, read in place;
+ * (n, k) rows: b = n, hw = 1, ldc = 1, ldb = k); row i = image * hw + pixel, n = b * hw; labels int64 [n].
+ * Definition: d_ij = sqrt(max(|x_i - x_j|^2, 1e-12));  d_ap(i) = max over j with t_j = t_i (j = i included),
+ *   d_an(i) = min over j with t_j != t_i;  L = mean_i max(0, d_ap(i) - d_an(i) + margin).
+ *   has_ignore != 0: rows labelled ignore_label are neither anchors nor candidates.  m = the number of anchors that
+ *   have a negative; the mean runs over them (with two or more distinct labels among the valid rows that is every valid
+ *   row; with fewer, m = 0 and the loss and the gradient are 0 -- decided on the device).
+ *   Labels are compared as int32 (their low 32 bits); the value -2^31 is reserved for "no label".
+ * Arithmetic:
+ *   rows    Xh = bf16(x), rounded once, [NP][k] (NP = n rounded up to 128, the padding zero);  s_i = sum_c Xh_ic^2 (fp32, of
+ *           the rounded values: lane-strided partials, then a butterfly)
+ *   mining  per 128 x 128 tile of ALL T x T tiles (one wavefront each, the full K in one run): G = Xh Xh^T (bf16 products,
+ *           fp32 sums);  d2_ij = (s_i + s_j) - 2 G_ij;  per anchor the maximum over equal labels and the minimum over
+ *           unequal labels with their indices, ties to the lowest index.  G and d2 stay in registers; per (tile row,
+ *           anchor) one (value, index) pair of each kind goes to memory, combined with the same tie rule (the rule makes
+ *           the combination independent of its order).  -> p(i), n(i)
+ *   values  |x_i - x_p|^2 and |x_i - x_n|^2 again for the selected pairs only, as direct fp32 sums of squared differences
+ *           of the UNROUNDED rows (64 lane-strided partials, then a butterfly); clamp, sqrt, hinge h_i.  Mining noise can
+ *           pick a neighbouring candidate; it cannot perturb the distance of the chosen one.
+ *   loss    loss[0] += weight * (sum_i h_i) / m  (256 strided partials, a butterfly per wavefront, (w0 + w1) + (w2 + w3))
+ *   dfeat (optional) bf16 [n][lddf], pixel-major -- the layout rgda_instnorm_bwd consumes.  With c = weight / m, for
+ *           every anchor i with h_i > 0:  row i += (c / d_ap)(x_i - x_p) - (c / d_an)(x_i - x_n);
+ *           row p -= (c / d_ap)(x_i - x_p);  row n += (c / d_an)(x_i - x_n);  a pair whose squared distance is below the
+ *           clamp contributes nothing.  Formed in fp32 from the unrounded rows, one workgroup per row r: its own anchor's
+ *           two terms first, then the anchors i != r that selected r in ascending i (found by scanning the p / n tables;
+ *           no floating-point atomics), rounded once.
+ *           accumulate != 0: added in fp32 to the rows that receive something, rounded once; every other row is left.
+ *           accumulate == 0: every row is written (its first k columns), the untouched ones as zeros.
+ *   Two calls on the same inputs are bit-identical.
+ * Before any launch: null feat / labels / loss / ws, ws not 256-byte aligned, k < 32 or k % 32 != 0, margin < 0 (or
+ * NaN), n < 2, ldc < hw, ldb < ldc * k, dfeat not 16-byte aligned, lddf % 8 != 0 or lddf < k: RGDA_ERR_ARG; n > 16384:
+ * RGDA_ERR_UNSUPPORTED; a short workspace: RGDA_ERR_WORKSPACE.
+ * ws: rgda_triplet_loss_workspace(n, k) bytes (0 for arguments the entry point rejects) =
+ *   256 + 9 a(4 NP) + a(16 T NP) + a(2 NP k) + a(4 NP k),   NP = 128 * ceil(n / 128), T = NP / 128,
+ *   a(x) = x rounded up to a multiple of 256  (the last term is the pixel-major f32 copy of the rows that the selected
+ *   distances and the gradient read: 128 MB at n = 16384, k = 2048).  Layout, in this order: the stats block (256 bytes:
+ *   int32 m, int32 number of positive hinges), then nine [NP] tables -- int32 staged labels, f32 s, int32 p, int32 n,
+ *   int32 p and n again with -1 where the pair carries no gradient, f32 d_ap and d_an (0 where it carries none), f32
+ *   hinge --, the mining partials, Xh, the f32 rows. */
+size_t rgda_triplet_loss_workspace(int n, int k);
+int rgda_triplet_loss(const float* feat, int b, int hw, int64_t ldc, int64_t ldb, const int64_t* labels, int k,
+                      float margin, int has_ignore, int ignore_label, float* loss, void* dfeat, int lddf,
+                      int accumulate, float weight, void* ws, size_t ws_bytes, rgda_stream_t stream);
+
 /* Factored form of the PPM heads' tap-shifted bilinear maps (regda/models/Encoder.py:30-51: Upsample(bilinear,
  * align_corners=False) of the s x s branches into the 3x3 / pad 1 conv_last): the map V[(y,x)][(jy,jx),(ky,kx)] =
  * Uy[y+ky-1][jy] * Ux[x+kx-1][jx] is separable, so V and V^T are applied as two short maps (csrc/mix_kernels.hip).

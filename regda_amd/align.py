@@ -10,6 +10,8 @@ rank 2), on the same kernel plans as the SSL step (regda_amd/ssl.py):
               with whiten_weight > 0: an extension, tools/train_align_reg.py never calls the whitener]
            [+ contrast_weight * 0.5 * (PixelContrastLoss(feat_s, label_s, argmax x2_s) + PixelContrastLoss(feat_t, label_t,
               argmax x2_t)) with contrast_weight > 0: an extension, tools/train_align_reg.py never constructs that loss]
+           [+ triplet_weight * 0.5 * (TripletLoss(feat_s rows, label_s_down) + TripletLoss(feat_t rows, label_t)) with
+              triplet_weight > 0: an extension, tools/train_align_reg.py never constructs that loss]
     -> backward -> clip_grad_norm_(32) -> SGD
 
 Differences to the SSL step that matter for the kernels: there is no CE on the target logits (their gradient is
@@ -24,7 +26,11 @@ one host sync per domain and step; a domain without a class of more than max_vie
 parameters are the reference's defaults, kept in `step.contrast` (a dict: temperature, base_temperature, max_samples,
 max_views, eps) and read at every step, so assigning `step.contrast['max_views'] = ...` changes them.  The head logits and
 the features of the fused model are f32, so the `.float()` below copies nothing.  `step.last_contrast` holds, per domain,
-the (order, counts, anchors, ranks) the term used, or None)."""
+the (order, counts, anchors, ranks) the term used, or None), and so the batch-hard triplet term (rgda_triplet_loss,
+added last, on the downscaled labels the whitening term uses, the step's ignore label excluded; its margin is kept in
+`step.triplet` (a dict) and read at every step; `step.loss_triplet` holds the term and `step.last_triplet`, per domain, what the
+kernel left on the device: `stats` (int32: rows in the mean, positive hinges) and the per-row tables of
+ops.triplet_tables)."""
 import torch
 
 from . import ops
@@ -38,7 +44,12 @@ BF = torch.bfloat16
 
 class AlignStep(SSLStep):
     def __init__(self, model, prototypes, pcl_temperature=8.0, align_domain=False, whiten_weight=0.0, mmd=None,
-                 domain_weight=1.0, contrast_weight=0.0, **kw):
+                 domain_weight=1.0, contrast_weight=0.0, triplet_weight=0.0, **kw):
+        # > 0: + triplet_weight * 0.5 * (TripletLoss(source rows) + TripletLoss(target rows)), regda/gast/triple.py
+        self.triplet_weight = float(triplet_weight)
+        if self.triplet_weight < 0.0:
+            raise ValueError('AlignStep: triplet_weight must be >= 0')
+        self.triplet = dict(margin=0.3)
         # > 0: + contrast_weight * 0.5 * (PixelContrastLoss(source) + PixelContrastLoss(target)), the reference's defaults
         self.contrast_weight = float(contrast_weight)
         if self.contrast_weight < 0.0:
@@ -64,6 +75,8 @@ class AlignStep(SSLStep):
         self.loss_white = torch.zeros(1, device=model.device)
         self.loss_contrast = torch.zeros(1, device=model.device)
         self.last_contrast = [None, None]
+        self.loss_triplet = torch.zeros(1, device=model.device)
+        self.last_triplet = [None, None]
 
     def step(self, images_s, label_s, images_t, regs_t, lr):
         """One stage-2 iteration.  Returns device tensors (loss_seg, loss_align, grad_norm_sq)."""
@@ -150,6 +163,13 @@ class AlignStep(SSLStep):
                     continue
                 ops.pixel_contrast_loss(f, order, counts, anchors, ranks, pc['temperature'], pc['base_temperature'], pc['eps'],
                                         0.5 * self.contrast_weight, loss=self.loss_contrast, dfeat=rows, accumulate=True)
+        if self.triplet_weight > 0.0:
+            self.loss_triplet.zero_()
+            sides = ((feat_s, label_s_down, gfeat[:nb * h * w]), (feat_t, label_t, gfeat[nb * h * w:]))
+            for side, (f, lab, rows) in enumerate(sides):
+                _, stats, ws = ops.triplet_loss(f, lab, self.triplet['margin'], self.ig, 0.5 * self.triplet_weight,
+                                                loss=self.loss_triplet, dfeat=rows, accumulate=True, return_ws=True)
+                self.last_triplet[side] = dict(ops.triplet_tables(ws, rows.shape[0]), stats=stats)
         self._backward_and_update(T, main, g1, g2, gfeat=gfeat)
         self.last_hard, self.last_label_t, self.last_label_s_down = hard, label_t, label_s_down
         return loss_seg, self.loss_align, self.gn

@@ -1,0 +1,1 @@
+from .triple import TripletLoss  # noqa: F401

@@ -1379,6 +1379,61 @@ def pixel_contrast_loss(feat, order, counts, anchors, ranks, temperature=0.1, ba
     return loss
 
 
+TRIPLET_MAX_ROWS = 16384      # n rgda_triplet_loss serves
+
+
+def _triplet_np(n):
+    return (n + 127) // 128 * 128
+
+
+def triplet_loss(feat, labels, margin=0.3, ignore_label=None, weight=1.0, loss=None, dfeat=None, accumulate=False,
+                 return_ws=False):
+    """TripletLoss(margin)(rows of feat, labels) (regda/gast/triple.py: batch-hard mining) on rgda_triplet_loss: feat f32
+    NCHW (b, k, h, w) (the pixels are the rows; read in place through its channel and image strides) or (n, k) rows;
+    labels int64 with n elements.  ignore_label None: every value is a label, as in the reference; an integer: rows with
+    that label are neither anchors nor candidates and the mean runs over the others.  loss (f32[1]) += weight * L;
+    dfeat (optional) bf16 [n, >= k] pixel-major rows: (+)= weight * dL / dfeat (accumulate=False writes every row).
+    Fewer than two distinct labels among the valid rows: loss and gradient 0 (decided on the device).
+    Returns (loss, stats): the (accumulating) fp32 loss tensor and int32 [2] on the device, (m = the rows the mean ran
+    over, the number of positive hinges) -- a view of this call's workspace (with return_ws the workspace itself is
+    returned as a third value; triplet_tables reads it)."""
+    _need_cuda(feat, labels, dfeat)
+    if feat.dim() == 4:
+        feat, ldb, ldc = _feat_in_place(feat)
+        b, k, h, w = feat.shape
+        hw = h * w
+    else:
+        assert feat.dim() == 2, 'triplet_loss: NCHW (b, k, h, w) features or (n, k) rows'
+        feat = feat.contiguous().float()
+        b, k = feat.shape
+        hw, ldc, ldb = 1, 1, k
+    n = b * hw
+    assert labels.dtype == torch.int64 and labels.numel() == n, (labels.dtype, labels.shape, feat.shape)
+    labels = labels.contiguous().view(-1)
+    if dfeat is not None:
+        assert dfeat.dtype == torch.bfloat16 and dfeat.dim() == 2 and dfeat.shape[0] == n and dfeat.stride(1) == 1
+    if loss is None:
+        loss = torch.zeros(1, device=feat.device)
+    L = lib()
+    ws = _ws(L.size('rgda_triplet_loss_workspace', n, k), feat.device)
+    L.call('rgda_triplet_loss', feat.data_ptr(), b, hw, ldc, ldb, labels.data_ptr(), k, float(margin),
+           int(ignore_label is not None), int(ignore_label or 0), loss.data_ptr(), _p(dfeat),
+           _ld(dfeat) if dfeat is not None else 0, int(bool(accumulate)), float(weight), ws.data_ptr(), ws.numel(), _stream())
+    stats = ws[:8].view(torch.int32)
+    return (loss, stats, ws) if return_ws else (loss, stats)
+
+
+def triplet_tables(ws, n):
+    """The per-row tables rgda_triplet_loss left in its workspace (the layout of include/rgda_hip.h), for diagnostics and
+    tests: -> dict of [n] tensors: p, n (the selected positive / negative, -1: none), d_ap, d_an (0 where the pair carries
+    no gradient), hinge."""
+    v = _triplet_np(n) * 4
+    def table(j, dtype):
+        return ws[256 + j * v:256 + (j + 1) * v].view(dtype)[:n]
+    return dict(p=table(2, torch.int32), n=table(3, torch.int32), d_ap=table(6, torch.float32),
+                d_an=table(7, torch.float32), hinge=table(8, torch.float32))
+
+
 # ---------------------------------------------------------------- ASPP head (Classifier_Module)
 def _ptr_array(tensors):
     import ctypes
