@@ -648,6 +648,25 @@ int rgda_window_finish(float* full, const float* count, int n, int C, int H, int
 int rgda_resize_bilinear_ac(const float* src, float* dst, int N, int C, int h, int w, int H, int W,
                             rgda_stream_t stream);
 
+/* Multi-scale testing (regda/utils/tools.py:108-129, predict_multiscale): the batched window loop over the image resampled
+ * to Hs x Ws, and the per-scale result brought back to H x W and added to the sum over the scales.  The resampling in both
+ * directions is rgda_resize_bilinear_ac's arithmetic (ndimage.zoom(order=1, prefilter=False) is align_corners=True
+ * bilinear), fused so that neither the scaled image nor the normalised scaled probabilities are ever stored.
+ *
+ * rgda_window_gather_scaled: rgda_window_gather on the Hs x Ws image, bit for bit rgda_window_gather applied to
+ * rgda_resize_bilinear_ac(normalised source, (Hs, Ws)).  Window rows (image, y1, x1) index the Hs x Ws image and are checked
+ * against it (Hs >= Th, Ws >= Tw); a uint8 source goes through lut tap by tap, before the blend (normalise, then resize).
+ *
+ * rgda_scale_merge: acc f32 [n][C][H][W] += rgda_resize_bilinear_ac(full_s / count_s, (H, W)) and cnt f32 [n][1][H][W] += 1,
+ * bit for bit rgda_window_normalise(full_s f32 [n][C][Hs][Ws], count_s f32 [n][1][Hs][Ws]), the resize and the add (NaN where
+ * those give NaN: a count of 0 under a tap); full_s is only read.  rgda_window_finish(acc, cnt) then gives the mean.
+ * Errors before any launch: null pointers, sizes outside the above (RGDA_ERR_ARG). */
+int rgda_window_gather_scaled(const float* src_f32, const uint8_t* src_u8, const float* lut, const int32_t* windows, int K,
+                              int views, int n, int C, int H, int W, int Hs, int Ws, int Th, int Tw, float* out, int* flag,
+                              rgda_stream_t stream);
+int rgda_scale_merge(const float* full_s, const float* count_s, int n, int C, int Hs, int Ws, int H, int W, float* acc,
+                     float* cnt, rgda_stream_t stream);
+
 /* ------------------------------------------------------------- training augmentation of raw tiles */
 
 /* BaseData.__getitem__ + the training transforms (regda/datasets/basedata.py:68-98, regda/aug/augmentation.py; the

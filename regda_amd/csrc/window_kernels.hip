@@ -4,6 +4,7 @@
 // window_crop + dihedral, tta_predict's de-augmented mean + window_accumulate, and window_normalise + argmax (+ the
 // confusion matrix) bit for bit.  A window table row is (image, y1, x1), int32, in DEVICE memory (a plan can record the
 // call); rows are checked where they are read, an invalid row is skipped and sets *flag.
+// rgda_window_gather_scaled / rgda_scale_merge run the same loop over the image at several scales (tools.py:108-129).
 #include "common.h"
 
 namespace {
@@ -150,7 +151,120 @@ __global__ void __launch_bounds__(WIN_THREADS) window_finish_kernel(float* __res
     }
 }
 
+// Multi-scale testing (regda/utils/tools.py:108-129): the align_corners=True resize of resize_ac_kernel
+// (teacher_kernels.hip) fused into the window gather and into the per-scale merge.  Source position of output index I
+// along an axis with `in` source samples, exactly as resize_ac_kernel forms it (f = s * (float)I, truncate, clamp the
+// upper neighbour); the callers blend in its association with contraction off.  i0 is also kept inside the source, which
+// changes nothing where resize_ac_kernel itself stays inside it.
+__device__ __forceinline__ void ac_source(float s, int I, int in, int& i0, int& i1, float& l) {
+#pragma clang fp contract(off)
+    const float f = s * (float)I;
+    i0 = (int)f;
+    if (i0 > in - 1) i0 = in - 1;
+    i1 = i0 + ((i0 < in - 1) ? 1 : 0);
+    l = f - (float)i0;
+}
+
+// Pixel (Y, X) of plane c of the Hs x Ws image resize_ac_kernel would make of the (normalised) H x W source `img`; a uint8
+// tap goes through lut first.
+__device__ __forceinline__ float scaled_pixel(const float* __restrict__ f32, const uint8_t* __restrict__ u8,
+                                              const float* __restrict__ lut, int H, int W, float sy, float sx, int Y, int X) {
+#pragma clang fp contract(off)
+    int ya, yb, xa, xb;
+    float ly, lx;
+    ac_source(sy, Y, H, ya, yb, ly);
+    ac_source(sx, X, W, xa, xb, lx);
+    const float my = 1.f - ly, mx = 1.f - lx;
+    const long long oa = (long long)ya * W, ob = (long long)yb * W;
+    float taa, tab, tba, tbb;
+    if (u8) {
+        taa = lut[u8[(oa + xa) * 3]]; tab = lut[u8[(oa + xb) * 3]];
+        tba = lut[u8[(ob + xa) * 3]]; tbb = lut[u8[(ob + xb) * 3]];
+    } else {
+        taa = f32[oa + xa]; tab = f32[oa + xb];
+        tba = f32[ob + xa]; tbb = f32[ob + xb];
+    }
+    const float top = mx * taa + lx * tab;                               // ATen's association
+    const float bot = mx * tba + lx * tbb;
+    return my * top + ly * bot;
+}
+
+// window_gather_kernel on that image, which is never stored: window rows index, and are checked against, the Hs x Ws
+// image.  blockIdx.y walks the planes rc = (w*V + v)*C + c, so the window row, the view and the channel are uniform in
+// a workgroup; a thread makes VEC consecutive pixels of one output row (VEC = 4: Tw % 4 == 0, out 16-byte aligned).
+template <int VEC>
+__global__ void __launch_bounds__(WIN_THREADS) window_gather_scaled_kernel(const float* __restrict__ src_f32,
+                                                                           const uint8_t* __restrict__ src_u8,
+                                                                           const float* __restrict__ lut,
+                                                                           const int32_t* __restrict__ wins, int planes, int V,
+                                                                           int n, int C, int H, int W, int Hs, int Ws,
+                                                                           int Th, int Tw, float sy, float sx,
+                                                                           float* __restrict__ out, int* __restrict__ flag) {
+    const int per_row = Tw / VEC, per = Th * per_row;
+    for (int rc = blockIdx.y; rc < planes; rc += gridDim.y) {
+        const int c = rc % C, r = rc / C;
+        const int w = r / V, v = r - w * V;
+        const int img = wins[3 * w], y1 = wins[3 * w + 1], x1 = wins[3 * w + 2];
+        const bool ok = window_ok(img, y1, x1, n, Hs, Ws, Th, Tw);
+        if (!ok && flag && threadIdx.x == 0) *flag = 1;
+        const float* f32 = src_f32 ? src_f32 + ((long long)img * C + c) * H * W : nullptr;
+        const uint8_t* u8 = src_u8 ? src_u8 + (long long)img * H * W * 3 + c : nullptr;
+        const float* t = src_u8 ? lut + c * 256 : nullptr;
+        float* o = out + (long long)rc * Th * Tw;
+        for (int q = blockIdx.x * WIN_THREADS + threadIdx.x; q < per; q += gridDim.x * WIN_THREADS) {
+            const int i = q / per_row, j = (q - i * per_row) * VEC;
+            float res[VEC];
+#pragma unroll
+            for (int u = 0; u < VEC; ++u) {
+                res[u] = 0.f;
+                if (ok) {
+                    int y, x;
+                    view_source(v, Th, i, j + u, y, x);
+                    res[u] = scaled_pixel(f32, u8, t, H, W, sy, sx, y + y1, x + x1);
+                }
+            }
+            if (VEC == 4) *reinterpret_cast<float4*>(o + (long long)i * Tw + j) = make_float4(res[0], res[1], res[2], res[3]);
+            else o[(long long)i * Tw + j] = res[0];
+        }
+    }
+}
+
+// acc[n][c][Y][X] += resize_ac(full_s / count_s)[n][c][Y][X], cnt[n][0][Y][X] += 1: window_norm_kernel's __fdiv_rn on the
+// four taps, resize_ac_kernel's blend, one add.  One thread per output pixel: the coordinates and the four count taps
+// once, then the classes.  full_s is only read.
+__global__ void __launch_bounds__(WIN_THREADS) scale_merge_kernel(const float* __restrict__ full_s,
+                                                                  const float* __restrict__ count_s, int n, int C, int Hs,
+                                                                  int Ws, int H, int W, float sy, float sx,
+                                                                  float* __restrict__ acc, float* __restrict__ cnt) {
+#pragma clang fp contract(off)
+    const long long HW = (long long)H * W, HWs = (long long)Hs * Ws, total = (long long)n * HW;
+    for (long long e = (long long)blockIdx.x * WIN_THREADS + threadIdx.x; e < total; e += (long long)gridDim.x * WIN_THREADS) {
+        const long long img = e / HW, p = e % HW;
+        const int X = (int)(p % W), Y = (int)(p / W);
+        int ya, yb, xa, xb;
+        float ly, lx;
+        ac_source(sy, Y, Hs, ya, yb, ly);
+        ac_source(sx, X, Ws, xa, xb, lx);
+        const float my = 1.f - ly, mx = 1.f - lx;
+        const long long oaa = (long long)ya * Ws + xa, oab = (long long)ya * Ws + xb;
+        const long long oba = (long long)yb * Ws + xa, obb = (long long)yb * Ws + xb;
+        const float* k = count_s + img * HWs;
+        const float kaa = k[oaa], kab = k[oab], kba = k[oba], kbb = k[obb];
+        for (int c = 0; c < C; ++c) {
+            const float* s = full_s + (img * C + c) * HWs;
+            const float top = mx * __fdiv_rn(s[oaa], kaa) + lx * __fdiv_rn(s[oab], kab);
+            const float bot = mx * __fdiv_rn(s[oba], kba) + lx * __fdiv_rn(s[obb], kbb);
+            float* a = acc + (img * C + c) * HW + p;
+            *a = *a + (my * top + ly * bot);
+        }
+        cnt[e] = cnt[e] + 1.f;
+    }
+}
+
 int grid_of(long long total, int cap) { long long g = (total + WIN_THREADS - 1) / WIN_THREADS; return (int)(g > cap ? cap : (g < 1 ? 1 : g)); }
+
+// the scale exactly as ATen computes it (area_pixel_compute_scale, align_corners): a float division on the host
+float ac_scale(int in, int out) { return (out > 1) ? (float)(in - 1) / (float)(out - 1) : 0.f; }
 
 }  // namespace
 
@@ -163,6 +277,32 @@ extern "C" int rgda_window_gather(const float* src_f32, const uint8_t* src_u8, c
     const long long total = (long long)K * views * C * Th * Tw;
     window_gather_kernel<<<grid_of(total, 65535), WIN_THREADS, 0, to_stream(stream)>>>(src_f32, src_u8, lut, windows, K, views,
                                                                                          n, C, H, W, Th, Tw, out, flag);
+    RGDA_CHECK_LAUNCH();
+    return RGDA_OK;
+}
+
+extern "C" int rgda_window_gather_scaled(const float* src_f32, const uint8_t* src_u8, const float* lut,
+                                         const int32_t* windows, int K, int views, int n, int C, int H, int W, int Hs, int Ws,
+                                         int Th, int Tw, float* out, int* flag, rgda_stream_t stream) {
+    if (!windows || !out || (!src_f32) == (!src_u8) || (src_u8 && (!lut || C != 3))) return RGDA_ERR_ARG;
+    if (K < 1 || n < 1 || C < 1 || H < 1 || W < 1 || Th < 1 || Tw < 1 || Hs < Th || Ws < Tw) return RGDA_ERR_ARG;
+    if ((views != 1 && views != 8) || (views == 8 && Th != Tw)) return RGDA_ERR_ARG;
+    const long long planes = (long long)K * views * C;
+    if (planes > 0x7fffffffLL || (long long)Th * Tw > (1LL << 30)) return RGDA_ERR_ARG;
+    const bool vec = Tw % 4 == 0 && (uintptr_t)out % 16 == 0;
+    const dim3 grid(grid_of((long long)Th * Tw / (vec ? 4 : 1), 1024), (unsigned)(planes > 65535 ? 65535 : planes));
+    auto kernel = vec ? window_gather_scaled_kernel<4> : window_gather_scaled_kernel<1>;
+    kernel<<<grid, WIN_THREADS, 0, to_stream(stream)>>>(src_f32, src_u8, lut, windows, (int)planes, views, n, C, H, W, Hs, Ws,
+                                                        Th, Tw, ac_scale(H, Hs), ac_scale(W, Ws), out, flag);
+    RGDA_CHECK_LAUNCH();
+    return RGDA_OK;
+}
+
+extern "C" int rgda_scale_merge(const float* full_s, const float* count_s, int n, int C, int Hs, int Ws, int H, int W,
+                                float* acc, float* cnt, rgda_stream_t stream) {
+    if (!full_s || !count_s || !acc || !cnt || n < 1 || C < 1 || Hs < 1 || Ws < 1 || H < 1 || W < 1) return RGDA_ERR_ARG;
+    scale_merge_kernel<<<grid_of((long long)n * H * W, 65535), WIN_THREADS, 0, to_stream(stream)>>>(
+        full_s, count_s, n, C, Hs, Ws, H, W, ac_scale(Hs, H), ac_scale(Ws, W), acc, cnt);
     RGDA_CHECK_LAUNCH();
     return RGDA_OK;
 }

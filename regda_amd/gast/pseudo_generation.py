@@ -19,7 +19,7 @@ def pseudo_selection(mask, cutoff_top=0.8, cutoff_low=0.6, return_type='ndarray'
 
 
 def gener_target_pseudo(_cfg, model, pseudo_loader, save_pseudo_label_path, slide=True, save_prob=False,
-                        size=(1024, 1024), ignore_label=-1, window_batch=None):
+                        size=(1024, 1024), ignore_label=-1, window_batch=None, scales=None):
     """Teacher pass over the target set (pseudo_generation.py:96-153): eval-mode sliding-window + 8-view TTA
     inference per tile.  `save_prob=True` writes the soft labels the SSL loader reads back -- a (C, h, w) fp32 CPU tensor
     `torch.save`d as `<fname>.pt` (pseudo_generation.py:135-136, basedata.py:86).  `save_prob=False` writes the HARD
@@ -28,8 +28,12 @@ def gener_target_pseudo(_cfg, model, pseudo_loader, save_pseudo_label_path, slid
     the reference hands that array to cv2.imwrite; here Pillow writes it (the container's bytes differ, the decoded
     pixels are the same array).  The colour visualisations (VisualizeSegmm) are not reproduced.
     window_batch=K (with slide): consecutive tiles of one shape are grouped until they hold K windows, which go through
-    the model K x 8 views at a time (pre_slide(window_batch=K)); the files are written per tile, in loader order."""
-    from ..utils.tools import check_window_batch, pre_slide, window_groups
+    the model K x 8 views at a time (pre_slide(window_batch=K)); the files are written per tile, in loader order.
+    scales (with slide): multi-scale testing -- the probabilities are predict_multiscale(tta=True)'s over `scales`, per
+    tile, or per group with window_batch=K."""
+    from ..utils.tools import check_window_batch, pre_slide, predict_multiscale, window_groups
+    if scales is not None and not slide:
+        raise ValueError('gener_target_pseudo: scales= is multi-scale sliding-window inference and needs slide=True')
     model.eval()
     os.makedirs(save_pseudo_label_path, exist_ok=True)
     num_classes = getattr(_cfg, 'NUM_CLASSES', None) or model.num_classes
@@ -53,7 +57,10 @@ def gener_target_pseudo(_cfg, model, pseudo_loader, save_pseudo_label_path, slid
             check_window_batch(window_batch, tta=True)
             for group in window_groups(pseudo_loader, tta=True, window_batch=window_batch):
                 img = torch.cat([ret for ret, _ in group]).cuda()
-                cls = pre_slide(model, img, num_classes=num_classes, tta=True, window_batch=window_batch)
+                if scales is not None:
+                    cls = predict_multiscale(model, img, scales, num_classes=num_classes, tta=True, window_batch=window_batch)
+                else:
+                    cls = pre_slide(model, img, num_classes=num_classes, tta=True, window_batch=window_batch)
                 off = 0
                 for ret, ret_gt in group:
                     b = ret.shape[0]
@@ -62,5 +69,8 @@ def gener_target_pseudo(_cfg, model, pseudo_loader, save_pseudo_label_path, slid
             return
         for ret, ret_gt in pseudo_loader:
             ret = ret.cuda()
-            cls = pre_slide(model, ret, num_classes=num_classes, tta=True) if slide else model(ret)
+            if scales is not None:
+                cls = predict_multiscale(model, ret, scales, num_classes=num_classes, tta=True, window_batch=None)
+            else:
+                cls = pre_slide(model, ret, num_classes=num_classes, tta=True) if slide else model(ret)
             write(cls, ret_gt)

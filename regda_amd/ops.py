@@ -927,6 +927,48 @@ def window_gather(src, windows, tile, views=1, lut=None, out=None, flag=None):
     return out
 
 
+def window_gather_scaled(src, windows, tile, scaled_size, views=1, lut=None, out=None, flag=None):
+    """rgda_window_gather_scaled: window_gather on the (Hs, Ws) = `scaled_size` image resize_bilinear_ac would make of the
+    normalised source, without storing it; windows index the scaled image.  Arguments as window_gather."""
+    _need_cuda(src, windows, lut, out, flag)
+    th, tw = tile
+    hs, ws = (int(v) for v in scaled_size)
+    if src.dtype == torch.uint8:
+        if src.dim() != 4 or src.shape[3] != 3 or lut is None:
+            raise ValueError('window_gather_scaled: a uint8 source is [n][H][W][3] and needs lut')
+        n, H, W, c = src.shape
+        f32, u8 = None, src.contiguous()
+    else:
+        if src.dtype != torch.float32 or src.dim() != 4:
+            raise ValueError('window_gather_scaled: the source is f32 [n][C][H][W] or uint8 [n][H][W][3]')
+        n, c, H, W = src.shape
+        f32, u8 = src.contiguous(), None
+    if windows.dtype != torch.int32 or windows.dim() != 2 or windows.shape[1] != 3 or not windows.is_contiguous():
+        raise ValueError('window_gather_scaled: windows must be a contiguous int32 [K][3] table')
+    k = windows.shape[0]
+    if out is None:
+        out = torch.empty(k * views, c, th, tw, device=src.device)
+    assert tuple(out.shape) == (k * views, c, th, tw) and out.dtype == torch.float32 and out.is_contiguous()
+    lib().call('rgda_window_gather_scaled', _p(f32), _p(u8), _p(lut), windows.data_ptr(), k, views, n, c, H, W, hs, ws, th,
+               tw, out.data_ptr(), _p(flag), _stream())
+    return out
+
+
+def scale_merge(full_s, count_s, acc, cnt):
+    """rgda_scale_merge: acc [n][C][H][W] += resize_bilinear_ac(full_s / count_s, (H, W)), cnt [n][1][H][W] += 1; full_s
+    [n][C][Hs][Ws] and count_s [n][1][Hs][Ws] are one scale's window sums and visit counts, left as they are."""
+    _need_cuda(full_s, count_s, acc, cnt)
+    n, c, hs, ws = full_s.shape
+    H, W = acc.shape[-2:]
+    if tuple(count_s.shape) != (n, 1, hs, ws) or tuple(acc.shape) != (n, c, H, W) or tuple(cnt.shape) != (n, 1, H, W):
+        raise ValueError('scale_merge: full_s %s, count_s %s, acc %s, cnt %s' %
+                         (tuple(full_s.shape), tuple(count_s.shape), tuple(acc.shape), tuple(cnt.shape)))
+    assert full_s.dtype == count_s.dtype == acc.dtype == cnt.dtype == torch.float32
+    assert full_s.is_contiguous() and count_s.is_contiguous() and acc.is_contiguous() and cnt.is_contiguous()
+    lib().call('rgda_scale_merge', full_s.data_ptr(), count_s.data_ptr(), n, c, hs, ws, H, W, acc.data_ptr(), cnt.data_ptr(),
+               _stream())
+
+
 def window_scatter(pred, windows, full, count, rows, views=1, flag=None):
     """rgda_window_scatter: full [n][C][H][W] / count [n][1][H][W] += the K windows of pred [K*views][C][Th][Tw], in table
     order.  rows = (row0, nrows): the span of the flattened n*H image rows the windows cover."""

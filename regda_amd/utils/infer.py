@@ -5,7 +5,8 @@ import numpy as np
 import torch
 
 from .. import aug, ops
-from .tools import batched_slide_supported, pre_slide, slide_accumulate
+from .tools import (batched_slide_supported, check_scales, multiscale_accumulate, pre_slide, predict_multiscale,
+                    slide_accumulate)
 
 
 def scene_table(cfg):
@@ -16,23 +17,36 @@ def scene_table(cfg):
 
 
 def predict_scene(model, image_u8, cfg, num_classes, tile_size=(512, 512), tta=False, window_batch=16,
-                  return_probs=False):
+                  return_probs=False, scales=None):
     """argmax(pre_slide(model, normalise(image), num_classes, tile_size, tta)) of one scene as a uint8 (H, W) label map
     on the GPU (`.cpu().numpy()` is the array infer_single.py saves as prediction.png).  image_u8: uint8 (H, W, 3) numpy
     array or tensor, on the host or the device.  Sets model.eval() as the reference does.  window_batch: windows per
     forward (x 8 views with tta); None runs the per-window path on a normalised fp32 copy.  A scene smaller than the
     tile (or a non-square tile with tta) takes the per-window path too.  return_probs: also return the (1, C, H, W)
-    probabilities."""
+    probabilities.  scales: multi-scale testing -- the argmax of predict_multiscale(model, normalise(image), scales, ...);
+    the windows of every scale are made from the uint8 scene (rgda_window_gather_scaled), so neither a normalised nor a
+    rescaled copy of it is stored."""
     img = torch.as_tensor(np.ascontiguousarray(image_u8) if isinstance(image_u8, np.ndarray) else image_u8)
     if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3:
         raise ValueError('predict_scene: the scene must be uint8 (H, W, 3), got %s %s' % (img.dtype, tuple(img.shape)))
     dev = torch.device('cuda', torch.cuda.current_device())
     img = img.to(dev).contiguous()[None]
     H, W = img.shape[1], img.shape[2]
+    if scales is not None:
+        scales = tuple(scales)
+        check_scales(H, W, scales)
     lut = scene_table(cfg).to(dev)
     model.eval()
     with torch.no_grad():
-        if window_batch is not None and batched_slide_supported((H, W), tile_size, tta):
+        if scales is not None and window_batch is not None:
+            full, count = multiscale_accumulate(model, img, num_classes, scales, tile_size, tta, window_batch, lut=lut)
+            labels = torch.empty(1, H, W, dtype=torch.uint8, device=dev)
+            ops.window_finish(full, count, labels=labels)
+        elif scales is not None:
+            x = ops.augment_tiles(img, torch.zeros(1, 4, dtype=torch.int32), lut, (H, W))['image']
+            full = predict_multiscale(model, x, scales, tile_size, num_classes, tta, window_batch=None)
+            labels = ops.argmax_nchw(full).to(torch.uint8)
+        elif window_batch is not None and batched_slide_supported((H, W), tile_size, tta):
             full, count = slide_accumulate(model, img, num_classes, tile_size, tta, window_batch, lut=lut)
             labels = torch.empty(1, H, W, dtype=torch.uint8, device=dev)
             ops.window_finish(full, count, labels=labels)

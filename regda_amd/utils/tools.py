@@ -1,5 +1,5 @@
-"""loss_calc / learning-rate schedule / config import / sliding-window + TTA inference -- mirror of
-regda/utils/tools.py:51-97,132-152,173-207,240-260."""
+"""loss_calc / learning-rate schedule / config import / sliding-window + TTA + multi-scale inference -- mirror of
+regda/utils/tools.py:51-97,108-129,132-152,173-207,240-260."""
 import importlib
 import os
 import shutil
@@ -152,16 +152,21 @@ def check_window_batch(window_batch, tile_size=(512, 512), tta=False):
     return k
 
 
-def slide_accumulate(model, image, num_classes, tile_size=(512, 512), tta=False, window_batch=16, lut=None):
+def slide_accumulate(model, image, num_classes, tile_size=(512, 512), tta=False, window_batch=16, lut=None,
+                     scaled_size=None):
     """The batched window loop without the final division: -> (full (n, C, H, W), count (n, 1, H, W)) as pre_slide holds
     them before rgda_window_normalise.  image: f32 (n, c, H, W), or uint8 (n, H, W, 3) with `lut` (f32 [3][256] device
     table), on the GPU; batched_slide_supported must hold.  Windows are taken image by image in pre_slide's order,
-    `window_batch` of them (x 8 views with tta) per forward."""
+    `window_batch` of them (x 8 views with tta) per forward.
+    scaled_size=(Hs, Ws): the same loop over ops.resize_bilinear_ac(normalised image, (Hs, Ws)), which is never stored
+    (rgda_window_gather_scaled makes each window from the source); full and count are then Hs x Ws."""
     K = check_window_batch(window_batch, tile_size, tta)
     if image.dtype == torch.uint8:
         n, H, W, _ = image.shape
     else:
         n, _, H, W = image.shape
+    if scaled_size is not None:
+        H, W = scaled_size
     th, tw = tile_size
     assert batched_slide_supported((H, W), tile_size, tta)
     views = 8 if tta else 1
@@ -172,7 +177,10 @@ def slide_accumulate(model, image, num_classes, tile_size=(512, 512), tta=False,
     for s in range(0, len(rows), K):
         chunk = rows[s:s + K]
         wins = table[s:s + len(chunk)]
-        batch = ops.window_gather(image, wins, tile_size, views, lut=lut)
+        if scaled_size is None:
+            batch = ops.window_gather(image, wins, tile_size, views, lut=lut)
+        else:
+            batch = ops.window_gather_scaled(image, wins, tile_size, scaled_size, views, lut=lut)
         pred = model(batch)
         r0 = min(i * H + y1 for i, y1, _ in chunk)
         r1 = max(i * H + y1 + th for i, y1, _ in chunk)
@@ -202,6 +210,101 @@ def pre_slide(model, image, num_classes=7, tile_size=(512, 512), tta=False, wind
         ops.window_accumulate(padded.contiguous(), full_probs, count, y1, x1, h, w)
     ops.window_normalise(full_probs, count)
     return full_probs
+
+
+# ----------------------------------------------------------------------------- multi-scale testing (tools.py:108-129)
+DEFAULT_SCALES = (0.75, 1.0, 1.25, 1.5, 1.75, 2.0)
+
+
+def scaled_size(H, W, s):
+    """The size ndimage.zoom(image, (1, 1, s, s)) gives an H x W image (tools.py:122): Python's round of H * s, W * s."""
+    return int(round(H * s)), int(round(W * s))
+
+
+def check_scales(H, W, scales):
+    """-> [(Hs, Ws)] of `scales` for an H x W image; ValueError for no scale, a scale that is not a positive finite number
+    and a scale whose image has no pixels."""
+    scales = [float(s) for s in scales]
+    if not scales:
+        raise ValueError('multi-scale inference needs at least one scale')
+    sizes = []
+    for s in scales:
+        if not (0 < s < float('inf')):
+            raise ValueError('scales must be positive, got %r' % (s,))
+        hs, ws = scaled_size(H, W, s)
+        if hs < 1 or ws < 1:
+            raise ValueError('scale %r of a %dx%d image has no pixels' % (s, H, W))
+        sizes.append((hs, ws))
+    return sizes
+
+
+def multiscale_accumulate(model, image, num_classes, scales, tile_size=(512, 512), tta=False, window_batch=16, lut=None):
+    """The sum over `scales` of the sliding-window probabilities of the rescaled image, each brought back to H x W:
+    -> (acc (n, C, H, W), cnt (n, 1, H, W) = len(scales)); ops.window_finish(acc, cnt) is the mean.  image as for
+    slide_accumulate (f32 NCHW, or uint8 NHWC with `lut`).  Per scale, in the given order, the windows of the Hs x Ws
+    image go through the model exactly as slide_accumulate would take them from it (rgda_window_gather_scaled builds them
+    from the source), and rgda_scale_merge divides by the visit count, resizes back and adds in one pass; the scale's
+    n * (C + 1) * Hs * Ws * 4 bytes are released before the next scale.  A scaled image smaller than the tile (or a
+    non-square tile with tta) is materialised and takes pre_slide's per-window path."""
+    check_window_batch(window_batch, tile_size, tta)
+    if image.dtype == torch.uint8:
+        n, H, W, _ = image.shape
+    else:
+        n, _, H, W = image.shape
+    sizes = check_scales(H, W, scales)
+    acc = torch.zeros(n, num_classes, H, W, device=image.device)
+    cnt = torch.zeros(n, 1, H, W, device=image.device)
+    x = None
+    for size in sizes:
+        if batched_slide_supported(size, tile_size, tta):
+            full_s, count_s = slide_accumulate(model, image, num_classes, tile_size, tta, window_batch, lut=lut,
+                                               scaled_size=size)
+            ops.scale_merge(full_s, count_s, acc, cnt)
+            del full_s, count_s
+            continue
+        if x is None:
+            x = image
+            if image.dtype == torch.uint8:      # the normalised image through the identity element of rgda_augment_tiles
+                x = ops.augment_tiles(image, torch.zeros(n, 4, dtype=torch.int32), lut, (H, W))['image']
+        xs = ops.resize_bilinear_ac(x, size)
+        if tta and n > 1:                       # tta_predict takes one image
+            probs = torch.cat([pre_slide(model, xs[i:i + 1], num_classes, tile_size, True) for i in range(n)])
+        else:
+            probs = pre_slide(model, xs, num_classes, tile_size, tta)
+        acc += ops.resize_bilinear_ac(probs, (H, W))
+        cnt += 1
+    return acc, cnt
+
+
+def predict_multiscale(model, image, scales=DEFAULT_SCALES, tile_size=(512, 512), num_classes=None, tta=False,
+                       window_batch=16):
+    """Multi-scale testing (tools.py:108-129): the mean over `scales` of the class probabilities of the image resampled
+    by each scale, brought back to the image's size; (n, C, H, W).  Kept from the reference: the default scales, the
+    resampling of the image (ndimage.zoom(order=1, prefilter=False), which is align_corners=True bilinear to
+    scaled_size(H, W, s)), the align_corners=True resize of the probabilities and the mean.
+    The reference's function cannot run: it adds the (1, C, H, W) prediction in place into a (1, 1, H, W) accumulator,
+    which raises for C > 1.  Beyond mending that, this one differs in three ways: the image is resampled on the GPU, not by
+    scipy on the host; each scaled image goes through pre_slide's windows of `tile_size` (with `tta` through the 8 views)
+    instead of one whole-image forward, which a scene does not fit; and the probabilities come back to the image's size,
+    where the reference resizes them to `tile_size`.  The division by len(scales) is IEEE (rgda_window_finish).
+    num_classes: model.num_classes when None.  window_batch=K: K windows per forward (multiscale_accumulate);
+    None: the composition resize_bilinear_ac -> pre_slide -> resize_bilinear_ac per scale."""
+    n, _, H, W = image.shape
+    scales = tuple(scales)
+    sizes = check_scales(H, W, scales)
+    if num_classes is None:
+        num_classes = model.num_classes
+    image = image.contiguous().float()
+    if window_batch is not None:
+        acc, cnt = multiscale_accumulate(model, image, num_classes, scales, tile_size, tta, window_batch)
+        ops.window_finish(acc, cnt)
+        return acc
+    acc = torch.zeros(n, num_classes, H, W, device=image.device)
+    for size in sizes:
+        probs = pre_slide(model, ops.resize_bilinear_ac(image, size), num_classes, tile_size, tta)
+        acc += ops.resize_bilinear_ac(probs, (H, W))
+    ops.window_normalise(acc, torch.full((n, 1, H, W), float(len(sizes)), device=image.device))
+    return acc
 
 
 def window_groups(loader, tile_size=(512, 512), tta=False, window_batch=16):

@@ -1,7 +1,7 @@
 """Sliding-window inference: the per-window path against window_batch = K.
 
     python scripts/dev/infer_bench.py [--models resnet101,resnet50] [--ks 4,8,16,32] [--tiles 64] [--eval-items 200]
-                                      [--scene 6000] [--sections invariance,tiles,image,scene,eval]
+                                      [--scene 6000] [--sections invariance,tiles,image,scene,eval,multiscale]
 
 Random-init Deeplabv2 (6 classes, confident classifiers as in bench.py), eval mode, synthetic inputs.  Prints one JSON
 line per measurement:
@@ -11,6 +11,10 @@ line per measurement:
   image       one 1024^2 (LoveDA-sized) image
   scene       a uint8 scene through predict_scene (per-window: window_batch=None)
   eval        one evaluate() call over `--eval-items` 512^2 items, wall time and peak device memory
+  multiscale  the uint8 scene through predict_scene(scales=(1.0, 1.5), window_batch=16): wall time and
+              peak memory against the single-scale call, and per scale the device time of the two fused kernels
+              (rgda_window_gather_scaled over all window batches, rgda_scale_merge) against the composition each
+              replaces (normalise + resize_bilinear_ac + window_gather; window_normalise + resize_bilinear_ac + add)
 """
 import argparse
 import json
@@ -144,6 +148,77 @@ def evaluation(m, rt, ks, n_items):
              peak_gib=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))
 
 
+def device_ms(fn, reps=5):
+    """Median device time of fn() over `reps` runs after one warm-up, by events on the current stream."""
+    fn()
+    ts = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    return sorted(ts)[len(ts) // 2]
+
+
+def multiscale(m, rt, size, scales=(1.0, 1.5), k=16, ncls=6, tile=(512, 512)):
+    import numpy as np
+    from configs import ToPotsdam
+    from regda_amd import ops
+    from regda_amd.utils.infer import predict_scene, scene_table
+    from regda_amd.utils.tools import scaled_size, window_list
+    s = torch.from_numpy(np.random.default_rng(4).integers(0, 256, (size, size, 3), dtype=np.uint8))
+    for sc in (None, scales):
+        torch.cuda.reset_peak_memory_stats()
+        fn = lambda: predict_scene(m, s, ToPotsdam, ncls, tta=False, window_batch=k, scales=sc)     # noqa: E731
+        fn()
+        wall, host = timed(fn)
+        nw = sum(len(window_list(*scaled_size(size, size, x), tile)) for x in (sc or (1.0,)))
+        emit(section='multiscale', model=rt, size=size, scales=sc, window_batch=k, windows=nw, s=round(wall, 3),
+             host_s=round(host, 3), tiles_per_s=round(nw / wall, 2),
+             peak_gib=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2))
+    img = s.cuda()[None]
+    lut = scene_table(ToPotsdam).cuda()
+    zero = torch.zeros(1, 4, dtype=torch.int32)
+    acc, cnt = torch.zeros(1, ncls, size, size, device='cuda'), torch.zeros(1, 1, size, size, device='cuda')
+    for sc in scales:
+        hs, ws = scaled_size(size, size, sc)
+        rows = [(0, y1, x1) for (y1, x1, _, _) in window_list(hs, ws, tile)]
+        table = torch.tensor(rows, dtype=torch.int32).cuda()
+        chunks = [table[i:i + k] for i in range(0, len(rows), k)]
+        bufs = {c.shape[0]: torch.empty(c.shape[0], 3, *tile, device='cuda') for c in chunks}
+
+        def gather_fused():
+            for c in chunks:
+                ops.window_gather_scaled(img, c, tile, (hs, ws), lut=lut, out=bufs[c.shape[0]])
+
+        def gather_composed():
+            xs = ops.resize_bilinear_ac(ops.augment_tiles(img, zero, lut, (size, size))['image'], (hs, ws))
+            for c in chunks:
+                ops.window_gather(xs, c, tile, out=bufs[c.shape[0]])
+        full_s = torch.rand(1, ncls, hs, ws, device='cuda')
+        count_s = torch.ones(1, 1, hs, ws, device='cuda')          # / 1: the composition may divide in place every run
+
+        def merge_fused():
+            ops.scale_merge(full_s, count_s, acc, cnt)
+
+        def merge_composed():
+            ops.window_normalise(full_s, count_s)
+            acc.add_(ops.resize_bilinear_ac(full_s, (size, size)))
+            cnt.add_(1)
+        t = {}
+        for _ in range(2):                                           # alternate the arms
+            for name, fn in (('gather_fused', gather_fused), ('gather_composed', gather_composed),
+                             ('merge_fused', merge_fused), ('merge_composed', merge_composed)):
+                t.setdefault(name, []).append(device_ms(fn))
+        emit(section='multiscale_kernels', model=rt, size=size, scale=sc, scaled=[hs, ws], windows=len(rows), window_batch=k,
+             **{name + '_ms': [round(v, 3) for v in vs] for name, vs in t.items()},
+             gather_fused_ms_per_launch=round(min(t['gather_fused']) / len(chunks), 4))
+        del full_s, count_s, bufs
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--models', default='resnet101,resnet50')
@@ -168,6 +243,8 @@ def main():
             scene(m, rt, ks, a.scene)
         if 'eval' in sections:
             evaluation(m, rt, ks, a.eval_items)
+        if 'multiscale' in sections and rt == 'resnet101':
+            multiscale(m, rt, a.scene)
         del m
         torch.cuda.empty_cache()
 
