@@ -776,9 +776,13 @@ int rgda_confusion_accumulate(const int64_t* y_true, const int64_t* y_pred, int6
  *   the normalised prototypes sit in LDS: C * K floats plus the partial sums within 160 KB (C = 16: K = 2048 fits, 4096 does
  *   not; beyond it RGDA_ERR_UNSUPPORTED).
  *   logits = normalize(feat_p) . normalize(protos)^T / temperature   (tnf.normalize: x / max(||x||, 1e-12))
- *   loss[0] += weight * mean over the kept pixels of cross_entropy(logits, label)      (NaN-free only if one is kept)
+ *   loss[0] += weight * mean over the kept pixels of cross_entropy(logits, label)      (NaN if none is kept, and NaN
+ *   if any kept pixel's loss is not finite -- a NaN or Inf feature -- however many such pixels there are)
  *   dfeat (optional) bf16 [b*h*w][lddf], pixel-major -- the layout rgda_instnorm_bwd consumes: (+)= weight * dloss/dfeat
- * ws (rgda_pcl_loss_workspace bytes): normalised prototypes, valid-pixel count, flag (bit 2: label outside [0,C)). */
+ * ws (rgda_pcl_loss_workspace bytes): float pn[C][K] normalised prototypes, padded to 256 bytes | int valid-pixel count |
+ *   int flag | rgda_stat_t loss total.  The call clears count, flag and total first.  flag bit 2 (value 4): a label
+ *   outside [0,C) that is not ignore_label (such a pixel is dropped like an ignored one); bit 3 (value 8): the loss of a
+ *   32-pixel block was not finite or left the fixed-point range (|partial| >= 2^19), and loss[0] is NaN. */
 size_t rgda_pcl_loss_workspace(int C, int K);
 int rgda_pcl_loss(const float* feat, const int64_t* labels, const float* protos, float* loss, void* dfeat,
                   int lddf, int accumulate, int b, int K, int C, int h, int w, int ignore_label,

@@ -3,7 +3,10 @@
 #include "common.h"
 #include <math.h>
 
-// ws layout: float pn[C][K] (L2-normalised prototypes) | int count (valid pixels) | pad
+// ws layout: float pn[C][K] (L2-normalised prototypes) | int count (valid pixels) | int flag | rgda_stat_t loss total
+// flag: bit 2 (value 4) a label outside [0, C) that is not ignore_label; bit 3 (value 8) a pixel block whose loss partial
+// stat_add() poisoned (not finite, or out of the fixed-point range): the total is then unusable and the loss reads NaN
+constexpr int PCL_FLAG_LABEL = 4, PCL_FLAG_NONFINITE = 8;
 // one workgroup per class: pn[c] = protos[c] / max(||protos[c]||, 1e-12)   (tnf.normalize, loss.py:41)
 __global__ void __launch_bounds__(256) pcl_prep_kernel(const float* __restrict__ protos, float* __restrict__ pn, int K) {
     __shared__ float red[4];
@@ -29,7 +32,7 @@ __global__ void __launch_bounds__(256) pcl_count_kernel(const int64_t* __restric
     }
     c = (int)wave_sum((float)c);            // <= 64 * (n / grid) per wave: exact in fp32 for the maps we see (< 2^24)
     if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, c);
-    if (bad) atomicOr(flag, 4);
+    if (bad) atomicOr(flag, PCL_FLAG_LABEL);
 }
 
 // Workgroup = PX pixels x SL k-slices.  Pass 1: ||f||^2 and the C dot products with the normalised prototypes
@@ -40,7 +43,8 @@ __global__ void __launch_bounds__(256) pcl_count_kernel(const int64_t* __restric
 template <int C, int PX, int SL>
 __global__ void __launch_bounds__(PX * SL) pcl_kernel(const float* __restrict__ feat, const int64_t* __restrict__ labels,
                                                       const float* __restrict__ pn, const int* __restrict__ count,
-                                                      rgda_stat_t* loss_acc, bf16_t* __restrict__ dfeat, int lddf, int accumulate,
+                                                      rgda_stat_t* loss_acc, int* flag, bf16_t* __restrict__ dfeat, int lddf,
+                                                      int accumulate,
                                                       int K, int hw, int ignore_label, float inv_temp, float weight) {
     extern __shared__ float lds[];          // pn[C][K] | red[SL][PX][C+1] | coef[PX][C+1] | tile (bf16 [PX][KC+8])
     constexpr int KC = 128;                 // channels per transposed store chunk
@@ -108,33 +112,50 @@ __global__ void __launch_bounds__(PX * SL) pcl_kernel(const float* __restrict__ 
             }
             cf[0] = gd * inv_temp / (nrm * nrm * nrm);            // beta
         }
-        // loss: one fixed-point integer atomic per wave (order-independent total, common.h: stat_add)
+        // loss: one fixed-point integer atomic per wave (order-independent total, common.h: stat_add).  A partial that
+        // stat_add would poison is flagged instead: sixteen poisons of 3 * 2^60 wrap the 64-bit total back to the sum of the
+        // healthy blocks, so the finish kernel cannot tell from the total's magnitude.
         float tot = contrib;
         for (int o = PX / 2; o > 0; o >>= 1) tot += __shfl_xor(tot, o, 64);
-        if (lane == 0 && tot != 0.f) stat_add(loss_acc, tot, RGDA_STAT_FRAC_BWD);
+        if (lane == 0 && tot != 0.f) {
+            if (fabsf(ldexpf(tot, RGDA_STAT_FRAC_BWD)) < 0x1p59f) stat_add(loss_acc, tot, RGDA_STAT_FRAC_BWD);
+            else atomicOr(flag, PCL_FLAG_NONFINITE);
+        }
     }
     __syncthreads();
     if (!dfeat) return;
     // ---- pass 2: gradient, KC channels per round; thread = (pixel lane, KC/SL consecutive channels)
-    constexpr int PER = KC / SL;
+    constexpr int PER = KC / SL;             // 8 or 16: whole 8-channel vectors
+    static_assert(PER % 8 == 0, "a thread's channels of one chunk are whole 16-byte vectors");
     constexpr int TS = KC + 8;              // padded tile row (bf16 elements)
     const float* cf = coef + lane * (C + 1);
     float alpha[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) alpha[c] = cf[1 + c];
     const float beta = cf[0];
+    // accumulate: the old bf16 value joins the fp32 gradient before the one rounding to bf16 (rounding the gradient first
+    // and the sum again loses up to a bf16 half-ulp of the gradient where the two cancel).  A thread's PER channels are
+    // whole 16-byte vectors of its pixel's row; the row is rewritten only after the barrier below.
+    const bf16_t* orow = dfeat + ((size_t)b * hw + (ok ? p : 0)) * lddf;
     for (int kc = 0; kc < K; kc += KC) {
 #pragma unroll
-        for (int j = 0; j < PER; ++j) {
-            const int k = kc + slice * PER + j;
-            float gk = 0.f;
-            if (k < K) {
-                const float v = f[(size_t)k * hw];
-                gk = -beta * v;
+        for (int j0 = 0; j0 < PER; j0 += 8) {
+            const int kb = kc + slice * PER + j0;
+            u16x8 old = {0, 0, 0, 0, 0, 0, 0, 0};
+            if (accumulate && ok && kb < K) old = *(const u16x8*)(orow + kb);
 #pragma unroll
-                for (int c = 0; c < C; ++c) gk += alpha[c] * lpn[c * K + k];
+            for (int e = 0; e < 8; ++e) {
+                const int k = kb + e;
+                float gk = 0.f;
+                if (k < K) {
+                    const float v = f[(size_t)k * hw];
+                    gk = -beta * v;
+#pragma unroll
+                    for (int c = 0; c < C; ++c) gk += alpha[c] * lpn[c * K + k];
+                    if (accumulate) gk += bf2f(old[e]);
+                }
+                tile[lane * TS + slice * PER + j0 + e] = f2bf(gk);
             }
-            tile[lane * TS + slice * PER + j] = f2bf(gk);
         }
         __syncthreads();
         // PX rows x KC/8 vectors
@@ -142,14 +163,8 @@ __global__ void __launch_bounds__(PX * SL) pcl_kernel(const float* __restrict__ 
             const int row = v / (KC / 8), cv = v % (KC / 8);
             const int pp = blockIdx.x * PX + row, k = kc + cv * 8;
             if (pp < hw && k < K) {
-                u16x8 val = *(const u16x8*)(tile + row * TS + cv * 8);
-                bf16_t* dst = dfeat + ((size_t)b * hw + pp) * lddf + k;
-                if (accumulate) {
-                    u16x8 old = *(const u16x8*)dst;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) val[e] = f2bf(bf2f(val[e]) + bf2f(old[e]));
-                }
-                *(u16x8*)dst = val;
+                const u16x8 val = *(const u16x8*)(tile + row * TS + cv * 8);
+                *(u16x8*)(dfeat + ((size_t)b * hw + pp) * lddf + k) = val;
             }
         }
         __syncthreads();
@@ -157,9 +172,10 @@ __global__ void __launch_bounds__(PX * SL) pcl_kernel(const float* __restrict__ 
 }
 
 // *loss += the accumulated total; no pixel kept: nn.CrossEntropyLoss averages over zero elements -> NaN loss (and zero
-// gradients), like the reference
-__global__ void pcl_loss_finish_kernel(const rgda_stat_t* acc, const int* count, float* loss) {
-    *loss += (*count == 0) ? __builtin_nanf("") : (float)((double)*acc * (1.0 / (double)(1ll << RGDA_STAT_FRAC_BWD)));
+// gradients), like the reference; a kept pixel whose loss is not finite -> NaN, whatever the number of such blocks
+__global__ void pcl_loss_finish_kernel(const rgda_stat_t* acc, const int* count, const int* flag, float* loss) {
+    const bool nan = *count == 0 || (*flag & PCL_FLAG_NONFINITE);
+    *loss += nan ? __builtin_nanf("") : (float)((double)*acc * (1.0 / (double)(1ll << RGDA_STAT_FRAC_BWD)));
 }
 
 static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -207,13 +223,13 @@ extern "C" int rgda_pcl_loss(const float* feat, const int64_t* labels, const flo
         if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)pcl_kernel<C, PX, SL>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                    (int)lds) != hipSuccess)
             return RGDA_ERR_LAUNCH;
-        pcl_kernel<C, PX, SL><<<grid, PX * SL, lds, st>>>(feat, labels, pn, count, lacc, (bf16_t*)dfeat, lddf, accumulate, K, h * w,
-                                                          ignore_label, 1.f / temperature, weight);
+        pcl_kernel<C, PX, SL><<<grid, PX * SL, lds, st>>>(feat, labels, pn, count, lacc, flag, (bf16_t*)dfeat, lddf, accumulate,
+                                                          K, h * w, ignore_label, 1.f / temperature, weight);
         RGDA_CHECK_LAUNCH();
         return RGDA_OK;
     });
     if (rc != RGDA_OK) return rc;
-    pcl_loss_finish_kernel<<<1, 1, 0, st>>>(lacc, count, loss);
+    pcl_loss_finish_kernel<<<1, 1, 0, st>>>(lacc, count, flag, loss);
     RGDA_CHECK_LAUNCH();
     return RGDA_OK;
 }

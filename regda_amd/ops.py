@@ -1221,9 +1221,18 @@ def confusion_accumulate(y_true, y_pred, cm, flag):
 
 
 # ----------------------------------------------------------------------------- stage 2 ("align")
-def pcl_loss(feat, labels, protos, temperature=8.0, ignore_label=-1, weight=1.0, loss=None, dfeat=None, accumulate=False):
+def pcl_flag(ws, class_num, k):
+    """The int32 flag word of a workspace that rgda_pcl_loss has used (one host sync): bit 2 (value 4) a label outside
+    [0, class_num) that is not ignore_label, bit 3 (value 8) a kept pixel whose loss is not finite (the loss reads NaN)."""
+    off = (int(class_num) * int(k) * 4 + 255) // 256 * 256 + 4
+    return int(ws[off:off + 4].view(torch.int32).item())
+
+
+def pcl_loss(feat, labels, protos, temperature=8.0, ignore_label=-1, weight=1.0, loss=None, dfeat=None, accumulate=False,
+             ws=None):
     """PrototypeContrastiveLoss forward (+ gradient w.r.t. feat into `dfeat` bf16 [b*h*w, K] when given).
-    Returns the (accumulating) fp32 loss tensor."""
+    Returns the (accumulating) fp32 loss tensor.  `ws`: a caller-owned uint8 workspace of at least
+    rgda_pcl_loss_workspace(C, K) bytes, whose flag word pcl_flag() reads afterwards; nothing here synchronises."""
     _need_cuda(feat, labels, protos)
     feat = feat.contiguous().float()
     b, K, h, w = feat.shape
@@ -1233,7 +1242,9 @@ def pcl_loss(feat, labels, protos, temperature=8.0, ignore_label=-1, weight=1.0,
     if loss is None:
         loss = torch.zeros(1, device=feat.device)
     L = lib()
-    ws = _ws(L.size('rgda_pcl_loss_workspace', C, K), feat.device)
+    if ws is None:
+        ws = _ws(L.size('rgda_pcl_loss_workspace', C, K), feat.device)
+    assert ws.dtype == torch.uint8 and ws.is_cuda and ws.is_contiguous()
     L.call('rgda_pcl_loss', feat.data_ptr(), labels.data_ptr(), protos.data_ptr(), loss.data_ptr(), _p(dfeat),
            _ld(dfeat) if dfeat is not None else 0, int(bool(accumulate)), b, K, C, h, w, ignore_label, float(temperature),
            float(weight), ws.data_ptr(), ws.numel(), _stream())
