@@ -215,13 +215,48 @@ enum rgda_loss_kind {
     RGDA_LOSS_FOCAL = 2,
     RGDA_LOSS_GHM = 3,
     RGDA_LOSS_UPS = 4,
-    RGDA_LOSS_UVEM = 5
+    RGDA_LOSS_UVEM = 5,
+    RGDA_LOSS_GDP = 6          /* served by rgda_upsample_gdp; rgda_upsample_loss answers RGDA_ERR_ARG for it */
 };
 size_t rgda_upsample_loss_workspace(int kind, int b, int c, int h, int w, int H, int W);
 int rgda_upsample_loss(int kind, int heads, const float* p1, const float* p2, const int64_t* label,
                        const float* soft, const float* class_weight, float* acc_sum, double m, double t, double gamma, float thresh,
                        double momentum, float* loss, float* g1, float* g2, int b, int c, int h, int w, int H,
                        int W, int ignore_label, void* ws, size_t ws_bytes, rgda_stream_t stream);
+
+/* loss_calc([p1,p2], label, GDPLoss(bins=30), multi=True) forward + d(loss)/d(logits)
+ *   regda/gast/balance.py:218-303; regda/utils/tools.py:240-254.
+ * Per head call (head 1 first) on the logits upsampled bilinearly (align_corners=True) to the label size:
+ *   g = |softmax(z)[label] - 1| (-1 where ignored); bins = histc(g, 30, 0, 1); bins = (bins + flip(bins)) * 0.5 (:261-262);
+ *   acc_sum (device f32[30], in/out) = momentum * acc_sum + (1 - momentum) * bins, or bins at momentum 0 (:267-270);
+ *   bins_weight = where(acc_sum != 0, 1 - acc_sum / (sum(acc_sum) + 1e-7), 0) / (max + 1e-7) (:290-295; device f32[30],
+ *   out: the weights of the LAST head call); weight = bins_weight[bucketize(g) - 1] (0 outside 1..30: a pixel with
+ *   p_y == 1 exactly is counted in the histogram and weighs 0) + pixel_weight[pixel] + class_weight[head][label], the
+ *   two optional terms present iff their pointer is non-NULL, / the number of terms (:277-283);
+ *   loss = sum(ce * weight) / (#(label != -1) + 1e-7) (:284), mean over the heads.  Weights carry no gradient.
+ * pixel_weight: NULL or f32[b*H*W] (Aligner.get_prototype_weight_4pixel, rgda_proto_pixel_weight; shared by both heads);
+ * class_weight: NULL or f32[2][c].  heads, p1, p2, label, loss, g1, g2, the class counts and the size limit: as
+ * rgda_upsample_loss.  The statistic pass is RGDA_LOSS_GHM's own kernel; workspace: rgda_upsample_gdp_workspace bytes
+ * (2 bytes of scratch per pixel).  All labels ignored: loss 0, gradient 0.  Deterministic, nothing read back. */
+size_t rgda_upsample_gdp_workspace(int b, int c, int h, int w, int H, int W);
+int rgda_upsample_gdp(int heads, const float* p1, const float* p2, const int64_t* label,
+                      const float* pixel_weight, const float* class_weight, float* acc_sum, float* bins_weight,
+                      double momentum, float* loss, float* g1, float* g2, int b, int c, int h, int w, int H,
+                      int W, int ignore_label, void* ws, size_t ws_bytes, rgda_stream_t stream);
+
+/* Aligner.get_prototype_weight_4pixel(feats, label_hard)   regda/gast/alignment.py:267-281 (+ _pearson_dist :396-423).
+ * feat NCHW f32 (b,k,h,w); protos (c,k) f32; label (b,H,W) int64; out f32[b*H*W]:
+ *   sim = 1 / pearson_dist(feat, protos) at (b,c,h,w) -> bilinear align_corners=True to (H,W) -> softmax over the classes
+ *   (temperature 1: the reference's `temp` argument is unused) -> / (per-pixel max + 1e-7) -> the value at the pixel's
+ *   label, 0 where the label is ignore_label (or outside [0, c)).
+ * sim: NULL, or the similarity map f32 (b,c,h,w) already computed (the base of rgda_label_refine's workspace after a call
+ * with the prototype view): the similarity pass is skipped, feat / protos / ws may be NULL and k is not used.
+ * 6 <= c <= 16; without sim the prototype limits of rgda_label_refine apply (k % 4 == 0, c * k floats + partial sums in
+ * LDS); the pick pass stages 2 * c * w floats in at most 64 KB of LDS (c = 16: w <= 512). */
+size_t rgda_proto_pixel_weight_workspace(int b, int c, int k, int h, int w);
+int rgda_proto_pixel_weight(const float* feat, const float* protos, const float* sim, const int64_t* label,
+                            float* out, int b, int k, int c, int h, int w, int H, int W, int ignore_label,
+                            void* ws, size_t ws_bytes, rgda_stream_t stream);
 
 /* Deeplabv2 eval-branch output  regda/models/Encoder.py:152-155:
  * (softmax(up(x1)) + softmax(up(x2))) / 2, up = bilinear align_corners=True.  6 <= c <= 16. */

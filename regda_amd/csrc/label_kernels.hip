@@ -901,6 +901,105 @@ static int refine_run(const float* feat, const float* protos, const float* p1, c
 }
 
 // --------------------------------------------------------------------------------------
+// Aligner.get_prototype_weight_4pixel   (regda/gast/alignment.py:267-281)
+// --------------------------------------------------------------------------------------
+// The prototype view of label_refine with a label pick at the end: sim = 1 / pearson_dist (proto_center_kernel +
+// pearson_sim_kernel, as refine_launch runs them), then per output pixel the bilinear (align_corners=True) upsample of
+// sim, softmax over the classes (temperature 1), / (per-pixel maximum + 1e-7), the value at the pixel's label.  One
+// workgroup per output row with the two low-resolution sim rows staged in LDS (rows[C][2][w]), as the loss row pass
+// stages logits; the interpolation is refine_apply_kernel's, operation for operation.
+template <int C>
+__global__ void __launch_bounds__(256) proto_pick_kernel(const float* __restrict__ sim, const int64_t* __restrict__ label,
+                                                         float* __restrict__ out, int h, int w, int H, int W,
+                                                         int ignore_label) {
+    extern __shared__ float rows[];
+    const int b = blockIdx.y, Y = blockIdx.x;
+    const Lerp ly = lerp_ac(Y, h, H);
+    for (int i = threadIdx.x; i < C * 2 * w; i += 256) {
+        const int x = i % w, r = (i / w) & 1, c = i / (2 * w);
+        rows[i] = sim[((size_t)b * C + c) * h * w + (size_t)(r ? ly.i1 : ly.i0) * w + x];
+    }
+    __syncthreads();
+    for (int X = threadIdx.x; X < W; X += 256) {
+        const size_t pix = ((size_t)b * H + Y) * W + X;
+        const long long lab = label[pix];
+        const Lerp lx = lerp_ac(X, w, W);
+        float a[C], ma = -INFINITY;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const float* r = rows + (size_t)c * 2 * w;
+            const float top = __fadd_rn(__fmul_rn(lx.l0, r[lx.i0]), __fmul_rn(lx.l1, r[lx.i1]));
+            const float bot = __fadd_rn(__fmul_rn(lx.l0, r[w + lx.i0]), __fmul_rn(lx.l1, r[w + lx.i1]));
+            a[c] = __fadd_rn(__fmul_rn(ly.l0, top), __fmul_rn(ly.l1, bot));
+            ma = fmaxf(ma, a[c]);
+        }
+        float sa = 0.f;
+#pragma unroll
+        for (int c = 0; c < C; ++c) { a[c] = expf(a[c] - ma); sa += a[c]; }
+        float pmax = 0.f, pl = 0.f;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            a[c] = a[c] / sa;
+            pmax = fmaxf(pmax, a[c]);
+            pl = (lab == c) ? a[c] : pl;
+        }
+        // the one-hot of an ignored label is all zero (_index2onehot, :440-453): weight 0
+        const bool on = lab != ignore_label && lab >= 0 && lab < C;
+        out[pix] = on ? pl / (pmax + 1e-7f) : 0.f;
+    }
+}
+
+// the launches of rgda_proto_pixel_weight for one class count; workspace: sim[b][c][hw] | pstd[c] | pc[c][k]
+template <int C>
+static int pixel_weight_launch(const float* feat, const float* protos, const float* sim, const int64_t* label, float* out,
+                               int b, int k, int h, int w, int H, int W, int ignore_label, char* base, size_t row_lds,
+                               rgda_stream_t stream) {
+    hipStream_t st = to_stream(stream);
+    if (!sim) {
+        float* simw = (float*)base;
+        float* pstd = (float*)(base + align256((size_t)b * C * h * w * 4));
+        float* pc = (float*)((char*)pstd + align256((size_t)C * 4));
+        proto_center_kernel<<<C, 256, 0, st>>>(protos, pc, pstd, k);
+        RGDA_CHECK_LAUNCH();
+        constexpr int PX = 32, SL = refine_slices(C);
+        const size_t lds = refine_lds(C, k);
+        if (lds > 64 * 1024 &&
+            hipFuncSetAttribute((const void*)pearson_sim_kernel<C, PX, SL>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds) != hipSuccess)
+            return RGDA_ERR_LAUNCH;
+        pearson_sim_kernel<C, PX, SL><<<dim3(cdiv(h * w, PX), b), PX * SL, lds, st>>>(feat, pc, pstd, simw, k, h * w);
+        RGDA_CHECK_LAUNCH();
+        sim = simw;
+    }
+    proto_pick_kernel<C><<<dim3(H, b), 256, row_lds, st>>>(sim, label, out, h, w, H, W, ignore_label);
+    RGDA_CHECK_LAUNCH();
+    return RGDA_OK;
+}
+
+extern "C" size_t rgda_proto_pixel_weight_workspace(int b, int c, int k, int h, int w) {
+    // sim[b][c][hw] | pstd[c] | pc[c][k]
+    if (b <= 0 || c <= 0 || k < 0 || h <= 0 || w <= 0) return 0;
+    return align256((size_t)b * c * h * w * 4) + align256((size_t)c * 4) + (size_t)c * k * 4;
+}
+
+extern "C" int rgda_proto_pixel_weight(const float* feat, const float* protos, const float* sim_in, const int64_t* label,
+                                       float* out, int b, int k, int c, int h, int w, int H, int W, int ignore_label,
+                                       void* ws, size_t ws_bytes, rgda_stream_t stream) {
+    if (!label || !out || (!sim_in && (!feat || !protos || !ws))) return RGDA_ERR_ARG;
+    if (!class_count_ok(c)) return RGDA_ERR_UNSUPPORTED;
+    if (b <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return RGDA_ERR_ARG;
+    if (!sim_in && (k < 2 || k > 4096 || (k & 3))) return RGDA_ERR_ARG;
+    if (!sim_in && refine_lds(c, k) > RGDA_LDS_MAX) return RGDA_ERR_UNSUPPORTED;       // label_refine's prototype limit
+    const size_t row_lds = (size_t)c * 2 * w * 4;
+    if (row_lds > 64 * 1024) return RGDA_ERR_UNSUPPORTED;                               // c = 16: w <= 512
+    if (!sim_in && ws_bytes < rgda_proto_pixel_weight_workspace(b, c, k, h, w)) return RGDA_ERR_WORKSPACE;
+    return with_classes(c, [&](auto cc) {
+        return pixel_weight_launch<decltype(cc)::value>(feat, protos, sim_in, label, out, b, k, h, w, H, W, ignore_label,
+                                                        (char*)ws, row_lds, stream);
+    });
+}
+
+// --------------------------------------------------------------------------------------
 // SAM region map assembly   (regda/utils/local_region_homog.py:51-56, inside SAM.get_local_regions)
 // --------------------------------------------------------------------------------------
 // region[p] = 1 + the LAST mask index k (generator order) with areas[k] >= threshold and masks[k][p] != 0, else 0:

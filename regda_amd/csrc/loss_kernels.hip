@@ -17,6 +17,10 @@
 //            per-row loss partials, d loss / d logits contracted horizontally
 //   col / reduce: vertical contraction; fixed-order double reduction of the row partials.
 // No float atomics anywhere; nothing is read back to the host.
+//
+// GDPLoss (rgda_upsample_gdp; balance.py:218-303) runs on the same passes: GHM's stat pass as it is (the same |p_y - 1|,
+// bins and edges), a global stage of its own (symmetrised histogram, acc_sum EMA, bin weights) and the GDP branch of the
+// grad pass, whose per-pixel weight is the bin weight + the optional prototype weight + the optional class weight.
 #include "common.h"
 
 namespace {
@@ -49,6 +53,7 @@ struct LossHdr {
     int rem[2];
     float denom[2];
     float acc[2][32];                    // GHM acc_sum after the head-1 and after the head-2 update
+    float bw[2][32];                     // GDP bins_weight of the head-1 and of the head-2 call
 };
 
 struct LossParams {
@@ -64,7 +69,8 @@ static size_t align256_(size_t x) { return (x + 255) & ~(size_t)255; }
 static size_t scratch_bytes(int kind, size_t n) {
     switch (kind) {
         case RGDA_LOSS_OHEM: return 2 * n * 4;
-        case RGDA_LOSS_GHM: return 2 * n;
+        case RGDA_LOSS_GHM:
+        case RGDA_LOSS_GDP: return 2 * n;
         case RGDA_LOSS_UPS:
         case RGDA_LOSS_UVEM: return n * 4;
         default: return 0;
@@ -278,6 +284,47 @@ __global__ void __launch_bounds__(64) loss_finalize_kernel(int kind, int heads, 
     hdr->denom[t] = denom;
 }
 
+// GDPLoss's global stage (balance.py:261-270,290-295), one workgroup.  Per head call, head 1 first:
+//   bins = (histc(g) + flip(histc(g))) * 0.5;  acc_sum = momentum * acc_sum + (1 - momentum) * bins  (momentum 0: bins)
+//   bins_weight = where(acc_sum != 0, 1 - acc_sum / (sum(acc_sum) + 1e-7), 0) / (max + 1e-7)
+// The 30-element sum is taken in double in bin order and rounded once, the maximum in bin order: every lane of the
+// first wave walks the same staged values, so all of them hold the same bits.  One head: the second "head" is the same
+// prediction and reuses the first state, as in GHM.
+__global__ void __launch_bounds__(64) gdp_finalize_kernel(int heads, LossHdr* hdr, float* acc_sum, float* bins_weight,
+                                                          LossParams prm) {
+    const int t = threadIdx.x;
+    __shared__ float s_a[GHM_BINS], s_b[GHM_BINS];
+    float a = t < GHM_BINS ? acc_sum[t] : 0.f, bw = 0.f;
+    for (int hd = 0; hd < heads; ++hd) {
+        if (t < GHM_BINS) {
+            int n = 0, nf = 0;
+            for (int r = 0; r < CNT_REPL; ++r) { n += hdr->ghm_hist[r][hd][t]; nf += hdr->ghm_hist[r][hd][GHM_BINS - 1 - t]; }
+            const float bins = __fmul_rn(__fadd_rn((float)n, (float)nf), 0.5f);
+            a = prm.mom > 0.f ? __fadd_rn(__fmul_rn(prm.mom, a), __fmul_rn(prm.omm, bins)) : bins;
+            s_a[t] = a;
+        }
+        __syncthreads();
+        double tot = 0.0;
+        for (int i = 0; i < GHM_BINS; ++i) tot += (double)s_a[i];
+        const float den = __fadd_rn((float)tot, 1e-7f);
+        const float v = (t < GHM_BINS && a != 0.f) ? __fsub_rn(1.f, __fdiv_rn(a, den)) : 0.f;
+        if (t < GHM_BINS) s_b[t] = v;
+        __syncthreads();
+        float mx = s_b[0];
+        for (int i = 1; i < GHM_BINS; ++i) mx = fmaxf(mx, s_b[i]);
+        bw = __fdiv_rn(v, __fadd_rn(mx, 1e-7f));
+        if (t < 32) hdr->bw[hd][t] = t < GHM_BINS ? bw : 0.f;
+        __syncthreads();
+    }
+    if (t < 32 && heads == 1) hdr->bw[1][t] = t < GHM_BINS ? bw : 0.f;
+    if (t < GHM_BINS) { acc_sum[t] = a; bins_weight[t] = bw; }
+    if (t < 2) {                         // the denominator is GHM's: #(label != -1) + 1e-7 (balance.py:284)
+        int n = 0;
+        for (int r = 0; r < CNT_REPL; ++r) n += hdr->cnt[r][CNT_LIT];
+        hdr->denom[t] = __fadd_rn((float)n, 1e-7f);
+    }
+}
+
 // One radix pass of the OHEM top-k: histogram of one digit of the keys that match the prefix resolved so far; the last
 // workgroup to arrive finds the digit of the rem-th largest key.  Keys: f32 bits of the loss (>= 0, so the bit pattern
 // is monotone) in the high word, n - 1 - pixel index in the low word: unique, ties of the loss go to the lower index.
@@ -380,6 +427,7 @@ template <int KIND, int C>
 __global__ void __launch_bounds__(256) loss_grad_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
                                                         const int64_t* __restrict__ label,
                                                         const float* __restrict__ class_weight,
+                                                        const float* __restrict__ pixel_weight,
                                                         const LossHdr* __restrict__ hdr, const void* __restrict__ scratch,
                                                         float* partial, float* T, int h, int w, int H, int W,
                                                         int ignore_label, LossParams prm, int want_grad) {
@@ -393,6 +441,9 @@ __global__ void __launch_bounds__(256) loss_grad_kernel(const float* __restrict_
     const size_t n = (size_t)gridDim.y * H * W;
     const Lerp ly = row_lerp<KIND != KIND_CE>(Y, h, H);
     if (KIND == RGDA_LOSS_GHM && threadIdx.x < 64) s_acc[threadIdx.x >> 5][threadIdx.x & 31] = hdr->acc[threadIdx.x >> 5][threadIdx.x & 31];
+    if (KIND == RGDA_LOSS_GDP && threadIdx.x < 64) s_acc[threadIdx.x >> 5][threadIdx.x & 31] = hdr->bw[threadIdx.x >> 5][threadIdx.x & 31];
+    // GDP: the number of weight terms, 1 + prototype_refine + class_balance (balance.py:283)
+    const float gdp_div = 1.f + (pixel_weight ? 1.f : 0.f) + (class_weight ? 1.f : 0.f);
     stage_rows<C>(rows, p1, p2, b, ly.i0, ly.i1, h, w);
     float inv_d0 = 0.f, inv_d1 = 0.f;    // CE has no header
     unsigned long long cut0 = 0ull, cut1 = 0ull;
@@ -412,6 +463,7 @@ __global__ void __launch_bounds__(256) loss_grad_kernel(const float* __restrict_
         const int li = valid ? (int)lab : 0;
         float f = 0.f;
         if constexpr (KIND == RGDA_LOSS_UPS || KIND == RGDA_LOSS_UVEM) f = ((const float*)scratch)[pix];
+        if constexpr (KIND == RGDA_LOSS_GDP) f = pixel_weight ? pixel_weight[pix] : 0.f;
 #pragma unroll
         for (int hd = 0; hd < 2; ++hd) {
             float m, e[C], se, zl;
@@ -446,6 +498,15 @@ __global__ void __launch_bounds__(256) loss_grad_kernel(const float* __restrict_
                     const float wg = (ind > 0 && ind <= GHM_BINS) ? 1.f / s_acc[hd][ind - 1] : 0.f;
                     lp = ce * wg;
                     dce = wg * inv_d;
+                } else if constexpr (KIND == RGDA_LOSS_GDP) {
+                    // weight_bins (+ weight_prototype) (+ class weight), in the reference's order (balance.py:277-283);
+                    // a pixel with p_y == 1 exactly has bucket 0: counted in the histogram, bin weight 0
+                    const int ind = ((const uint8_t*)scratch)[hd * n + pix];
+                    float wp = (ind > 0 && ind <= GHM_BINS) ? s_acc[hd][ind - 1] : 0.f;
+                    if (pixel_weight) wp = __fadd_rn(wp, f);
+                    if (class_weight) wp = __fadd_rn(wp, valid ? cw : 0.f);
+                    lp = __fdiv_rn(__fmul_rn(ce, wp), gdp_div);
+                    dce = __fdiv_rn(wp, gdp_div) * inv_d;
                 } else {                 // UPS / UVEM: f = 0 where u > t (the gated CE), the uncertainty weight else
                     const float wt = f * cw;
                     lp = wt * ce;
@@ -528,6 +589,8 @@ struct LossCall {
     const float *p1, *p2, *soft, *class_weight;
     const int64_t* label;
     float *acc_sum, *loss, *g1, *g2;
+    const float* pixel_weight;           // GDP
+    float* bins_weight;                  // GDP
     LossHdr* hdr;
     void* scratch;
     float *partial, *T;
@@ -548,12 +611,17 @@ static int run_passes(const LossCall& a, rgda_stream_t stream) {
             const size_t zero = KIND == RGDA_LOSS_OHEM ? offsetof(LossHdr, cut) : offsetof(LossHdr, sel_arrived);
             if (zero_bytes(a.hdr, zero, stream) != RGDA_OK) return RGDA_ERR_LAUNCH;
             const size_t lds = uv ? 0 : (size_t)2 * C * 2 * a.w * 4;
-            if (lds_attr((const void*)loss_stat_kernel<KIND, C>, lds) != RGDA_OK) return RGDA_ERR_LAUNCH;
-            loss_stat_kernel<KIND, C><<<rows_grid, 256, lds, st>>>(a.p1, a.p2, a.label, a.soft, a.class_weight, a.hdr,
+            // GDP's statistic pass is GHM's, the same instantiation
+            constexpr int STAT = KIND == RGDA_LOSS_GDP ? (int)RGDA_LOSS_GHM : KIND;
+            if (lds_attr((const void*)loss_stat_kernel<STAT, C>, lds) != RGDA_OK) return RGDA_ERR_LAUNCH;
+            loss_stat_kernel<STAT, C><<<rows_grid, 256, lds, st>>>(a.p1, a.p2, a.label, a.soft, a.class_weight, a.hdr,
                                                                 a.scratch, a.h, a.w, a.H, a.W, a.ignore_label, a.prm);
             RGDA_CHECK_LAUNCH();
         }
-        loss_finalize_kernel<<<1, 64, 0, st>>>(KIND, a.heads, a.hdr, a.acc_sum, a.prm, n);
+        if constexpr (KIND == RGDA_LOSS_GDP)
+            gdp_finalize_kernel<<<1, 64, 0, st>>>(a.heads, a.hdr, a.acc_sum, a.bins_weight, a.prm);
+        else
+            loss_finalize_kernel<<<1, 64, 0, st>>>(KIND, a.heads, a.hdr, a.acc_sum, a.prm, n);
         RGDA_CHECK_LAUNCH();
         if constexpr (KIND == RGDA_LOSS_OHEM) {
             const int blocks = (int)min((long long)cdiv(n, 256 * 8), 512ll);
@@ -565,8 +633,8 @@ static int run_passes(const LossCall& a, rgda_stream_t stream) {
     }
     const size_t lds = grad_lds(C, a.w, a.W, want);
     if (lds_attr((const void*)loss_grad_kernel<KIND, C>, lds) != RGDA_OK) return RGDA_ERR_LAUNCH;
-    loss_grad_kernel<KIND, C><<<rows_grid, 256, lds, st>>>(a.p1, a.p2, a.label, a.class_weight, a.hdr, a.scratch,
-                                                        a.partial, a.T, a.h, a.w, a.H, a.W, a.ignore_label, a.prm, want);
+    loss_grad_kernel<KIND, C><<<rows_grid, 256, lds, st>>>(a.p1, a.p2, a.label, a.class_weight, a.pixel_weight, a.hdr,
+                                                        a.scratch, a.partial, a.T, a.h, a.w, a.H, a.W, a.ignore_label, a.prm, want);
     RGDA_CHECK_LAUNCH();
     if (want) {
         loss_col_kernel<C><<<cdiv((long long)2 * a.b * C * a.h * a.w, 256), 256, 0, st>>>(a.T, a.g1, a.g2, a.b, a.h, a.w,
@@ -587,6 +655,7 @@ static int run_kind(int kind, const LossCall& a, rgda_stream_t stream) {
         case RGDA_LOSS_GHM: return run_passes<RGDA_LOSS_GHM, C>(a, stream);
         case RGDA_LOSS_UPS: return run_passes<RGDA_LOSS_UPS, C>(a, stream);
         case RGDA_LOSS_UVEM: return run_passes<RGDA_LOSS_UVEM, C>(a, stream);
+        case RGDA_LOSS_GDP: return run_passes<RGDA_LOSS_GDP, C>(a, stream);
         default: return RGDA_ERR_ARG;
     }
 }
@@ -674,4 +743,41 @@ extern "C" int rgda_upsample_loss(int kind, int heads, const float* p1, const fl
     prm.mom = (float)momentum;
     prm.omm = (float)(1.0 - momentum);
     return run_kind(kind, c, a, stream);
+}
+
+extern "C" size_t rgda_upsample_gdp_workspace(int b, int c, int h, int w, int H, int W) {
+    if (b <= 0 || c <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return 0;
+    const size_t n = (size_t)b * H * W;
+    return align256_(sizeof(LossHdr)) + align256_((size_t)b * H * 2 * 4) + align256_((size_t)b * H * 2 * c * w * 4) +
+           scratch_bytes(RGDA_LOSS_GDP, n);
+}
+
+extern "C" int rgda_upsample_gdp(int heads, const float* p1, const float* p2, const int64_t* label,
+                                 const float* pixel_weight, const float* class_weight, float* acc_sum, float* bins_weight,
+                                 double momentum, float* loss, float* g1, float* g2, int b, int c, int h, int w, int H,
+                                 int W, int ignore_label, void* ws, size_t ws_bytes, rgda_stream_t stream) {
+    if (heads != 1 && heads != 2) return RGDA_ERR_ARG;
+    if (!p1 || !p2 || !label || !loss || !ws || ((g1 == nullptr) != (g2 == nullptr))) return RGDA_ERR_ARG;
+    if (heads == 1 && p2 != p1) return RGDA_ERR_ARG;
+    if (!acc_sum || !bins_weight || !(momentum >= 0.0 && momentum < 1.0)) return RGDA_ERR_ARG;
+    if (b <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return RGDA_ERR_ARG;
+    if ((long long)b * H * W >= (1ll << 31)) return RGDA_ERR_ARG;
+    if (!class_count_ok(c)) return RGDA_ERR_UNSUPPORTED;
+    if (ws_bytes < rgda_upsample_gdp_workspace(b, c, h, w, H, W)) return RGDA_ERR_WORKSPACE;
+    if (grad_lds(c, w, W, g1 != nullptr) > MAX_ROW_LDS) return RGDA_ERR_UNSUPPORTED;
+    LossCall a{};
+    a.p1 = p1, a.p2 = p2, a.class_weight = class_weight, a.pixel_weight = pixel_weight, a.label = label;
+    a.acc_sum = acc_sum, a.bins_weight = bins_weight, a.loss = loss, a.g1 = g1, a.g2 = g2;
+    char* base = (char*)ws;
+    a.hdr = (LossHdr*)base;
+    base += align256_(sizeof(LossHdr));
+    a.partial = (float*)base;
+    base += align256_((size_t)b * H * 2 * 4);
+    a.T = (float*)base;
+    base += align256_((size_t)b * H * 2 * c * w * 4);
+    a.scratch = base;
+    a.heads = heads, a.b = b, a.h = h, a.w = w, a.H = H, a.W = W, a.ignore_label = ignore_label;
+    a.prm.mom = (float)momentum;
+    a.prm.omm = (float)(1.0 - momentum);
+    return run_kind(RGDA_LOSS_GDP, c, a, stream);
 }

@@ -3,6 +3,7 @@ regda/gast/alignment.py that the authors' recipe (runs/regda/run_2potsdam.sh) us
 with and without the superpixel view; every `mode`), update_prototype (:86-90), align_domain (CORAL, :79-84, or
 the MMD of the reference's commented `self.mmd`, :68), whiten_class_ware (ClassWareWhitening, :165-170),
 update_avg / init_avg (the prototype initialisation of tools/init_prototypes.py, :107-126), DownscaleLabel (:456-481).
+get_prototype_weight_4pixel (:267-281), the prototype weight GDPLoss adds to its pixel weights, is provided too.
 MMD carries a gradient (only its bandwidth is detached, regda/gast/mmd.py:34) and is provided.  align_class and
 align_instance are not: their distances end in `.detach()` in the reference, so they carry no gradient.
 """
@@ -112,6 +113,17 @@ class Aligner:
     def update_prototype(self, feat, label):
         """Update global prototypes by source features and labels (alignment.py:86-90)."""
         return ops.proto_update(feat.detach(), label, self.prototypes, 16, self.ignore_label, 0.75, self.decay)
+
+    def get_prototype_weight_4pixel(self, feats, label_hard, temp=2.0):
+        """alignment.py:267-281: per label pixel, how well the feature under it agrees with the prototype of ITS label --
+        1 / pearson_dist upsampled (bilinear, align_corners=True) to the label size, softmax over the classes, divided
+        by the per-pixel maximum + 1e-7, picked at the label; 0 where the label is ignored.  Flat f32 [b*H*W], detached
+        (GDPLoss.set_prototype_weight_4pixel takes it).  `temp` is accepted and unused, as in the reference (its softmax
+        runs at temperature 1)."""
+        if label_hard.dim() == 4:
+            label_hard = label_hard.squeeze(1)
+        return ops.proto_pixel_weight(feats.detach(), self.prototypes, label_hard.long(),
+                                      ignore_label=self.ignore_label).detach()
 
     def label_refine(self, label_t_sup, feat_t, preds_t, label_t_soft, refine=True, mode='all', temp=2.0):
         """alignment.py:194-265: every `mode`, one or two prediction tensors, with or without the superpixel view

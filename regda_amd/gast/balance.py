@@ -1,7 +1,8 @@
 """CrossEntropy + ClassBalance -- mirror of regda/gast/balance.py:15-101 (the "CE + reweight" of the
 SSL path).  The loss is evaluated by the fused bilinear-upsample + CE kernel (`rgda_upsample_ce`).
 The losses of the --ls / --lt flags -- OhemCrossEntropy, FocalLoss, GHMLoss, UPSLoss, UVEMLoss (balance.py:104-216,
-306-435) -- and loss_calc_uvem (:438-460) run on the fused upsample + loss kernels of `rgda_upsample_loss`."""
+306-435) -- and loss_calc_uvem (:438-460) run on the fused upsample + loss kernels of `rgda_upsample_loss`; GDPLoss
+(:218-303) on those of `rgda_upsample_gdp`."""
 import torch
 import torch.distributed as dist
 import torch.nn as nn
@@ -175,6 +176,72 @@ class GHMLoss(_FusedLoss):
         return self.acc_sum / (self.acc_sum.sum() + 1e-7)
 
 
+class GDPLoss(_FusedLoss):
+    """balance.py:218-303 (`rgda_upsample_gdp`).  The per-pixel weight is the mean of up to three terms: the
+    gradient-density weight `bins_weight[bucketize(|p_y - 1|) - 1]`, with prototype_refine the prototype weight handed
+    over by set_prototype_weight_4pixel (Aligner.get_prototype_weight_4pixel), with class_balance the ClassBalance weight
+    of the pixel's label.  acc_sum and bins_weight stay on the device and are updated in place (acc_sum once per head),
+    so a captured or recorded step advances them at every replay.
+
+    `class_balancer` is the loss's own ClassBalance(class_num, ignore_label, 0.99, temp) when class_balance is on and None
+    otherwise; a balancer passed in replaces it (a data-parallel run hands over one that carries its process group)."""
+    kind = 'gdp'
+
+    def __init__(self, bins=30, momentum=0.99, class_num=7, ignore_label=-1, class_balance=False, prototype_refine=False,
+                 temp=0.5, class_balancer=None, device='cuda'):
+        super().__init__()
+        if bins != 30:
+            raise NotImplementedError('GDPLoss: bins=30 only')
+        self.bins_num, self.momentum, self.ignore_label = bins, momentum, ignore_label
+        self.class_num, self.temp = class_num, temp
+        self.class_balance, self.prototype_refine = class_balance, prototype_refine
+        edges = [float(x) / bins for x in range(bins + 1)]
+        edges[-1] = edges[-1] + 1e-3
+        self.edges = torch.tensor(edges, dtype=torch.float32, device=device)
+        self.acc_sum = torch.zeros(bins, device=device)
+        self.bins_weight = torch.zeros(bins, device=device)
+        self.weight_prototype = None
+        self.class_balancer = None
+        if class_balance:
+            self.class_balancer = class_balancer if class_balancer is not None else ClassBalance(
+                class_num=class_num, ignore_label=ignore_label, decay=0.99, temperature=temp)
+
+    def set_prototype_weight_4pixel(self, weight_prototype):
+        """The prototype weights of the NEXT forward call(s): f32, one per label pixel (any shape)."""
+        self.weight_prototype = weight_prototype
+
+    def _pixel_weight(self, labels):
+        if not self.prototype_refine:
+            return None
+        w = self.weight_prototype
+        if w is None:
+            raise RuntimeError('GDPLoss(prototype_refine=True): call set_prototype_weight_4pixel(weights) before the loss '
+                               '(Aligner.get_prototype_weight_4pixel gives them)')
+        if w.numel() != labels.numel():
+            raise ValueError(f'GDPLoss: {w.numel()} prototype weights for {labels.numel()} label pixels')
+        return w.detach().reshape(-1).float().contiguous()
+
+    def launch(self, p1, p2, labels, soft=None, class_weight=None, g1=None, g2=None, heads=2, want_grad=True,
+               pixel_weight=None):
+        # `soft` unused; pixel_weight: the fused steps pass theirs, the module path the one that was set
+        if pixel_weight is None:
+            pixel_weight = self._pixel_weight(labels)
+        return ops.upsample_gdp(p1, p2, labels, self.acc_sum, self.bins_weight, pixel_weight=pixel_weight,
+                                class_weight=class_weight, momentum=float(self.momentum),
+                                ignore_label=self.ignore_label, want_grad=want_grad, g1=g1, g2=g2, heads=heads)
+
+    def forward(self, preds, targets):
+        return self._run(preds, targets, None)
+
+    def get_g_distribution(self):
+        """(acc_sum normalised, bins_weight, the balancer's report) as balance.py:302-303; without class_balance the
+        report is that of the reference's idle balancer (uniform frequencies)."""
+        bal = self.class_balancer
+        if bal is None:
+            bal = ClassBalance(class_num=self.class_num, ignore_label=self.ignore_label, decay=0.99, temperature=self.temp)
+        return self.acc_sum / (self.acc_sum.sum() + 1e-7), self.bins_weight, str(bal)
+
+
 class UPSLoss(_FusedLoss):
     """balance.py:306-345: CE where the soft label's entropy u <= threshold, / #(u <= threshold, valid)."""
     kind = 'ups'
@@ -235,7 +302,7 @@ def loss_calc_uvem(pred, label, label_soft, loss_fn, multi=True):
 
 
 SOURCE_LOSSES = ('CrossEntropy', 'OhemCrossEntropy')
-TARGET_LOSSES = ('ours', 'uvem', 'ohem', 'focal', 'ghm', 'ups', 'none')
+TARGET_LOSSES = ('ours', 'uvem', 'ohem', 'focal', 'ghm', 'ups', 'gdp', 'none')
 
 
 def source_loss(ls, class_balancer=None, ignore_label=-1):
@@ -248,9 +315,11 @@ def source_loss(ls, class_balancer=None, ignore_label=-1):
 
 
 def target_loss(lt, class_balancer=None, uvem_m=0.2, uvem_t=0.7, uvem_g=4.0, class_num=6, ignore_label=-1,
-                device='cuda'):
+                device='cuda', gdp_prototype=False, gdp_class_balance=False, gdp_momentum=0.99, gdp_temp=0.5):
     """--lt with --bct and --uvem-m/-t/-g, exactly as tools/train_ssl_reg.py:135-158: ours / uvem and ups honour the
-    balancer, ohem, focal and ghm are built without one, none is CrossEntropy (with it)."""
+    balancer, ohem, focal and ghm are built without one, none is CrossEntropy (with it).  'gdp' (no flag of the
+    reference's scripts constructs it) is GDPLoss with the gdp_* options; with gdp_class_balance a `class_balancer`
+    given here replaces the loss's internal one."""
     if lt not in TARGET_LOSSES:
         raise ValueError(f'--lt {lt!r}: one of {TARGET_LOSSES}')
     if lt in ('ours', 'uvem'):
@@ -264,4 +333,8 @@ def target_loss(lt, class_balancer=None, uvem_m=0.2, uvem_t=0.7, uvem_g=4.0, cla
         return GHMLoss(bins=30, momentum=0.99, ignore_label=ignore_label, device=device)
     if lt == 'ups':
         return UPSLoss(threshold=0.7, class_balancer=class_balancer, class_num=class_num, ignore_label=ignore_label)
+    if lt == 'gdp':
+        return GDPLoss(bins=30, momentum=gdp_momentum, class_num=class_num, ignore_label=ignore_label,
+                       class_balance=gdp_class_balance, prototype_refine=gdp_prototype, temp=gdp_temp,
+                       class_balancer=class_balancer if gdp_class_balance else None, device=device)
     return CrossEntropy(ignore_label=ignore_label, class_balancer=class_balancer)

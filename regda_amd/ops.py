@@ -188,8 +188,10 @@ def masks_to_regions(masks, areas, area_threshold=1024):
     return out
 
 
-def label_refine(feat, protos, p1, p2, soft, temp=2.0, out=None, return_ws=False, views=3):
-    """views: bit 0 = prototype view, bit 1 = prediction view (3 = mode 'all'); inputs of a view that is off may be None."""
+def label_refine(feat, protos, p1, p2, soft, temp=2.0, out=None, return_ws=False, views=3, return_sim=False):
+    """views: bit 0 = prototype view, bit 1 = prediction view (3 = mode 'all'); inputs of a view that is off may be None.
+    return_sim (with return_ws and the prototype view): also the similarity map 1 / pearson_dist (b,c,h,w) at the base of
+    the workspace, what proto_pixel_weight takes as `sim` -> (out, classmax workspace, sim)."""
     pview, lview = bool(views & 1), bool(views & 2)
     assert views in (1, 2, 3)
     soft = soft.contiguous().float()
@@ -222,6 +224,9 @@ def label_refine(feat, protos, p1, p2, soft, temp=2.0, out=None, return_ws=False
                float(temp), views, ws.data_ptr(), ws.numel(), _stream())
     if return_ws:
         off = L.size('rgda_label_refine_classmax_offset', b, c, h, w)
+        if return_sim:
+            assert pview
+            return out, ws[off:], ws[:b * c * h * w * 4].view(torch.float32).view(b, c, h, w)
         return out, ws[off:]
     return out
 
@@ -397,7 +402,8 @@ def upsample_ce(p1, p2, label, ignore_label=-1, class_weight=None, want_grad=Tru
     return loss, g1, g2
 
 
-LOSS_KINDS = {'ohem': 1, 'focal': 2, 'ghm': 3, 'ups': 4, 'uvem': 5}      # enum rgda_loss_kind (include/rgda_hip.h)
+# enum rgda_loss_kind (include/rgda_hip.h); 'gdp' is served by upsample_gdp (rgda_upsample_gdp), not by upsample_loss
+LOSS_KINDS = {'ohem': 1, 'focal': 2, 'ghm': 3, 'ups': 4, 'uvem': 5, 'gdp': 6}
 
 
 def upsample_loss(kind, p1, p2, label, soft=None, class_weight=None, acc_sum=None, m=0.2, t=0.7, gamma=4.0,
@@ -424,6 +430,61 @@ def upsample_loss(kind, p1, p2, label, soft=None, class_weight=None, acc_sum=Non
            float(m), float(t), float(gamma), float(thresh), float(momentum), loss.data_ptr(), _p(g1), _p(g2), b, c, h,
            w, H, W, ignore_label, ws.data_ptr(), ws.numel(), _stream())
     return loss, g1, g2
+
+
+def upsample_gdp(p1, p2, label, acc_sum, bins_weight, pixel_weight=None, class_weight=None, momentum=0.99,
+                 ignore_label=-1, want_grad=True, g1=None, g2=None, heads=2):
+    """loss_calc(multi=True) with GDPLoss(bins=30) (rgda_upsample_gdp; balance.py:218-303) -> (loss f32[1], g1, g2).
+    acc_sum: the loss's device state f32[30], updated in place once per head; bins_weight: f32[30], receives the bin
+    weights of the last head call.  pixel_weight: None or f32[b*H*W], the prototype weight of every label pixel
+    (proto_pixel_weight; prototype_refine), shared by both heads; class_weight: None or f32[2, C] (class_balance).
+    heads=1: one call on one prediction (the gradient is then g1 + g2)."""
+    _need_cuda(p1, p2, label, pixel_weight, class_weight, acc_sum, bins_weight)
+    p1, p2, label, cw, loss, g1, g2 = _upsample_operands(p1, p2, label, class_weight, want_grad, g1, g2)
+    b, c, h, w = p1.shape
+    H, W = label.shape[-2:]
+    for t in (acc_sum, bins_weight):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == 30
+    if pixel_weight is not None:
+        assert pixel_weight.dtype == torch.float32 and pixel_weight.is_contiguous() and pixel_weight.numel() == b * H * W
+    if cw is not None:
+        assert cw.shape == (2, c)
+    L = lib()
+    ws = _ws(L.size('rgda_upsample_gdp_workspace', b, c, h, w, H, W), p1.device)
+    if heads == 1:
+        p2 = p1
+    L.call('rgda_upsample_gdp', heads, p1.data_ptr(), p2.data_ptr(), label.data_ptr(), _p(pixel_weight), _p(cw),
+           acc_sum.data_ptr(), bins_weight.data_ptr(), float(momentum), loss.data_ptr(), _p(g1), _p(g2), b, c, h, w, H, W,
+           ignore_label, ws.data_ptr(), ws.numel(), _stream())
+    return loss, g1, g2
+
+
+def proto_pixel_weight(feat, protos, label, sim=None, ignore_label=-1, out=None):
+    """Aligner.get_prototype_weight_4pixel (rgda_proto_pixel_weight; alignment.py:267-281) -> f32 [b*H*W]: the prototype
+    agreement of every label pixel with its own label, 0 where the label is ignored.  feat (b,k,h,w), protos (c,k),
+    label int64 (b,H,W).  sim: the similarity map (b,c,h,w) a label_refine call with the prototype view has already
+    computed (label_refine(..., return_sim=True)): the similarity pass is skipped and feat / protos may be None."""
+    _need_cuda(feat, protos, label, sim)
+    label = label.contiguous()
+    assert label.dtype == torch.int64 and label.dim() == 3
+    b, H, W = label.shape
+    L = lib()
+    if sim is not None:
+        assert sim.dtype == torch.float32 and sim.is_contiguous() and sim.dim() == 4 and sim.shape[0] == b
+        c, (h, w), k = sim.shape[1], sim.shape[-2:], 0
+        ws = None
+    else:
+        feat, protos = feat.contiguous().float(), protos.contiguous().float()
+        k, (h, w), c = feat.shape[1], feat.shape[-2:], protos.shape[0]
+        assert feat.shape[0] == b and protos.shape == (c, k)
+        ws = _ws(L.size('rgda_proto_pixel_weight_workspace', b, c, k, h, w), label.device)
+    if out is None:
+        out = torch.empty(b * H * W, dtype=torch.float32, device=label.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == b * H * W
+    L.call('rgda_proto_pixel_weight', _p(feat if sim is None else None), _p(protos if sim is None else None), _p(sim),
+           label.data_ptr(), out.data_ptr(), b, k, c, h, w, H, W, ignore_label, _p(ws), 0 if ws is None else ws.numel(),
+           _stream())
+    return out
 
 
 def teacher_probs(p1, p2, size):

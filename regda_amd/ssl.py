@@ -23,7 +23,7 @@ class SSLStep:
                  sam_refine=True, refine_label=True, ema_decay=None, max_regions=4096, bucket_elems=12 << 20,
                  process_group=None, overlap_wgrad=True, overlap_comm=True, class_balancer_s=None,
                  class_balancer_t=None, grad_payload='fp32', comm=None, loss_s='CrossEntropy', loss_t='none',
-                 uvem_m=0.2, uvem_t=0.7, uvem_g=4.0):
+                 uvem_m=0.2, uvem_t=0.7, uvem_g=4.0, gdp_prototype=True, gdp_class_balance=False):
         ops.check_class_count(class_num, type(self).__name__)
         self.model = model
         self.C, self.ig = class_num, ignore_label
@@ -63,8 +63,12 @@ class SSLStep:
         # --ls / --lt (+ --uvem-m/-t/-g) of tools/train_ssl_reg.py:52-63,134-158: regda_amd.gast.balance losses whose
         # fused kernels (rgda_upsample_ce / rgda_upsample_loss) the step launches directly
         self.loss_fn_s = source_loss(loss_s, class_balancer_s, ignore_label)
+        # loss_t='gdp': GDPLoss (balance.py:218-303).  gdp_prototype adds the prototype weight of every pseudo-labelled
+        # pixel (Aligner.get_prototype_weight_4pixel on feat_t and the step's final pseudo labels, from the prototypes as
+        # label_refine reads them), gdp_class_balance the class weight (class_balancer_t if given, else the loss's own)
         self.loss_fn_t = target_loss(loss_t, class_balancer_t, uvem_m, uvem_t, uvem_g, class_num, ignore_label,
-                                     device=dev)
+                                     device=dev, gdp_prototype=gdp_prototype, gdp_class_balance=gdp_class_balance)
+        self.last_proto_weight = None
         self._graph = None
         self._plan = None
         self._proto_ready = None
@@ -236,9 +240,13 @@ class SSLStep:
         f = self.loss_fn_s
         return f.launch(s1, s2, label_s, class_weight=self._class_weights(f.class_balancer, label_s), g1=g1, g2=g2)[0]
 
-    def _target_loss(self, t1, t2, hard, soft, g1, g2):
-        """loss_calc / loss_calc_uvem(target, loss_fn_t) on the pseudo labels (ups / uvem also read the refined soft label)."""
+    def _target_loss(self, t1, t2, hard, soft, g1, g2, proto_weight=None):
+        """loss_calc / loss_calc_uvem(target, loss_fn_t) on the pseudo labels (ups / uvem also read the refined soft label,
+        gdp the prototype weights of the pseudo labels)."""
         f = self.loss_fn_t
+        if f.kind == 'gdp':
+            return f.launch(t1, t2, hard, class_weight=self._class_weights(f.class_balancer, hard), g1=g1, g2=g2,
+                            pixel_weight=proto_weight)[0]
         return f.launch(t1, t2, hard, soft=soft if f.kind in ('ups', 'uvem') else None,
                         class_weight=self._class_weights(f.class_balancer, hard), g1=g1, g2=g2)[0]
 
@@ -310,20 +318,32 @@ class SSLStep:
         fuse_lrh = (self.refine_label and self.sam_refine and not self.keep_debug and self.max_regions <= 65535
                     and (soft_t.shape[-1] * soft_t.shape[-2]) % 4 == 0)
         hard = None
+        # GDPLoss(prototype_refine): the prototype weights of the final pseudo labels, from the prototypes as they stand
+        # BEFORE this step's update_prototype.  label_refine's similarity map (the base of its workspace) is exactly that
+        # and is reused; without label_refine the weights read the prototypes themselves, so the source half's prototype
+        # update is released only behind them
+        want_pw = self.loss_fn_t.kind == 'gdp' and self.loss_fn_t.prototype_refine
+        sim = None
         if self.refine_label:
-            soft, cm = ops.label_refine(feat_t, self.prototypes, t1, t2, soft_t, self.temp, return_ws=True)
+            soft, cm, *sim = ops.label_refine(feat_t, self.prototypes, t1, t2, soft_t, self.temp, return_ws=True,
+                                              return_sim=want_pw)
+            sim = sim[0] if sim else None
             if not fuse_lrh:
                 hard = ops.pseudo_select(soft, self.top, self.low, self.ig, classmax_ws=cm, check=False)
         else:
             soft = soft_t
             hard = ops.pseudo_select(soft_t, self.top, self.low, self.ig, check=False)
         exchange_protos = self.reducer.active
-        if side is not None:
-            # update_prototype rewrites the prototypes label_refine has just read
+        late_protos = want_pw and sim is None
+
+        def source_prototypes():
+            # update_prototype rewrites the prototypes label_refine (or the prototype weights) has just read
             plan.wait_event(side, plan.record_event(main))
             with ops.use_stream(side):
                 self._proto_local(feat_s, label_s, exchange_protos)
-            source_done = plan.record_event(side)
+            return plan.record_event(side)
+        if side is not None and not late_protos:
+            source_done = source_prototypes()
         if self.keep_debug:
             self.debug = dict(t1=t1, t2=t2, s1=s1, s2=s2, feat_t=feat_t, feat_s=feat_s, soft_in=soft_t, soft=soft,
                               hard_selected=hard)
@@ -338,6 +358,13 @@ class SSLStep:
                     self.lrh_ws = torch.empty(need, dtype=torch.uint8, device=m.device)
                 hard = ops.lrh(hard, regs.contiguous(), self.percent, self.C, self.ig, self.max_regions, check=False,
                                ws=self.lrh_ws)
+        proto_weight = None
+        if want_pw:
+            proto_weight = ops.proto_pixel_weight(None if sim is not None else feat_t, self.prototypes, hard, sim=sim,
+                                                  ignore_label=self.ig)
+        self.last_proto_weight = proto_weight
+        if side is not None and late_protos:
+            source_done = source_prototypes()
         if side is None:
             self._proto_local(feat_s, label_s, exchange_protos)
         if exchange_protos:
@@ -360,7 +387,7 @@ class SSLStep:
         # ---- losses + d(loss)/d(logits)
         if side is None:
             loss_s = self._source_loss(s1, s2, label_s, g1[:nb], g2[:nb])
-        loss_t = self._target_loss(t1, t2, hard, soft, g1[nb:], g2[nb:])
+        loss_t = self._target_loss(t1, t2, hard, soft, g1[nb:], g2[nb:], proto_weight)
         if side is not None:
             plan.wait_event(main, source_done)       # source loss, its logit gradients, the new prototypes
         self._mark('label path + losses done')

@@ -1,7 +1,9 @@
-"""dev: the fused --ls / --lt losses (rgda_upsample_loss) against the CE call (rgda_upsample_ce) at 8 x 6 x 32 x 32 ->
-512 x 512 (HIP-event time per loss_calc call, with gradients; algorithmic bytes), and the step time of
-SSLStep(loss_t='uvem' / 'ohem') against the default, as bench.py builds it (ResNet-101, 8 + 8 images, recorded plan).
-    python scripts/dev/loss_bench.py [--no-step]"""
+"""dev: the fused --ls / --lt losses (rgda_upsample_loss; GDPLoss: rgda_upsample_gdp, plain and with the prototype and
+class weights) against the CE call (rgda_upsample_ce) at 8 x 6 x 32 x 32 -> 512 x 512 (HIP-event time per loss_calc
+call, with gradients; algorithmic bytes), rgda_proto_pixel_weight with and without a precomputed similarity map, and
+the step time of SSLStep(loss_t='uvem' / 'ohem' / 'ghm' / 'gdp') against the default, as bench.py builds it (ResNet-101,
+8 + 8 images, recorded plan; --eager: eager steps).
+    python scripts/dev/loss_bench.py [--no-step] [--eager] [--only ghm,gdp]"""
 import os
 import sys
 
@@ -41,7 +43,15 @@ def loss_calls():
     # the stat pass and read by the gradient pass, low-res logits and gradients (2 heads)
     low = 2 * 2 * b * c * h * h * 4
     passes = {'ce': 1, 'focal': 1}
-    scratch = {'ohem': 2 * npix * 4, 'ghm': 2 * npix, 'ups': npix * 4, 'uvem': npix * 4}
+    scratch = {'ohem': 2 * npix * 4, 'ghm': 2 * npix, 'gdp': 2 * npix, 'ups': npix * 4, 'uvem': npix * 4}
+    bw = torch.zeros(30, device='cuda')
+    acc_gdp = torch.zeros(30, device='cuda')
+    pw = torch.rand(npix, generator=g).cuda()
+    cw = torch.rand(2, c, generator=g).cuda()
+    feat = torch.randn(b, 2048, h, h, generator=g).cuda()
+    protos = torch.randn(c, 2048, generator=g).cuda()
+    _, _, sim = ops.label_refine(feat, protos, p1, p2, soft, 2.0, return_ws=True, return_sim=True)
+    pw_out = torch.empty(npix, device='cuda')
     runs = [('ce', lambda: ops.upsample_ce(p1, p2, lab, -1, None, True, g1, g2))]
     kw = dict(thresh=0.35667494, momentum=0.99, g1=g1, g2=g2)
     runs += [('ohem', lambda: ops.upsample_loss('ohem', p1, p2, lab, **kw)),
@@ -49,14 +59,25 @@ def loss_calls():
              ('focal', lambda: ops.upsample_loss('focal', p1, p2, lab, gamma=2.0, **kw)),
              ('ghm', lambda: ops.upsample_loss('ghm', p1, p2, lab, acc_sum=acc, **kw)),
              ('ups', lambda: ops.upsample_loss('ups', p1, p2, lab, soft=soft, t=0.7, **kw)),
-             ('uvem', lambda: ops.upsample_loss('uvem', p1, p2, lab, soft=soft, m=0.2, t=0.7, gamma=4.0, **kw))]
+             ('uvem', lambda: ops.upsample_loss('uvem', p1, p2, lab, soft=soft, m=0.2, t=0.7, gamma=4.0, **kw)),
+             ('gdp', lambda: ops.upsample_gdp(p1, p2, lab, acc_gdp, bw, g1=g1, g2=g2)),
+             ('gdp +pw+cw', lambda: ops.upsample_gdp(p1, p2, lab, acc_gdp, bw, pixel_weight=pw, class_weight=cw, g1=g1,
+                                                     g2=g2))]
+    only = sys.argv[sys.argv.index('--only') + 1].split(',') if '--only' in sys.argv else None
+    if only:
+        runs = [r for r in runs if r[0] == 'ce' or r[0].split()[0] in only]
     t_ce = None
     for name, fn in runs:
         t = t_of(fn)
         t_ce = t if t_ce is None else t_ce
         k = name.split()[0]
         nbytes = passes.get(k, 2) * npix * 8 + 2 * scratch.get(k, 0) + low + (c * npix * 4 if k in ('ups', 'uvem') else 0)
+        nbytes += 2 * npix * 4 if name == 'gdp +pw+cw' else 0         # the prototype weights, read once per head
         print('%-11s %7.1f us  %.2fx CE   %6.1f MB algorithmic' % (name, t, t / t_ce, nbytes / 1e6), flush=True)
+    if only is None or 'gdp' in only:
+        for name, fn in (('proto_pixel_weight', lambda: ops.proto_pixel_weight(feat, protos, lab, out=pw_out)),
+                         ('proto_pixel_weight sim=', lambda: ops.proto_pixel_weight(None, None, lab, sim=sim, out=pw_out))):
+            print('%-24s %7.1f us' % (name, t_of(fn)), flush=True)
 
 
 def step_times():
@@ -65,7 +86,9 @@ def step_times():
     from regda_amd.synthetic import make_batch
     batch = make_batch(b=8, size=512, seed=2333, with_soft=True)
     protos = torch.randn(6, 2048, generator=torch.Generator().manual_seed(0))
-    for lt in ('none', 'uvem', 'ohem'):
+    eager = '--eager' in sys.argv
+    only = sys.argv[sys.argv.index('--only') + 1].split(',') if '--only' in sys.argv else ('none', 'uvem', 'ohem', 'ghm', 'gdp')
+    for lt in [k for k in ('none', 'uvem', 'ohem', 'ghm', 'gdp') if k in only]:
         torch.manual_seed(2333)
         model = Deeplabv2(dict(backbone=dict(resnet_type='resnet101', output_stride=16, pretrained=False),
                                multi_layer=True, cascade=False, use_ppm=True,
@@ -76,9 +99,10 @@ def step_times():
         args = (batch['images_s'], batch['label_s'], batch['images_t'], batch['soft_t'], batch['regs_t'])
         for _ in range(2):
             st.step(*args, 1e-3)
-        st.record_plan(*args)
+        if not eager:
+            st.record_plan(*args)
         t = t_of(lambda: st.step(*args, 1e-3), reps=10) / 1e3
-        print('SSLStep(loss_t=%r): %.2f ms per step (recorded plan)' % (lt, t), flush=True)
+        print('SSLStep(loss_t=%r): %.2f ms per step (%s)' % (lt, t, 'eager' if eager else 'recorded plan'), flush=True)
         del st, model
         torch.cuda.empty_cache()
 
