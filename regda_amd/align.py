@@ -136,25 +136,25 @@ class AlignStep(SSLStep):
         loss_seg = self._source_loss(s1, s2, label_s, g1[:nb], g2[:nb])
         n, k, h, w = feat.shape
         gfeat = torch.empty(n * h * w, k, dtype=BF, device=m.device)
+        # per domain: features, full-size and downscaled labels, head-2 logits, its gradient rows.  Every term adds onto
+        # the rows in the order PCL, domain, whitening, contrast, triplet (bf16 accumulation depends on it)
+        sides = ((feat_s, label_s, label_s_down, s2, gfeat[:nb * h * w]), (feat_t, label_t, label_t, t2, gfeat[nb * h * w:]))
         self.loss_align.zero_()
-        ops.pcl_loss(feat_s, label_s_down, self.prototypes, self.pcl_temp, self.ig, 0.5, loss=self.loss_align,
-                     dfeat=gfeat[:nb * h * w])
-        ops.pcl_loss(feat_t, label_t, self.prototypes, self.pcl_temp, self.ig, 0.5, loss=self.loss_align,
-                     dfeat=gfeat[nb * h * w:])
+        for f, _, lab, _, rows in sides:
+            ops.pcl_loss(f, lab, self.prototypes, self.pcl_temp, self.ig, 0.5, loss=self.loss_align, dfeat=rows)
         if self.align_domain:
             self.loss_domain.zero_()
             domain_loss(self.domain_kind, self.mmd, feat_s, feat_t, self.domain_weight, loss=self.loss_domain,
-                        dfeat_s=gfeat[:nb * h * w], dfeat_t=gfeat[nb * h * w:], accumulate=True)
+                        dfeat_s=sides[0][4], dfeat_t=sides[1][4], accumulate=True)
         if self.whiten_weight > 0.0:
             self.loss_white.zero_()
-            for f, lab, rows in ((feat_s, label_s_down, gfeat[:nb * h * w]), (feat_t, label_t, gfeat[nb * h * w:])):
+            for f, _, lab, _, rows in sides:
                 ops.whiten_loss(f, lab, self.C, 32, self.ig, 0.5 * self.whiten_weight, loss=self.loss_white, dfeat=rows,
                                 accumulate=True)
         if self.contrast_weight > 0.0:
             self.loss_contrast.zero_()
             pc = self.contrast
-            sides = ((feat_s, label_s, s2, gfeat[:nb * h * w]), (feat_t, label_t, t2, gfeat[nb * h * w:]))
-            for side, (f, lab, logits, rows) in enumerate(sides):
+            for side, (f, lab, _, logits, rows) in enumerate(sides):
                 lab = lab.reshape(lab.shape[0], *lab.shape[-2:])
                 order, counts, anchors, ranks, _ = select_and_plan(lab, logits.float(), self.C, (h, w), self.ig,
                                                                    pc['max_samples'], pc['max_views'], None)
@@ -165,8 +165,7 @@ class AlignStep(SSLStep):
                                         0.5 * self.contrast_weight, loss=self.loss_contrast, dfeat=rows, accumulate=True)
         if self.triplet_weight > 0.0:
             self.loss_triplet.zero_()
-            sides = ((feat_s, label_s_down, gfeat[:nb * h * w]), (feat_t, label_t, gfeat[nb * h * w:]))
-            for side, (f, lab, rows) in enumerate(sides):
+            for side, (f, _, lab, _, rows) in enumerate(sides):
                 _, stats, ws = ops.triplet_loss(f, lab, self.triplet['margin'], self.ig, 0.5 * self.triplet_weight,
                                                 loss=self.loss_triplet, dfeat=rows, accumulate=True, return_ws=True)
                 self.last_triplet[side] = dict(ops.triplet_tables(ws, rows.shape[0]), stats=stats)

@@ -11,12 +11,12 @@
 //   gram   : one wavefront per (upper 128 x 128 tile, K split): the raw accumulators -> part   pc_gram_kernel
 //   reduce : G = (sum of the splits, in order) / temperature, fp32, to both triangles         pc_reduce_kernel
 //   row    : one wavefront per row: m, neg, sum over positives of lp and of 1 / d, P          pc_row_kernel
-//   loss   : loss[0] += weight * -(T / Tb) / N * sum_r rowloss_r, in order                    pc_loss_kernel
+//   loss   : loss[0] += weight * -(T / Tb) / N * sum_r rowloss_r, in order                    rows_loss_sum
 //   pair   : M = bf16(W + W^T) [NP][NP], the padding zero                                     pc_pair_kernel
 //   grad   : C[c][r] = sum_q X^T[c][q] M[r][q] (the shape of mmd_grad_kernel);
 //            dfeat[pixel of r][c] (+)= weight / T * C[c][r]                                   pc_grad_kernel
-#include "common.h"
-#include "gram_tile.h"
+// The feature view, the staging tile, the loss sum and the gradient store are those of feat_rows.h.
+#include "feat_rows.h"
 
 namespace {
 
@@ -25,8 +25,6 @@ constexpr int PC_MAX_HW = 16384;             // keys of one image sit in LDS as 
 constexpr int PC_MAX_ROWS = 4096;
 constexpr int PC_MAX_SPLIT = 8;
 constexpr int PC_SPLIT_JOBS = 256;           // K is split until the tile jobs reach about one per CU
-
-size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct PcPlan {
     int N, np, T, U, S, kchunk;
@@ -57,13 +55,6 @@ PcPlan make_plan(int N, int k) {
     p.off_m = o;    o += a256((size_t)p.np * p.np * 2);
     p.bytes = o;
     return p;
-}
-
-__device__ __forceinline__ float block_sum4(float s, float* red) {
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 }  // namespace
@@ -163,29 +154,10 @@ __global__ void __launch_bounds__(256) pc_rows_kernel(const int32_t* __restrict_
 
 // 64 rows x 64 channels per workgroup: bf16(feat) to the channel-major image and, through LDS, to the pixel-major one;
 // the padding rows are written as zeros
-__global__ void __launch_bounds__(256) pc_gather_kernel(const float* __restrict__ feat, long long ldc, long long ldb, int hw,
-                                                        const int* __restrict__ rowpix, int N, int np, int k,
+__global__ void __launch_bounds__(256) pc_gather_kernel(FeatView f, const int* __restrict__ rowpix, int N, int np, int k,
                                                         bf16_t* __restrict__ xt, bf16_t* __restrict__ xp) {
-    __shared__ bf16_t tile[64][66];
-    const int r0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const int r = r0 + tx;
-    const int g = rowpix[r];
-    const int img = g / hw, pix = g - img * hw;
-    const float* src = feat + (size_t)img * ldb + pix;
-    for (int cc = ty; cc < 64; cc += 4) {
-        const int c = c0 + cc;
-        if (c < k) {
-            const bf16_t v = r < N ? f2bf(src[(size_t)c * ldc]) : (bf16_t)0;
-            xt[(size_t)c * np + r] = v;
-            tile[tx][cc] = v;
-        }
-    }
-    __syncthreads();
-    for (int rr = ty; rr < 64; rr += 4) {
-        const int c = c0 + tx;
-        if (c < k) xp[(size_t)(r0 + rr) * k + c] = tile[rr][tx];
-    }
+    const int r0 = blockIdx.x * 64;
+    stage_tile64(f, [=](int r) { return r0 + r < N ? rowpix[r0 + r] : -1; }, 64, nullptr, blockIdx.y * 64, k, xt, np, r0, xp);
 }
 
 // job = (upper tile u, split s), one wavefront each: the accumulators of X[I] X[J]^T over the split's channels go to
@@ -274,14 +246,6 @@ __global__ void __launch_bounds__(256) pc_row_kernel(const float* __restrict__ G
     }
 }
 
-__global__ void __launch_bounds__(256) pc_loss_kernel(const float* __restrict__ rowloss, int N, float* loss, float scale) {
-    __shared__ float red[4];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < N; i += 256) s += rowloss[i];
-    s = block_sum4(s, red);
-    if (threadIdx.x == 0) loss[0] += scale * s;
-}
-
 // W_rq = d L / d l_rq: c_r (1 - e / (e + neg_r + eps)) for a positive q, -c_r e s1_r for a negative q, 0 on the
 // diagonal, e = exp(G_rq - m_r).  M_rq = bf16(W_rq + W_qr) (G is stored symmetric, so W_qr is read from the same G_rq).
 static __device__ __forceinline__ float pc_w(float g, bool pos, float m, float neg, float s1, float c, float eps) {
@@ -337,31 +301,9 @@ __global__ void __launch_bounds__(256, 1) pc_grad_kernel(const bf16_t* __restric
 #pragma unroll
         for (int j = 0; j < 2; ++j) acc[i][j] = f32x16{};
     tile_nt<2>(xt, np, mt * CT, k - 1, M, np, nt * GN, N - 1, 0, np, acc);
-    const int lane = threadIdx.x & 63, h = lane >> 5;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int r = nt * GN + 32 * j + (lane & 31);
-        bf16_t* orow = out + (size_t)rowpix[min(r, N - 1)] * ld;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int c = mt * CT + 32 * i + 8 * q + 4 * h;
-                if (r < N && c < k) {
-                    float v0 = scale * acc[i][j][4 * q], v1 = scale * acc[i][j][4 * q + 1];
-                    float v2 = scale * acc[i][j][4 * q + 2], v3 = scale * acc[i][j][4 * q + 3];
-                    uint2* dst = (uint2*)(orow + c);
-                    if (accumulate) {
-                        const uint2 o = *dst;
-                        v0 += __uint_as_float(o.x << 16);
-                        v1 += __uint_as_float(o.x & 0xffff0000u);
-                        v2 += __uint_as_float(o.y << 16);
-                        v3 += __uint_as_float(o.y & 0xffff0000u);
-                    }
-                    *dst = uint2{pack2bf(v0, v1), pack2bf(v2, v3)};
-                }
-            }
-    }
+    // selected row r scatters to its pixel's gradient row; every column takes scale * acc
+    grad_tile_store(acc, mt, nt, N, k, accumulate, [=](int r) { return out + (size_t)rowpix[r] * ld; },
+                    [=](int) { return [=](F4 a, int) { return F4{scale * a.v0, scale * a.v1, scale * a.v2, scale * a.v3}; }; });
 }
 
 extern "C" int rgda_pixel_contrast_select(const int64_t* labels, const void* predict, int predict_kind, int b, int C, int H,
@@ -390,8 +332,8 @@ extern "C" int rgda_pixel_contrast_loss(const float* feat, int b, int hw, int64_
     if (!feat || !order || !counts || !anchors || !ranks || !loss || !ws || ((uintptr_t)ws & 255)) return RGDA_ERR_ARG;
     if (b <= 0 || hw <= 0 || k < 32 || (k & 31) || A < 0 || n_view < 0) return RGDA_ERR_ARG;
     if (!(temperature > 0.f) || !(base_temperature > 0.f) || !(eps >= 0.f)) return RGDA_ERR_ARG;
-    if ((long long)b * hw > (1ll << 24) || ldc < hw || (b > 1 && ldb < ldc * k)) return RGDA_ERR_ARG;
-    if (dfeat && (lddf < k || (lddf & 7) || ((uintptr_t)dfeat & 15))) return RGDA_ERR_ARG;
+    if ((long long)b * hw > (1ll << 24) || !feat_view_ok(b, hw, ldc, ldb, k)) return RGDA_ERR_ARG;
+    if (!grad_rows_ok(dfeat, lddf, k, 16)) return RGDA_ERR_ARG;
     if (C < 2 || C > PC_MAX_CLASSES) return RGDA_ERR_UNSUPPORTED;
     const long long Nl = (long long)A * n_view;
     if (Nl < 1 || Nl > PC_MAX_ROWS) return RGDA_ERR_UNSUPPORTED;
@@ -411,7 +353,7 @@ extern "C" int rgda_pixel_contrast_loss(const float* feat, int b, int hw, int64_
     const int np = p.np;
     pc_rows_kernel<<<cdiv(np, 256), 256, 0, st>>>(order, counts, anchors, ranks, A, n_view, b, hw, C, N, np, rowpix, rowcls);
     RGDA_CHECK_LAUNCH();
-    pc_gather_kernel<<<dim3(np / 64, cdiv(k, 64)), 256, 0, st>>>(feat, (long long)ldc, (long long)ldb, hw, rowpix, N, np, k, xt, xp);
+    pc_gather_kernel<<<dim3(np / 64, cdiv(k, 64)), 256, 0, st>>>(FeatView{feat, (long long)ldc, (long long)ldb, hw, b * hw}, rowpix, N, np, k, xt, xp);
     RGDA_CHECK_LAUNCH();
     pc_gram_kernel<<<cdiv(p.U * p.S, 4), 256, 0, st>>>(xp, np, k, p.T, p.S, p.kchunk, p.U * p.S, part);
     RGDA_CHECK_LAUNCH();
@@ -420,8 +362,7 @@ extern "C" int rgda_pixel_contrast_loss(const float* feat, int b, int hw, int64_
     const float cscale = -(temperature / base_temperature) / (float)N;
     pc_row_kernel<<<np / 4, 256, 0, st>>>(G, rowcls, N, np, eps, cscale, stat);
     RGDA_CHECK_LAUNCH();
-    pc_loss_kernel<<<1, 256, 0, st>>>(stat + (size_t)4 * np, N, loss, weight * cscale);
-    RGDA_CHECK_LAUNCH();
+    if (rows_loss_sum(stat + (size_t)4 * np, N, loss, weight * cscale, st) != RGDA_OK) return RGDA_ERR_LAUNCH;
     if (!dfeat) return RGDA_OK;
     pc_pair_kernel<<<dim3(cdiv(np / 2, 256), np), 256, 0, st>>>(G, rowcls, stat, N, np, eps, M);
     RGDA_CHECK_LAUNCH();

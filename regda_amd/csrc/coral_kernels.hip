@@ -8,19 +8,18 @@
 //            one wavefront per job, split-K partials to the workspace                 coral_cov_kernel
 //   reduce : D = sum(source partials) / (ns - 1) - sum(target partials) / (nt - 1) in a fixed order; bf16(D) to both
 //            triangles; per-band sum of D^2                                           coral_reduce_kernel
-//   loss   : loss[0] += weight * sum(D^2) / (4 d^2), one thread, fixed order            coral_loss_kernel
+//   loss   : loss[0] += weight * sum(D^2) / (4 d^2), one thread, fixed order            rows_loss_sum
 //   grad   : dX^T = D . Xc^T  ->  dfeat = (+/-) weight / (d^2 (n - 1)) * dX (+ dfeat)      coral_grad_kernel
 //
 // Both products are C[m][n] = sum_k P[m][k] Q[n][k] with P and Q row-major bf16 and K contiguous: the tile routine of
-// gram_tile.h (a 128 x 128 tile per wavefront, fragments loaded straight from global memory, no LDS).
-#include "common.h"
-#include "gram_tile.h"
+// gram_tile.h (a 128 x 128 tile per wavefront, fragments loaded straight from global memory, no LDS).  The feature view,
+// the staging tile, the sums and the gradient store are those of feat_rows.h.
+#include "feat_rows.h"
 
 namespace {
 
 constexpr int TILE_FLOATS = CT * CT;
 
-size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
 int round32(int x) { return (x + 31) & ~31; }
 
 // split-K of the covariance product: a few jobs per domain and upper tile so that about 1024 wavefronts (one per
@@ -59,62 +58,28 @@ CoralPlan make_plan(int ns, int nt, int d) {
     return p;
 }
 
-struct Feat {
-    const float* x;
-    long long ldc, ldb;          // channel and image strides (elements); pixels of one image are contiguous
-    int hw, n;
-};
-
 }  // namespace
 
 // one workgroup per (channel, domain): fp32 sum over the n rows, thread-strided then a fixed tree
-__global__ void __launch_bounds__(256) coral_mean_kernel(Feat fs, Feat ft, float* __restrict__ mean, int d) {
+__global__ void __launch_bounds__(256) coral_mean_kernel(FeatView fs, FeatView ft, float* __restrict__ mean, int d) {
     __shared__ float red[4];
     const int c = blockIdx.x;
-    const Feat f = blockIdx.y ? ft : fs;
-    const float* xc = f.x + (size_t)c * f.ldc;
-    float s = 0.f;
-    for (int g = threadIdx.x; g < f.n; g += 256) {
-        const int b = g / f.hw, p = g - b * f.hw;
-        s += xc[(size_t)b * f.ldb + p];
-    }
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) mean[blockIdx.y * d + c] = ((red[0] + red[1]) + (red[2] + red[3])) / (float)f.n;
+    const FeatView f = blockIdx.y ? ft : fs;
+    const float s = block_sum4(feat_channel_partial(f, c), red);
+    if (threadIdx.x == 0) mean[blockIdx.y * d + c] = s / (float)f.n;
 }
 
 // 64 channels x 64 rows per workgroup: bf16(x - mu) to the channel-major image (coalesced along the rows) and,
 // through LDS, to the pixel-major image (coalesced along the channels; skipped when xs == nullptr)
-__global__ void __launch_bounds__(256) coral_center_kernel(Feat fs, Feat ft, const float* __restrict__ mean,
+__global__ void __launch_bounds__(256) coral_center_kernel(FeatView fs, FeatView ft, const float* __restrict__ mean,
                                                            bf16_t* cts, bf16_t* ctt, int ldcs, int ldct,
                                                            bf16_t* xs, bf16_t* xt, int d) {
-    __shared__ bf16_t tile[64][66];
     const bool tgt = blockIdx.z != 0;
-    const Feat f = tgt ? ft : fs;
-    const int g0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
+    const FeatView f = tgt ? ft : fs;
+    const int g0 = blockIdx.x * 64;
     if (g0 >= f.n) return;
-    bf16_t* ct = tgt ? ctt : cts;
-    const int ldct_ = tgt ? ldct : ldcs;
-    bf16_t* xp = tgt ? xt : xs;
-    const float* mu = mean + (tgt ? d : 0);
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const int g = g0 + tx;
-    const int b = g / f.hw, p = g - b * f.hw;
-    for (int cc = ty; cc < 64; cc += 4) {
-        const int c = c0 + cc;
-        if (c < d && g < f.n) {
-            const bf16_t v = f2bf(f.x[(size_t)b * f.ldb + (size_t)c * f.ldc + p] - mu[c]);
-            ct[(size_t)c * ldct_ + g] = v;
-            tile[tx][cc] = v;
-        }
-    }
-    if (!xp) return;
-    __syncthreads();
-    for (int gg = ty; gg < 64; gg += 4) {
-        const int c = c0 + tx;
-        if (g0 + gg < f.n && c < d) xp[(size_t)(g0 + gg) * d + c] = tile[gg][tx];
-    }
+    stage_tile64(f, [g0](int r) { return g0 + r; }, f.n - g0, mean + (tgt ? d : 0), blockIdx.y * 64, d, tgt ? ctt : cts,
+                 tgt ? ldct : ldcs, g0, tgt ? xt : xs);
 }
 
 // job = u * (Ss + St) + q: upper tile u, K chunk q (q < Ss: source, else target).  Partials in the accumulator's own
@@ -188,20 +153,8 @@ __global__ void __launch_bounds__(256) coral_reduce_kernel(const float* __restri
         }
         sq *= 2.f;
     }
-    sq = wave_sum(sq);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sq;
-    __syncthreads();
-    if (threadIdx.x == 0) lpart[u * 4 + band] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-__global__ void __launch_bounds__(256) coral_loss_kernel(const float* __restrict__ lpart, int nparts, float* loss, float scale) {
-    __shared__ float red[4];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < nparts; i += 256) s += lpart[i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) loss[0] += scale * ((red[0] + red[1]) + (red[2] + red[3]));
+    sq = block_sum4(sq, red);
+    if (threadIdx.x == 0) lpart[u * 4 + band] = sq;
 }
 
 // job < js: source, else target.  C[c'][p] = sum_c D[c'][c] Xc[p][c] = dX[p][c']: a lane's registers 4g .. 4g+3 are
@@ -227,31 +180,11 @@ __global__ void __launch_bounds__(256, 1) coral_grad_kernel(const bf16_t* __rest
 #pragma unroll
         for (int j = 0; j < 2; ++j) acc[i][j] = f32x16{};
     tile_nt<2>(dbf, d, mt * CT, d - 1, g.x, d, nt * GN, g.n - 1, 0, d, acc);
-    const int lane = threadIdx.x & 63, h = lane >> 5;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int p = nt * GN + 32 * j + (lane & 31);
-        bf16_t* orow = g.out + (size_t)min(p, g.n - 1) * g.ld;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int c = mt * CT + 32 * i + 8 * q + 4 * h;
-                float v0 = acc[i][j][4 * q] * g.scale, v1 = acc[i][j][4 * q + 1] * g.scale;
-                float v2 = acc[i][j][4 * q + 2] * g.scale, v3 = acc[i][j][4 * q + 3] * g.scale;
-                if (p < g.n && c < d) {
-                    uint2* dst = (uint2*)(orow + c);
-                    if (accumulate) {
-                        const uint2 o = *dst;
-                        v0 += __uint_as_float(o.x << 16);
-                        v1 += __uint_as_float(o.x & 0xffff0000u);
-                        v2 += __uint_as_float(o.y << 16);
-                        v3 += __uint_as_float(o.y & 0xffff0000u);
-                    }
-                    *dst = uint2{pack2bf(v0, v1), pack2bf(v2, v3)};
-                }
-            }
-    }
+    // row p of this side's gradient; every column takes acc * scale
+    grad_tile_store(acc, mt, nt, g.n, d, accumulate, [=](int p) { return g.out + (size_t)p * g.ld; },
+                    [=](int) {
+                        return [=](F4 a, int) { return F4{a.v0 * g.scale, a.v1 * g.scale, a.v2 * g.scale, a.v3 * g.scale}; };
+                    });
 }
 
 extern "C" size_t rgda_coral_loss_workspace(int ns, int nt, int d) {
@@ -267,9 +200,8 @@ extern "C" int rgda_coral_loss(const float* feat_s, int bs, int hws, int64_t ldc
     if (bs <= 0 || bt <= 0 || hws <= 0 || hwt <= 0 || d < 32 || (d & 31)) return RGDA_ERR_ARG;
     const long long ns = (long long)bs * hws, nt = (long long)bt * hwt;
     if (ns < 2 || nt < 2 || ns > (1 << 30) || nt > (1 << 30)) return RGDA_ERR_ARG;
-    if (ldcs < hws || ldct < hwt || (bs > 1 && ldbs < ldcs * d) || (bt > 1 && ldbt < ldct * d)) return RGDA_ERR_ARG;
-    if (dfeat_s && (ldds < d || (ldds & 7) || ((uintptr_t)dfeat_s & 7))) return RGDA_ERR_ARG;
-    if (dfeat_t && (lddt < d || (lddt & 7) || ((uintptr_t)dfeat_t & 7))) return RGDA_ERR_ARG;
+    if (!feat_view_ok(bs, hws, ldcs, ldbs, d) || !feat_view_ok(bt, hwt, ldct, ldbt, d)) return RGDA_ERR_ARG;
+    if (!grad_rows_ok(dfeat_s, ldds, d, 8) || !grad_rows_ok(dfeat_t, lddt, d, 8)) return RGDA_ERR_ARG;
     const CoralPlan p = make_plan((int)ns, (int)nt, d);
     if (ws_bytes < p.bytes) return RGDA_ERR_WORKSPACE;
     hipStream_t st = to_stream(stream);
@@ -286,8 +218,8 @@ extern "C" int rgda_coral_loss(const float* feat_s, int bs, int hws, int64_t ldc
     // the K padding of the channel-major images must be zero (it enters the covariance sums)
     if (p.nsp != ns && zero_bytes(cts, (size_t)d * p.nsp * 2, stream) != RGDA_OK) return RGDA_ERR_LAUNCH;
     if (p.ntp != nt && zero_bytes(ctt, (size_t)d * p.ntp * 2, stream) != RGDA_OK) return RGDA_ERR_LAUNCH;
-    const Feat fs{feat_s, (long long)ldcs, (long long)ldbs, hws, (int)ns};
-    const Feat ft{feat_t, (long long)ldct, (long long)ldbt, hwt, (int)nt};
+    const FeatView fs{feat_s, (long long)ldcs, (long long)ldbs, hws, (int)ns};
+    const FeatView ft{feat_t, (long long)ldct, (long long)ldbt, hwt, (int)nt};
     coral_mean_kernel<<<dim3(d, 2), 256, 0, st>>>(fs, ft, mean, d);
     RGDA_CHECK_LAUNCH();
     coral_center_kernel<<<dim3(cdiv(ns > nt ? ns : nt, 64), cdiv(d, 64), 2), 256, 0, st>>>(fs, ft, mean, cts, ctt, p.nsp,
@@ -299,8 +231,7 @@ extern "C" int rgda_coral_loss(const float* feat_s, int bs, int hws, int64_t ldc
     coral_reduce_kernel<<<dim3(p.U, 4), 256, 0, st>>>(part, p.Ss, p.St, p.T, d, 1.f / (float)(ns - 1), 1.f / (float)(nt - 1),
                                                       dbf, lpart);
     RGDA_CHECK_LAUNCH();
-    coral_loss_kernel<<<1, 256, 0, st>>>(lpart, p.U * 4, loss, weight / (4.f * (float)d * (float)d));
-    RGDA_CHECK_LAUNCH();
+    if (rows_loss_sum(lpart, p.U * 4, loss, weight / (4.f * (float)d * (float)d), st) != RGDA_OK) return RGDA_ERR_LAUNCH;
     if (!grad) return RGDA_OK;
     const float dd = (float)d * (float)d;
     const int T = p.T;

@@ -5,7 +5,7 @@
 //   centre : Xc = bf16(total - mu), once, in two layouts: pixel-major [n_pad][d] (the Gram product sums over channels)
 //            and channel-major [d][n_pad] (the gradient product sums over pixels); n_pad = n rounded up to 128, the
 //            padding zero                                                               mmd_center_kernel
-//   norms  : r_i = sum_c Xc[i][c]^2 (fp32, of the rounded row); csum[c] = sum_i Xc[i][c]     mmd_rownorm_kernel, mmd_colsum_kernel
+//   norms  : r_i = sum_c Xc[i][c]^2 (fp32, of the rounded row); csum[c] = sum_i Xc[i][c]     rows_sumsq, mmd_colsum_kernel
 //   bw     : bw = fix_sigma, or (2 n sum r_i - 2 |csum|^2) / (n^2 - n) = the mean pairwise squared distance; / kernel_mul^(kernel_num / 2);
 //            1 / bw_q = 1 / (bw kernel_mul^q) to the workspace -- on the device, no read-back          mmd_bandwidth_kernel
 //   pairs  : one wavefront per upper 128 x 128 tile of the n x n matrix, K = d: g = Xc Xc^T, l2 = max(r_i + r_j - 2 g, 0)
@@ -13,23 +13,21 @@
 //            0 (padding); the tile's sum of s kappa (twice off the diagonal) -> lpart; W = bf16(s sum_q exp(-l2 / bw_q) / bw_q)
 //            (0 on the diagonal) to both triangles of W [n_pad][n_pad]; the row sums (and, off the diagonal, the column
 //            sums) of the rounded W per tile -> rp[other tile index][row]                  mmd_pair_kernel
-//   reduce : rho_i = sum over the tile columns of rp, in order; loss[0] += weight * sum(lpart), in order     mmd_rho_kernel, mmd_loss_kernel
+//   reduce : rho_i = sum over the tile columns of rp, in order; loss[0] += weight * sum(lpart), in order     mmd_rho_kernel, rows_loss_sum
 //   grad   : C[c][p] = sum_j Xc^T[c][j] W[p][j] (the shape of coral_grad_kernel);
 //            dfeat[p][c] (+)= -4 weight (rho_p Xc[p][c] - C[c][p])                           mmd_grad_kernel
 //   linear : L = |mean_s - mean_t|^2 / d; rows 2 (mean_s - mean_t) / (d ns), -2 (...) / (d nt)   mmd_linear_loss_kernel, mmd_linear_grad_kernel
 //
 // d L / d x_i = sum_j 2 s_ij kappa'(l2_ij) 2 (x_i - x_j) with kappa' = -sum_q exp(-l2 / bw_q) / bw_q (the bandwidth is a
 // constant of the backward, as in the reference: it is taken from `.data`), which is the -4 (rho_i x_i - sum_j W_ij x_j)
-// above; distances do not see the shift by mu.
-#include "common.h"
-#include "gram_tile.h"
+// above; distances do not see the shift by mu.  The feature view, the staging tile, the sums and the gradient store are
+// those of feat_rows.h.
+#include "feat_rows.h"
 
 namespace {
 
 constexpr int MAX_KERNELS = 8;
 constexpr int MAX_ROWS = 32768;  // W is n_pad^2 bf16: 2 GB at the limit
-
-size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct MmdPlan {
     int d, ns, nt, n, np, T, U;
@@ -57,48 +55,17 @@ MmdPlan make_plan(int ns, int nt, int d) {
     return p;
 }
 
-struct MmdFeat {
-    const float* x;
-    long long ldc, ldb;          // channel and image strides (elements); pixels of one image are contiguous
-    int hw, n;
-};
-
-// one side of the gradient: rows row0 .. row0 + n of `total` go to out[0 .. n)
-struct MmdSide {
-    bf16_t* out;
-    int row0, n, ld;
-};
-
-__device__ __forceinline__ float block_sum4(float s, float* red) {
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 }  // namespace
 
 // one workgroup per channel: fp32 sums over the source rows and over the target rows, thread-strided then a fixed tree;
 // mean[c] = mean_s, mean[d + c] = mean_t, mean[2d + c] = mu
-__global__ void __launch_bounds__(256) mmd_mean_kernel(MmdFeat fs, MmdFeat ft, float* __restrict__ mean, int d) {
+__global__ void __launch_bounds__(256) mmd_mean_kernel(FeatView fs, FeatView ft, float* __restrict__ mean, int d) {
     __shared__ float red[2][4];
     const int c = blockIdx.x;
-#pragma unroll
-    for (int side = 0; side < 2; ++side) {
-        const MmdFeat f = side ? ft : fs;
-        const float* xc = f.x + (size_t)c * f.ldc;
-        float s = 0.f;
-        for (int g = threadIdx.x; g < f.n; g += 256) {
-            const int b = g / f.hw, p = g - b * f.hw;
-            s += xc[(size_t)b * f.ldb + p];
-        }
-        s = wave_sum(s);
-        if ((threadIdx.x & 63) == 0) red[side][threadIdx.x >> 6] = s;
-    }
-    __syncthreads();
+    float ss = feat_channel_partial(fs, c), st = feat_channel_partial(ft, c);
+    ss = block_sum4(ss, red[0]);
+    st = block_sum4(st, red[1]);
     if (threadIdx.x == 0) {
-        const float ss = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-        const float st = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
         mean[c] = ss / (float)fs.n;
         mean[d + c] = st / (float)ft.n;
         mean[2 * d + c] = (ss + st) / (float)(fs.n + ft.n);
@@ -107,50 +74,13 @@ __global__ void __launch_bounds__(256) mmd_mean_kernel(MmdFeat fs, MmdFeat ft, f
 
 // 64 channels x 64 rows of one domain per workgroup: bf16(x - mu) to the channel-major image (coalesced along the
 // rows) and, through LDS, to the pixel-major image (coalesced along the channels)
-__global__ void __launch_bounds__(256) mmd_center_kernel(MmdFeat fs, MmdFeat ft, const float* __restrict__ mu,
+__global__ void __launch_bounds__(256) mmd_center_kernel(FeatView fs, FeatView ft, const float* __restrict__ mu,
                                                          bf16_t* __restrict__ xt, bf16_t* __restrict__ xp, int np, int d) {
-    __shared__ bf16_t tile[64][66];
     const bool tgt = blockIdx.z != 0;
-    const MmdFeat f = tgt ? ft : fs;
-    const int g0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
+    const FeatView f = tgt ? ft : fs;
+    const int g0 = blockIdx.x * 64;
     if (g0 >= f.n) return;
-    const int row0 = tgt ? fs.n : 0;
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const int g = g0 + tx;
-    const int b = g / f.hw, p = g - b * f.hw;
-    for (int cc = ty; cc < 64; cc += 4) {
-        const int c = c0 + cc;
-        if (c < d && g < f.n) {
-            const bf16_t v = f2bf(f.x[(size_t)b * f.ldb + (size_t)c * f.ldc + p] - mu[c]);
-            xt[(size_t)c * np + row0 + g] = v;
-            tile[tx][cc] = v;
-        }
-    }
-    __syncthreads();
-    for (int gg = ty; gg < 64; gg += 4) {
-        const int c = c0 + tx;
-        if (g0 + gg < f.n && c < d) xp[(size_t)(row0 + g0 + gg) * d + c] = tile[gg][tx];
-    }
-}
-
-// one wavefront per row of the pixel-major image (the padding rows too: they give 0): r_i, lane-strided then a fixed tree
-__global__ void __launch_bounds__(256) mmd_rownorm_kernel(const bf16_t* __restrict__ xp, float* __restrict__ r, int np, int d) {
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (i >= np) return;
-    const bf16_t* row = xp + (size_t)i * d;
-    float s = 0.f;
-    for (int c = lane * 8; c < d; c += 512) {
-        const uint4 v = *(const uint4*)(row + c);
-        const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float lo = __uint_as_float(w[e] << 16), hi = __uint_as_float(w[e] & 0xffff0000u);
-            s += lo * lo;
-            s += hi * hi;
-        }
-    }
-    s = wave_sum(s);
-    if (lane == 0) r[i] = s;
+    stage_tile64(f, [g0](int r) { return g0 + r; }, f.n - g0, mu, blockIdx.y * 64, d, xt, np, (tgt ? fs.n : 0) + g0, xp);
 }
 
 // one workgroup per channel: csum[c] = sum over the rows of the channel-major image (the padding is zero)
@@ -309,23 +239,15 @@ __global__ void __launch_bounds__(256) mmd_rho_kernel(const float* __restrict__ 
     rho[i] = s;
 }
 
-__global__ void __launch_bounds__(256) mmd_loss_kernel(const float* __restrict__ lpart, int nparts, float* loss, float scale) {
-    __shared__ float red[4];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < nparts; i += 256) s += lpart[i];
-    s = block_sum4(s, red);
-    if (threadIdx.x == 0) loss[0] += scale * s;
-}
-
 // job < js: source, else target.  C[c][p] = sum_j Xc^T[c][j] W[p][j]: a lane's registers 4g .. 4g+3 are four consecutive
 // channels of one pixel -> one 8-byte store into the pixel-major bf16 gradient rows
 __global__ void __launch_bounds__(256, 1) mmd_grad_kernel(const bf16_t* __restrict__ xt, const bf16_t* __restrict__ xp,
-                                                          const bf16_t* __restrict__ W, const float* __restrict__ rho, MmdSide gs,
-                                                          MmdSide gt, int js, int njobs, int d, int np, float scale, int accumulate) {
+                                                          const bf16_t* __restrict__ W, const float* __restrict__ rho, GradRows gs,
+                                                          GradRows gt, int js, int njobs, int d, int np, float scale, int accumulate) {
     const int job = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (job >= njobs) return;
     const bool tgt = job >= js;
-    const MmdSide g = tgt ? gt : gs;
+    const GradRows g = tgt ? gt : gs;
     const int jj = tgt ? job - js : job;
     const int T = (d + CT - 1) / CT;
     const int mt = jj % T, nt = jj / T;
@@ -335,37 +257,19 @@ __global__ void __launch_bounds__(256, 1) mmd_grad_kernel(const bf16_t* __restri
 #pragma unroll
         for (int j = 0; j < 2; ++j) acc[i][j] = f32x16{};
     tile_nt<2>(xt, np, mt * CT, d - 1, W, np, g.row0 + nt * GN, g.row0 + g.n - 1, 0, np, acc);
-    const int lane = threadIdx.x & 63, h = lane >> 5;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int p = nt * GN + 32 * j + (lane & 31);
-        const int pc = min(p, g.n - 1);
-        bf16_t* orow = g.out + (size_t)pc * g.ld;
-        const bf16_t* xrow = xp + (size_t)(g.row0 + pc) * d;
-        const float rh = rho[g.row0 + pc];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int c = mt * CT + 32 * i + 8 * q + 4 * h;
-                if (p < g.n && c < d) {
-                    const uint2 x = *(const uint2*)(xrow + c);
-                    float v0 = scale * (rh * __uint_as_float(x.x << 16) - acc[i][j][4 * q]);
-                    float v1 = scale * (rh * __uint_as_float(x.x & 0xffff0000u) - acc[i][j][4 * q + 1]);
-                    float v2 = scale * (rh * __uint_as_float(x.y << 16) - acc[i][j][4 * q + 2]);
-                    float v3 = scale * (rh * __uint_as_float(x.y & 0xffff0000u) - acc[i][j][4 * q + 3]);
-                    uint2* dst = (uint2*)(orow + c);
-                    if (accumulate) {
-                        const uint2 o = *dst;
-                        v0 += __uint_as_float(o.x << 16);
-                        v1 += __uint_as_float(o.x & 0xffff0000u);
-                        v2 += __uint_as_float(o.y << 16);
-                        v3 += __uint_as_float(o.y & 0xffff0000u);
-                    }
-                    *dst = uint2{pack2bf(v0, v1), pack2bf(v2, v3)};
-                }
-            }
-    }
+    // row p of this side's gradient; a column loads its rho and its row of Xc once, then scale * (rho x - acc) per quad
+    grad_tile_store(acc, mt, nt, g.n, d, accumulate, [=](int p) { return g.out + (size_t)p * g.ld; },
+                    [=](int p) {
+                        const bf16_t* xrow = xp + (size_t)(g.row0 + p) * d;
+                        const float rh = rho[g.row0 + p];
+                        return [=](F4 a, int c) {
+                            const uint2 x = *(const uint2*)(xrow + c);
+                            return F4{scale * (rh * __uint_as_float(x.x << 16) - a.v0),
+                                      scale * (rh * __uint_as_float(x.x & 0xffff0000u) - a.v1),
+                                      scale * (rh * __uint_as_float(x.y << 16) - a.v2),
+                                      scale * (rh * __uint_as_float(x.y & 0xffff0000u) - a.v3)};
+                        };
+                    });
 }
 
 // linear MMD (MMDLoss.forward_linear, mmd.py:41-44): loss[0] += scale * sum_c (mean_s - mean_t)^2, scale = weight / d
@@ -381,9 +285,9 @@ __global__ void __launch_bounds__(256) mmd_linear_loss_kernel(const float* __res
 }
 
 // one thread per (row, four channels); blockIdx.y: 0 source, 1 target.  sc = +/- 2 weight / (d n_side)
-__global__ void __launch_bounds__(256) mmd_linear_grad_kernel(const float* __restrict__ mean, MmdSide gs, MmdSide gt, int d,
+__global__ void __launch_bounds__(256) mmd_linear_grad_kernel(const float* __restrict__ mean, GradRows gs, GradRows gt, int d,
                                                               float scs, float sct, int accumulate) {
-    const MmdSide g = blockIdx.y ? gt : gs;
+    const GradRows g = blockIdx.y ? gt : gs;
     if (!g.out) return;
     const float sc = blockIdx.y ? sct : scs;
     const int q = d >> 2;
@@ -393,15 +297,7 @@ __global__ void __launch_bounds__(256) mmd_linear_grad_kernel(const float* __res
     float v[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) v[k] = sc * (mean[c + k] - mean[d + c + k]);
-    uint2* dst = (uint2*)(g.out + (size_t)row * g.ld + c);
-    if (accumulate) {
-        const uint2 o = *dst;
-        v[0] += __uint_as_float(o.x << 16);
-        v[1] += __uint_as_float(o.x & 0xffff0000u);
-        v[2] += __uint_as_float(o.y << 16);
-        v[3] += __uint_as_float(o.y & 0xffff0000u);
-    }
-    *dst = uint2{pack2bf(v[0], v[1]), pack2bf(v[2], v[3])};
+    store4_bf16(g.out + (size_t)row * g.ld + c, v[0], v[1], v[2], v[3], accumulate);
 }
 
 extern "C" size_t rgda_mmd_loss_workspace(int ns, int nt, int d) {
@@ -421,19 +317,18 @@ extern "C" int rgda_mmd_loss(const float* feat_s, int bs, int hws, int64_t ldcs,
     const long long ns = (long long)bs * hws, nt = (long long)bt * hwt;
     if (ns < 2 || nt < 2) return RGDA_ERR_ARG;
     if (ns + nt > MAX_ROWS) return RGDA_ERR_UNSUPPORTED;
-    if (ldcs < hws || ldct < hwt || (bs > 1 && ldbs < ldcs * d) || (bt > 1 && ldbt < ldct * d)) return RGDA_ERR_ARG;
-    if (dfeat_s && (ldds < d || (ldds & 7) || ((uintptr_t)dfeat_s & 7))) return RGDA_ERR_ARG;
-    if (dfeat_t && (lddt < d || (lddt & 7) || ((uintptr_t)dfeat_t & 7))) return RGDA_ERR_ARG;
+    if (!feat_view_ok(bs, hws, ldcs, ldbs, d) || !feat_view_ok(bt, hwt, ldct, ldbt, d)) return RGDA_ERR_ARG;
+    if (!grad_rows_ok(dfeat_s, ldds, d, 8) || !grad_rows_ok(dfeat_t, lddt, d, 8)) return RGDA_ERR_ARG;
     const MmdPlan p = make_plan((int)ns, (int)nt, d);
     // the linear form uses the means only: the first region of the plan
     if (ws_bytes < (kernel_type == RGDA_MMD_LINEAR ? p.off_xp : p.bytes)) return RGDA_ERR_WORKSPACE;
     hipStream_t st = to_stream(stream);
     char* w = (char*)ws;
     float* mean = (float*)(w + p.off_mean);
-    const MmdFeat fs{feat_s, (long long)ldcs, (long long)ldbs, hws, (int)ns};
-    const MmdFeat ft{feat_t, (long long)ldct, (long long)ldbt, hwt, (int)nt};
-    const MmdSide gs{(bf16_t*)dfeat_s, 0, (int)ns, ldds};
-    const MmdSide gt{(bf16_t*)dfeat_t, (int)ns, (int)nt, lddt};
+    const FeatView fs{feat_s, (long long)ldcs, (long long)ldbs, hws, (int)ns};
+    const FeatView ft{feat_t, (long long)ldct, (long long)ldbt, hwt, (int)nt};
+    const GradRows gs{(bf16_t*)dfeat_s, 0, (int)ns, ldds};
+    const GradRows gt{(bf16_t*)dfeat_t, (int)ns, (int)nt, lddt};
     const bool grad = dfeat_s || dfeat_t;
     mmd_mean_kernel<<<d, 256, 0, st>>>(fs, ft, mean, d);
     RGDA_CHECK_LAUNCH();
@@ -464,8 +359,7 @@ extern "C" int rgda_mmd_loss(const float* feat_s, int bs, int hws, int64_t ldcs,
     }
     mmd_center_kernel<<<dim3(cdiv(ns > nt ? ns : nt, 64), cdiv(d, 64), 2), 256, 0, st>>>(fs, ft, mean + 2 * d, xt, xp, np, d);
     RGDA_CHECK_LAUNCH();
-    mmd_rownorm_kernel<<<np / 4, 256, 0, st>>>(xp, r, np, d);
-    RGDA_CHECK_LAUNCH();
+    if (rows_sumsq(xp, np, d, r, st) != RGDA_OK) return RGDA_ERR_LAUNCH;
     mmd_colsum_kernel<<<d, 256, 0, st>>>(xt, csum, np);
     RGDA_CHECK_LAUNCH();
     const double pairs = (double)n * (double)n - (double)n;
@@ -477,8 +371,7 @@ extern "C" int rgda_mmd_loss(const float* feat_s, int bs, int hws, int64_t ldcs,
     mmd_pair_kernel<<<cdiv(p.U, 4), 256, 0, st>>>(xp, r, bwv, kernel_num, (int)ns, n, np, d, p.T, p.U, 1.f / (float)ns,
                                                   -1.f / (float)nt, W, rp, lpart);
     RGDA_CHECK_LAUNCH();
-    mmd_loss_kernel<<<1, 256, 0, st>>>(lpart, p.U, loss, weight);
-    RGDA_CHECK_LAUNCH();
+    if (rows_loss_sum(lpart, p.U, loss, weight, st) != RGDA_OK) return RGDA_ERR_LAUNCH;
     if (!grad) return RGDA_OK;
     mmd_rho_kernel<<<cdiv(np, 256), 256, 0, st>>>(rp, rho, np, p.T);
     RGDA_CHECK_LAUNCH();

@@ -4,7 +4,7 @@
 //
 //   stage  : Xf = the f32 rows, pixel-major [NP][k]; Xh = bf16(Xf); lab = int32 labels, TP_NONE for ignored rows and the
 //            padding; NP = n rounded up to 128, the padding zero                               tp_stage_kernel
-//   sq     : s_i = sum_c Xh_ic^2, one wavefront per row                                       tp_sq_kernel
+//   sq     : s_i = sum_c Xh_ic^2, one wavefront per row                                       rows_sumsq
 //   mine   : one wavefront per 128 x 128 tile (I, J) of ALL T x T tiles: G = Xh[I] Xh[J]^T in registers; a lane holds one
 //            column (an anchor of J) and 64 rows (candidates of I), so the search over the candidates runs in registers
 //            and ends with ONE exchange between the two half-waves: (max, argmax | same label), (min, argmin | other
@@ -14,8 +14,9 @@
 //   loss   : m, the number of active hinges, loss[0] += weight * sum hinge / m, one workgroup  tp_loss_kernel
 //   grad   : one workgroup per row r: the anchors that selected r are found by scanning the target tables (ballots into
 //            an LDS bit mask) and added in ascending anchor order                              tp_grad_kernel
-#include "common.h"
-#include "gram_tile.h"
+// The feature view and the row norms are those of feat_rows.h; the stage tile here is f32 with two pixel-major outputs
+// and the labels, so it stays its own.
+#include "feat_rows.h"
 
 namespace {
 
@@ -23,8 +24,6 @@ constexpr int TP_MAX_ROWS = 16384;
 constexpr int TP_NONE = (int)0x80000000;     // staged label of a row that takes no part
 constexpr float TP_CLAMP = 1e-12f;
 constexpr int TP_LIST = 1024;                // anchors per target row listed in LDS (more: the mask is walked instead)
-
-size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct TpPlan {
     int n, np, T;
@@ -83,8 +82,7 @@ __device__ __forceinline__ Pick wave_pick(Pick a) {
 
 // 64 rows x 64 channels per workgroup: the strided feature rows -> Xf (f32) and Xh (bf16), pixel-major, through LDS;
 // the padding rows as zeros.  The workgroups of the first channel block also stage the labels.
-__global__ void __launch_bounds__(256) tp_stage_kernel(const float* __restrict__ feat, long long ldc, long long ldb, int hw,
-                                                       const int64_t* __restrict__ labels, int has_ignore, int ignore_label,
+__global__ void __launch_bounds__(256) tp_stage_kernel(FeatView f, const int64_t* __restrict__ labels, int has_ignore, int ignore_label,
                                                        int n, int np, int k, float* __restrict__ xf, bf16_t* __restrict__ xh,
                                                        int* __restrict__ lab) {
     __shared__ float tile[64][65];
@@ -100,11 +98,9 @@ __global__ void __launch_bounds__(256) tp_stage_kernel(const float* __restrict__
         lab[r] = l;
     }
     const int rc = min(r, n - 1);
-    const int img = rc / hw, pix = rc - img * hw;
-    const float* src = feat + (size_t)img * ldb + pix;
     for (int cc = ty; cc < 64; cc += 4) {
         const int c = c0 + cc;
-        if (c < k) tile[tx][cc] = r < n ? src[(size_t)c * ldc] : 0.f;
+        if (c < k) tile[tx][cc] = r < n ? feat_at(f, rc, c) : 0.f;
     }
     __syncthreads();
     const int c = c0 + tx;
@@ -114,26 +110,6 @@ __global__ void __launch_bounds__(256) tp_stage_kernel(const float* __restrict__
             xf[(size_t)(r0 + rr) * k + c] = v;
             xh[(size_t)(r0 + rr) * k + c] = f2bf(v);
         }
-}
-
-// s_r = sum of squares of the bf16 row: lane l sums the elements 8 l + 512 t + e (e < 8) in order, then the butterfly
-__global__ void __launch_bounds__(256) tp_sq_kernel(const bf16_t* __restrict__ xh, int np, int k, float* __restrict__ s) {
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (r >= np) return;
-    const bf16_t* row = xh + (size_t)r * k;
-    float acc = 0.f;
-    for (int c = 8 * lane; c < k; c += 512) {
-        const uint4 v = *(const uint4*)(row + c);
-        const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float lo = __uint_as_float(w[e] << 16), hi = __uint_as_float(w[e] & 0xffff0000u);
-            acc += lo * lo;
-            acc += hi * hi;
-        }
-    }
-    acc = wave_sum(acc);
-    if (lane == 0) s[r] = acc;
 }
 
 // job = I * T + J, one wavefront each.  Candidates are the 128 rows of tile I (the P operand), anchors the 128 rows of
@@ -388,8 +364,7 @@ extern "C" int rgda_triplet_loss(const float* feat, int b, int hw, int64_t ldc, 
                                  int accumulate, float weight, void* ws, size_t ws_bytes, rgda_stream_t stream) {
     if (!feat || !labels || !loss || !ws || ((uintptr_t)ws & 255)) return RGDA_ERR_ARG;
     if (b <= 0 || hw <= 0 || k < 32 || (k & 31) || !(margin >= 0.f)) return RGDA_ERR_ARG;
-    if (ldc < hw || (b > 1 && ldb < ldc * k)) return RGDA_ERR_ARG;
-    if (dfeat && (lddf < k || (lddf & 7) || ((uintptr_t)dfeat & 15))) return RGDA_ERR_ARG;
+    if (!feat_view_ok(b, hw, ldc, ldb, k) || !grad_rows_ok(dfeat, lddf, k, 16)) return RGDA_ERR_ARG;
     const long long nl = (long long)b * hw;
     if (nl < 2) return RGDA_ERR_ARG;
     if (nl > TP_MAX_ROWS) return RGDA_ERR_UNSUPPORTED;
@@ -416,11 +391,10 @@ extern "C" int rgda_triplet_loss(const float* feat, int b, int hw, int64_t ldc, 
     bf16_t* xh = (bf16_t*)(wsp + p.off_xh);
     float* xf = (float*)(wsp + p.off_xf);
     const int np = p.np, T = p.T;
-    tp_stage_kernel<<<dim3(np / 64, cdiv(k, 64)), 256, 0, st>>>(feat, (long long)ldc, (long long)ldb, hw, labels, has_ignore,
-                                                                ignore_label, n, np, k, xf, xh, lab);
+    tp_stage_kernel<<<dim3(np / 64, cdiv(k, 64)), 256, 0, st>>>(FeatView{feat, (long long)ldc, (long long)ldb, hw, n}, labels,
+                                                                has_ignore, ignore_label, n, np, k, xf, xh, lab);
     RGDA_CHECK_LAUNCH();
-    tp_sq_kernel<<<np / 4, 256, 0, st>>>(xh, np, k, s);
-    RGDA_CHECK_LAUNCH();
+    if (rows_sumsq(xh, np, k, s, st) != RGDA_OK) return RGDA_ERR_LAUNCH;
     tp_mine_kernel<<<cdiv((long long)T * T, 4), 256, 0, st>>>(xh, s, lab, np, k, T, pmaxv, pmaxi, pminv, pmini);
     RGDA_CHECK_LAUNCH();
     tp_final_kernel<<<np / 4, 256, 0, st>>>(xf, lab, pmaxv, pmaxi, pminv, pmini, np, k, T, margin, P, N, TP, TN, DP, DN, H);

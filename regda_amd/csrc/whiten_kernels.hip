@@ -15,22 +15,21 @@
 //            wavefronts in 32-row groups, the four partials added in wavefront order through LDS;
 //            D = S / (n_c - 1) - I in fp32; bf16(D) to the workspace; mean(D^2) -> lpart[class][group]
 //            (n_c <= 1: 0)                                                             whiten_cov_kernel
-//   loss   : loss[0] += weight * sum(lpart), fixed order                                whiten_loss_kernel
+//   loss   : loss[0] += weight * sum(lpart), fixed order                                rows_loss_sum
 //   zero   : accumulate == 0 only: the rows of ignored pixels and of classes with n_c <= 1 := 0   whiten_zero_kernel
 //   grad   : per (64-row tile, group): dX^T = bf16(D) . Xc^T -> dfeat[pixel][group block]
 //            = 4 weight / (s^2 (n_c - 1)) * dX (+ dfeat), rows scattered back through sidx  whiten_grad_kernel
 //
 // Both products are C[m][n] = sum_k P[m][k] Q[n][k] with P and Q row-major bf16 and K contiguous (the layout of
 // coral_kernels.hip): v_mfma_f32_32x32x16_bf16 fragments are plain 16-byte loads from global memory, lane half h and
-// element j of k-step t take k = 16h + 8t + j in both operands.
-#include "common.h"
+// element j of k-step t take k = 16h + 8t + j in both operands.  The feature view, the staging tile, the sums and the
+// gradient store are those of feat_rows.h.
+#include "feat_rows.h"
 
 namespace {
 
 constexpr int RT = 64;           // rows per tile of the sorted order: every class starts on a tile boundary
 // workspace header (256 bytes of int32): flag | cnt[16] | off[17]
-
-size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct WhitenPlan {
     int n, k, C, G, s, NP;
@@ -54,12 +53,6 @@ WhitenPlan make_plan(int n, int k, int C, int G) {
     p.bytes = o;
     return p;
 }
-
-struct Feat {
-    const float* x;
-    long long ldc, ldb;          // channel and image strides (elements); pixels of one image are contiguous
-    int hw, n;
-};
 
 }  // namespace
 
@@ -134,24 +127,17 @@ __global__ void __launch_bounds__(1024) whiten_index_kernel(const int64_t* __res
 }
 
 // one workgroup per channel: for every class the fp32 sum over its pixels (sorted order), thread-strided then a fixed tree
-__global__ void __launch_bounds__(256) whiten_mean_kernel(Feat f, const int* __restrict__ hdr, const int* __restrict__ sidx,
+__global__ void __launch_bounds__(256) whiten_mean_kernel(FeatView f, const int* __restrict__ hdr, const int* __restrict__ sidx,
                                                           float* __restrict__ mean, int k, int C) {
     __shared__ float red[4];
     const int ch = blockIdx.x;
-    const float* xc = f.x + (size_t)ch * f.ldc;
     for (int c = 0; c < C; ++c) {
         const int nc = hdr[1 + c], o = hdr[17 + c];
         if (nc <= 1) continue;
         float s = 0.f;
-        for (int j = threadIdx.x; j < nc; j += 256) {
-            const int g = sidx[o + j];
-            const int b = g / f.hw, p = g - b * f.hw;
-            s += xc[(size_t)b * f.ldb + p];
-        }
-        s = wave_sum(s);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-        __syncthreads();
-        if (threadIdx.x == 0) mean[(size_t)c * k + ch] = ((red[0] + red[1]) + (red[2] + red[3])) / (float)nc;
+        for (int j = threadIdx.x; j < nc; j += 256) s += feat_at(f, sidx[o + j], ch);
+        s = block_sum4(s, red);
+        if (threadIdx.x == 0) mean[(size_t)c * k + ch] = s / (float)nc;
         __syncthreads();
     }
 }
@@ -159,31 +145,13 @@ __global__ void __launch_bounds__(256) whiten_mean_kernel(Feat f, const int* __r
 // 64 channels x one 64-row tile per workgroup: bf16(x - mu[class]) (0 for the pad rows) to the channel-major image and,
 // through LDS, to the pixel-major image (skipped when xp == nullptr).  Tiles of no class or of a class with n_c <= 1
 // are not written: nobody reads them.
-__global__ void __launch_bounds__(256) whiten_center_kernel(Feat f, const int* __restrict__ hdr, const int* __restrict__ sidx,
+__global__ void __launch_bounds__(256) whiten_center_kernel(FeatView f, const int* __restrict__ hdr, const int* __restrict__ sidx,
                                                             const int* __restrict__ tcls, const float* __restrict__ mean,
                                                             bf16_t* __restrict__ ct, bf16_t* __restrict__ xp, int k, int NP) {
-    __shared__ bf16_t tile[64][66];
     const int cls = tcls[blockIdx.x];
     if (cls < 0 || hdr[1 + cls] <= 1) return;
-    const int j0 = blockIdx.x * RT, c0 = blockIdx.y * 64;
-    const float* mu = mean + (size_t)cls * k;
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const int g = sidx[j0 + tx];
-    const int b = g >= 0 ? g / f.hw : 0, p = g >= 0 ? g - b * f.hw : 0;
-    for (int cc = ty; cc < 64; cc += 4) {
-        const int c = c0 + cc;
-        if (c < k) {
-            const bf16_t v = g >= 0 ? f2bf(f.x[(size_t)b * f.ldb + (size_t)c * f.ldc + p] - mu[c]) : (bf16_t)0;
-            ct[(size_t)c * NP + j0 + tx] = v;
-            tile[tx][cc] = v;
-        }
-    }
-    if (!xp) return;
-    __syncthreads();
-    for (int gg = ty; gg < 64; gg += 4) {
-        const int c = c0 + tx;
-        if (c < k) xp[(size_t)(j0 + gg) * k + c] = tile[gg][tx];
-    }
+    const int j0 = blockIdx.x * RT;
+    stage_tile64(f, [=](int r) { return sidx[j0 + r]; }, RT, mean + (size_t)cls * k, blockIdx.y * 64, k, ct, NP, j0, xp);
 }
 
 // workgroup (group g, class c): S = Xc[class rows][group block]^T Xc[...], NT = s / 32 blocks of 32 channels a side
@@ -264,16 +232,6 @@ __global__ void __launch_bounds__(256) whiten_cov_kernel(const bf16_t* __restric
     if (lane == 0) lpart[c * G + g] = sq / (float)(s * s);
 }
 
-__global__ void __launch_bounds__(256) whiten_loss_kernel(const float* __restrict__ lpart, int nparts, float* loss, float scale) {
-    __shared__ float red[4];
-    float s = 0.f;
-    for (int i = threadIdx.x; i < nparts; i += 256) s += lpart[i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) loss[0] += scale * ((red[0] + red[1]) + (red[2] + red[3]));
-}
-
 // one wavefront per pixel: rows that the gradient product does not write (ignored label, class with n_c <= 1) := 0
 __global__ void __launch_bounds__(256) whiten_zero_kernel(const int64_t* __restrict__ labels, const int* __restrict__ hdr, int n,
                                                           int C, int ignore_label, bf16_t* __restrict__ dfeat, int lddf, int k) {
@@ -342,15 +300,7 @@ __global__ void __launch_bounds__(256) whiten_grad_kernel(const bf16_t* __restri
                 const int c = 32 * i + 8 * q + 4 * h;
                 float v0 = acc[i][j][4 * q] * scale, v1 = acc[i][j][4 * q + 1] * scale;
                 float v2 = acc[i][j][4 * q + 2] * scale, v3 = acc[i][j][4 * q + 3] * scale;
-                uint2* dst = (uint2*)(orow + c);
-                if (accumulate) {
-                    const uint2 o = *dst;
-                    v0 += __uint_as_float(o.x << 16);
-                    v1 += __uint_as_float(o.x & 0xffff0000u);
-                    v2 += __uint_as_float(o.y << 16);
-                    v3 += __uint_as_float(o.y & 0xffff0000u);
-                }
-                *dst = uint2{pack2bf(v0, v1), pack2bf(v2, v3)};
+                store4_bf16(orow + c, v0, v1, v2, v3, accumulate);
             }
     }
 }
@@ -367,8 +317,7 @@ extern "C" int rgda_whiten_loss(const float* feat, int b, int hw, int64_t ldc, i
     if (b <= 0 || hw <= 0 || k <= 0 || groups <= 0 || k % groups) return RGDA_ERR_ARG;
     const long long nn = (long long)b * hw;
     if (nn > (1 << 24)) return RGDA_ERR_ARG;
-    if (ldc < hw || (b > 1 && ldb < ldc * k)) return RGDA_ERR_ARG;
-    if (dfeat && (lddf < k || (lddf & 7) || ((uintptr_t)dfeat & 15))) return RGDA_ERR_ARG;
+    if (!feat_view_ok(b, hw, ldc, ldb, k) || !grad_rows_ok(dfeat, lddf, k, 16)) return RGDA_ERR_ARG;
     if ((uintptr_t)ws & 255) return RGDA_ERR_ARG;          // the 16-byte fragment loads of ct, xp and dmat start at 256-byte offsets
     if (!class_count_ok(C)) return RGDA_ERR_UNSUPPORTED;
     if (!block_ok(k / groups)) return RGDA_ERR_UNSUPPORTED;
@@ -385,7 +334,7 @@ extern "C" int rgda_whiten_loss(const float* feat, int b, int hw, int64_t ldc, i
     bf16_t* xp = dfeat ? (bf16_t*)(w + p.off_xp) : nullptr;
     bf16_t* dmat = (bf16_t*)(w + p.off_dmat);
     float* lpart = (float*)(w + p.off_lpart);
-    const Feat f{feat, (long long)ldc, (long long)ldb, hw, n};
+    const FeatView f{feat, (long long)ldc, (long long)ldb, hw, n};
     const int G = groups, NT = p.s / 32, tiles = p.NP / RT;
     whiten_index_kernel<<<1, 1024, 0, st>>>(labels, n, C, ignore_label, p.NP, hdr, sidx, tcls);
     RGDA_CHECK_LAUNCH();
@@ -401,8 +350,7 @@ extern "C" int rgda_whiten_loss(const float* feat, int b, int hw, int64_t ldc, i
         default: whiten_cov_kernel<4><<<cg, 256, 0, st>>>(ct, p.NP, hdr, G, dmat, lpart); break;
     }
     RGDA_CHECK_LAUNCH();
-    whiten_loss_kernel<<<1, 256, 0, st>>>(lpart, C * G, loss, weight);
-    RGDA_CHECK_LAUNCH();
+    if (rows_loss_sum(lpart, C * G, loss, weight, st) != RGDA_OK) return RGDA_ERR_LAUNCH;
     if (!dfeat) return RGDA_OK;
     bf16_t* df = (bf16_t*)dfeat;
     if (!accumulate) {

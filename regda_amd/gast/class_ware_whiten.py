@@ -7,25 +7,7 @@ fused steps hand to the instance-norm backward)."""
 import torch
 
 from .. import ops
-
-
-class _Whiten(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, feats, labels, class_num, groups, ignore_label):
-        b, k, h, w = feats.shape
-        g = torch.empty(b * h * w, k, dtype=torch.bfloat16, device=feats.device) if ctx.needs_input_grad[0] else None
-        loss = ops.whiten_loss(feats.detach(), labels, class_num, groups, ignore_label, 1.0, dfeat=g)
-        ctx.save_for_backward(g)
-        ctx.shape = feats.shape
-        return loss.view(())
-
-    @staticmethod
-    def backward(ctx, gout):
-        g, = ctx.saved_tensors
-        if g is None:
-            return None, None, None, None, None
-        b, k, h, w = ctx.shape
-        return gout * g.float().view(b, h, w, k).permute(0, 3, 1, 2), None, None, None, None
+from ._rowsgrad import rows_loss
 
 
 class ClassWareWhitening(torch.nn.Module):
@@ -57,4 +39,5 @@ class ClassWareWhitening(torch.nn.Module):
         if s not in ops.WHITEN_BLOCKS:
             raise NotImplementedError(f'ClassWareWhitening: {s} channels per group (k = {feats.shape[1]}, groups = '
                                       f'{self.groups}); served are {ops.WHITEN_BLOCKS} channels per group')
-        return _Whiten.apply(feats, labels.long(), C, self.groups, self.ignore_label)
+        labels = labels.long()
+        return rows_loss(lambda x, g: ops.whiten_loss(x, labels, C, self.groups, self.ignore_label, 1.0, dfeat=g), feats)

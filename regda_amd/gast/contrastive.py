@@ -14,7 +14,7 @@ prediction differs from it.  Features are not normalised, as in the reference.""
 import torch
 
 from .. import ops
-from .coral import _as_input
+from ._rowsgrad import rows_loss
 
 
 def plan_anchors(counts, max_samples=1024, max_views=100, generator=None):
@@ -66,23 +66,6 @@ def select_and_plan(labels, predict, class_num, size, ignore_label, max_samples,
     return order, counts, anchors.to(labels.device), ranks.to(labels.device), flag
 
 
-class _PixelContrast(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, feats, order, counts, anchors, ranks, temperature, base_temperature, eps):
-        b, k, h, w = feats.shape
-        g = torch.empty(b * h * w, k, dtype=torch.bfloat16, device=feats.device) if ctx.needs_input_grad[0] else None
-        loss = ops.pixel_contrast_loss(feats.detach(), order, counts, anchors, ranks, temperature, base_temperature, eps,
-                                       dfeat=g)
-        ctx.save_for_backward(g)
-        ctx.shape = feats.shape
-        return loss.view(())
-
-    @staticmethod
-    def backward(ctx, g):
-        (gf,) = ctx.saved_tensors
-        return (None if gf is None else g * _as_input(gf, ctx.shape),) + (None,) * 7
-
-
 class PixelContrastLoss(torch.nn.Module):
     """class_num: the number of classes the labels take (the reference finds them with `unique`; the kernel sorts into
     2 <= class_num <= 16 classes); generator: the CPU generator of the `randperm` draws (None: the global one, as in the
@@ -115,4 +98,5 @@ class PixelContrastLoss(torch.nn.Module):
         if anchors is None:
             raise ValueError(f'PixelContrastLoss: no class of any image has more than max_views = {self.max_views} '
                              f'labelled pixels, so there is no anchor to contrast')
-        return _PixelContrast.apply(feats, order, counts, anchors, ranks, self.temperature, self.base_temperature, self.eps)
+        return rows_loss(lambda x, g: ops.pixel_contrast_loss(x, order, counts, anchors, ranks, self.temperature,
+                                                              self.base_temperature, self.eps, dfeat=g), feats)

@@ -9,27 +9,7 @@ forms an (n, n, d) tensor; the kernel works from the Gram product and serves up 
 import torch
 
 from .. import ops
-from .coral import _as_input, _rows
-
-
-class _MMD(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, source, target, kernel_type, kernel_mul, kernel_num, fix_sigma):
-        want = ctx.needs_input_grad
-        gs = torch.empty(_rows(source), dtype=torch.bfloat16, device=source.device) if want[0] else None
-        gt = torch.empty(_rows(target), dtype=torch.bfloat16, device=target.device) if want[1] else None
-        loss = ops.mmd_loss(source.detach(), target.detach(), 1.0, kernel_type, kernel_mul, kernel_num, fix_sigma,
-                            dfeat_s=gs, dfeat_t=gt)
-        ctx.save_for_backward(gs, gt)
-        ctx.shapes = (source.shape, target.shape)
-        return loss.view(())
-
-    @staticmethod
-    def backward(ctx, g):
-        gs, gt = ctx.saved_tensors
-        ss, ts = ctx.shapes
-        return (None if gs is None else g * _as_input(gs, ss), None if gt is None else g * _as_input(gt, ts),
-                None, None, None, None)
+from ._rowsgrad import rows_loss
 
 
 class MMDLoss(torch.nn.Module):
@@ -47,4 +27,5 @@ class MMDLoss(torch.nn.Module):
         """source (ns, d), target (nt, d) -> the scalar MMD (mmd.py:46-58); ns != nt is served.  NCHW (b, d, h, w) maps
         are taken too (their pixels are the rows, without the permuted copy)."""
         assert source.dim() == target.dim() and source.dim() in (2, 4) and source.shape[1] == target.shape[1]
-        return _MMD.apply(source, target, self.kernel_type, self.kernel_mul, self.kernel_num, self.fix_sigma)
+        return rows_loss(lambda s, t, gs, gt: ops.mmd_loss(s, t, 1.0, self.kernel_type, self.kernel_mul, self.kernel_num,
+                                                           self.fix_sigma, dfeat_s=gs, dfeat_t=gt), source, target)

@@ -13,22 +13,7 @@ the reference) removes the rows of that label from the anchors and the candidate
 import torch
 
 from .. import ops
-from .coral import _as_input, _rows
-
-
-class _Triplet(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, inputs, targets, margin, ignore_label):
-        g = torch.empty(_rows(inputs), dtype=torch.bfloat16, device=inputs.device) if ctx.needs_input_grad[0] else None
-        loss, _ = ops.triplet_loss(inputs.detach(), targets, margin, ignore_label, dfeat=g)
-        ctx.save_for_backward(g)
-        ctx.shape = inputs.shape
-        return loss.view(())
-
-    @staticmethod
-    def backward(ctx, g):
-        (gf,) = ctx.saved_tensors
-        return (None if gf is None else g * _as_input(gf, ctx.shape), None, None, None)
+from ._rowsgrad import rows_loss
 
 
 class TripletLoss(torch.nn.Module):
@@ -43,4 +28,4 @@ class TripletLoss(torch.nn.Module):
         """inputs (n, k) rows, targets int64 (n) -> the scalar loss (triple.py:30-55).  An NCHW (b, k, h, w) map is taken
         too (its pixels are the rows, without the permuted copy), with targets of b * h * w elements."""
         assert inputs.dim() in (2, 4)
-        return _Triplet.apply(inputs, targets, self.margin, self.ignore_label)
+        return rows_loss(lambda x, g: ops.triplet_loss(x, targets, self.margin, self.ignore_label, dfeat=g)[0], inputs)

@@ -1289,6 +1289,36 @@ def pcl_flag(ws, class_num, k):
     return int(ws[off:off + 4].view(torch.int32).item())
 
 
+def _feat_rows(x, who):
+    """The rows of a feature loss -> (f32 tensor, b, hw, ld_channel, ld_image, k): an NCHW (b, k, h, w) map, read in
+    place through its channel and image strides when the pixels of an image are contiguous (NCHW, channel slices, batch
+    slices) and copied otherwise (another dtype, channels-last); or (n, k) rows (n images of one pixel)."""
+    if x.dim() == 2:
+        x = x.contiguous().float()
+        n, k = x.shape
+        return x, n, 1, 1, k, k
+    assert x.dim() == 4, f'{who}: NCHW (b, k, h, w) features or (n, k) rows'
+    x = x.float()
+    b, k, h, w = x.shape
+    ldb, ldc = x.stride(0), x.stride(1)
+    if not ((w == 1 or x.stride(3) == 1) and (h == 1 or x.stride(2) == w) and ldc >= h * w and (b == 1 or ldb >= ldc * k)):
+        x = x.contiguous()
+        ldb, ldc = k * h * w, h * w
+    return x, b, h * w, ldc, ldb, k
+
+
+def _grad_rows(g, n):
+    """an optional gradient buffer: bf16 [n, >= k] pixel-major rows -> (pointer, leading dimension)"""
+    if g is None:
+        return 0, 0
+    assert g.dtype == torch.bfloat16 and g.dim() == 2 and g.shape[0] == n and g.stride(1) == 1, (g.dtype, g.shape, n)
+    return g.data_ptr(), g.stride(0)
+
+
+def _loss_out(loss, device):
+    return torch.zeros(1, device=device) if loss is None else loss
+
+
 def pcl_loss(feat, labels, protos, temperature=8.0, ignore_label=-1, weight=1.0, loss=None, dfeat=None, accumulate=False,
              ws=None):
     """PrototypeContrastiveLoss forward (+ gradient w.r.t. feat into `dfeat` bf16 [b*h*w, K] when given).
@@ -1300,27 +1330,15 @@ def pcl_loss(feat, labels, protos, temperature=8.0, ignore_label=-1, weight=1.0,
     labels = labels.contiguous().view(b, h, w)
     assert labels.dtype == torch.int64 and protos.is_contiguous() and protos.dtype == torch.float32
     C = protos.shape[0]
-    if loss is None:
-        loss = torch.zeros(1, device=feat.device)
+    loss = _loss_out(loss, feat.device)
     L = lib()
     if ws is None:
         ws = _ws(L.size('rgda_pcl_loss_workspace', C, K), feat.device)
     assert ws.dtype == torch.uint8 and ws.is_cuda and ws.is_contiguous()
-    L.call('rgda_pcl_loss', feat.data_ptr(), labels.data_ptr(), protos.data_ptr(), loss.data_ptr(), _p(dfeat),
-           _ld(dfeat) if dfeat is not None else 0, int(bool(accumulate)), b, K, C, h, w, ignore_label, float(temperature),
+    L.call('rgda_pcl_loss', feat.data_ptr(), labels.data_ptr(), protos.data_ptr(), loss.data_ptr(),
+           *_grad_rows(dfeat, b * h * w), int(bool(accumulate)), b, K, C, h, w, ignore_label, float(temperature),
            float(weight), ws.data_ptr(), ws.numel(), _stream())
     return loss
-
-
-def _coral_side(x):
-    """-> (tensor, b, hw, ld_channel, ld_image): NCHW (b, d, h, w), or (n, d) rows (b = n images of one pixel)."""
-    x = x.contiguous().float()
-    if x.dim() == 4:
-        b, d, h, w = x.shape
-        return x, b, h * w, h * w, d * h * w, d
-    assert x.dim() == 2, 'coral_loss: NCHW (b, d, h, w) features or (n, d) rows'
-    n, d = x.shape
-    return x, n, 1, 1, d, d
 
 
 def coral_loss(feat_s, feat_t, weight=1.0, loss=None, dfeat_s=None, dfeat_t=None, accumulate=False):
@@ -1329,20 +1347,16 @@ def coral_loss(feat_s, feat_t, weight=1.0, loss=None, dfeat_s=None, dfeat_t=None
     dfeat_s / dfeat_t (optional) bf16 [n, >= d] pixel-major rows: (+)= weight * d CORAL / d feat (rgda_coral_loss).
     Returns the (accumulating) fp32 loss tensor."""
     _need_cuda(feat_s, feat_t, dfeat_s, dfeat_t)
-    xs, bs, hws, lcs, lbs, d = _coral_side(feat_s)
-    xt, bt, hwt, lct, lbt, dt = _coral_side(feat_t)
+    xs, bs, hws, lcs, lbs, d = _feat_rows(feat_s, 'coral_loss')
+    xt, bt, hwt, lct, lbt, dt = _feat_rows(feat_t, 'coral_loss')
     if d != dt:
         raise ValueError(f'coral_loss: feature dimensions differ ({d} vs {dt})')
-    for g, n in ((dfeat_s, bs * hws), (dfeat_t, bt * hwt)):
-        if g is not None:
-            assert g.dtype == torch.bfloat16 and g.dim() == 2 and g.shape[0] == n and g.stride(1) == 1, (g.shape, n)
-    if loss is None:
-        loss = torch.zeros(1, device=xs.device)
+    loss = _loss_out(loss, xs.device)
     L = lib()
     ws = _ws(L.size('rgda_coral_loss_workspace', bs * hws, bt * hwt, d), xs.device)
     L.call('rgda_coral_loss', xs.data_ptr(), bs, hws, lcs, lbs, xt.data_ptr(), bt, hwt, lct, lbt, d, loss.data_ptr(),
-           _p(dfeat_s), _ld(dfeat_s) if dfeat_s is not None else 0, _p(dfeat_t), _ld(dfeat_t) if dfeat_t is not None else 0,
-           int(bool(accumulate)), float(weight), ws.data_ptr(), ws.numel(), _stream())
+           *_grad_rows(dfeat_s, bs * hws), *_grad_rows(dfeat_t, bt * hwt), int(bool(accumulate)), float(weight),
+           ws.data_ptr(), ws.numel(), _stream())
     return loss
 
 
@@ -1359,15 +1373,11 @@ def mmd_loss(feat_s, feat_t, weight=1.0, kernel_type='rbf', kernel_mul=2.0, kern
     if kernel_type not in MMD_KERNEL_TYPES:
         raise ValueError(f"mmd_loss: kernel_type {kernel_type!r}; served are 'rbf' and 'linear'")
     _need_cuda(feat_s, feat_t, dfeat_s, dfeat_t)
-    xs, bs, hws, lcs, lbs, d = _coral_side(feat_s)
-    xt, bt, hwt, lct, lbt, dt = _coral_side(feat_t)
+    xs, bs, hws, lcs, lbs, d = _feat_rows(feat_s, 'mmd_loss')
+    xt, bt, hwt, lct, lbt, dt = _feat_rows(feat_t, 'mmd_loss')
     if d != dt:
         raise ValueError(f'mmd_loss: feature dimensions differ ({d} vs {dt})')
-    for g, n in ((dfeat_s, bs * hws), (dfeat_t, bt * hwt)):
-        if g is not None:
-            assert g.dtype == torch.bfloat16 and g.dim() == 2 and g.shape[0] == n and g.stride(1) == 1, (g.shape, n)
-    if loss is None:
-        loss = torch.zeros(1, device=xs.device)
+    loss = _loss_out(loss, xs.device)
     L = lib()
     nbytes = L.size('rgda_mmd_loss_workspace', bs * hws, bt * hwt, d)
     if kernel_type == 'linear' and nbytes:
@@ -1375,8 +1385,8 @@ def mmd_loss(feat_s, feat_t, weight=1.0, kernel_type='rbf', kernel_mul=2.0, kern
     ws = _ws(nbytes, xs.device)
     L.call('rgda_mmd_loss', xs.data_ptr(), bs, hws, lcs, lbs, xt.data_ptr(), bt, hwt, lct, lbt, d,
            MMD_KERNEL_TYPES[kernel_type], float(kernel_mul), int(kernel_num), float(fix_sigma or 0.0), loss.data_ptr(),
-           _p(dfeat_s), _ld(dfeat_s) if dfeat_s is not None else 0, _p(dfeat_t), _ld(dfeat_t) if dfeat_t is not None else 0,
-           int(bool(accumulate)), float(weight), ws.data_ptr(), ws.numel(), _stream())
+           *_grad_rows(dfeat_s, bs * hws), *_grad_rows(dfeat_t, bt * hwt), int(bool(accumulate)), float(weight),
+           ws.data_ptr(), ws.numel(), _stream())
     return loss
 
 
@@ -1395,42 +1405,21 @@ def whiten_loss(feat, labels, class_num, groups, ignore_label=-1, weight=1.0, lo
     with return_ws: int32 word 0 is the flag, words 1..16 the per-class pixel counts)."""
     _need_cuda(feat, labels, dfeat)
     assert feat.dim() == 4, 'whiten_loss: NCHW (b, k, h, w) features'
-    feat = feat.float()
-    b, k, h, w = feat.shape
-    ldb, ldc = feat.stride(0), feat.stride(1)
-    if not ((w == 1 or feat.stride(3) == 1) and (h == 1 or feat.stride(2) == w) and ldc >= h * w and
-            (b == 1 or ldb >= ldc * k)):
-        feat = feat.contiguous()
-        ldb, ldc = k * h * w, h * w
-    assert labels.dtype == torch.int64 and labels.numel() == b * h * w, (labels.dtype, labels.shape, feat.shape)
-    labels = labels.contiguous().view(b, h, w)
-    if dfeat is not None:
-        assert dfeat.dtype == torch.bfloat16 and dfeat.dim() == 2 and dfeat.shape[0] == b * h * w and dfeat.stride(1) == 1
-    if loss is None:
-        loss = torch.zeros(1, device=feat.device)
+    feat, b, hw, ldc, ldb, k = _feat_rows(feat, 'whiten_loss')
+    assert labels.dtype == torch.int64 and labels.numel() == b * hw, (labels.dtype, labels.shape, feat.shape)
+    labels = labels.contiguous().view(-1)
+    loss = _loss_out(loss, feat.device)
     L = lib()
-    ws = _ws(L.size('rgda_whiten_loss_workspace', b * h * w, k, int(class_num), int(groups)), feat.device)
-    L.call('rgda_whiten_loss', feat.data_ptr(), b, h * w, ldc, ldb, labels.data_ptr(), k, int(class_num),
-           int(groups), int(ignore_label), loss.data_ptr(), _p(dfeat), _ld(dfeat) if dfeat is not None else 0,
-           int(bool(accumulate)), float(weight), ws.data_ptr(), ws.numel(), _stream())
+    ws = _ws(L.size('rgda_whiten_loss_workspace', b * hw, k, int(class_num), int(groups)), feat.device)
+    L.call('rgda_whiten_loss', feat.data_ptr(), b, hw, ldc, ldb, labels.data_ptr(), k, int(class_num),
+           int(groups), int(ignore_label), loss.data_ptr(), *_grad_rows(dfeat, b * hw), int(bool(accumulate)),
+           float(weight), ws.data_ptr(), ws.numel(), _stream())
     if check and int(ws[:4].view(torch.int32).item()) & 4:
         raise ValueError('whiten_loss: a label is outside [0, class_num) and is not ignore_label')
     return (loss, ws) if return_ws else loss
 
 
 PIXEL_CONTRAST_MAX_ROWS = 4096      # N = anchors * views rgda_pixel_contrast_loss serves
-
-
-def _feat_in_place(feat):
-    """-> (f32 tensor, image stride, channel stride): read in place when the pixels of an image are contiguous"""
-    feat = feat.float()
-    b, k, h, w = feat.shape
-    ldb, ldc = feat.stride(0), feat.stride(1)
-    if not ((w == 1 or feat.stride(3) == 1) and (h == 1 or feat.stride(2) == w) and ldc >= h * w and
-            (b == 1 or ldb >= ldc * k)):
-        feat = feat.contiguous()
-        ldb, ldc = k * h * w, h * w
-    return feat, ldb, ldc
 
 
 def pixel_contrast_select(labels, predict, class_num, size, ignore_label=-1, check=False):
@@ -1472,24 +1461,20 @@ def pixel_contrast_loss(feat, order, counts, anchors, ranks, temperature=0.1, ba
     (accumulate=False writes every row, the unselected ones as zeros).  Returns the (accumulating) fp32 loss tensor."""
     _need_cuda(feat, order, counts, anchors, ranks, dfeat)
     assert feat.dim() == 4, 'pixel_contrast_loss: NCHW (b, k, h, w) features'
-    feat, ldb, ldc = _feat_in_place(feat)
-    b, k, h, w = feat.shape
+    feat, b, hw, ldc, ldb, k = _feat_rows(feat, 'pixel_contrast_loss')
     C = counts.shape[1]
     for t in (order, counts, anchors, ranks):
         assert t.dtype == torch.int32 and t.is_contiguous(), (t.dtype, t.shape)
-    assert tuple(order.shape) == (b, h * w) and tuple(counts.shape) == (b, C, 2), (order.shape, counts.shape)
+    assert tuple(order.shape) == (b, hw) and tuple(counts.shape) == (b, C, 2), (order.shape, counts.shape)
     A, n_view = ranks.shape
     assert tuple(anchors.shape) == (A, 3), anchors.shape
-    if dfeat is not None:
-        assert dfeat.dtype == torch.bfloat16 and dfeat.dim() == 2 and dfeat.shape[0] == b * h * w and dfeat.stride(1) == 1
-    if loss is None:
-        loss = torch.zeros(1, device=feat.device)
+    loss = _loss_out(loss, feat.device)
     L = lib()
     ws = _ws(L.size('rgda_pixel_contrast_loss_workspace', A * n_view, k), feat.device)
-    L.call('rgda_pixel_contrast_loss', feat.data_ptr(), b, h * w, ldc, ldb, k, C, order.data_ptr(), counts.data_ptr(),
+    L.call('rgda_pixel_contrast_loss', feat.data_ptr(), b, hw, ldc, ldb, k, C, order.data_ptr(), counts.data_ptr(),
            anchors.data_ptr(), A, ranks.data_ptr(), n_view, float(temperature), float(base_temperature), float(eps),
-           loss.data_ptr(), _p(dfeat), _ld(dfeat) if dfeat is not None else 0, int(bool(accumulate)), float(weight),
-           ws.data_ptr(), ws.numel(), _stream())
+           loss.data_ptr(), *_grad_rows(dfeat, b * hw), int(bool(accumulate)), float(weight), ws.data_ptr(), ws.numel(),
+           _stream())
     return loss
 
 
@@ -1512,27 +1497,16 @@ def triplet_loss(feat, labels, margin=0.3, ignore_label=None, weight=1.0, loss=N
     over, the number of positive hinges) -- a view of this call's workspace (with return_ws the workspace itself is
     returned as a third value; triplet_tables reads it)."""
     _need_cuda(feat, labels, dfeat)
-    if feat.dim() == 4:
-        feat, ldb, ldc = _feat_in_place(feat)
-        b, k, h, w = feat.shape
-        hw = h * w
-    else:
-        assert feat.dim() == 2, 'triplet_loss: NCHW (b, k, h, w) features or (n, k) rows'
-        feat = feat.contiguous().float()
-        b, k = feat.shape
-        hw, ldc, ldb = 1, 1, k
+    feat, b, hw, ldc, ldb, k = _feat_rows(feat, 'triplet_loss')
     n = b * hw
     assert labels.dtype == torch.int64 and labels.numel() == n, (labels.dtype, labels.shape, feat.shape)
     labels = labels.contiguous().view(-1)
-    if dfeat is not None:
-        assert dfeat.dtype == torch.bfloat16 and dfeat.dim() == 2 and dfeat.shape[0] == n and dfeat.stride(1) == 1
-    if loss is None:
-        loss = torch.zeros(1, device=feat.device)
+    loss = _loss_out(loss, feat.device)
     L = lib()
     ws = _ws(L.size('rgda_triplet_loss_workspace', n, k), feat.device)
     L.call('rgda_triplet_loss', feat.data_ptr(), b, hw, ldc, ldb, labels.data_ptr(), k, float(margin),
-           int(ignore_label is not None), int(ignore_label or 0), loss.data_ptr(), _p(dfeat),
-           _ld(dfeat) if dfeat is not None else 0, int(bool(accumulate)), float(weight), ws.data_ptr(), ws.numel(), _stream())
+           int(ignore_label is not None), int(ignore_label or 0), loss.data_ptr(),
+           *_grad_rows(dfeat, n), int(bool(accumulate)), float(weight), ws.data_ptr(), ws.numel(), _stream())
     stats = ws[:8].view(torch.int32)
     return (loss, stats, ws) if return_ws else (loss, stats)
 

@@ -95,6 +95,22 @@ def test_coral_loss_accumulate_weight_and_identical_domains():
     assert 0.0 <= loss0.item() <= 1e-12 * rl.item()
     for g0, ref in ((g0s, rgs), (g0t, rgt)):
         assert g0.float().abs().max().item() <= 1e-5 * ref.abs().max().item()
+    # d = 96 (one and a half 64-channel staging tiles, less than one 128 x 128 product tile), both domains batch and
+    # channel slices of wider maps, read in place through their strides (image stride > channels x channel stride), dfeat
+    # wider than d: against the emulated contract, with the bounds of the production-shape test (like roundings on both
+    # sides, so they do not depend on the shape)
+    s96 = (torch.randn(4, 128, 8, 12, generator=gen).cuda()[1:, 16:112],
+           torch.randn(3, 128, 16, 8, generator=gen).mul(0.7).cuda()[:2, 16:112])
+    assert not s96[0].is_contiguous() and tuple(s96[0].shape) == (3, 96, 8, 12) and tuple(s96[1].shape) == (2, 96, 16, 8)
+    wide = [torch.zeros(n, 104, dtype=BF, device='cuda') for n in (288, 256)]
+    l96 = ops.coral_loss(*s96, dfeat_s=wide[0][:, :96], dfeat_t=wide[1][:, :96])
+    el, *eg = emulate_contract(_rows(s96[0].cpu()), _rows(s96[1].cpu()))
+    print('coral d=96: loss', l96.item(), 'contract', el.item())
+    assert abs(l96.item() - el.item()) <= 1e-4 * el.item()
+    for got, ref in zip(wide, eg):
+        err = ((got[:, :96].float().cpu() - ref).norm() / ref.norm()).item()
+        print('coral d=96: gradient relative norm', err)
+        assert err < 5e-3 and float(got[:, 96:].float().abs().max()) == 0.0
     with pytest.raises(ValueError):
         ops.coral_loss(fs[:, :100].cuda(), ft[:, :100].cuda())
     with pytest.raises(ValueError):
