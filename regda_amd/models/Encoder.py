@@ -15,10 +15,10 @@ nn.Parameter objects are zero-copy views with the reference's logical [Cout,Cin,
 bf16 mirror for the forward pass, a transposed bf16 copy for the data-gradient pass and ONE flat fp32
 gradient buffer (what the RCCL all-reduce and the fused SGD kernel work on).
 """
+import collections
 import contextlib
 import math
-
-import os
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -238,6 +238,72 @@ class _Lazy:
 FROM_X = 'sign-from-x'      # tape marker (in the ReLU-mask slot): the unit's activation was never written; the backward
                             # kernels recompute its ReLU sign from the raw convolution output (relu == 2)
 
+# backward always launches the queued weight gradients where it leaves these stages, so that what is still queued when
+# the main chain ends is one stage's worth, whatever the wgrad_group_gflop threshold
+WGRAD_FLUSH_AFTER = ('layer2',)
+
+
+class _Unit(NamedTuple):
+    """Tape entry of one conv + BatchNorm (+ ReLU) unit: what its backward reads."""
+    x: object           # input (a _Lazy where the producer's activation was never written; the stem: the images / patch matrix)
+    c: object           # raw convolution output
+    y: object           # activation (None until / unless a BatchNorm apply pass writes it)
+    mi: object          # (mean, invstd) per BatchNorm group
+    dims: tuple         # (N, H, W, Ho, Wo)
+    nscale: object      # Dropout2d scale of the heads' last unit, or None
+    rmask: object       # ReLU sign mask, None, or FROM_X
+
+    @property
+    def on_operand_path(self):
+        """BatchNorm + ReLU ran on the consumer's operand path: no y, no sign mask."""
+        return self.rmask is FROM_X
+
+
+class _UnitBwd:
+    """What a unit's neighbours leave for its backward before it runs (T['unit_bwd'][key])."""
+    sums = None         # BatchNorm-backward sums already reduced in the producing data-gradient conv's epilogue
+    presums = None      # arena slice reserved by a producer that could not fuse: the unit reduces into it itself
+    wgrad = None        # (dc, dW, geometry, flop) of the consumer's weight gradient: its operand, this unit's activation,
+                        # is written by this unit's backward apply
+
+
+_NO_UNIT_BWD = _UnitBwd()
+
+
+class _WgradQueue:
+    """The weight gradients waiting for a grouped launch (ops.conv2d_wgrad_grouped items) and their FLOP total."""
+
+    def __init__(self):
+        self.items, self.flop, self._apart = [], 0.0, None
+
+    def take(self):
+        items, self.items, self.flop = self.items, [], 0.0
+        return items
+
+    def add(self, item, flop):
+        if self._apart is not None:
+            self._apart.append((item, flop))
+        else:
+            self.items.append(item)
+            self.flop += flop
+
+    def due(self, gflop):
+        return self._apart is None and self.flop >= gflop * 1e9
+
+    @contextlib.contextmanager
+    def apart(self, side):
+        """Items added inside go to the list `side` and nothing is due: their operands are written by a launch that has
+        not been made yet, or on another stream.  The caller joins `side` once they exist for the main stream."""
+        self._apart = side
+        try:
+            yield
+        finally:
+            self._apart = None
+
+    def join(self, side):
+        for item, flop in side:
+            self.add(item, flop)
+
 
 def _attach(root, dotted, kind, tensor):
     """Register `tensor` as parameter/buffer under the reference's dotted name, creating containers."""
@@ -255,6 +321,11 @@ def _attach(root, dotted, kind, tensor):
 
 def _pad64(n):
     return (n + 63) // 64 * 64
+
+
+def _nchw(t, N, h, w):
+    """A pixel-major map as NCHW fp32 (the debug taps)."""
+    return t.float().reshape(N, h, w, -1).permute(0, 3, 1, 2)
 
 
 def _param_entries(resnet_type, head_kind, num_classes):
@@ -361,13 +432,9 @@ class Deeplabv2(nn.Module):
         self._init_weights()
         self._anchor = torch.zeros(1, device=self.device, requires_grad=True)   # routes autograd into backward()
         self._drop_override = None
-        self.fuse_bn_bwd = True      # fold BN-backward reductions into the producing data-gradient conv
         # weight gradients are collected and launched in groups (rgda_conv2d_wgrad_grouped) once this much work
-        # is pending; 0 = one launch per layer
+        # is pending; 0 = one launch per layer (and always where backward leaves a WGRAD_FLUSH_AFTER stage)
         self.wgrad_group_gflop = 500.0
-        # ... and always where backward leaves these stages (so that what is still queued when the main chain ends is
-        # one stage's worth, whatever the threshold): '' = never
-        self.wgrad_flush_after = ('layer2',)
         # keep ReLU sign bits (1/16 of y) for the backward pass instead of re-reading y, for units with at least this
         # many channels (0 / False = never, 1 / True = always).  Round 1 kept them for the 1024-channel units only; with
         # the leaner BatchNorm kernels of round 2 every unit pays (A/B on one box: threshold 1024 -> 21.83, 512 -> 21.77,
@@ -376,14 +443,8 @@ class Deeplabv2(nn.Module):
         # PPM heads: apply the tap-shifted bilinear maps in their separable form (csrc/mix_kernels.hip); False = the
         # one-pass sparse maps (rgda_spatial_mix / rgda_spatial_mix_multi), kept as the cross-check
         self.factored_ppm = True
-        self.parallel_heads = True       # training forward: the second head on its own stream
         self.group_small_convs = True    # the PPM branches' small convolutions: the four scales in one launch (rgda_conv2d_grouped)
         self.small_bn = True             # ... and their BatchNorms: statistics + apply / reduce + apply of the four scales in one launch
-        self.parallel_tails = True       # backward: the PPM half of a head on the head stream, under the other head's convolution
-        self.early_last_flush = True     # layer1's weight gradients start before the stem's backward
-        self.fused_stem = True           # conv1 straight from the image where the map width allows it (rgda_stem_conv)
-        self.fused_stem_wgrad = True     # ... and its weight gradient too (rgda_stem_wgrad): no patch matrix at all
-        self.parallel_ds = True          # downsample branches on the head stream
         # bn1 / bn2 (+ ReLU) of every bottleneck and the stem's bn1 run on the CONSUMER's operand path (the next
         # convolution / the max-pool) wherever a kernel carries the transform: the activation is never written in the
         # forward pass (ops.conv2d_bnin).  False = one rgda_bn_train_apply pass per unit (the cross-check)
@@ -511,7 +572,6 @@ class Deeplabv2(nn.Module):
                 'wz': [torch.zeros(9 * 512, 1, 512, dtype=BF, device=dev) for _ in POOL_SCALES],
                 'wzt': [torch.zeros(512, 1, 9 * 512, dtype=BF, device=dev) for _ in POOL_SCALES],
             }
-        self._hw_ready = None
         # the head slices are two more tables for the same kernel: the forward operands (feature half + stacked tap
         # filters; also all the EMA teacher needs) and the transposes for the gradient w.r.t. the PPM branches
 
@@ -620,9 +680,6 @@ class Deeplabv2(nn.Module):
         if self.flat_p._version != self._synced_version:
             self.sync_weights()
 
-    def _load_from_state_dict(self, *a, **k):
-        super()._load_from_state_dict(*a, **k)
-
     def load_state_dict(self, state_dict, strict=True, **kw):
         r = super().load_state_dict(state_dict, strict=strict, **kw)
         self.sync_weights()
@@ -677,6 +734,19 @@ class Deeplabv2(nn.Module):
         self._drop_override = None if m5 is None else (m5, m6)
 
     # ------------------------------------------------------------------ building blocks
+    def _side_stream(self):
+        """What training runs beside the main chain: second head, downsample branches, image copies, PPM backward."""
+        if self._head_stream is None:
+            self._head_stream = torch.cuda.Stream(device=self.device)
+        return self._head_stream
+
+    def _relu_mask(self, relu, rows, ch):
+        """The backward pass needs only the SIGN of a ReLU unit's y: one bit per element, written next to y by the
+        apply pass, or None.  The byte stores cost the forward ~2 us per launch: relu_sign_mask says which units pay."""
+        if relu and self.relu_sign_mask and ch >= self.relu_sign_mask:
+            return torch.empty(rows, ch // 8, dtype=torch.uint8, device=self.device)
+        return None
+
     def _mats(self, h, w):
         key = (h, w)
         if key not in self._mat_cache:
@@ -733,7 +803,7 @@ class Deeplabv2(nn.Module):
             else:
                 ops.conv2d(*whole)
         except ValueError:
-            Ng, C = N // G, c.shape[1]
+            Ng = N // G
             st = stats.view(G, -1)
             for g in range(G):
                 ro = slice(g * Ng * Ho * Wo, (g + 1) * Ng * Ho * Wo)
@@ -748,20 +818,19 @@ class Deeplabv2(nn.Module):
         """The ordinary apply pass for a deferred unit whose consumer has no operand-transform kernel."""
         mi = torch.empty(lz.G, 2, lz.bn.c, device=self.device)
         y = torch.empty(lz.M, lz.bn.c, dtype=BF, device=self.device)
-        rmask = (torch.empty(lz.M, lz.bn.c // 8, dtype=torch.uint8, device=self.device)
-                 if (lz.relu and self.relu_sign_mask and lz.bn.c >= self.relu_sign_mask) else None)
-        geom = T[lz.key][4]
-        ops.bn_train_apply(lz.c, lz.stats, mi, lz.bn.rm, lz.bn.rv, lz.bn.nbt, lz.bn.gamma, lz.bn.beta, y, lz.M, lz.bn.c,
-                           lz.relu, None, None, geom[3] * geom[4], groups=lz.G, relu_mask=rmask)
+        rmask = self._relu_mask(lz.relu, lz.M, lz.bn.c)
         e = T[lz.key]
-        T[lz.key] = (e[0], e[1], y, mi, e[4], e[5], rmask)
+        _, _, _, Ho, Wo = e.dims
+        ops.bn_train_apply(lz.c, lz.stats, mi, lz.bn.rm, lz.bn.rv, lz.bn.nbt, lz.bn.gamma, lz.bn.beta, y, lz.M, lz.bn.c,
+                           lz.relu, None, None, Ho * Wo, groups=lz.G, relu_mask=rmask)
+        T[lz.key] = _Unit(e.x, e.c, y, mi, e.dims, e.nscale, rmask)
         return y
 
     def _bn_operand(self, T, lz):
         """rgda_bn_operand of a deferred unit + its tape entry: (mean, invstd) are written by the consumer's launch."""
         mi = torch.empty(lz.G, 2, lz.bn.c, device=self.device)
         e = T[lz.key]
-        T[lz.key] = (e[0], e[1], None, mi, e[4], e[5], FROM_X)
+        T[lz.key] = _Unit(e.x, e.c, None, mi, e.dims, e.nscale, FROM_X)
         bnop = ops.bn_operand(lz.stats, lz.bn.gamma, lz.bn.beta, mi, lz.bn.rm, lz.bn.rv, lz.bn.nbt, lz.G, lz.relu)
         T['keep'].append(bnop)
         return bnop
@@ -803,17 +872,14 @@ class Deeplabv2(nn.Module):
             else:       # stem: GEMM over the im2col matrix
                 self._conv_stats(x, wb, c, stats, G, N, Ho, Wo, Ho, Wo, 1, 1, 0, 1)
         if defer and self.bn_on_operand and res is None and nscale is None:
-            T[key] = (x, c, None, None, (N, H, W, Ho, Wo), None, None)      # completed by the consumer (_bn_operand / _materialise)
+            T[key] = _Unit(x, c, None, None, (N, H, W, Ho, Wo), None, None)     # completed by the consumer (_bn_operand / _materialise)
             return _Lazy(key, c, stats, bn, G, relu, M), Ho, Wo
         mi = torch.empty(G, 2, conv.co, device=self.device)
         y = torch.empty(M, conv.co, dtype=BF, device=self.device)
-        # the backward pass needs only the SIGN of y (ReLU): one bit per element written next to y.  The byte
-        # stores cost the forward ~2 us per launch, so only wide units do it (see relu_sign_mask).
-        rmask = (torch.empty(M, conv.co // 8, dtype=torch.uint8, device=self.device)
-                 if (relu and self.relu_sign_mask and conv.co >= self.relu_sign_mask) else None)
+        rmask = self._relu_mask(relu, M, conv.co)
         ops.bn_train_apply(c, stats, mi, bn.rm, bn.rv, bn.nbt, bn.gamma, bn.beta, y, M, conv.co, relu, res, nscale,
                            Ho * Wo, groups=G, relu_mask=rmask)
-        T[key] = (x, c, y, mi, (N, H, W, Ho, Wo), nscale, rmask)
+        T[key] = _Unit(x, c, y, mi, (N, H, W, Ho, Wo), nscale, rmask)
         return y, Ho, Wo
 
     def _head_last_fwd(self, T, head, xn, qs, N, h, w, nscale):
@@ -822,12 +888,10 @@ class Deeplabv2(nn.Module):
         channels; the four upsampled PPM branches contribute  V_i @ (q_i W_i^T)  (ppm_tap_matrix), i.e. four tiny
         1x1 convs at s x s resolution and one spatial mix, added in the feature conv's epilogue before the BN
         statistics.  Exactly the reference arithmetic re-associated; half the FLOPs of the head conv."""
-        C, B = self.convs, self.bns
-        conv, bn = C[f'{head}.conv_last.0'], B[f'{head}.conv_last.1']
+        bn = self.bns[f'{head}.conv_last.1']
         hw = self.head_w[head]
         dev = self.device
         HW, M = h * w, N * h * w
-        mats = self._mats(h, w)
         zs, queue = [], []
         for i, s in enumerate(POOL_SCALES):
             z = torch.empty(N * s * s, 9 * 512, dtype=BF, device=dev)
@@ -845,6 +909,7 @@ class Deeplabv2(nn.Module):
             ops.sparse_mix(zs, fm['fwd'], rows, N, 512)
             ops.group_mix(rows, fm['Wxt'], ppm, N * h, w, fm['R'], 512)
         else:
+            mats = self._mats(h, w)
             ops.spatial_mix_multi(zs, [mats[s][4] for s in POOL_SCALES], ppm, N, HW, 512)
         train = T is not None
         G = T['groups'] if train else 1
@@ -856,53 +921,45 @@ class Deeplabv2(nn.Module):
         if train:
             ops.bn_train_apply(c, stats, mi, bn.rm, bn.rv, bn.nbt, bn.gamma, bn.beta, y, M, 512, True, None, nscale,
                                HW, groups=G)
-            T[f'{head}.last'] = (xn, c, y, mi, (N, h, w, h, w), nscale, None)
+            T[f'{head}.last'] = _Unit(xn, c, y, mi, (N, h, w, h, w), nscale, None)
             T[f'{head}.last.q'] = qs
         else:
             ops.bn_finalize(None, mi, bn.rm, bn.rv, None, M, 512)
             ops.bn_apply(c, mi, bn.gamma, bn.beta, y, M, 512, True, None, nscale, HW, groups=G)
         return y
 
-    def _head_last_bwd(self, T, head, g, dfeat_prev, tail=True):
-        """Backward of _head_last_fwd: BN backward, then dW / dX of the feature half as an ordinary 3x3 conv over 2048
-        channels and, per PPM branch, dZ_i = V_i^T @ dc (a pooling with the tap-shifted bilinear weights),
-        dq_i = dZ_i W_i and dW_i = dZ_i^T q_i at s x s resolution.  Returns (dfeat [M,2048], [dq_i]); tail=False: the
-        feature half only -> (dfeat, dc), the caller runs _head_last_bwd_tail."""
-        C, B = self.convs, self.bns
-        conv, bn = C[f'{head}.conv_last.0'], B[f'{head}.conv_last.1']
-        hw = self.head_w[head]
+    def _head_last_bwd(self, T, head, g, dfeat_prev):
+        """Backward of the feature half of _head_last_fwd: BN backward, then dW (queued) / dX of an ordinary 3x3 conv over
+        2048 channels, the data gradient added onto `dfeat_prev`.  Returns (dfeat [M,2048], dc); _head_last_bwd_tail is
+        the PPM half."""
+        conv, bn = self.convs[f'{head}.conv_last.0'], self.bns[f'{head}.conv_last.1']
         dev = self.device
-        key = f'{head}.last'
-        xn, c, y, mi, (N, h, w, _, _), nscale, _ = T[key]
-        qs = T[key + '.q']
+        e = T[f'{head}.last']
+        N, h, w, _, _ = e.dims
         HW, M, G = h * w, N * h * w, T['groups']
-        mats = self._mats(h, w)
         sums = T['sums_pool'].take(G * NREP * 2 * 512)
-        ops.bn_bwd_reduce(g, y, c, mi, sums, M, 512, True, nscale, HW, groups=G)
+        ops.bn_bwd_reduce(g, e.y, e.c, e.mi, sums, M, 512, True, e.nscale, HW, groups=G)
         dc = torch.empty(M, 512, dtype=BF, device=dev)
-        ops.bn_bwd_apply(g, y, c, mi, bn.gamma, sums, dc, M, 512, True, None, bn.dgamma, bn.dbeta, nscale, HW, groups=G)
+        ops.bn_bwd_apply(g, e.y, e.c, e.mi, bn.gamma, sums, dc, M, 512, True, None, bn.dgamma, bn.dbeta, e.nscale, HW,
+                         groups=G)
         gview = conv.g.view(512, 9, 4096)
         # the weight gradients go straight into the channel slices of the master gradient (row stride 4096)
-        T['wgrad_pending'].append((xn, dc, gview[:, :, :2048], N, h, w, h, w, 3, 3, 1, 1, 1))
-        T['wgrad_pending_flop'] += 2.0 * M * 512 * 2048 * 9
+        T['wgrads'].add((e.x, dc, gview[:, :, :2048], N, h, w, h, w, 3, 3, 1, 1, 1), 2.0 * M * 512 * 2048 * 9)
         dfeat = torch.empty(M, 2048, dtype=BF, device=dev)
         ops.conv2d(dc, conv.wtb[:2048], dfeat, N, h, w, h, w, 3, 3, 1, 1, 1, 1, dfeat_prev, None)
         T['keep'].append((dc, dfeat))
-        if tail:
-            return dfeat, self._head_last_bwd_tail(T, head, dc)
         return dfeat, dc
 
     def _head_last_bwd_tail(self, T, head, dc):
-        """The PPM half of _head_last_bwd: dZ_i = V_i^T dc, dq_i = dZ_i W_i, dW_i queued -> [dq_i].  A dozen launches of at
-        most 113 workgroups: with `parallel_tails` they run on the head stream under the other head's convolution."""
-        C = self.convs
-        conv = C[f'{head}.conv_last.0']
+        """The PPM half of a head's backward: per branch dZ_i = V_i^T @ dc (a pooling with the tap-shifted bilinear
+        weights), dq_i = dZ_i W_i and dW_i = dZ_i^T q_i (queued) at s x s resolution -> [dq_i].  A dozen launches of at most
+        113 workgroups: with a weight-gradient stream they run on the side stream under the other head's convolution."""
+        conv = self.convs[f'{head}.conv_last.0']
         hw = self.head_w[head]
         dev = self.device
-        xn, c, y, mi, (N, h, w, _, _), nscale, _ = T[f'{head}.last']
+        N, h, w, _, _ = T[f'{head}.last'].dims
         qs = T[f'{head}.last.q']
         HW = h * w
-        mats = self._mats(h, w)
         gview = conv.g.view(512, 9, 4096)
         dqs = []
         if self.factored_ppm:       # V^T @ dc: the x map once for all scales, then one y map per scale
@@ -917,7 +974,7 @@ class Deeplabv2(nn.Module):
                 dz = dzs[i]
             else:
                 dz = torch.empty(N * s * s * 9, 512, dtype=BF, device=dev)
-                ops.spatial_mix(dc, mats[s][5], dz, N, 9 * s * s, HW, 512)
+                ops.spatial_mix(dc, self._mats(h, w)[s][5], dz, N, 9 * s * s, HW, 512)
             dzr = dz.view(N * s * s, 9 * 512)
             dq = torch.empty(N * s * s, 512, dtype=BF, device=dev)
             # dq_i = dZ_i W_i: K = 4608 on 1 - 9 pixel tiles (72 K tiles on 4 - 36 workgroups, 35 us each alone): the four
@@ -927,7 +984,8 @@ class Deeplabv2(nn.Module):
             else:
                 ops.conv2d(dzr, hw['wzt'][i], dq, N, s, s, s, s, 1, 1, 1, 0, 1)
             # nine stacked 1x1 filters (rows tap * 512 + co) written channel-major into [co][tap][2048 + 512 i ...]
-            T['wgrad_pending'].append((qs[i], dzr, gview[:, :, 2048 + 512 * i: 2048 + 512 * (i + 1)], N, s, s, s, s, 1, 1, 1, 0, 1))
+            T['wgrads'].add((qs[i], dzr, gview[:, :, 2048 + 512 * i: 2048 + 512 * (i + 1)], N, s, s, s, s, 1, 1, 1, 0, 1),
+                            2.0 * N * s * s * 9 * 512 * 512)
             T['keep'].append((dz, dq))
             dqs.append(dq)
         if queue:
@@ -967,7 +1025,7 @@ class Deeplabv2(nn.Module):
         """Launch the queued weight gradients (grouped by kernel) -- on the second HIP stream when there is one,
         next to the BN-backward / data-gradient chain of the layers below, which is the critical path -- and
         release the all-reduce progress mark that was waiting for them."""
-        pend = T['wgrad_pending']
+        pend = T['wgrads'].take()
         if pend:
             side = T.get('wgrad_stream')
             if side is None:
@@ -979,27 +1037,19 @@ class Deeplabv2(nn.Module):
                 # keep the operands alive until the streams join (no record_stream: the step must stay
                 # capturable into a hipGraph)
                 T['keep'].extend((it[0], it[1]) for it in pend)
-            post = T.get('wgrad_post')
-            if post:        # strided adds of densely written gradients (head convs), behind the launch that made them
-                if side is None:
-                    for fn in post:
-                        plan.host(fn)
-                else:
-                    with ops.use_stream(side):
-                        for fn in post:
-                            plan.host(fn)
-                T['wgrad_post'] = []
-            T['wgrad_pending'] = []
-            T['wgrad_pending_flop'] = 0.0
         off = T.pop('progress_deferred', None)
         if off is not None:
             T['on_progress'](off)
+
+    def _flush_wgrads_if_due(self, T):
+        if T['wgrads'].due(self.wgrad_group_gflop):
+            self._flush_wgrads(T)
 
     def _progress(self, T, offset):
         """All gradients of the parameters at flat offsets >= `offset` have been produced or queued."""
         if T.get('on_progress') is None:
             return
-        if T['wgrad_pending']:
+        if T['wgrads'].items:
             T['progress_deferred'] = offset       # released by the flush that launches the queued layers
         else:
             T['on_progress'](offset)
@@ -1009,38 +1059,37 @@ class Deeplabv2(nn.Module):
         """Backward of one conv+BN(+ReLU) unit.  `consumer` = (tape key, relu) of the unit that will consume this
         unit's data gradient: its BN-backward reduction is then folded into our data-gradient conv's epilogue.
         `dx_res` (+ optional ReLU sign mask gating it) is added to the data gradient in the same epilogue."""
-        x, c, y, mi, (N, H, W, Ho, Wo), nscale, rmask = T[key]
+        e = T[key]
+        x, c, mi, nscale = e.x, e.c, e.mi, e.nscale
+        N, H, W, Ho, Wo = e.dims
         M, C, G = N * Ho * Wo, conv.co, T['groups']
         # a unit whose BatchNorm + ReLU ran on its consumer's operand path: no y, no sign mask -- the ReLU sign is recomputed
         # from c (relu == 2), and the activation the consumer's WEIGHT gradient needs is written by our backward apply
-        from_x = rmask is FROM_X
-        rl = 2 if (from_x and relu) else relu
-        if from_x:
-            rmask = None
-        sums = T.pop('sums:' + key, None)
-        deferred = T.pop('wgrad_deferred:' + key, None)
+        rl = 2 if (e.on_operand_path and relu) else relu
+        rmask = None if e.on_operand_path else e.rmask
+        y = e.y if (rl == 1 and rmask is None) else None        # the kernels read y only for a ReLU sign nothing else gives
+        mine = T['unit_bwd'].pop(key, _NO_UNIT_BWD)
+        sums, deferred = mine.sums, mine.wgrad
         dc = torch.empty(M, C, dtype=BF, device=self.device)
         gm = torch.empty(M, C, dtype=BF, device=self.device) if want_gmask else None
         act = torch.empty(M, C, dtype=BF, device=self.device) if deferred is not None else None
         if (bn_queue is not None and conv_queue is not None and sums is None and rl != 2 and nscale is None and not want_gmask
-                and deferred is None and M // G <= ops.BN_SMALL_MAX_ROWS and ('presums:' + key) not in T):
+                and deferred is None and M // G <= ops.BN_SMALL_MAX_ROWS and mine.presums is None):
             # a small map: reduce + apply in one workgroup per 128 channels, launched by the caller together with its
             # siblings (ops.bn_bwd_small) -- and before the data gradients it queues in conv_queue
-            bn_queue.append((g, y if (rl == 1 and rmask is None) else None, c, mi, bn.gamma, dc, bn.dgamma, bn.dbeta, M, C,
-                             rl, G, rmask))
+            bn_queue.append((g, y, c, mi, bn.gamma, dc, bn.dgamma, bn.dbeta, M, C, rl, G, rmask))
         else:
             if sums is None:
-                sums = T.pop('presums:' + key, None)        # arena slice reserved by a producer that could not fuse
+                sums = mine.presums
                 if sums is None:
                     sums = T['sums_pool'].take(G * NREP * 2 * C)
-                ops.bn_bwd_reduce(g, y if (rl == 1 and rmask is None) else None, c, mi, sums, M, C, rl, nscale, Ho * Wo,
-                                  groups=G, relu_mask=rmask, gamma=bn.gamma, beta=bn.beta)
-            ops.bn_bwd_apply(g, y if (rl == 1 and rmask is None) else None, c, mi, bn.gamma, sums, dc, M, C, rl, gm,
-                             bn.dgamma, bn.dbeta, nscale, Ho * Wo, groups=G, relu_mask=rmask, beta=bn.beta, act_out=act)
+                ops.bn_bwd_reduce(g, y, c, mi, sums, M, C, rl, nscale, Ho * Wo, groups=G, relu_mask=rmask, gamma=bn.gamma,
+                                  beta=bn.beta)
+            ops.bn_bwd_apply(g, y, c, mi, bn.gamma, sums, dc, M, C, rl, gm, bn.dgamma, bn.dbeta, nscale, Ho * Wo, groups=G,
+                             relu_mask=rmask, beta=bn.beta, act_out=act)
         if deferred is not None:        # the consumer's weight gradient: its operand exists from here on
             ddc, dg, geom, flop = deferred
-            T['wgrad_pending'].append((act, ddc, dg) + geom)
-            T['wgrad_pending_flop'] += flop
+            T['wgrads'].add((act, ddc, dg) + geom, flop)
         if stem:
             if isinstance(x, tuple):        # the fp32 image batches themselves (one per BatchNorm group): no patch matrix
                 Ng = N // len(x)
@@ -1055,33 +1104,32 @@ class Deeplabv2(nn.Module):
         wgeom = (N, H, W, Ho, Wo, conv.k, conv.k, conv.stride, conv.pad, conv.dil)
         wflop = 2.0 * M * conv.co * conv.ci * conv.k * conv.k
         if isinstance(x, _Lazy):        # the operand was never written: queued by the producing unit's backward (above)
-            T['wgrad_deferred:' + x.key] = (dc, conv.g, wgeom, wflop)
+            T['unit_bwd'][x.key].wgrad = (dc, conv.g, wgeom, wflop)
         else:
-            T['wgrad_pending'].append((x, dc, conv.g) + wgeom)
-            T['wgrad_pending_flop'] += wflop
-        if T['wgrad_pending_flop'] >= self.wgrad_group_gflop * 1e9:
-            self._flush_wgrads(T)
+            T['wgrads'].add((x, dc, conv.g) + wgeom, wflop)
+        self._flush_wgrads_if_due(T)
         dx = None
         if need_dx:
             dx = torch.empty(N * H * W, conv.ci, dtype=BF, device=self.device)
             fused = False
-            if consumer is not None and self.fuse_bn_bwd:
+            if consumer is not None:
                 ckey, crelu = consumer
-                cx, cc, cy, cmi, (cN, cH, cW, cHo, cWo), cns, cmask = T[ckey]
-                assert cN * cHo * cWo == N * H * W and cc.shape[1] == conv.ci
+                ce = T[ckey]
+                cN, _, _, cHo, cWo = ce.dims
+                assert cN * cHo * cWo == N * H * W and ce.c.shape[1] == conv.ci
                 csums = T['sums_pool'].take(G * NREP * 2 * conv.ci)
-                cbn = None
-                if cmask is FROM_X:     # the consumer's activation was never written: its ReLU sign comes from cc
+                cbn, cmask = None, ce.rmask
+                if ce.on_operand_path:      # the consumer's activation was never written: its ReLU sign comes from its c
                     cbn, cmask, crelu = x.bn, None, (2 if crelu else 0)
                 try:
                     ops.conv2d_bnbwd(dc, conv.wtb, dx, N, Ho, Wo, H, W, conv.k, conv.k, conv.stride, conv.pad, conv.dil,
-                                     1, dx_res, csums, G, cy if (crelu == 1 and cmask is None) else None, cc, cmi, crelu,
-                                     cns, cHo * cWo, relu_mask=cmask, res_mask=dx_res_mask,
+                                     1, dx_res, csums, G, ce.y if (crelu == 1 and cmask is None) else None, ce.c, ce.mi, crelu,
+                                     ce.nscale, cHo * cWo, relu_mask=cmask, res_mask=dx_res_mask,
                                      bn_gamma=None if cbn is None else cbn.gamma, bn_beta=None if cbn is None else cbn.beta)
-                    T['sums:' + ckey] = csums
+                    T['unit_bwd'][ckey].sums = csums
                     fused = True
                 except ValueError:          # row groups do not tile (tiny maps): plain conv, standalone reduction
-                    T['presums:' + ckey] = csums
+                    T['unit_bwd'][ckey].presums = csums
             if not fused:
                 if conv_queue is not None:      # launched by the caller, grouped with its siblings (ops.conv2d_grouped)
                     conv_queue.append((dc, conv.wtb, dx, N, Ho, Wo, H, W, conv.k, conv.k, conv.stride, conv.pad, conv.dil, 1,
@@ -1094,10 +1142,9 @@ class Deeplabv2(nn.Module):
     def _stem_fwd(self, T, xs, Ng, H, W, H1, W1, main_stream):
         """conv1 + bn1 + ReLU from the fp32 images in one convolution kernel per BatchNorm group (rgda_stem_conv: no patch
         matrix).  The weight gradient reads the images again at the end of backward (rgda_stem_wgrad): training keeps
-        private copies of them, made on the head stream next to the forward (without `fused_stem_wgrad`: the patch matrix
-        of rgda_stem_im2col instead); -> (activation, event after the copies / the im2col)."""
+        private copies of them, made on the side stream next to the forward; -> (activation, event after the copies)."""
         dev = self.device
-        conv, bn = self.convs['encoder.resnet.conv1'], self.bns['encoder.resnet.bn1']
+        bn = self.bns['encoder.resnet.bn1']
         G = len(xs)
         N, M = Ng * G, Ng * G * H1 * W1
         y = torch.empty(M, 64, dtype=BF, device=dev)
@@ -1106,24 +1153,15 @@ class Deeplabv2(nn.Module):
                 ops.stem_conv_bneval(xg, self.stem_wb, y[gi * Ng * H1 * W1:(gi + 1) * Ng * H1 * W1], bn.rm, bn.rv, bn.gamma,
                                      bn.beta, True, Ng, H, W, H1, W1)
             return y, None
-        side = None
-        if self.parallel_heads:
-            if self._head_stream is None:
-                self._head_stream = torch.cuda.Stream(device=dev)
-            side = self._head_stream
-            plan.wait_event(side, plan.record_event(main_stream))       # the images are ready on the main stream
-        with (ops.use_stream(side) if side is not None else contextlib.nullcontext()):
-            if self.fused_stem_wgrad:
-                # the weight gradient reads the images again at the END of backward (rgda_stem_wgrad): private copies, so
-                # the caller's buffers are free for the next batch once the forward has read them (25 MB, beside the forward)
-                col = tuple(torch.empty_like(xg) for xg in xs)
-                for i in range(0, len(xs), 4):
-                    ops.copy_multi(list(zip(col[i:i + 4], xs[i:i + 4])))
-            else:
-                col = torch.empty(M, STEM_KP, dtype=BF, device=dev)
-                for gi, xg in enumerate(xs):
-                    ops.stem_im2col(xg, col[gi * Ng * H1 * W1:(gi + 1) * Ng * H1 * W1], Ng, H, W, H1, W1)
-            col_ready = plan.record_event(side) if side is not None else None
+        side = self._side_stream()
+        plan.wait_event(side, plan.record_event(main_stream))       # the images are ready on the main stream
+        with ops.use_stream(side):
+            # the weight gradient reads the images again at the END of backward (rgda_stem_wgrad): private copies, so
+            # the caller's buffers are free for the next batch once the forward has read them (25 MB, beside the forward)
+            col = tuple(torch.empty_like(xg) for xg in xs)
+            for i in range(0, len(xs), 4):
+                ops.copy_multi(list(zip(col[i:i + 4], xs[i:i + 4])))
+            col_ready = plan.record_event(side)
         c = torch.empty(M, 64, dtype=BF, device=dev)
         stats = T['stats_pool'].take(G * NREP * 2 * 64)
         st = stats.view(G, -1)
@@ -1132,13 +1170,13 @@ class Deeplabv2(nn.Module):
         if self.bn_on_operand and 'stem' in self.bn_operand_units and getattr(self, '_debug_taps', None) is None:
             # bn1 + ReLU run on the max-pool's operand path (ops.maxpool_fwd_bnin): the 64-channel full-resolution
             # activation (134 MB for 16 images of 512 x 512) is never written
-            T['stem'] = (col, c, None, None, (N, H, W, H1, W1), None, None)
+            T['stem'] = _Unit(col, c, None, None, (N, H, W, H1, W1), None, None)
             return _Lazy('stem', c, stats, bn, G, True, M), col_ready
         mi = torch.empty(G, 2, 64, device=dev)
-        rmask = (torch.empty(M, 8, dtype=torch.uint8, device=dev) if (self.relu_sign_mask and 64 >= self.relu_sign_mask) else None)
+        rmask = self._relu_mask(True, M, 64)
         ops.bn_train_apply(c, stats, mi, bn.rm, bn.rv, bn.nbt, bn.gamma, bn.beta, y, M, 64, True, None, None, H1 * W1, groups=G,
                            relu_mask=rmask)
-        T['stem'] = (col, c, y, mi, (N, H, W, H1, W1), None, rmask)
+        T['stem'] = _Unit(col, c, y, mi, (N, H, W, H1, W1), None, rmask)
         return y, col_ready
 
     def _block_fwd(self, T, blk, y, N, h, w, main_stream, bs=None):
@@ -1174,7 +1212,7 @@ class Deeplabv2(nn.Module):
         p, inpl, planes, stride, dil, ds = blk
         # identity blocks: the skip-path gradient g * [y3 > 0] is never written -- conv1's data-gradient epilogue
         # adds g gated by bn3's ReLU sign mask (when the unit kept one)
-        g3, m3 = g, T[p + '.3'][6]
+        g3, m3 = g, T[p + '.3'].rmask
         gate_in_epilogue = (not ds) and (m3 is not None)
         da2, gm = self._cbr_bwd(T, p + '.3', C[p + '.conv3'], B[p + '.bn3'], g, True,
                                 want_gmask=not gate_in_epilogue, consumer=(p + '.2', True))
@@ -1199,11 +1237,10 @@ class Deeplabv2(nn.Module):
         Ng, _, H, W = xs[0].shape
         N = Ng * len(xs)
         assert T is None or T['groups'] == len(xs)
-        C = self.convs
-        B = self.bns
+        C, B = self.convs, self.bns
         H1, W1 = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
         col_ready = None
-        if W1 % 64 == 0 and self.fused_stem and 3 * H * W < (1 << 28):      # (what rgda_stem_conv / rgda_stem_wgrad serve)
+        if W1 % 64 == 0 and 3 * H * W < (1 << 28):      # (what rgda_stem_conv / rgda_stem_wgrad serve)
             a0, col_ready = self._stem_fwd(T, xs, Ng, H, W, H1, W1, main_stream)
         else:
             col = torch.empty(N * H1 * W1, STEM_KP, dtype=BF, device=dev)
@@ -1222,20 +1259,16 @@ class Deeplabv2(nn.Module):
             T['pool'] = (idx, (N, H1, W1, H2, W2))
         dbg = getattr(self, '_debug_taps', None)
         if dbg is not None:
-            dbg['stem'] = a0.float().reshape(N, H1, W1, -1).permute(0, 3, 1, 2)       # (debug taps keep the stem materialised)
-            dbg['pool'] = y.float().reshape(N, H2, W2, -1).permute(0, 3, 1, 2)
+            dbg['stem'] = _nchw(a0, N, H1, W1)       # (debug taps keep the stem materialised)
+            dbg['pool'] = _nchw(y, N, H2, W2)
         h, w = H2, W2
         # a downsample branch (first block of a layer) only meets the main branch in bn3's residual add: in training it
         # runs on the head stream next to conv1 .. conv3
-        bs = None
-        if T is not None and self.parallel_heads and self.parallel_ds:
-            if self._head_stream is None:
-                self._head_stream = torch.cuda.Stream(device=dev)
-            bs = self._head_stream
+        bs = self._side_stream() if T is not None else None
         for blk in self.blocks:
             y, h, w = self._block_fwd(T, blk, y, N, h, w, main_stream, bs)
             if dbg is not None:
-                dbg[blk[0]] = y.float().reshape(N, h, w, -1).permute(0, 3, 1, 2)
+                dbg[blk[0]] = _nchw(y, N, h, w)
         return self._heads_fwd(T, y, N, h, w, main_stream, col_ready)
 
     def _heads_fwd(self, T, y, N, h, w, main_stream, col_ready=None):
@@ -1249,7 +1282,7 @@ class Deeplabv2(nn.Module):
         feat = torch.empty(N, 2048, h, w, device=dev) if T is not None else None   # eval returns probabilities only
         imi = torch.empty(N, 2, 2048, device=dev)
         ops.instnorm_fwd(y, xn, None, feat, imi, N, HW, 2048)
-        if col_ready is not None:           # the stem's patch matrix (written beside the forward) is backward's operand
+        if col_ready is not None:           # the stem's image copies (made beside the forward) are backward's operand
             plan.wait_event(main_stream, col_ready)
         def wait_head_weights():                                   # head weight slices rebuilt on another stream
             if self._hw_ready is not None:
@@ -1263,7 +1296,6 @@ class Deeplabv2(nn.Module):
             if T is not None:
                 T['out_shape'] = tuple(x1.shape)
             return x1, x2, feat
-        mats = self._mats(h, w)
         if T is not None:
             # Dropout2d(0.1) keep-masks, scaled: drawn from torch's generator at every step (a host action of a plan)
             both = torch.empty(2, N, 512, device=dev)
@@ -1291,20 +1323,17 @@ class Deeplabv2(nn.Module):
             ops.group_mix(xn, pm['Px'], prow, N * h, pm['R'], w, 2048)
             ops.sparse_mix([prow], pm['fwd'], pooled_all, N, 2048)
         else:
+            mats = self._mats(h, w)
             for s, pooled in zip(POOL_SCALES, pooled_all):
                 ops.spatial_mix(xn, mats[s][0], pooled, N, s * s, HW, 2048)
         # The two heads are independent: in training the second one runs on its own stream, so that its dozen small
         # launches (PPM branches, Z convs, mixes) overlap the first head's 280 us convolution instead of queueing
         # behind it.
-        hs = None
-        if T is not None and self.parallel_heads:
-            if self._head_stream is None:
-                self._head_stream = torch.cuda.Stream(device=dev)
-            hs = self._head_stream
-            caller = main_stream
-            plan.wait_event(hs, plan.record_event(caller))
+        if T is not None:
+            hs = self._side_stream()
+            plan.wait_event(hs, plan.record_event(main_stream))
         for hi, head in enumerate(('layer5', 'layer6')):
-            with (ops.use_stream(hs) if (hs is not None and hi == 1) else contextlib.nullcontext()):
+            with (ops.use_stream(hs) if (T is not None and hi == 1) else contextlib.nullcontext()):
                 qs = []
                 pre = [None] * len(POOL_SCALES)
                 G = T['groups'] if T is not None else 1
@@ -1321,11 +1350,10 @@ class Deeplabv2(nn.Module):
                         cc = torch.empty(Ms, cv.co, dtype=BF, device=dev)
                         y = torch.empty(Ms, cv.co, dtype=BF, device=dev)
                         mi = torch.empty(G, 2, cv.co, device=dev)
-                        rmask = (torch.empty(Ms, cv.co // 8, dtype=torch.uint8, device=dev)
-                                 if (self.relu_sign_mask and cv.co >= self.relu_sign_mask) else None)
+                        rmask = self._relu_mask(True, Ms, cv.co)
                         queue.append((pooled_all[i], cv.wb, cc, N, s, s, s, s, cv.k, cv.k, cv.stride, cv.pad, cv.dil))
                         bnq.append((cc, y, mi, bn.rm, bn.rv, bn.nbt, bn.gamma, bn.beta, Ms, cv.co, True, G, rmask))
-                        T[f'{head}.ppm{i}'] = (pooled_all[i], cc, y, mi, (N, s, s, s, s), None, rmask)
+                        T[f'{head}.ppm{i}'] = _Unit(pooled_all[i], cc, y, mi, (N, s, s, s, s), None, rmask)
                         qs.append(y)
                     ops.conv2d_grouped(queue)
                     ops.bn_train_small(bnq)
@@ -1349,26 +1377,25 @@ class Deeplabv2(nn.Module):
                                                 pooled_all[i], N, s, s, True, preconv=pre[i])
                         qs.append(q)
                     if dbg is not None:
-                        dbg[f'{head}.q{i}'] = q.float().reshape(N, s, s, -1).permute(0, 3, 1, 2)
+                        dbg[f'{head}.q{i}'] = _nchw(q, N, s, s)
                 hid = self._head_last_fwd(T, head, xn, qs, N, h, w, masks[hi])
                 if dbg is not None:
-                    dbg[head + '.hidden'] = hid.float().reshape(N, h, w, -1).permute(0, 3, 1, 2)
+                    dbg[head + '.hidden'] = _nchw(hid, N, h, w)
                 cl = C[f'{head}.conv_last.4']
                 lg = torch.empty(N, self.num_classes, h, w, device=dev)
                 ops.classifier_fwd(hid, cl.w.view(cl.co, cl.ci), cl.bias, lg, N, HW, 512, self.num_classes)
                 if T is not None:
                     T[f'{head}.cls'] = (hid, (N, h, w))
                 logits.append(lg)
-        if hs is not None:
-            plan.wait_event(caller, plan.record_event(hs))
         if T is not None:
+            plan.wait_event(main_stream, plan.record_event(hs))
             T['out_shape'] = tuple(logits[0].shape)
         return logits[0], logits[1], feat
 
     def _begin_backward(self, T, on_progress=None):
         """Per-step state of a backward pass on tape T (the queue of pending weight gradients, the statistic arena)."""
         T['on_progress'] = on_progress
-        T['wgrad_pending'], T['wgrad_pending_flop'], T['wgrad_post'] = [], 0.0, []
+        T['wgrads'], T['unit_bwd'] = _WgradQueue(), collections.defaultdict(_UnitBwd)
         T['sums_pool'] = T['sums_pool_next']
 
     def _heads_bwd(self, T, g1, g2, gfeat, bwd_stream):
@@ -1378,31 +1405,25 @@ class Deeplabv2(nn.Module):
         C, B = self.convs, self.bns
         y4, imi, (N, h, w) = T['inorm']
         HW, M = h * w, N * h * w
-        mats = self._mats(h, w) if self.head_kind == 'ppm' else None
         dfeat = None
         dpools = [None] * len(POOL_SCALES)
         dbg = getattr(self, '_debug_grads', None)
         tail_stream, tail_wgrads = None, []
-        if self.head_kind == 'ppm' and self.parallel_heads and self.parallel_tails and T.get('wgrad_stream') is not None:
-            if self._head_stream is None:
-                self._head_stream = torch.cuda.Stream(device=dev)
-            tail_stream = self._head_stream
-
-        def nchw(t, hh, ww):
-            return t.float().reshape(N, hh, ww, -1).permute(0, 3, 1, 2)
+        if self.head_kind == 'ppm' and T.get('wgrad_stream') is not None:
+            tail_stream = self._side_stream()
         if self.head_kind == 'aspp':
             g = torch.empty(M, 2048, dtype=BF, device=dev)
             ops.instnorm_bwd(self._aspp_bwd(T, g1, g2), gfeat, None, y4, imi, g, N, HW, 2048)
-        for hi, (head, gl) in enumerate((('layer5', g1), ('layer6', g2)) if self.head_kind == 'ppm' else ()):
+        for head, gl in ((('layer5', g1), ('layer6', g2)) if self.head_kind == 'ppm' else ()):
             hid, _ = T[f'{head}.cls']
             cl = C[f'{head}.conv_last.4']
             dh = torch.empty(M, 512, dtype=BF, device=dev)
             ops.classifier_bwd(hid, cl.w.view(cl.co, cl.ci), gl, dh, cl.g.view(cl.co, cl.ci),
                                cl.gbias, N, HW, 512, self.num_classes)
             # the second head's feature gradient is added onto the first head's in the conv epilogue
-            dfeat, dc_head = self._head_last_bwd(T, head, dh, dfeat, tail=False)
+            dfeat, dc_head = self._head_last_bwd(T, head, dh, dfeat)
             if dbg is not None:
-                dbg[head + '.hidden'] = nchw(dh, h, w)
+                dbg[head + '.hidden'] = _nchw(dh, N, h, w)
 
             def ppm_tail(head=head, dc_head=dc_head):
                 dqs = self._head_last_bwd_tail(T, head, dc_head)
@@ -1418,43 +1439,26 @@ class Deeplabv2(nn.Module):
                     ops.conv2d_grouped(queue)       # the four scales' 512 -> 2048 data gradients in one launch
             if tail_stream is None and not (self.group_small_convs and self.small_bn):
                 ppm_tail()                  # every unit's BatchNorm backward is launched inside its _cbr_bwd: flushes are safe there
-                if T['wgrad_pending_flop'] >= self.wgrad_group_gflop * 1e9:
-                    self._flush_wgrads(T)
             elif tail_stream is None:
                 # the branches' weight-gradient operands (dc) are written by ops.bn_bwd_small at the END of the tail: they
-                # are queued apart (no flush can fire inside the tail) and join the pending list once it has been launched
-                pend, flop = T['wgrad_pending'], T['wgrad_pending_flop']
+                # are queued apart (no flush can fire inside the tail) and join the queue once it has been launched
                 mine = []
-                T['wgrad_pending'], T['wgrad_pending_flop'] = mine, float('-inf')
-                try:
+                with T['wgrads'].apart(mine):
                     ppm_tail()
-                finally:
-                    T['wgrad_pending'], T['wgrad_pending_flop'] = pend, flop
-                T['wgrad_pending'].extend(mine)
-                T['wgrad_pending_flop'] += sum(2.0 * it[3] * it[6] * it[7] * it[2].numel() for it in mine)
-                if T['wgrad_pending_flop'] >= self.wgrad_group_gflop * 1e9:
-                    self._flush_wgrads(T)
+                T['wgrads'].join(mine)
             else:
                 # the PPM half of the head's backward (mixes, dq, the branches' BatchNorm and data gradients: ~90 us of launches
-                # of <= 113 workgroups) on the head stream, under the OTHER head's 230 us convolution.  Its weight-gradient
-                # operands are queued apart and join the pending list behind the stream join: a flush orders the weight-gradient
+                # of <= 113 workgroups) on the side stream, under the OTHER head's 230 us convolution.  Its weight-gradient
+                # operands are queued apart and join the queue behind the stream join: a flush orders the weight-gradient
                 # stream behind the MAIN stream only
                 plan.wait_event(tail_stream, plan.record_event(bwd_stream))
-                pend, flop = T['wgrad_pending'], T['wgrad_pending_flop']
-                T['wgrad_pending'], T['wgrad_pending_flop'] = tail_wgrads, float('-inf')
-                try:
-                    with ops.use_stream(tail_stream):
-                        ppm_tail()
-                finally:
-                    T['wgrad_pending'], T['wgrad_pending_flop'] = pend, flop
-                if T['wgrad_pending_flop'] >= self.wgrad_group_gflop * 1e9:
-                    self._flush_wgrads(T)
+                with T['wgrads'].apart(tail_wgrads), ops.use_stream(tail_stream):
+                    ppm_tail()
+            self._flush_wgrads_if_due(T)
         if tail_stream is not None:
             plan.wait_event(bwd_stream, plan.record_event(tail_stream))
-            T['wgrad_pending'].extend(tail_wgrads)
-            T['wgrad_pending_flop'] += sum(2.0 * it[3] * it[6] * it[7] * it[2].numel() for it in tail_wgrads)
-            if T['wgrad_pending_flop'] >= self.wgrad_group_gflop * 1e9:
-                self._flush_wgrads(T)
+            T['wgrads'].join(tail_wgrads)
+            self._flush_wgrads_if_due(T)
         if self.head_kind == 'ppm':
             gpool = torch.empty(M, 2048, dtype=BF, device=dev)
             if self.factored_ppm:
@@ -1463,7 +1467,7 @@ class Deeplabv2(nn.Module):
                 ops.sparse_mix(dpools, pm['bwd'], prow, N, 2048)
                 ops.group_mix(prow, pm['Pxt'], gpool, N * h, w, pm['R'], 2048)
             else:
-                ops.spatial_mix_multi(dpools, [mats[s][1] for s in POOL_SCALES], gpool, N, HW, 2048)
+                ops.spatial_mix_multi(dpools, [self._mats(h, w)[s][1] for s in POOL_SCALES], gpool, N, HW, 2048)
             g = torch.empty(M, 2048, dtype=BF, device=dev)
             ops.instnorm_bwd(dfeat, gfeat, gpool, y4, imi, g, N, HW, 2048)
             del dfeat, gpool
@@ -1486,29 +1490,24 @@ class Deeplabv2(nn.Module):
         C, B = self.convs, self.bns
         _, _, (N, h, w) = T['inorm']
         dbg = getattr(self, '_debug_grads', None)
-
-        def nchw(t, hh, ww):
-            return t.float().reshape(N, hh, ww, -1).permute(0, 3, 1, 2)
         self._progress(T, self._offset_of('layer5.' + self._head_first))
         hh, ww = h, w
-        order = [b[0] for b in self.blocks]
         for bi in range(len(self.blocks) - 1, -1, -1):
             p, inpl, planes, stride, dil, ds = self.blocks[bi]
             if dbg is not None:
-                dbg[p] = nchw(g, hh, ww)
+                dbg[p] = _nchw(g, N, hh, ww)
                 hh, ww = hh * stride, ww * stride
             # the gradient that leaves this block is consumed by bn3 of the block above it in the net
-            below = (order[bi - 1] + '.3', True) if bi > 0 else None
+            below = (self.blocks[bi - 1][0] + '.3', True) if bi > 0 else None
             g = self._block_bwd(T, self.blocks[bi], g, below)
             self._progress(T, self._offset_of(p + '.conv1'))
-            if bi > 0 and T['wgrad_pending']:
+            if bi > 0 and T['wgrads'].items:
                 stage = p.split('.')[-2]                      # 'encoder.resnet.layerK.i' -> 'layerK'
-                if stage in self.wgrad_flush_after and self.blocks[bi - 1][0].split('.')[-2] != stage:
+                if stage in WGRAD_FLUSH_AFTER and self.blocks[bi - 1][0].split('.')[-2] != stage:
                     self._flush_wgrads(T)
         # layer1's queued weight gradients go to the second stream NOW, next to the stem's backward (max-pool, BN, its
         # own weight gradient: ~0.4 ms on this stream) -- flushed after it they were a tail the optimizer waited for
-        if self.early_last_flush:
-            self._flush_wgrads(T)
+        self._flush_wgrads(T)
         idx, (N, H1, W1, H2, W2) = T['pool']
         ga0 = torch.empty(N * H1 * W1, 64, dtype=BF, device=dev)
         ops.maxpool_bwd(g, idx, ga0, N, H1, W1, 64, H2, W2)
