@@ -244,6 +244,50 @@ int rgda_upsample_gdp(int heads, const float* p1, const float* p2, const int64_t
                       double momentum, float* loss, float* g1, float* g2, int b, int c, int h, int w, int H,
                       int W, int ignore_label, void* ws, size_t ws_bytes, rgda_stream_t stream);
 
+/* entropyloss(logits, weight) / kldloss(logits, weight), IAST's region regularisers   regda/utils/tools.py:376-398
+ * forward + d / d(logits), on the same pipeline.  Per head on the logits upsampled bilinearly (align_corners=True, the
+ * arithmetic of rgda_upsample_ce) to (H, W); h == H, w == W is the plain call on full-resolution logits:
+ *   ent = sum_pix w_e * (-sum_c p_c log p_c) / #(w_e > 0)          kld = sum_pix w_k * (-(1/c) sum_c log p_c) / #(w_k > 0)
+ * with log p = z - logsumexp(z), never log(p): a probability that underflows contributes 0.
+ * terms: RGDA_REG_ENT | RGDA_REG_KLD, the terms computed; a term that is off costs nothing, its loss slot is 0 and its
+ *   weight map and lambda are not looked at.
+ * w_ent, w_kld: f32[b*H*W] (any float: it multiplies the term, only > 0 counts in the denominator), or NULL = derived in
+ *   registers from `label` (int64 (b,H,W); may be NULL when no term derives): w_e = (label == ignore_label),
+ *   w_k = (label != ignore_label), IAST's ignored and confident regions.
+ * loss: f32[2] = (ent, kld), unscaled, the mean over the heads.  g1, g2: NULL or NCHW f32 (b,c,h,w), per head the
+ *   gradient of 0.5 * (lambda_ent * ent_h + lambda_kld * kld_h); accumulate 0: written, 1: added onto what they hold
+ *   (one f32 addition of the finished value).  heads 1: one prediction (p2 == p1; g1 + g2 is its gradient, no 0.5).
+ * empty_is_zero: a term whose denominator is 0 is 0 / 0 = NaN with a NaN gradient as in the reference (0), or exactly 0
+ *   with a gradient of exactly 0 (1).
+ * The two counts are taken on the device with integer atomics, the sums in a fixed order: deterministic, nothing read
+ * back.  6 <= c <= 16 and the row-LDS limit of rgda_upsample_ce (RGDA_ERR_UNSUPPORTED); b * H * W < 2^31. */
+enum rgda_reg_term { RGDA_REG_ENT = 1, RGDA_REG_KLD = 2 };
+size_t rgda_upsample_reg_workspace(int b, int c, int h, int w, int H, int W);
+int rgda_upsample_reg(int heads, const float* p1, const float* p2, const int64_t* label, const float* w_ent,
+                      const float* w_kld, int terms, float lambda_ent, float lambda_kld, int accumulate,
+                      int empty_is_zero, float* loss, float* g1, float* g2, int b, int c, int h, int w, int H, int W,
+                      int ignore_label, void* ws, size_t ws_bytes, rgda_stream_t stream);
+
+/* IAST, instance-adaptive pseudo-labels: ias_thresh and the loop body of generate_pseudo   regda/utils/tools.py:323-373
+ * Three stages over one workspace of rgda_iast_workspace(n, c, H, W) bytes (0 = bad arguments), laid out as
+ *   int32 hist[c][RGDA_IAST_BINS] | f32 maxp[n*H*W] | uint8 arg[n*H*W], each piece starting on a 256-byte boundary.
+ * rgda_iast_hist: probs NCHW f32 (n,c,H,W).  CONTRACT: every value is finite and 0 <= p <= 1 (a softmax); a maximum outside
+ *   it is not counted.  Per pixel arg = the FIRST maximum over the classes, maxp its value; hist[arg][bits] counts maxp
+ *   rounded to fp16 (round to nearest even, numpy's astype(float16)) by its bit pattern 0 .. 0x7C00 -- an exact
+ *   histogram of the per-class fp16 lists the reference builds.  The histogram is cleared by the call.
+ * rgda_iast_percentile: out[k] = f32(np.percentile([prepend[k]] + the fp16 values of class k (as f64), 100 * q[k])), the
+ *   'linear' method in f64 as numpy evaluates it; prepend, q: device f64[c], 0 <= q <= 1; a class without pixels
+ *   returns prepend[k].  Needs only the histogram piece of the workspace.
+ * rgda_iast_label: label (uint8, n*H*W) = arg + 1, 0 where (double)maxp < cls_thresh[arg]; cls_thresh: device f64[c].
+ * 6 <= c <= 16 (RGDA_ERR_UNSUPPORTED); n * H * W < 2^31.  Integer atomics only: deterministic. */
+#define RGDA_IAST_BINS 0x7C01
+size_t rgda_iast_workspace(int n, int c, int H, int W);
+int rgda_iast_hist(const float* probs, int n, int c, int H, int W, void* ws, size_t ws_bytes, rgda_stream_t stream);
+int rgda_iast_percentile(const double* prepend, const double* q, float* out, int c, const void* ws, size_t ws_bytes,
+                         rgda_stream_t stream);
+int rgda_iast_label(const double* cls_thresh, uint8_t* label, int n, int c, int H, int W, const void* ws,
+                    size_t ws_bytes, rgda_stream_t stream);
+
 /* Aligner.get_prototype_weight_4pixel(feats, label_hard)   regda/gast/alignment.py:267-281 (+ _pearson_dist :396-423).
  * feat NCHW f32 (b,k,h,w); protos (c,k) f32; label (b,H,W) int64; out f32[b*H*W]:
  *   sim = 1 / pearson_dist(feat, protos) at (b,c,h,w) -> bilinear align_corners=True to (H,W) -> softmax over the classes

@@ -56,6 +56,8 @@ class AlignStep(SSLStep):
             raise ValueError('AlignStep: contrast_weight must be >= 0')
         self.contrast = dict(temperature=0.1, base_temperature=0.07, max_samples=1024, max_views=100, eps=1e-5)
         self.domain_kind, self.mmd = domain_kind(align_domain, mmd)
+        if kw.get('ent_weight') or kw.get('kld_weight'):
+            raise NotImplementedError('the IAST regularisers (ent_weight / kld_weight) belong to the SSL step')
         kw.setdefault('proto_decay', 0.999)        # Aligner(decay=0.999), train_align_reg.py:112-113
         kw['ema_decay'] = None
         super().__init__(model, prototypes, **kw)

@@ -21,6 +21,9 @@
 // GDPLoss (rgda_upsample_gdp; balance.py:218-303) runs on the same passes: GHM's stat pass as it is (the same |p_y - 1|,
 // bins and edges), a global stage of its own (symmetrised histogram, acc_sum EMA, bin weights) and the GDP branch of the
 // grad pass, whose per-pixel weight is the bin weight + the optional prototype weight + the optional class weight.
+//
+// IAST's entropy / KLD region regularisers (rgda_upsample_reg; regda/utils/tools.py:376-398) are a row pass of their own
+// on the same staging, contraction and reduction, behind a count pass for their two denominators (at the end of this file).
 #include "common.h"
 
 namespace {
@@ -77,12 +80,10 @@ static size_t scratch_bytes(int kind, size_t n) {
     }
 }
 
-// the softmax of the upsampled logits z of one head at one output pixel, from the two low-res rows staged in LDS:
-// m = max z, e = exp(z - m), se = sum e (classes in order), zl = z of class li
+// the upsampled logits z of one head at one output pixel and their maximum m, from the two low-res rows staged in LDS
 template <int C>
-__device__ __forceinline__ void up_softmax(const float* rows, int w, int hd, const Lerp& ly, const Lerp& lx, int li,
-                                           float& m, float e[C], float& se, float& zl) {
-    float z[C];
+__device__ __forceinline__ void up_logits(const float* rows, int w, int hd, const Lerp& ly, const Lerp& lx, float z[C],
+                                          float& m) {
     m = -INFINITY;
 #pragma unroll
     for (int c = 0; c < C; ++c) {
@@ -92,6 +93,15 @@ __device__ __forceinline__ void up_softmax(const float* rows, int w, int hd, con
         z[c] = __fadd_rn(__fmul_rn(ly.l0, top), __fmul_rn(ly.l1, bot));
         m = fmaxf(m, z[c]);
     }
+}
+
+// the softmax of the upsampled logits z of one head at one output pixel:
+// m = max z, e = exp(z - m), se = sum e (classes in order), zl = z of class li
+template <int C>
+__device__ __forceinline__ void up_softmax(const float* rows, int w, int hd, const Lerp& ly, const Lerp& lx, int li,
+                                           float& m, float e[C], float& se, float& zl) {
+    float z[C];
+    up_logits<C>(rows, w, hd, ly, lx, z, m);
     se = 0.f;
     zl = 0.f;
 #pragma unroll
@@ -532,8 +542,9 @@ __global__ void __launch_bounds__(256) loss_grad_kernel(const float* __restrict_
     contract_row<C>(G, lxi, lxl, T, b, Y, w, H, W);
 }
 
-// vertical contraction T -> g[head][b][c][y][x]
-template <int C>
+// vertical contraction T -> g[head][b][c][y][x]; ACC (rgda_upsample_reg, accumulate): one f32 add of the finished value
+// onto what g holds
+template <int C, bool ACC = false>
 __global__ void __launch_bounds__(256) loss_col_kernel(const float* __restrict__ T, float* g1, float* g2, int b_n, int h,
                                                        int w, int H) {
     int i = blockIdx.x * 256 + threadIdx.x;
@@ -549,8 +560,8 @@ __global__ void __launch_bounds__(256) loss_col_kernel(const float* __restrict__
         float wt = ((ly.i0 == y) ? ly.l0 : 0.f) + ((ly.i1 == y) ? ly.l1 : 0.f);
         acc += wt * T[(((size_t)b * H + Y) * 2 * C + hd * C + c) * w + x];
     }
-    float* g = hd ? g2 : g1;
-    g[(((size_t)b * C + c) * h + y) * w + x] = acc;
+    float* g = (hd ? g2 : g1) + (((size_t)b * C + c) * h + y) * w + x;
+    *g = ACC ? __fadd_rn(*g, acc) : acc;
 }
 
 // per head: the row partials in a fixed order in double, / the head's denominator -- CE (no header): * 1 / #pixels,
@@ -663,6 +674,194 @@ static int run_kind(int kind, const LossCall& a, rgda_stream_t stream) {
 // the class counts served: common.h, class_count_ok
 static int run_kind(int kind, int c, const LossCall& a, rgda_stream_t stream) {
     return with_classes(c, [&](auto cc) { return run_kind<decltype(cc)::value>(kind, a, stream); });
+}
+
+// ------------------------------------------------------------------------ entropy / KLD regularisers (rgda_upsample_reg)
+// IAST's region regularisers (regda/utils/tools.py:376-398) on the row pass above:
+//   count    #(w_e > 0), #(w_k > 0) over the batch: integer atomics over CNT_REPL copies
+//   grad     one workgroup per output row: the upsampled logits, log p = (z - m) - log(sum e) (never log(p): a
+//            probability that underflows gives 0 * finite = 0), the four row partials (term x head), d / d logits
+//            contracted horizontally
+//   col / reduce: as above (col with the accumulate variant).
+struct RegHdr {
+    int cnt[CNT_REPL][2];                // w_e > 0, w_k > 0
+};
+
+struct RegParams {
+    float se, sk;                        // lambda * 0.5 (the mean over the two heads); 0 for a term that is off
+    int terms, empty_is_zero, ignore_label;
+};
+
+// a pixel's two weights: the caller's map, or derived from the label (entropy: ignored pixels, KLD: labelled pixels)
+__device__ __forceinline__ void reg_weights(const int64_t* __restrict__ label, const float* __restrict__ w_ent,
+                                            const float* __restrict__ w_kld, size_t pix, const RegParams& prm, float& we,
+                                            float& wk) {
+    const bool need_label = ((prm.terms & RGDA_REG_ENT) && !w_ent) || ((prm.terms & RGDA_REG_KLD) && !w_kld);
+    const bool ignored = need_label ? label[pix] == prm.ignore_label : false;
+    we = (prm.terms & RGDA_REG_ENT) ? (w_ent ? w_ent[pix] : (ignored ? 1.f : 0.f)) : 0.f;
+    wk = (prm.terms & RGDA_REG_KLD) ? (w_kld ? w_kld[pix] : (ignored ? 0.f : 1.f)) : 0.f;
+}
+
+__global__ void __launch_bounds__(256) reg_count_kernel(const int64_t* __restrict__ label, const float* __restrict__ w_ent,
+                                                        const float* __restrict__ w_kld, RegHdr* hdr, long long n,
+                                                        RegParams prm) {
+    __shared__ int s_cnt[2];
+    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    int ne = 0, nk = 0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        float we, wk;
+        reg_weights(label, w_ent, w_kld, (size_t)i, prm, we, wk);
+        ne += we > 0.f;
+        nk += wk > 0.f;
+    }
+    if (ne) atomicAdd(&s_cnt[0], ne);
+    if (nk) atomicAdd(&s_cnt[1], nk);
+    __syncthreads();
+    if (threadIdx.x < 2 && s_cnt[threadIdx.x]) atomicAdd(&hdr->cnt[blockIdx.x % CNT_REPL][threadIdx.x], s_cnt[threadIdx.x]);
+}
+
+// the two denominators from the copies (any order: integers), by every workgroup that needs them; s_tot: int[2] in LDS,
+// valid after the caller's next barrier
+__device__ __forceinline__ void reg_totals(const RegHdr* __restrict__ hdr, int* s_tot) {
+    if (threadIdx.x < 2) {
+        int n = 0;
+        for (int r = 0; r < CNT_REPL; ++r) n += hdr->cnt[r][threadIdx.x];
+        s_tot[threadIdx.x] = n;
+    }
+}
+
+template <int C>
+__global__ void __launch_bounds__(256) reg_grad_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
+                                                       const int64_t* __restrict__ label, const float* __restrict__ w_ent,
+                                                       const float* __restrict__ w_kld, const RegHdr* __restrict__ hdr,
+                                                       float* partial, float* T, int h, int w, int H, int W, RegParams prm,
+                                                       int want_grad) {
+    extern __shared__ float lds[];
+    float* rows = lds;
+    float* G = lds + 2 * C * 2 * w;
+    int* lxi = (int*)(G + (want_grad ? 2 * C * W : 0));
+    float* lxl = (float*)(lxi + W);
+    __shared__ int s_tot[2];
+    const int b = blockIdx.y, Y = blockIdx.x;
+    const Lerp ly = row_lerp<false>(Y, h, H);
+    reg_totals(hdr, s_tot);
+    stage_rows<C>(rows, p1, p2, b, ly.i0, ly.i1, h, w);
+    __syncthreads();
+    // an empty region: 1 / 0 = inf and 0 * inf = NaN as the reference's 0 / 0, or a term of exactly 0
+    const float inv_de = (s_tot[0] == 0 && prm.empty_is_zero) ? 0.f : 1.f / (float)s_tot[0];
+    const float inv_dk = (s_tot[1] == 0 && prm.empty_is_zero) ? 0.f : 1.f / (float)s_tot[1];
+    const float ge = (prm.terms & RGDA_REG_ENT) ? prm.se * inv_de : 0.f;
+    const float gk = (prm.terms & RGDA_REG_KLD) ? prm.sk * inv_dk : 0.f;
+    constexpr float inv_c = 1.f / (float)C;
+    float lsum[4] = {0.f, 0.f, 0.f, 0.f};       // entropy head 1, 2; KLD head 1, 2
+    for (int X = threadIdx.x; X < W; X += 256) {
+        const Lerp lx = lerp_ac(X, w, W);
+        lxi[X] = lx.i0;
+        lxl[X] = lx.l1;
+        const size_t pix = ((size_t)b * H + Y) * W + X;
+        float we, wk;
+        reg_weights(label, w_ent, w_kld, pix, prm, we, wk);
+        const float ae = we * ge, ak = wk * gk;
+#pragma unroll
+        for (int hd = 0; hd < 2; ++hd) {
+            float z[C], e[C], m, se = 0.f;
+            up_logits<C>(rows, w, hd, ly, lx, z, m);
+#pragma unroll
+            for (int c = 0; c < C; ++c) { z[c] -= m; e[c] = expf(z[c]); se += e[c]; }
+            const float lg = logf(se), inv_se = 1.f / se;
+            float ent = 0.f, sl = 0.f;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                z[c] -= lg;              // log p
+                e[c] *= inv_se;          // p
+                ent -= e[c] * z[c];
+                sl += z[c];
+            }
+            lsum[hd] += we * ent;
+            lsum[2 + hd] += wk * (-sl * inv_c);
+            if (want_grad) {
+#pragma unroll
+                for (int c = 0; c < C; ++c)
+                    G[(hd * C + c) * W + X] = ae * (-e[c] * (z[c] + ent)) + ak * (e[c] - inv_c);
+            }
+        }
+    }
+    __shared__ float red[4][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        lsum[k] = wave_sum(lsum[k]);
+        if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = lsum[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < 4)
+        partial[((size_t)b * H + Y) * 4 + threadIdx.x] =
+            red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+    if (!want_grad) return;
+    contract_row<C>(G, lxi, lxl, T, b, Y, w, H, W);
+}
+
+// per term and head: the row partials in a fixed order in double, / the term's count; then the mean over the heads
+__global__ void __launch_bounds__(256) reg_reduce_kernel(const float* __restrict__ partial, const RegHdr* __restrict__ hdr,
+                                                         float* loss, int n, RegParams prm) {
+    __shared__ double red[4][256];
+    __shared__ int s_tot[2];
+    reg_totals(hdr, s_tot);
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = threadIdx.x; i < n; i += 256)
+        for (int k = 0; k < 4; ++k) s[k] += partial[4 * (size_t)i + k];
+    for (int k = 0; k < 4; ++k) red[k][threadIdx.x] = s[k];
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o)
+            for (int k = 0; k < 4; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x < 2) {
+        const int t = threadIdx.x;
+        float v = 0.f;
+        if ((prm.terms & (t ? RGDA_REG_KLD : RGDA_REG_ENT)) && !(s_tot[t] == 0 && prm.empty_is_zero)) {
+            const double d = (double)s_tot[t];
+            v = ((float)(red[2 * t][0] / d) + (float)(red[2 * t + 1][0] / d)) / 2.f;
+        }
+        loss[t] = v;
+    }
+}
+
+struct RegCall {
+    const float *p1, *p2, *w_ent, *w_kld;
+    const int64_t* label;
+    float *loss, *g1, *g2;
+    RegHdr* hdr;
+    float *partial, *T;
+    int b, h, w, H, W, accumulate;
+    RegParams prm;
+};
+
+template <int C>
+static int run_reg(const RegCall& a, rgda_stream_t stream) {
+    hipStream_t st = to_stream(stream);
+    const int want = a.g1 != nullptr;
+    const long long n = (long long)a.b * a.H * a.W;
+    if (zero_bytes(a.hdr, sizeof(RegHdr), stream) != RGDA_OK) return RGDA_ERR_LAUNCH;
+    reg_count_kernel<<<(int)min((long long)cdiv(n, 256 * 8), 1024ll), 256, 0, st>>>(a.label, a.w_ent, a.w_kld, a.hdr, n, a.prm);
+    RGDA_CHECK_LAUNCH();
+    const size_t lds = grad_lds(C, a.w, a.W, want);
+    if (lds_attr((const void*)reg_grad_kernel<C>, lds) != RGDA_OK) return RGDA_ERR_LAUNCH;
+    reg_grad_kernel<C><<<dim3(a.H, a.b), 256, lds, st>>>(a.p1, a.p2, a.label, a.w_ent, a.w_kld, a.hdr, a.partial, a.T, a.h, a.w,
+                                                      a.H, a.W, a.prm, want);
+    RGDA_CHECK_LAUNCH();
+    if (want) {
+        const int blocks = cdiv((long long)2 * a.b * C * a.h * a.w, 256);
+        if (a.accumulate)
+            loss_col_kernel<C, true><<<blocks, 256, 0, st>>>(a.T, a.g1, a.g2, a.b, a.h, a.w, a.H);
+        else
+            loss_col_kernel<C, false><<<blocks, 256, 0, st>>>(a.T, a.g1, a.g2, a.b, a.h, a.w, a.H);
+        RGDA_CHECK_LAUNCH();
+    }
+    reg_reduce_kernel<<<1, 256, 0, st>>>(a.partial, a.hdr, a.loss, a.b * a.H, a.prm);
+    RGDA_CHECK_LAUNCH();
+    return RGDA_OK;
 }
 
 }  // namespace
@@ -780,4 +979,39 @@ extern "C" int rgda_upsample_gdp(int heads, const float* p1, const float* p2, co
     a.prm.mom = (float)momentum;
     a.prm.omm = (float)(1.0 - momentum);
     return run_kind(RGDA_LOSS_GDP, c, a, stream);
+}
+
+extern "C" size_t rgda_upsample_reg_workspace(int b, int c, int h, int w, int H, int W) {
+    if (b <= 0 || c <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return 0;
+    return align256_(sizeof(RegHdr)) + align256_((size_t)b * H * 4 * 4) + (size_t)b * H * 2 * c * w * 4;
+}
+
+extern "C" int rgda_upsample_reg(int heads, const float* p1, const float* p2, const int64_t* label, const float* w_ent,
+                                 const float* w_kld, int terms, float lambda_ent, float lambda_kld, int accumulate,
+                                 int empty_is_zero, float* loss, float* g1, float* g2, int b, int c, int h, int w, int H,
+                                 int W, int ignore_label, void* ws, size_t ws_bytes, rgda_stream_t stream) {
+    if (heads != 1 && heads != 2) return RGDA_ERR_ARG;
+    if (!p1 || !p2 || !loss || !ws || ((g1 == nullptr) != (g2 == nullptr))) return RGDA_ERR_ARG;
+    if (heads == 1 && p2 != p1) return RGDA_ERR_ARG;
+    if (terms < 1 || terms > (RGDA_REG_ENT | RGDA_REG_KLD)) return RGDA_ERR_ARG;
+    // a derived mask reads the label
+    if (!label && (((terms & RGDA_REG_ENT) && !w_ent) || ((terms & RGDA_REG_KLD) && !w_kld))) return RGDA_ERR_ARG;
+    if (b <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return RGDA_ERR_ARG;
+    if ((long long)b * H * W >= (1ll << 31)) return RGDA_ERR_ARG;         // the two counts: 32 bits
+    if (!class_count_ok(c)) return RGDA_ERR_UNSUPPORTED;
+    if (ws_bytes < rgda_upsample_reg_workspace(b, c, h, w, H, W)) return RGDA_ERR_WORKSPACE;
+    if (grad_lds(c, w, W, g1 != nullptr) > MAX_ROW_LDS) return RGDA_ERR_UNSUPPORTED;
+    RegCall a{};
+    a.p1 = p1, a.p2 = p2, a.label = label, a.w_ent = w_ent, a.w_kld = w_kld;
+    a.loss = loss, a.g1 = g1, a.g2 = g2;
+    char* base = (char*)ws;
+    a.hdr = (RegHdr*)base;
+    base += align256_(sizeof(RegHdr));
+    a.partial = (float*)base;
+    base += align256_((size_t)b * H * 4 * 4);
+    a.T = (float*)base;
+    a.b = b, a.h = h, a.w = w, a.H = H, a.W = W, a.accumulate = accumulate != 0;
+    a.prm.terms = terms, a.prm.empty_is_zero = empty_is_zero != 0, a.prm.ignore_label = ignore_label;
+    a.prm.se = 0.5f * lambda_ent, a.prm.sk = 0.5f * lambda_kld;
+    return with_classes(c, [&](auto cc) { return run_reg<decltype(cc)::value>(a, stream); });
 }

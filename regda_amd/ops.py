@@ -459,6 +459,117 @@ def upsample_gdp(p1, p2, label, acc_sum, bins_weight, pixel_weight=None, class_w
     return loss, g1, g2
 
 
+REG_ENT, REG_KLD = 1, 2         # enum rgda_reg_term (include/rgda_hip.h)
+
+
+def _pixel_map(t, b, H, W, who):
+    """A caller's per-pixel weight map, (b, 1, H, W) or (b, H, W), as contiguous f32 (None stays None)."""
+    if t is None:
+        return None
+    if tuple(t.shape) not in ((b, 1, H, W), (b, H, W)):
+        raise ValueError(f'{who}: weight of shape {tuple(t.shape)}, expected ({b}, 1, {H}, {W}) or ({b}, {H}, {W})')
+    return t.contiguous().float()
+
+
+def upsample_reg(p1, p2, label=None, w_ent=None, w_kld=None, terms=REG_ENT | REG_KLD, lambda_ent=1.0, lambda_kld=1.0,
+                 size=None, ignore_label=-1, want_grad=True, g1=None, g2=None, accumulate=False, empty_is_zero=False,
+                 heads=2, loss=None):
+    """IAST's entropy and KLD-to-uniform regularisers on the upsampled logits (rgda_upsample_reg; tools.py:376-398)
+    -> (loss f32[2] = (ent, kld) unscaled, g1, g2).  w_ent / w_kld: a weight map (b, 1, H, W) or (b, H, W), or None =
+    derived from `label` (int64 (b, H, W)): entropy on the ignored pixels, KLD on the labelled ones.  g1 / g2 receive
+    (accumulate: are added) the gradient of 0.5 * (lambda_ent * ent + lambda_kld * kld) per head.  size: (H, W) when
+    there is no label to take it from.  heads=1: one prediction (p2 must be p1; the gradient is then g1 + g2)."""
+    _need_cuda(p1, p2, label, w_ent, w_kld)
+    p1, p2 = p1.contiguous().float(), p2.contiguous().float()
+    b, c, h, w = p1.shape
+    if not 1 <= int(terms) <= (REG_ENT | REG_KLD):
+        raise ValueError(f'upsample_reg: terms {terms!r}; REG_ENT, REG_KLD or both')
+    derives = bool(terms & REG_ENT and w_ent is None) or bool(terms & REG_KLD and w_kld is None)
+    if derives and label is None:
+        raise ValueError('upsample_reg: a term without a weight map derives its mask from `label`, which is missing')
+    # (H, W): given, else the label's, else that of the map of a term that is on (one exists: nothing is derived)
+    used = [t for t, on in ((label, True), (w_ent, terms & REG_ENT), (w_kld, terms & REG_KLD)) if on and t is not None]
+    H, W = (int(v) for v in (size if size is not None else used[0].shape[-2:]))
+    if label is not None:
+        if label.dtype != torch.int64 or tuple(label.shape) != (b, H, W):
+            raise ValueError(f'upsample_reg: label {label.dtype} {tuple(label.shape)}, expected int64 ({b}, {H}, {W})')
+        label = label.contiguous()
+    w_ent, w_kld = _pixel_map(w_ent, b, H, W, 'upsample_reg'), _pixel_map(w_kld, b, H, W, 'upsample_reg')
+    loss = torch.empty(2, dtype=torch.float32, device=p1.device) if loss is None else loss
+    if want_grad:
+        assert not accumulate or (g1 is not None and g2 is not None), 'accumulate adds onto given gradients'
+        g1 = torch.empty_like(p1) if g1 is None else g1
+        g2 = torch.empty_like(p2) if g2 is None else g2
+        assert g1.is_contiguous() and g2.is_contiguous() and g1.shape == p1.shape and g2.shape == p2.shape
+    else:
+        g1 = g2 = None
+    L = lib()
+    ws = _ws(L.size('rgda_upsample_reg_workspace', b, c, h, w, H, W), p1.device)
+    if heads == 1:
+        p2 = p1
+    L.call('rgda_upsample_reg', heads, p1.data_ptr(), p2.data_ptr(), _p(label), _p(w_ent), _p(w_kld), int(terms),
+           float(lambda_ent), float(lambda_kld), int(bool(accumulate)), int(bool(empty_is_zero)), loss.data_ptr(), _p(g1),
+           _p(g2), b, c, h, w, H, W, ignore_label, ws.data_ptr(), ws.numel(), _stream())
+    return loss, g1, g2
+
+
+IAST_BINS = 0x7C01      # RGDA_IAST_BINS: the non-negative fp16 bit patterns 0 .. 0x7C00
+
+
+def _align256(x):
+    return (x + 255) & ~255
+
+
+def iast_workspace(n, c, H, W, device):
+    check_class_count(c, 'iast')
+    return _ws(lib().size('rgda_iast_workspace', n, c, H, W), device)
+
+
+def iast_views(ws, n, c, H, W):
+    """The pieces of an IAST workspace -> (hist int32 [c, IAST_BINS], maxp f32 [n, H, W], arg uint8 [n, H, W])."""
+    npix = n * H * W
+    o1 = _align256(c * IAST_BINS * 4)
+    o2 = o1 + _align256(npix * 4)
+    return (ws[:c * IAST_BINS * 4].view(torch.int32).view(c, IAST_BINS), ws[o1:o1 + npix * 4].view(torch.float32).view(n, H, W),
+            ws[o2:o2 + npix].view(n, H, W))
+
+
+def iast_hist(probs, ws=None):
+    """probs f32 (n, c, H, W) in [0, 1] -> the workspace holding the per-pixel first argmax, its value and the per-class
+    fp16 histogram of the values (rgda_iast_hist; iast_views reads them)."""
+    _need_cuda(probs)
+    assert probs.dim() == 4 and probs.dtype == torch.float32
+    probs = probs.contiguous()
+    n, c, H, W = probs.shape
+    ws = iast_workspace(n, c, H, W, probs.device) if ws is None else ws
+    lib().call('rgda_iast_hist', probs.data_ptr(), n, c, H, W, ws.data_ptr(), ws.numel(), _stream())
+    return ws
+
+
+def iast_percentile(ws, prepend, q):
+    """-> f32 [c]: np.percentile([prepend[k]] + class k's fp16 confidences, 100 * q[k]) per class (rgda_iast_percentile).
+    prepend, q: device f64 [c]."""
+    _need_cuda(ws, prepend, q)
+    assert prepend.dtype == q.dtype == torch.float64 and prepend.is_contiguous() and q.is_contiguous()
+    c = prepend.numel()
+    assert q.numel() == c
+    out = torch.empty(c, dtype=torch.float32, device=ws.device)
+    lib().call('rgda_iast_percentile', prepend.data_ptr(), q.data_ptr(), out.data_ptr(), c, ws.data_ptr(), ws.numel(),
+               _stream())
+    return out
+
+
+def iast_label(ws, cls_thresh, n, H, W, out=None):
+    """-> uint8 (n, H, W): argmax + 1, 0 where the confidence is below its class's threshold (rgda_iast_label).
+    cls_thresh: device f64 [c]."""
+    _need_cuda(ws, cls_thresh)
+    assert cls_thresh.dtype == torch.float64 and cls_thresh.is_contiguous()
+    out = torch.empty((n, H, W), dtype=torch.uint8, device=ws.device) if out is None else out
+    lib().call('rgda_iast_label', cls_thresh.data_ptr(), out.data_ptr(), n, cls_thresh.numel(), H, W, ws.data_ptr(),
+               ws.numel(), _stream())
+    return out
+
+
 def proto_pixel_weight(feat, protos, label, sim=None, ignore_label=-1, out=None):
     """Aligner.get_prototype_weight_4pixel (rgda_proto_pixel_weight; alignment.py:267-281) -> f32 [b*H*W]: the prototype
     agreement of every label pixel with its own label, 0 where the label is ignored.  feat (b,k,h,w), protos (c,k),

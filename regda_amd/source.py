@@ -48,6 +48,8 @@ class SourceStep(SSLStep):
     def __init__(self, model, class_balancer_s=None, align_domain=False, class_num=6, loss_s='CrossEntropy', mmd=None,
                  domain_weight=1.0, **kw):
         self.domain_kind, self.mmd = domain_kind(align_domain, mmd)
+        if kw.get('ent_weight') or kw.get('kld_weight'):
+            raise NotImplementedError('the IAST regularisers (ent_weight / kld_weight) belong to the SSL step')
         kw['ema_decay'] = None
         kw.setdefault('sam_refine', False)
         kw.setdefault('refine_label', False)

@@ -23,7 +23,8 @@ class SSLStep:
                  sam_refine=True, refine_label=True, ema_decay=None, max_regions=4096, bucket_elems=12 << 20,
                  process_group=None, overlap_wgrad=True, overlap_comm=True, class_balancer_s=None,
                  class_balancer_t=None, grad_payload='fp32', comm=None, loss_s='CrossEntropy', loss_t='none',
-                 uvem_m=0.2, uvem_t=0.7, uvem_g=4.0, gdp_prototype=True, gdp_class_balance=False):
+                 uvem_m=0.2, uvem_t=0.7, uvem_g=4.0, gdp_prototype=True, gdp_class_balance=False, ent_weight=0.0,
+                 kld_weight=0.0):
         ops.check_class_count(class_num, type(self).__name__)
         self.model = model
         self.C, self.ig = class_num, ignore_label
@@ -69,6 +70,11 @@ class SSLStep:
         self.loss_fn_t = target_loss(loss_t, class_balancer_t, uvem_m, uvem_t, uvem_g, class_num, ignore_label,
                                      device=dev, gdp_prototype=gdp_prototype, gdp_class_balance=gdp_class_balance)
         self.last_proto_weight = None
+        # IAST's region regularisers (regda/utils/tools.py:376-398) on the target logits and the step's final pseudo
+        # labels: ent_weight * entropy over the ignored pixels + kld_weight * KLD-to-uniform over the labelled ones, one
+        # rgda_upsample_reg call behind the target loss that adds its gradient onto that loss's.  Both 0: no launch.
+        self.ent_weight, self.kld_weight = float(ent_weight), float(kld_weight)
+        self.loss_ent = self.loss_kld = None    # the unscaled terms of the last step (device tensors)
         self._graph = None
         self._plan = None
         self._proto_ready = None
@@ -250,6 +256,17 @@ class SSLStep:
         return f.launch(t1, t2, hard, soft=soft if f.kind in ('ups', 'uvem') else None,
                         class_weight=self._class_weights(f.class_balancer, hard), g1=g1, g2=g2)[0]
 
+    def _target_regularisers(self, t1, t2, hard, g1, g2):
+        """IAST's entropy / KLD terms on the pseudo labels' ignored / labelled regions (derived in the kernel, no weight
+        tensor); their gradient is added onto the target loss's in g1, g2.  An empty region gives a term of 0.  Ranks
+        of a data-parallel run use their local counts, like every other loss of the step."""
+        terms = (ops.REG_ENT if self.ent_weight else 0) | (ops.REG_KLD if self.kld_weight else 0)
+        if not terms:
+            return
+        reg = ops.upsample_reg(t1, t2, hard, terms=terms, lambda_ent=self.ent_weight, lambda_kld=self.kld_weight,
+                               ignore_label=self.ig, g1=g1, g2=g2, accumulate=True, empty_is_zero=True)[0]
+        self.loss_ent, self.loss_kld = reg[0], reg[1]
+
     def _mark(self, name, stream=None):
         if self.marks is not None:
             ev = torch.cuda.Event(enable_timing=True)
@@ -388,6 +405,9 @@ class SSLStep:
         if side is None:
             loss_s = self._source_loss(s1, s2, label_s, g1[:nb], g2[:nb])
         loss_t = self._target_loss(t1, t2, hard, soft, g1[nb:], g2[nb:], proto_weight)
+        self._target_regularisers(t1, t2, hard, g1[nb:], g2[nb:])
+        if self.keep_debug:
+            self.debug.update(g1_t=g1[nb:].clone(), g2_t=g2[nb:].clone())
         if side is not None:
             plan.wait_event(main, source_done)       # source loss, its logit gradients, the new prototypes
         self._mark('label path + losses done')

@@ -1,10 +1,12 @@
-"""loss_calc / learning-rate schedule / config import / sliding-window + TTA + multi-scale inference -- mirror of
-regda/utils/tools.py:51-97,108-129,132-152,173-207,240-260."""
+"""loss_calc / learning-rate schedule / config import / sliding-window + TTA + multi-scale inference / IAST
+self-training (adaptive pseudo-labels, entropy and KLD regularisers) -- mirror of
+regda/utils/tools.py:51-97,108-129,132-152,173-207,240-260,323-398."""
 import importlib
 import os
 import shutil
 from math import ceil
 
+import numpy as np
 import torch
 import torch.nn.functional as tnf
 
@@ -329,3 +331,109 @@ def window_groups(loader, tile_size=(512, 512), tta=False, window_batch=16):
             group, nwin = [], 0
     if group:
         yield group
+
+
+# ----------------------------------------------------------------------------- IAST self-training (tools.py:323-398)
+class _RegLoss(torch.autograd.Function):
+    """One of IAST's region regularisers on full-resolution logits: rgda_upsample_reg with h == H, w == W, one head, the
+    caller's weight map and the reference's 0 / 0 = NaN for an empty region."""
+
+    @staticmethod
+    def forward(ctx, logits, weight, term):
+        x = logits.detach()
+        want = ctx.needs_input_grad[0]
+        kw = dict(w_ent=weight) if term == ops.REG_ENT else dict(w_kld=weight)
+        loss, g1, g2 = ops.upsample_reg(x, x, terms=term, size=x.shape[-2:], want_grad=want, heads=1, **kw)
+        ctx.grad = g1.add_(g2).to(logits.dtype) if want else None
+        return loss[0 if term == ops.REG_ENT else 1].clone()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        return grad_out * ctx.grad, None, None
+
+
+def _reg_weight(weight, who):
+    if weight is None:          # the reference indexes it: TypeError there too
+        raise TypeError(f'{who}: weight is required (N x 1 x H x W)')
+    return weight.detach()
+
+
+def entropyloss(logits, weight=None):
+    """sum(-softmax * weight * log_softmax) / #(weight > 0) (tools.py:376-385).  logits N x C x H x W on the GPU, weight
+    N x 1 x H x W (or N x H x W).  Differentiable in the logits."""
+    return _RegLoss.apply(logits, _reg_weight(weight, 'entropyloss'), ops.REG_ENT)
+
+
+def kldloss(logits, weight):
+    """sum(-1 / C * weight * log_softmax) / #(weight > 0) (tools.py:388-398); arguments as entropyloss."""
+    return _RegLoss.apply(logits, _reg_weight(weight, 'kldloss'), ops.REG_KLD)
+
+
+class IASTSelector:
+    """The instance-adaptive selector of generate_pseudo's loop (tools.py:342-370 with ias_thresh, :323-332): per-class
+    thresholds `cls_thresh` (host float64, 0.9 at the start) that move, batch by batch, towards a percentile of the
+    class's confidences.  update() runs rgda_iast_hist / _percentile / _label; the C percentiles come back to the host
+    (the one sync per batch), where the EMA and the exponent are numpy's own arithmetic."""
+
+    def __init__(self, n_class=7, pl_alpha=0.2, pl_beta=0.9, pl_gamma=8.0):
+        ops.check_class_count(n_class, 'IASTSelector')
+        self.n_class, self.alpha, self.beta, self.gamma = n_class, pl_alpha, pl_beta, pl_gamma
+        self.cls_thresh = np.ones(n_class) * 0.9
+
+    def quantiles(self):
+        """q_c of np.percentile(arr, 100 * (1 - alpha * w_c ** gamma)), scalar by scalar as ias_thresh computes them."""
+        w = self.cls_thresh
+        q = np.array([np.true_divide(100 * (1 - self.alpha * w[c] ** self.gamma), 100) for c in range(self.n_class)],
+                     dtype=np.float64)
+        if not np.all((q >= 0) & (q <= 1)):
+            raise ValueError('Percentiles must be in the range [0, 100]')
+        return q
+
+    def update(self, probs):
+        """probs f32 (n, n_class, H, W) in [0, 1] on the GPU -> labels uint8 (n, H, W) on the GPU: argmax + 1, 0 where the
+        confidence is below its class's updated threshold."""
+        n, c, H, W = probs.shape
+        if c != self.n_class:
+            raise ValueError(f'IASTSelector: {c} channels for {self.n_class} classes')
+        ws = ops.iast_hist(probs.float())
+        tq = torch.from_numpy(np.stack([self.cls_thresh, self.quantiles()])).to(probs.device)
+        tmp = ops.iast_percentile(ws, tq[0], tq[1]).cpu().numpy()
+        # the moving average: the candidate's share in float32 (tmp's type), the sum in float64; a threshold that reaches
+        # 1 would select nothing and restarts at 0.999
+        moved = self.beta * self.cls_thresh + (1 - self.beta) * tmp
+        self.cls_thresh = np.where(moved >= 1, 0.999, moved)
+        return ops.iast_label(ws, torch.from_numpy(self.cls_thresh).to(probs.device), n, H, W)
+
+
+def _default_writer():
+    try:
+        from skimage.io import imsave
+        return imsave
+    except ImportError:
+        from PIL import Image
+        return lambda path, arr: Image.fromarray(arr).save(path)
+
+
+def generate_pseudo(model, target_loader, save_dir, n_class=7, pseudo_dict=None, logger=None, writer=None):
+    """IAST pseudo-label generation (tools.py:335-373): every batch of `target_loader` ((image, {'fname': [...]}))
+    goes through `model` in eval mode and an IASTSelector(pseudo_dict['pl_alpha' / 'pl_beta' / 'pl_gamma']); the uint8
+    labels are written with `writer(path, array)` (skimage's imsave, else PIL) to save_dir/pred/<fname>.  Returns that
+    directory.  The reference's palette visualisation (er.viz) is not provided."""
+    if pseudo_dict is None:
+        pseudo_dict = dict()
+    if logger is not None:
+        logger.info('Start generate pseudo labels: %s' % save_dir)
+    pred_dir = os.path.join(save_dir, 'pred')
+    os.makedirs(pred_dir, exist_ok=True)
+    if writer is None:
+        writer = _default_writer()
+    model.eval()
+    selector = IASTSelector(n_class, pseudo_dict['pl_alpha'], pseudo_dict['pl_beta'], pseudo_dict['pl_gamma'])
+    for image, labels in target_loader:
+        with torch.no_grad():
+            out = model(image.cuda())
+        probs = out[0] if isinstance(out, tuple) else out
+        label = selector.update(probs).cpu().numpy()
+        for i, fname in enumerate(labels['fname']):
+            writer(os.path.join(pred_dir, fname), label[i])
+    return pred_dir

@@ -1,9 +1,11 @@
 """dev: the fused --ls / --lt losses (rgda_upsample_loss; GDPLoss: rgda_upsample_gdp, plain and with the prototype and
 class weights) against the CE call (rgda_upsample_ce) at 8 x 6 x 32 x 32 -> 512 x 512 (HIP-event time per loss_calc
 call, with gradients; algorithmic bytes), rgda_proto_pixel_weight with and without a precomputed similarity map, and
-the step time of SSLStep(loss_t='uvem' / 'ohem' / 'ghm' / 'gdp') against the default, as bench.py builds it (ResNet-101,
-8 + 8 images, recorded plan; --eager: eager steps).
-    python scripts/dev/loss_bench.py [--no-step] [--eager] [--only ghm,gdp]"""
+IAST's regularisers (rgda_upsample_reg: derived masks, both terms, gradients accumulated) and adaptive pseudo-label
+stages (rgda_iast_hist / _percentile / _label at 8 x 6 x 512 x 512, random and all-confident probabilities), and
+the step time of SSLStep(loss_t='uvem' / 'ohem' / 'ghm' / 'gdp') and of SSLStep(ent_weight, kld_weight) ('reg') against
+the default, as bench.py builds it (ResNet-101, 8 + 8 images, recorded plan; --eager: eager steps).
+    python scripts/dev/loss_bench.py [--no-step] [--eager] [--only ghm,gdp,reg,iast]"""
 import os
 import sys
 
@@ -42,7 +44,7 @@ def loss_calls():
     # algorithmic bytes: int64 labels (read by each pass), the soft label (ups / uvem), the per-pixel scratch written by
     # the stat pass and read by the gradient pass, low-res logits and gradients (2 heads)
     low = 2 * 2 * b * c * h * h * 4
-    passes = {'ce': 1, 'focal': 1}
+    passes = {'ce': 1, 'focal': 1}       # (reg: the count pass and the row pass, 2)
     scratch = {'ohem': 2 * npix * 4, 'ghm': 2 * npix, 'gdp': 2 * npix, 'ups': npix * 4, 'uvem': npix * 4}
     bw = torch.zeros(30, device='cuda')
     acc_gdp = torch.zeros(30, device='cuda')
@@ -62,7 +64,9 @@ def loss_calls():
              ('uvem', lambda: ops.upsample_loss('uvem', p1, p2, lab, soft=soft, m=0.2, t=0.7, gamma=4.0, **kw)),
              ('gdp', lambda: ops.upsample_gdp(p1, p2, lab, acc_gdp, bw, g1=g1, g2=g2)),
              ('gdp +pw+cw', lambda: ops.upsample_gdp(p1, p2, lab, acc_gdp, bw, pixel_weight=pw, class_weight=cw, g1=g1,
-                                                     g2=g2))]
+                                                     g2=g2)),
+             ('reg', lambda: ops.upsample_reg(p1, p2, lab, lambda_ent=0.3, lambda_kld=0.1, g1=g1, g2=g2, accumulate=True,
+                                              empty_is_zero=True))]
     only = sys.argv[sys.argv.index('--only') + 1].split(',') if '--only' in sys.argv else None
     if only:
         runs = [r for r in runs if r[0] == 'ce' or r[0].split()[0] in only]
@@ -78,6 +82,27 @@ def loss_calls():
         for name, fn in (('proto_pixel_weight', lambda: ops.proto_pixel_weight(feat, protos, lab, out=pw_out)),
                          ('proto_pixel_weight sim=', lambda: ops.proto_pixel_weight(None, None, lab, sim=sim, out=pw_out))):
             print('%-24s %7.1f us' % (name, t_of(fn)), flush=True)
+    if only is None or 'iast' in only:
+        iast_stages(b, c, H, g)
+
+
+def iast_stages(n, c, H, g):
+    """The three stages of IASTSelector.update on random softmax probabilities and on all-confident ones (every pixel
+    exactly 1.0: one histogram bin per class takes every add)."""
+    conf = torch.zeros(n, c, H, H)
+    conf.scatter_(1, torch.randint(0, c, (n, 1, H, H), generator=g), 1.0)
+    inputs = (('uniform', torch.softmax(torch.randn(n, c, H, H, generator=g) * 3, 1).cuda()), ('confident', conf.cuda()))
+    prepend = torch.full((c,), 0.9, dtype=torch.float64, device='cuda')
+    q = torch.full((c,), 0.9139, dtype=torch.float64, device='cuda')
+    out = torch.empty(n, H, H, dtype=torch.uint8, device='cuda')
+    for name, probs in inputs:
+        ws = ops.iast_workspace(n, c, H, H, probs.device)
+        t_h = t_of(lambda: ops.iast_hist(probs, ws=ws))
+        t_p = t_of(lambda: ops.iast_percentile(ws, prepend, q))
+        t_l = t_of(lambda: ops.iast_label(ws, prepend, n, H, H, out=out))
+        mb = probs.numel() * 4 / 1e6
+        print('iast %-9s hist %7.1f us (%.0f MB of probabilities: %.2f TB/s)  percentile %6.1f us  label %6.1f us' %
+              (name, t_h, mb, mb / t_h, t_p, t_l), flush=True)
 
 
 def step_times():
@@ -87,15 +112,17 @@ def step_times():
     batch = make_batch(b=8, size=512, seed=2333, with_soft=True)
     protos = torch.randn(6, 2048, generator=torch.Generator().manual_seed(0))
     eager = '--eager' in sys.argv
-    only = sys.argv[sys.argv.index('--only') + 1].split(',') if '--only' in sys.argv else ('none', 'uvem', 'ohem', 'ghm', 'gdp')
-    for lt in [k for k in ('none', 'uvem', 'ohem', 'ghm', 'gdp') if k in only]:
+    only = sys.argv[sys.argv.index('--only') + 1].split(',') if '--only' in sys.argv else ('none', 'uvem', 'ohem', 'ghm', 'gdp',
+                                                                                          'reg')
+    for lt in [k for k in ('none', 'uvem', 'ohem', 'ghm', 'gdp', 'reg') if k in only]:
         torch.manual_seed(2333)
         model = Deeplabv2(dict(backbone=dict(resnet_type='resnet101', output_stride=16, pretrained=False),
                                multi_layer=True, cascade=False, use_ppm=True,
                                ppm=dict(num_classes=6, use_aux=False, fc_dim=2048), inchannels=2048, num_classes=6,
                                is_ins_norm=True))
         model.sync_weights()
-        st = SSLStep(model, protos, loss_t=lt)
+        # 'reg': the default target loss + IAST's entropy and KLD terms
+        st = SSLStep(model, protos, ent_weight=0.3, kld_weight=0.1) if lt == 'reg' else SSLStep(model, protos, loss_t=lt)
         args = (batch['images_s'], batch['label_s'], batch['images_t'], batch['soft_t'], batch['regs_t'])
         for _ in range(2):
             st.step(*args, 1e-3)
