@@ -1052,6 +1052,64 @@ int rgda_triplet_loss(const float* feat, int b, int hw, int64_t ldc, int64_t ldb
                       float margin, int has_ignore, int ignore_label, float* loss, void* dfeat, int lddf,
                       int accumulate, float weight, void* ws, size_t ws_bytes, rgda_stream_t stream);
 
+/* Deep Covariance Alignment (regda/dca_modules.py:20-188: CategoryAlign_Module.get_context :20-34,
+ * get_cross_corcoef_mat :47-57, regularize :59-76; ICR :79-105, CCR :108-133, MSE_intra :136-159, MSE_cross :162-188),
+ * forward + gradient w.r.t. the feature map in one call.  A side is b images: feat f32 (b, c, hw) addressed as in
+ * rgda_whiten_loss (ldc, ldb, read in place, once) and one or two prediction planes f32 (b, C, hw), contiguous.
+ * Definition, per side:
+ *   P (b, C, hw)  pred_kind 0: pred1 as given (probabilities);  1: softmax(pred1) over the classes;
+ *                 2: (softmax(pred1) + softmax(pred2)) / 2.  P is a constant: no gradient reaches the predictions.
+ *   Z[b][k] = sum_p P[b][k][p];   v[b][k][:] = sum_p feat[b][:][p] P[b][k][p] / Z[b][k]                     (:26-29)
+ *   ignore_bg != 0: class 0 is dropped, n = C - 1; else n = C                                                (:31-32)
+ *   u[b][k][ch] = v[b][k][ch] / max(sqrt(sum_k' v[b][k'][ch]^2), 1e-12) -- F.normalize(dim=1) runs over the CLASS axis,
+ *                 per image and channel                                                                      (:33)
+ *   kind 0 (cov): m_a = mean_b u_a, m_b = mean_b u_b (n, c);  R[i][j] = the Pearson coefficient of m_a[i][:] and
+ *                 m_b[j][:] over the c channels;  L = -mean_i log R[i][i] - mean_{i != j} log(1 - max(R[i][j], 1e-6)).
+ *                 An off-diagonal entry at or below 1e-6 carries no gradient; a non-positive diagonal entry gives a NaN
+ *                 (or infinite) loss as in the reference: nothing is clamped here.
+ *   kind 1 (mse): L = mean over (b, n, c) of (u_a - u_b)^2;  b_a == b_b.
+ *   CCR / MSE_cross: side a = the source without dfeat, side b = the target.  ICR / MSE_intra: the two sides are the
+ *   halves [:B / 2] and [B / 2:] of one batch, both with dfeat.
+ * Arithmetic (fp32 throughout, from the unrounded f32 features; no bf16 operand):
+ *   P       max-subtracted softmax: the hardware exp2 of (l - max) log2(e), the sum over the classes in ascending order,
+ *           one hardware reciprocal per pixel and map (each about one unit in the last place); formed per pixel in
+ *           registers in both passes and never written to memory
+ *   context one workgroup per (image, 64 channels) walks all pixels: wavefront q adds P x feat over the pixels 128 t + 32 q
+ *           + i (t ascending, four pixels per fp32 MFMA 16 x 16 x 4, fp32 operands); S = (q0 + q1) + (q2 + q3).  Z: thread
+ *           t < 128 adds the pixels t + 128 j, a butterfly per wavefront, (w0 + w1) + (w2 + w3).  v = S / Z, the sum of squares
+ *           over the classes in ascending order (fused), sqrt, u = v / max(., 1e-12).
+ *   cov     m = (sum_b u in ascending b) / b; centred by its mean over the channels; R = <a_i, b_j> / (sqrt(|a_i|^2)
+ *           sqrt(|b_j|^2)); channel sums: 256 strided partials, a butterfly per wavefront, (w0 + w1) + (w2 + w3);
+ *           L the same sum over the n * n entries;  loss[0] += weight * L
+ *   mse     one partial per 256 channels of an image, summed by one workgroup;  loss[0] += weight * sum / (b n c)
+ *   table   dL/dv in closed form (through u, the batch mean, R or the squared difference) divided by Z ->
+ *           G[b][k][ch], f32 (b, C, c) in the workspace; the row of a dropped class 0 is zero
+ *   dfeat (optional, per side) bf16 [b * hw][lddf], pixel-major -- the layout rgda_instnorm_bwd consumes: row b * hw + p,
+ *           channel ch = weight * sum_k P[b][k][p] G[b][k][ch] (k ascending, fused), rounded once.
+ *           accumulate != 0: the old bf16 value joins the fp32 one before the one rounding.  A side without dfeat gets no
+ *           gradient launch and its rows are not touched.
+ *   Two calls on the same inputs are bit-identical (no floating-point atomics).
+ * Before any launch: null feat / pred1 / loss / ws (pred2 with pred_kind 2; u for rgda_dca_context), ws not 256-byte
+ * aligned, c < 32 or c % 32 != 0, hw < 1, b < 1 on either side, pred_kind outside 0..2, kind outside 0..1, ldc < hw,
+ * ldb < ldc * c, a dfeat not 16-byte aligned, lddf % 8 != 0 or lddf < c, mse with b_a != b_b: RGDA_ERR_ARG; C outside
+ * 6..16: RGDA_ERR_UNSUPPORTED; a short workspace: RGDA_ERR_WORKSPACE.
+ * rgda_dca_context: one side -> u f32 (b, n, c), optionally v f32 (b, n, c) and Z f32 (b, C); ws:
+ *   rgda_dca_context_workspace(b, c) = a(4 b c) bytes, the class norms (b, c) before their clamp.
+ * rgda_dca_loss ws: rgda_dca_loss_workspace(b_a, b_b, c, C, ignore_bg) bytes (0 for arguments the entry point rejects) =
+ *   256 + sum over the sides of [a(4 b n c) + a(4 b c) + a(4 b C) + a(4 b C c)] + 2 a(8 n c) + a(4 (2 n + 2 n^2))
+ *   + a(4 ceil(c / 256) max(b_a, b_b)),   a(x) = x rounded up to a multiple of 256.  Layout, in this order: 256 spare
+ *   bytes; per side (a, then b) u (b, n, c), the class norms (b, c), Z (b, C), G (b, C, c); the centred means (2, n, c);
+ *   dL/dm (2, n, c); the squared norms of the centred means (2, n), R (n, n), dL/dR (n, n); the mse partials. */
+size_t rgda_dca_context_workspace(int b, int c);
+int rgda_dca_context(const float* feat, int b, int hw, int64_t ldc, int64_t ldb, const float* pred1, const float* pred2,
+                     int pred_kind, int c, int C, int ignore_bg, float* u, float* v, float* Z, void* ws, size_t ws_bytes,
+                     rgda_stream_t stream);
+size_t rgda_dca_loss_workspace(int b_a, int b_b, int c, int C, int ignore_bg);
+int rgda_dca_loss(const float* feat_a, int b_a, int64_t ldc_a, int64_t ldb_a, const float* pred1_a, const float* pred2_a,
+                  void* dfeat_a, const float* feat_b, int b_b, int64_t ldc_b, int64_t ldb_b, const float* pred1_b,
+                  const float* pred2_b, void* dfeat_b, int hw, int c, int C, int pred_kind, int ignore_bg, int kind,
+                  float* loss, int lddf, int accumulate, float weight, void* ws, size_t ws_bytes, rgda_stream_t stream);
+
 /* Factored form of the PPM heads' tap-shifted bilinear maps (regda/models/Encoder.py:30-51: Upsample(bilinear,
  * align_corners=False) of the s x s branches into the 3x3 / pad 1 conv_last): the map V[(y,x)][(jy,jx),(ky,kx)] =
  * Uy[y+ky-1][jy] * Ux[x+kx-1][jx] is separable, so V and V^T are applied as two short maps (csrc/mix_kernels.hip).

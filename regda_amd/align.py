@@ -12,6 +12,8 @@ rank 2), on the same kernel plans as the SSL step (regda_amd/ssl.py):
               argmax x2_t)) with contrast_weight > 0: an extension, tools/train_align_reg.py never constructs that loss]
            [+ triplet_weight * 0.5 * (TripletLoss(feat_s rows, label_s_down) + TripletLoss(feat_t rows, label_t)) with
               triplet_weight > 0: an extension, tools/train_align_reg.py never constructs that loss]
+           [+ dca_weight * (CCR(src, tgt) + ICR(src) + ICR(tgt)) on (x1, x2, feat) of each domain with dca_weight > 0
+              (regda/dca_modules.py, multi_layer=True): an extension, tools/train_align_reg.py never calls them]
     -> backward -> clip_grad_norm_(32) -> SGD
 
 Differences to the SSL step that matter for the kernels: there is no CE on the target logits (their gradient is
@@ -30,7 +32,10 @@ the (order, counts, anchors, ranks) the term used, or None), and so the batch-ha
 added last, on the downscaled labels the whitening term uses, the step's ignore label excluded; its margin is kept in
 `step.triplet` (a dict) and read at every step; `step.loss_triplet` holds the term and `step.last_triplet`, per domain, what the
 kernel left on the device: `stats` (int32: rows in the mean, positive hinges) and the per-row tables of
-ops.triplet_tables)."""
+ops.triplet_tables), and so the category alignment term (rgda_dca_loss, added after the triplet term: it needs no labels and
+no host draws, its predictions are the step's own head logits at feature resolution, taken as constants; its parameters
+are kept in `step.dca` (a dict: kind 'cov' or 'mse', ccr, icr, ignore_bg) and read at every step; `step.loss_dca` holds the
+term)."""
 import torch
 
 from . import ops
@@ -44,7 +49,12 @@ BF = torch.bfloat16
 
 class AlignStep(SSLStep):
     def __init__(self, model, prototypes, pcl_temperature=8.0, align_domain=False, whiten_weight=0.0, mmd=None,
-                 domain_weight=1.0, contrast_weight=0.0, triplet_weight=0.0, **kw):
+                 domain_weight=1.0, contrast_weight=0.0, triplet_weight=0.0, dca_weight=0.0, **kw):
+        # > 0: + dca_weight * (CCR(src, tgt) + ICR(src) + ICR(tgt)), regda/dca_modules.py with multi_layer=True
+        self.dca_weight = float(dca_weight)
+        if self.dca_weight < 0.0:
+            raise ValueError('AlignStep: dca_weight must be >= 0')
+        self.dca = dict(kind='cov', ccr=True, icr=True, ignore_bg=True)
         # > 0: + triplet_weight * 0.5 * (TripletLoss(source rows) + TripletLoss(target rows)), regda/gast/triple.py
         self.triplet_weight = float(triplet_weight)
         if self.triplet_weight < 0.0:
@@ -79,9 +89,13 @@ class AlignStep(SSLStep):
         self.last_contrast = [None, None]
         self.loss_triplet = torch.zeros(1, device=model.device)
         self.last_triplet = [None, None]
+        self.loss_dca = torch.zeros(1, device=model.device)
 
     def step(self, images_s, label_s, images_t, regs_t, lr):
         """One stage-2 iteration.  Returns device tensors (loss_seg, loss_align, grad_norm_sq)."""
+        if self.dca_weight > 0.0 and self.dca['icr'] and min(images_s.shape[0], images_t.shape[0]) < 2:
+            raise ValueError('AlignStep(dca_weight > 0): icr splits the batch of each domain in two; it needs at least two '
+                             'images per domain')
         self._check_shape(images_s, images_t)
         self.lr_dev.fill_(float(lr))
         with ops.use_stream(torch.cuda.current_stream()):
@@ -139,7 +153,7 @@ class AlignStep(SSLStep):
         n, k, h, w = feat.shape
         gfeat = torch.empty(n * h * w, k, dtype=BF, device=m.device)
         # per domain: features, full-size and downscaled labels, head-2 logits, its gradient rows.  Every term adds onto
-        # the rows in the order PCL, domain, whitening, contrast, triplet (bf16 accumulation depends on it)
+        # the rows in the order PCL, domain, whitening, contrast, triplet, DCA (bf16 accumulation depends on it)
         sides = ((feat_s, label_s, label_s_down, s2, gfeat[:nb * h * w]), (feat_t, label_t, label_t, t2, gfeat[nb * h * w:]))
         self.loss_align.zero_()
         for f, _, lab, _, rows in sides:
@@ -171,6 +185,19 @@ class AlignStep(SSLStep):
                 _, stats, ws = ops.triplet_loss(f, lab, self.triplet['margin'], self.ig, 0.5 * self.triplet_weight,
                                                 loss=self.loss_triplet, dfeat=rows, accumulate=True, return_ws=True)
                 self.last_triplet[side] = dict(ops.triplet_tables(ws, rows.shape[0]), stats=stats)
+        if self.dca_weight > 0.0:
+            self.loss_dca.zero_()
+            dc = self.dca
+            dom = ((feat_s, (s1, s2), sides[0][4], nb), (feat_t, (t1, t2), sides[1][4], n - nb))
+            if dc['ccr']:        # the source side is a constant: the target rows alone receive
+                ops.dca_loss(feat_s, (s1, s2), feat_t, (t1, t2), 'logits2', dc['kind'], dc['ignore_bg'], self.dca_weight,
+                             loss=self.loss_dca, dfeat_b=sides[1][4], accumulate=True)
+            if dc['icr']:
+                for f, (p1, p2), rows, bd in dom:
+                    q = bd // 2
+                    ops.dca_loss(f[:q], (p1[:q], p2[:q]), f[q:], (p1[q:], p2[q:]), 'logits2', dc['kind'], dc['ignore_bg'],
+                                 self.dca_weight, loss=self.loss_dca, dfeat_a=rows[:q * h * w], dfeat_b=rows[q * h * w:],
+                                 accumulate=True)
         self._backward_and_update(T, main, g1, g2, gfeat=gfeat)
         self.last_hard, self.last_label_t, self.last_label_s_down = hard, label_t, label_s_down
         return loss_seg, self.loss_align, self.gn
