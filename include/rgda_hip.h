@@ -1110,6 +1110,59 @@ int rgda_dca_loss(const float* feat_a, int b_a, int64_t ldc_a, int64_t ldb_a, co
                   const float* pred2_b, void* dfeat_b, int hw, int c, int C, int pred_kind, int ignore_bg, int kind,
                   float* loss, int lddf, int accumulate, float weight, void* ws, size_t ws_bytes, rgda_stream_t stream);
 
+/* Semantic-aware whitening (regda/gast/SAW.py:54-107: SAW of Peng et al., CVPR 2022), forward + gradient w.r.t. the
+ * feature map in one call.  feat f32 (b, k, hw) is addressed as in rgda_whiten_loss (ldc, ldb, read in place);
+ * cls_w f32 (n_cls, k) on the device, row r at cls_w + r * ldw: the classifier weight; selected int32 [C] in HOST memory:
+ * the rows of cls_w that take part, distinct, each in [0, n_cls).
+ * Definition:
+ *   A = |cls_w|;  G = k / C (integer division).  For class j the channels are ranked by A[selected[j]] in descending
+ *   order; equal values rank by the lower channel index (the reference's torch.sort leaves ties unspecified; this rule is
+ *   part of the contract).  Slot (g, j), g < G: ch[g][j] = the channel of rank g, wgh[g][j] = sigmoid(A[selected[j]][ch]).
+ *   Ranks >= G fill no slot; a channel fills at most one slot per class; two classes may put one channel into one group.
+ *   xt[b][g][j][p] = wgh[g][j] * feat[b][ch[g][j]][p];  cov[b][g] = xt xt^T / (hw - 1) (C x C, no mean centring; the
+ *   reference's eps * I lies on the diagonal, which the strict upper triangle never reads)
+ *   s[b][g] = sum over j < j' of |cov_jj'|;  nod = C (C - 1) / 2;  `margin` is the caller's (the reference: 0 when
+ *   relax_denom == 0, else nod // relax_denom)
+ *   L = sum_g sum_b max((s[b][g] - margin) / nod, 0) / b;   loss[0] += weight * L
+ *   For a (b, g) with s > margin ("active"):  dL/dxt_j[p] = sum_{j' != j} sign(cov_jj') xt_j'[p] / (b nod (hw - 1)),
+ *   sign(0) = 0;  dL/dfeat[b][c][p] = the sum over the slots (g, j) of channel c of wgh[g][j] dL/dxt_j[p].  cls_w
+ *   receives no gradient.
+ * Arithmetic (fp32 throughout, from the unrounded f32 features; the one bf16 value is the stored gradient):
+ *   plan    rank(c) = the number of channels with larger A, or equal A and lower index -- counted, not sorted, on the
+ *           device.  wgh: the sigmoid evaluated in double and rounded once.  A non-finite weight sets bit 0 of the flag
+ *           word and ranks as +inf; the loss and the gradient of such a call are unspecified, but nothing faults.
+ *   gram    one workgroup per (b, g): xt = wgh * x (one rounding); per pair, thread t adds the products of the pixels
+ *           t + 256 i in ascending i, a butterfly per wavefront, (w0 + w1) + (w2 + w3); cov = dot / (hw - 1); s adds
+ *           |cov| in pair order (j, j') row-major; active = s > margin; partial = (s - margin) / nod
+ *   loss    loss[0] += (weight / b) * sum of the partials (256 strided partials, a butterfly per wavefront,
+ *           (w0 + w1) + (w2 + w3))
+ *   slots   for an active (b, g): wgh_j coef sum_j' sign_jj' xt_j'[p] (j' ascending), coef = weight / (b nod (hw - 1)),
+ *           f32 (b, G, C, hw) in the workspace
+ *   dfeat (optional) bf16 [b * hw][lddf], pixel-major -- the layout rgda_instnorm_bwd consumes: channel c of row
+ *           b * hw + p = the sum of the slot gradients of c in class order (a gather through the inverse table: no
+ *           floating-point atomics, no scattered adds), rounded once.
+ *           accumulate == 0: every row is written in its first k columns; a channel that fills no slot, or whose groups
+ *           are all inactive in that image, as zeros.
+ *           accumulate != 0: added in fp32 to the old bf16 value, rounded once; those channels are left untouched.
+ *   Two calls on the same inputs are bit-identical.
+ * Served: C in {2, 4, 6, 8, 16} (the reference asserts it), C <= k <= 4096, hw >= 2 (the division by hw - 1),
+ * b * hw <= 2^24 (and b * G < 2^31): RGDA_ERR_UNSUPPORTED otherwise.  Before any launch: null feat / cls_w / selected /
+ * loss / ws, b, k or n_cls < 1, ldw < k, a negative or NaN margin, a selected entry outside [0, n_cls) or repeated,
+ * ldc < hw, ldb < ldc * k, dfeat not 16-byte aligned, lddf % 8 != 0 or lddf < k, ws not 256-byte aligned: RGDA_ERR_ARG;
+ * a short workspace: RGDA_ERR_WORKSPACE.
+ * ws: rgda_saw_loss_workspace(b, hw, k, C) bytes (0 for arguments the entry point rejects) =
+ *   256 + a(TS b G) + 2 a(4 b G) + 2 a(4 G C) + a(4 k C) + a(4 b G C hw),   TS = 4 * ceil((nod + 1) / 4),
+ *   a(x) = x rounded up to a multiple of 256.  A call without dfeat accepts a workspace without the last term.
+ *   Layout, in this order: 256 bytes whose first int32 is the flag word; the per-(b, g) table, TS bytes each: byte 0 the
+ *   active bit, bytes 1 .. nod the pair signs as int8 (-1, 0, 1), pairs (j, j'), j < j', row-major; s f32 (b, G); the
+ *   partial losses f32 (b, G); ch int32 (G, C); wgh f32 (G, C); the inverse table int32 (k, C): the rank g of the slot
+ *   channel c fills for class j, or -1; the slot gradients. */
+size_t rgda_saw_loss_workspace(int b, int hw, int k, int C);
+int rgda_saw_loss(const float* feat, int b, int hw, int64_t ldc, int64_t ldb, int k,
+                  const float* cls_w, int n_cls, int64_t ldw, const int32_t* selected, int C, float margin,
+                  float* loss, void* dfeat, int lddf, int accumulate, float weight,
+                  void* ws, size_t ws_bytes, rgda_stream_t stream);
+
 /* Factored form of the PPM heads' tap-shifted bilinear maps (regda/models/Encoder.py:30-51: Upsample(bilinear,
  * align_corners=False) of the s x s branches into the 3x3 / pad 1 conv_last): the map V[(y,x)][(jy,jx),(ky,kx)] =
  * Uy[y+ky-1][jy] * Ux[x+kx-1][jx] is separable, so V and V^T are applied as two short maps (csrc/mix_kernels.hip).

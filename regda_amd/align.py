@@ -14,6 +14,8 @@ rank 2), on the same kernel plans as the SSL step (regda_amd/ssl.py):
               triplet_weight > 0: an extension, tools/train_align_reg.py never constructs that loss]
            [+ dca_weight * (CCR(src, tgt) + ICR(src) + ICR(tgt)) on (x1, x2, feat) of each domain with dca_weight > 0
               (regda/dca_modules.py, multi_layer=True): an extension, tools/train_align_reg.py never calls them]
+           [+ saw_weight * 0.5 * (SAW(feat_s) + SAW(feat_t)) with saw_weight > 0 (regda/gast/SAW.py, the prototypes as the
+              classifier): an extension, tools/train_align_reg.py never constructs that loss]
     -> backward -> clip_grad_norm_(32) -> SGD
 
 Differences to the SSL step that matter for the kernels: there is no CE on the target logits (their gradient is
@@ -35,7 +37,17 @@ kernel left on the device: `stats` (int32: rows in the mean, positive hinges) an
 ops.triplet_tables), and so the category alignment term (rgda_dca_loss, added after the triplet term: it needs no labels and
 no host draws, its predictions are the step's own head logits at feature resolution, taken as constants; its parameters
 are kept in `step.dca` (a dict: kind 'cov' or 'mse', ccr, icr, ignore_bg) and read at every step; `step.loss_dca` holds the
-term)."""
+term), and so the semantic-aware whitening term (rgda_saw_loss, added after the DCA term; it needs no labels either.  Its
+parameters are kept in `step.saw` (a dict: relax_denom, selected_classes, classifier) and read at every step;
+`step.loss_saw` holds the term.  classifier None: the step's prototypes, after this step's EMA update, as PCL sees them --
+stage 2's PCL is a cosine classifier on `feat` with the prototypes as weights, so they are the (C, k) classifier this model
+has on that tensor; the PPM / ASPP heads have no 2-D weight on `feat`.  A caller's (n_cls, k) tensor or module replaces
+them.  selected_classes None: range(C) where C is one of the served counts 2, 4, 6, 8, 16; any other C (LoveDA's 7) needs
+a selection.  relax_denom defaults to 0 here, not to the reference's 2.0: `feat` is instance-normalised and the weights are
+sigmoids below 1, so each |cov| stays near or below 1 and a group's sum s over its 15 pairs (C = 6) rarely exceeds the
+margin 15 // 2.0 = 7 -- the term would be identically zero: on the features of the CPU oracle's untrained network the mean
+s was 1.3, and even with strongly correlated unit-variance features on the CPU it was 8.2, with 36 % of the groups clamped
+at that margin)."""
 import torch
 
 from . import ops
@@ -47,9 +59,28 @@ from .ssl import SSLStep
 BF = torch.bfloat16
 
 
+def saw_selection(class_num, selected_classes):
+    """The classes of the SAW term: the caller's selection, or every class where their number is one SAW serves.  The
+    step asks at every iteration (step.saw is read then), before it launches anything."""
+    if selected_classes is None:
+        if class_num not in ops.SAW_CLASS_COUNTS:
+            raise ValueError(f"AlignStep(saw_weight > 0): {class_num} classes, and SAW serves {ops.SAW_CLASS_COUNTS} selected "
+                             f"classes: set step.saw['selected_classes'] to that many of them")
+        selected_classes = range(class_num)
+    sel = [int(c) for c in selected_classes]
+    if len(sel) not in ops.SAW_CLASS_COUNTS:
+        raise ValueError(f"AlignStep(saw_weight > 0): {len(sel)} selected classes; SAW serves {ops.SAW_CLASS_COUNTS}")
+    return sel
+
+
 class AlignStep(SSLStep):
     def __init__(self, model, prototypes, pcl_temperature=8.0, align_domain=False, whiten_weight=0.0, mmd=None,
-                 domain_weight=1.0, contrast_weight=0.0, triplet_weight=0.0, dca_weight=0.0, **kw):
+                 domain_weight=1.0, contrast_weight=0.0, triplet_weight=0.0, dca_weight=0.0, saw_weight=0.0, **kw):
+        # > 0: + saw_weight * 0.5 * (SAW(feat_s) + SAW(feat_t)), regda/gast/SAW.py on the prototypes (or step.saw['classifier'])
+        self.saw_weight = float(saw_weight)
+        if self.saw_weight < 0.0:
+            raise ValueError('AlignStep: saw_weight must be >= 0')
+        self.saw = dict(relax_denom=0.0, selected_classes=None, classifier=None)
         # > 0: + dca_weight * (CCR(src, tgt) + ICR(src) + ICR(tgt)), regda/dca_modules.py with multi_layer=True
         self.dca_weight = float(dca_weight)
         if self.dca_weight < 0.0:
@@ -90,12 +121,15 @@ class AlignStep(SSLStep):
         self.loss_triplet = torch.zeros(1, device=model.device)
         self.last_triplet = [None, None]
         self.loss_dca = torch.zeros(1, device=model.device)
+        self.loss_saw = torch.zeros(1, device=model.device)
 
     def step(self, images_s, label_s, images_t, regs_t, lr):
         """One stage-2 iteration.  Returns device tensors (loss_seg, loss_align, grad_norm_sq)."""
         if self.dca_weight > 0.0 and self.dca['icr'] and min(images_s.shape[0], images_t.shape[0]) < 2:
             raise ValueError('AlignStep(dca_weight > 0): icr splits the batch of each domain in two; it needs at least two '
                              'images per domain')
+        if self.saw_weight > 0.0:
+            saw_selection(self.C, self.saw['selected_classes'])
         self._check_shape(images_s, images_t)
         self.lr_dev.fill_(float(lr))
         with ops.use_stream(torch.cuda.current_stream()):
@@ -153,7 +187,7 @@ class AlignStep(SSLStep):
         n, k, h, w = feat.shape
         gfeat = torch.empty(n * h * w, k, dtype=BF, device=m.device)
         # per domain: features, full-size and downscaled labels, head-2 logits, its gradient rows.  Every term adds onto
-        # the rows in the order PCL, domain, whitening, contrast, triplet, DCA (bf16 accumulation depends on it)
+        # the rows in the order PCL, domain, whitening, contrast, triplet, DCA, SAW (bf16 accumulation depends on it)
         sides = ((feat_s, label_s, label_s_down, s2, gfeat[:nb * h * w]), (feat_t, label_t, label_t, t2, gfeat[nb * h * w:]))
         self.loss_align.zero_()
         for f, _, lab, _, rows in sides:
@@ -198,6 +232,15 @@ class AlignStep(SSLStep):
                     ops.dca_loss(f[:q], (p1[:q], p2[:q]), f[q:], (p1[q:], p2[q:]), 'logits2', dc['kind'], dc['ignore_bg'],
                                  self.dca_weight, loss=self.loss_dca, dfeat_a=rows[:q * h * w], dfeat_b=rows[q * h * w:],
                                  accumulate=True)
+        if self.saw_weight > 0.0:
+            from .gast.SAW import classifier_weight
+            self.loss_saw.zero_()
+            sw = self.saw
+            cls_w = self.prototypes if sw['classifier'] is None else classifier_weight(sw['classifier']).to(m.device)
+            sel = saw_selection(self.C, sw['selected_classes'])
+            for f, _, _, _, rows in sides:
+                ops.saw_loss(f, cls_w, sel, sw['relax_denom'], 0.5 * self.saw_weight, loss=self.loss_saw, dfeat=rows,
+                             accumulate=True)
         self._backward_and_update(T, main, g1, g2, gfeat=gfeat)
         self.last_hard, self.last_label_t, self.last_label_s_down = hard, label_t, label_s_down
         return loss_seg, self.loss_align, self.gn

@@ -1707,6 +1707,72 @@ def dca_loss(feat_a, preds_a, feat_b, preds_b, pred_kind='logits2', kind='cov', 
     return (loss, ws) if return_ws else loss
 
 
+SAW_CLASS_COUNTS = (2, 4, 6, 8, 16)      # len(selected_classes) rgda_saw_loss serves (the reference asserts the same set)
+SAW_MAX_CHANNELS = 4096
+
+
+def saw_margin(C, relax_denom):
+    """SAW.__init__'s margin (regda/gast/SAW.py:33-37): 0 for relax_denom == 0, else nod // relax_denom (floor division)"""
+    nod = float(C * (C - 1) // 2)
+    return 0.0 if relax_denom == 0 else float(nod // relax_denom)
+
+
+def saw_loss(feat, cls_w, selected_classes, relax_denom=2.0, weight=1.0, loss=None, dfeat=None, accumulate=False,
+             check=False, return_ws=False):
+    """SAW(classifier, selected_classes, relax_denom)(feat) (regda/gast/SAW.py) on rgda_saw_loss: feat f32 (b, k, h, w),
+    read in place through its channel and image strides when the pixels of an image are contiguous, copied otherwise;
+    cls_w f32 (n_cls, k) on the device, the classifier weight (a constant: it receives no gradient; its channels are
+    ranked on the device, so a weight that changes every step costs no host sync); selected_classes: 2, 4, 6, 8 or 16
+    distinct rows of cls_w.  Equal |w| rank by the lower channel index.  loss (f32[1]) += weight * L; dfeat (optional)
+    bf16 [b*h*w, >= k] pixel-major rows: (+)= weight * dL / dfeat (accumulate=False writes every row; channels that take
+    no part as zeros).  check=True reads the flag word back (one host sync) and raises ValueError on a non-finite weight.
+    Returns the (accumulating) fp32 loss tensor (and the workspace with return_ws; saw_tables reads it)."""
+    import ctypes
+    _need_cuda(feat, cls_w, dfeat)
+    assert feat.dim() == 4, 'saw_loss: NCHW (b, k, h, w) features'
+    feat, b, hw, ldc, ldb, k = _feat_rows(feat, 'saw_loss')
+    sel = [int(c) for c in selected_classes]
+    C = len(sel)
+    if C not in SAW_CLASS_COUNTS:
+        raise ValueError(f'saw_loss: {C} selected classes; served are {SAW_CLASS_COUNTS}')
+    cls_w = cls_w.detach()
+    assert cls_w.dim() == 2 and cls_w.shape[1] == k, (cls_w.shape, k)
+    if cls_w.dtype != torch.float32 or cls_w.stride(1) != 1:
+        cls_w = cls_w.float().contiguous()
+    sel_host = (ctypes.c_int32 * C)(*sel)
+    loss = _loss_out(loss, feat.device)
+    L = lib()
+    ws = _ws(L.size('rgda_saw_loss_workspace', b, hw, k, C), feat.device)
+    L.call('rgda_saw_loss', feat.data_ptr(), b, hw, ldc, ldb, k, cls_w.data_ptr(), cls_w.shape[0], cls_w.stride(0),
+           sel_host, C, saw_margin(C, relax_denom), loss.data_ptr(), *_grad_rows(dfeat, b * hw), int(bool(accumulate)),
+           float(weight), ws.data_ptr(), ws.numel(), _stream())
+    if check and int(ws[:4].view(torch.int32).item()) & 1:
+        raise ValueError('saw_loss: a classifier weight is not finite')
+    return (loss, ws) if return_ws else loss
+
+
+def saw_tables(ws, b, k, C):
+    """What rgda_saw_loss left in its workspace (the layout of include/rgda_hip.h), for diagnostics and tests -> dict:
+    flag (int), ch int32 [G, C] and wgh f32 [G, C] (the slot tables), inv int32 [k, C] (the rank of the slot a channel
+    fills for a class, -1: none), active bool [b, G], signs int8 [b, G, nod] (pairs (j, j'), j < j', row-major),
+    s f32 [b, G]."""
+    a = lambda x: (x + 255) // 256 * 256      # noqa: E731
+    G, nod = k // C, C * (C - 1) // 2
+    TS = (nod + 1 + 3) // 4 * 4
+    o = 256
+    tab = ws[o:o + b * G * TS].view(torch.int8).view(b, G, TS)
+    o += a(b * G * TS)
+    s = ws[o:o + 4 * b * G].view(torch.float32).view(b, G)
+    o += 2 * a(4 * b * G)
+    ch = ws[o:o + 4 * G * C].view(torch.int32).view(G, C)
+    o += a(4 * G * C)
+    wgh = ws[o:o + 4 * G * C].view(torch.float32).view(G, C)
+    o += a(4 * G * C)
+    inv = ws[o:o + 4 * k * C].view(torch.int32).view(k, C)
+    return dict(flag=int(ws[:4].view(torch.int32).item()), ch=ch, wgh=wgh, inv=inv, active=tab[:, :, 0] != 0,
+                signs=tab[:, :, 1:1 + nod], s=s)
+
+
 # ---------------------------------------------------------------- ASPP head (Classifier_Module)
 def _ptr_array(tensors):
     import ctypes
