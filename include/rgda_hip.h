@@ -1163,6 +1163,65 @@ int rgda_saw_loss(const float* feat, int b, int hw, int64_t ldc, int64_t ldb, in
                   float* loss, void* dfeat, int lddf, int accumulate, float weight,
                   void* ws, size_t ws_bytes, rgda_stream_t stream);
 
+/* Transferable Normalization (regda/trans_norm.py:169-230: _TransNorm.forward of Wang et al., NeurIPS 2019; the two
+ * F.batch_norm calls, the four reductions over permuted copies, the cat and the Python sum over the channels), forward
+ * and backward, training and eval mode.
+ * x f32: n samples of C channels of s values; element (i, c, p) at x[i * ldb + c * ldc + p], p < s contiguous (the
+ * addressing of rgda_saw_loss; a 2-D (n, C) input is s = 1, ldc = 1, ldb >= C), read in place.  y, g and dx are f32 with
+ * strides of their own and must not overlap x.  weight / bias f32 [C], both or neither (NULL: 1 and 0).  rm_s, rv_s,
+ * rm_t, rv_t f32 [C]: running mean / variance of the source and target domain, all four or none (NULL: not tracked;
+ * training only).  saved f32 [5][C]: mean_s, rstd_s, mean_t, rstd_t, alpha -- written by the forward, read by the backward.
+ * Definition, training != 0:  samples [0, n_src) are the source domain (d = s), [n_src, n) the target domain (d = t);
+ *   mean_d, varb_d (biased), varu_d (unbiased) over the n_d * s values of channel c in domain d
+ *   rstd_d = 1 / sqrt(varb_d + eps);   z = (x - mean_d) * rstd_d * weight + bias
+ *   running: r = (1 - momentum) * r + momentum * stat, stat = mean_d for rm_d, varu_d for rv_d (updated in place)
+ *   dis = |mean_s / sqrt(varu_s + eps) - mean_t / sqrt(varu_t + eps)|;  prob = 1 / (1 + dis);
+ *   alpha = C * prob / sum_c prob;   y = z * (1 + alpha)
+ *   backward (alpha is a constant), a = 1 + alpha, gh = g * a * weight, xhat = (x - mean_d) * rstd_d:
+ *   dx = rstd_d * (gh - mean_d(gh) - xhat * mean_d(gh * xhat));  dweight = sum of g * a * xhat;  dbias = sum of g * a
+ * training == 0:  mean = rm_t, rstd = 1 / sqrt(rv_t + eps) for every sample (n_src is not read); alpha from the four
+ *   running vectors by the formulae above; nothing is updated; saved holds (rm_s, 1 / sqrt(rv_s + eps), rm_t,
+ *   1 / sqrt(rv_t + eps), alpha);  dx = g * a * weight * rstd_t, dweight and dbias as above with the target's xhat.
+ * Arithmetic:
+ *   stats    a thread keeps shifted sums about the first value x0 it reads, sum (x - x0) and sum (x - x0)^2 in fp32, and
+ *            turns them into a record (count, mean, M2) in double; the records of a wavefront (a tree: lanes (l, l + 32),
+ *            then 16, 8, 4, 2, 1), of the four wavefronts ((w0, w1), (w2, w3)) and of the K workgroups of a (channel,
+ *            domain) (ascending) are merged by Chan's formula in double.  No sum of squares of the raw values is formed:
+ *            |mean| >> std loses nothing.
+ *   finalize double: varb = M2 / count, varu = M2 / (count - 1); mean and rstd rounded once to fp32; the running
+ *            update evaluated in double from the old fp32 value and rounded once; prob rounded to fp32, sum_c prob in
+ *            double over those (one workgroup of 1024: thread t adds the channels t + 1024 i in ascending i, the
+ *            wavefront tree, the 16 wavefronts in ascending order), alpha = C * prob / sum rounded once.  Equal halves give dis = 0 and alpha = 1.0 exactly.
+ *   apply    double from the fp32 constants of the saved block, each operation rounded once in the order
+ *            ((x - mean) * rstd * w + b) * (1 + alpha), never contracted; y is that value rounded once to fp32.
+ *   backward sum g and sum g * xhat: fp32 within a thread, the same trees in double; dweight = a * (sum_s + sum_t) and
+ *            dbias likewise, rounded once; per domain A = rstd a w, B = A sum(g) / count, D = A sum(g xhat) / count
+ *            (double, rounded once to fp32);  dx = (A * g - B) - xhat * D in double from those, rounded once.
+ *   Two calls on the same inputs are bit-identical (no floating-point atomics).
+ * Launches: training forward 3 (stats, finalize, apply; x read twice), eval forward 2, backward 3 (reduce, finalize,
+ *   apply; g and x read twice each; eval without dweight / dbias: the apply alone; dx == NULL: no apply).  Nothing of
+ *   the input's size is written in between.  s >= 16: threads run along the planes (16-byte loads where s % 4 == 0 and
+ *   every base and stride is 16-byte aligned, 4-byte loads otherwise); s < 16: threads run along the channels.
+ * Served: C <= 2^20, n * s <= 2^30; training: 1 <= n_src < n and n_src * s >= 2 and (n - n_src) * s >= 2 (the unbiased
+ *   variance of each half): RGDA_ERR_UNSUPPORTED otherwise.  Before any launch: null x / y (g) / saved / ws, n, C or
+ *   s < 1, eps negative or NaN, momentum outside [0, 1], one of weight / bias without the other, some but not all of the
+ *   running vectors, training == 0 without them, n_src outside [0, n], ldc < s, ldb < ldc * C (of any map), ws not
+ *   256-byte aligned: RGDA_ERR_ARG; a short workspace: RGDA_ERR_WORKSPACE.
+ * ws: rgda_transnorm_fwd_workspace / _bwd_workspace (n, n_src, C, s, training) bytes, 0 for sizes the entry points do
+ *   not serve: the records, double [C][2][K][3] (forward) or double [C][2][K][2] then the coefficients f32 [6][C]
+ *   (backward), each rounded up to 256 bytes; K <= 64 is the library's split of a (channel, domain), and the query
+ *   returns enough for every alignment of the maps. */
+size_t rgda_transnorm_fwd_workspace(int n, int n_src, int C, int s, int training);
+int rgda_transnorm_fwd(const float* x, int n, int n_src, int C, int s, int64_t ldc, int64_t ldb, const float* weight,
+                       const float* bias, float* rm_s, float* rv_s, float* rm_t, float* rv_t, float eps, float momentum,
+                       int training, float* y, int64_t ldc_y, int64_t ldb_y, float* saved, void* ws, size_t ws_bytes,
+                       rgda_stream_t stream);
+size_t rgda_transnorm_bwd_workspace(int n, int n_src, int C, int s, int training);
+int rgda_transnorm_bwd(const float* g, int64_t ldc_g, int64_t ldb_g, const float* x, int n, int n_src, int C, int s,
+                       int64_t ldc, int64_t ldb, const float* weight, const float* saved, int training, float* dx,
+                       int64_t ldc_dx, int64_t ldb_dx, float* dweight, float* dbias, void* ws, size_t ws_bytes,
+                       rgda_stream_t stream);
+
 /* Factored form of the PPM heads' tap-shifted bilinear maps (regda/models/Encoder.py:30-51: Upsample(bilinear,
  * align_corners=False) of the s x s branches into the 3x3 / pad 1 conv_last): the map V[(y,x)][(jy,jx),(ky,kx)] =
  * Uy[y+ky-1][jy] * Ux[x+kx-1][jx] is separable, so V and V^T are applied as two short maps (csrc/mix_kernels.hip).

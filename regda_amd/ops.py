@@ -1773,6 +1773,80 @@ def saw_tables(ws, b, k, C):
                 signs=tab[:, :, 1:1 + nod], s=s)
 
 
+# ---------------------------------------------------------------- TransNorm (regda/trans_norm.py)
+TRANSNORM_PLANE_MIN = 16      # s >= 16: threads along the planes; below: along the channels (csrc/transnorm_kernels.hip)
+
+
+def _plane_view(x, who):
+    """_feat_rows for a normalisation layer -> (f32 tensor, n, C, s, ld_channel, ld_sample): an NCHW map as there, or
+    (n, C) rows read in place (s = 1) when the channels are contiguous, so that a column or row slice is not copied."""
+    if x.dim() == 2:
+        if x.dtype != torch.float32 or (x.shape[1] > 1 and x.stride(1) != 1) or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+            x = x.float().contiguous()
+        n, C = x.shape
+        return x, n, C, 1, 1, (x.stride(0) if n > 1 else C)
+    x, n, s, ldc, ldb, C = _feat_rows(x, who)
+    return x, n, C, s, ldc, ldb
+
+
+def _plane_out(out, like, who):
+    """The strides of an output map: `out` when given (f32, the shape of `like`, planes contiguous), else a new
+    contiguous tensor -> (tensor, ld_channel, ld_sample)."""
+    if out is None:
+        out = torch.empty(like.shape, dtype=torch.float32, device=like.device)
+    assert out.shape == like.shape and out.dtype == torch.float32 and out.is_cuda, (who, out.shape, out.dtype)
+    o, n, C, s, ldc, ldb = _plane_view(out, who)
+    if o.data_ptr() != out.data_ptr():
+        raise ValueError(f'{who}: the output buffer needs contiguous planes (strides {out.stride()})')
+    return out, ldc, ldb
+
+
+def transnorm_forward(x, n_src, weight, bias, running, eps=1e-5, momentum=0.1, training=True, out=None):
+    """_TransNorm.forward (regda/trans_norm.py:169-230) on rgda_transnorm_fwd.  x f32 (n, C, h, w) or (n, C), read in
+    place through its strides when its planes are contiguous; the first n_src samples are the source half.  weight / bias
+    f32 [C] or None; running: (running_mean_source, running_var_source, running_mean_target, running_var_target) f32 [C],
+    updated in place when training, or None (training only).  Returns (y, saved): y f32 of x's shape (`out` when given: a
+    buffer with contiguous planes, written in place) and saved f32 [5, C] = mean_s, rstd_s, mean_t, rstd_t, alpha for
+    transnorm_backward."""
+    _need_cuda(x, weight, bias, out, *(running or ()))
+    x, n, C, s, ldc, ldb = _plane_view(x.detach(), 'transnorm_forward')
+    y, ldcy, ldby = _plane_out(out, x, 'transnorm_forward')
+    for t in (weight, bias) + tuple(running or ()):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == C), 'transnorm: f32 [C] vectors'
+    rm_s, rv_s, rm_t, rv_t = running if running is not None else (None,) * 4
+    saved = torch.empty((5, C), dtype=torch.float32, device=x.device)
+    L = lib()
+    ws = _ws(L.size('rgda_transnorm_fwd_workspace', n, int(n_src), C, s, int(bool(training))), x.device)
+    L.call('rgda_transnorm_fwd', x.data_ptr(), n, int(n_src), C, s, ldc, ldb, _p(weight), _p(bias), _p(rm_s), _p(rv_s),
+           _p(rm_t), _p(rv_t), float(eps), float(momentum), int(bool(training)), y.data_ptr(), ldcy, ldby, saved.data_ptr(),
+           ws.data_ptr(), ws.numel(), _stream())
+    return y, saved
+
+
+def transnorm_backward(g, x, saved, n_src, weight, training=True, need_dx=True, need_dparams=True, dx=None):
+    """The gradient of transnorm_forward (rgda_transnorm_bwd): g, x f32 of one shape, read in place like x there; saved:
+    the forward's block.  Returns (dx, dweight, dbias): dx f32 of x's shape (`dx` when given) or None without need_dx,
+    dweight / dbias f32 [C] or None without need_dparams."""
+    _need_cuda(g, x, saved, weight, dx)
+    assert g.shape == x.shape, (g.shape, x.shape)
+    x, n, C, s, ldc, ldb = _plane_view(x.detach(), 'transnorm_backward')
+    g, _, _, _, ldcg, ldbg = _plane_view(g.detach(), 'transnorm_backward')
+    assert saved.shape == (5, C) and saved.dtype == torch.float32 and saved.is_contiguous()
+    assert weight is None or (weight.dtype == torch.float32 and weight.is_contiguous() and weight.numel() == C)
+    ldcd = ldbd = 0
+    if need_dx or dx is not None:
+        dx, ldcd, ldbd = _plane_out(dx, x, 'transnorm_backward')
+    dw = db = None
+    if need_dparams:
+        dw = torch.empty(C, dtype=torch.float32, device=x.device)
+        db = torch.empty(C, dtype=torch.float32, device=x.device)
+    L = lib()
+    ws = _ws(L.size('rgda_transnorm_bwd_workspace', n, int(n_src), C, s, int(bool(training))), x.device)
+    L.call('rgda_transnorm_bwd', g.data_ptr(), ldcg, ldbg, x.data_ptr(), n, int(n_src), C, s, ldc, ldb, _p(weight),
+           saved.data_ptr(), int(bool(training)), _p(dx), ldcd, ldbd, _p(dw), _p(db), ws.data_ptr(), ws.numel(), _stream())
+    return dx, dw, db
+
+
 # ---------------------------------------------------------------- ASPP head (Classifier_Module)
 def _ptr_array(tensors):
     import ctypes
