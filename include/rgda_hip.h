@@ -1222,6 +1222,64 @@ int rgda_transnorm_bwd(const float* g, int64_t ldc_g, int64_t ldb_g, const float
                        int64_t ldc_dx, int64_t ldb_dx, float* dweight, float* dbias, void* ws, size_t ws_bytes,
                        rgda_stream_t stream);
 
+/* ------------------------------------------------ output-space adversarial alignment (csrc/adv_kernels.hip)
+ * FCDiscriminator (regda/models/Discriminator.py:4-28: four Conv2d(4, stride 2, pad 1) + LeakyReLU(0.2) and a
+ * one-channel Conv2d of the same geometry) on pixel-major bf16 rows, fed by the softmax of the upsampled logits
+ * (AdaptSegNet, Tsai et al. 2018; the upsample is loss_calc's, regda/loss.py: bilinear, align_corners=True).  All
+ * activations are DENSE rows (row stride = channel count).  Deterministic: fixed summation orders, no floating-point
+ * atomics.  Every check comes before any launch; every row buffer must stay below 2^31 bytes (RGDA_ERR_UNSUPPORTED).
+ *
+ * rgda_adv_probs_fwd: x f32 (b, C, h, w) -> P bf16 [b*H*W][Cp], Cp = 16 (anything else: RGDA_ERR_UNSUPPORTED), channels
+ *   C .. Cp-1 zero.  mode 0: softmax over the classes of the bilinear (align_corners=True) upsample to H x W; mode 1: x
+ *   holds probabilities of size H x W (h == H, w == W) and is only packed.  6 <= C <= 16.  P 16-byte aligned.  One launch.
+ * rgda_adv_probs_bwd: dx f32 (b, C, h, w) += scale * (the transpose of that map applied to dP bf16 [b*H*W][Cp]).  mode 0:
+ *   the softmax backward with the probabilities recomputed from x in f32, then the transpose of the bilinear map in its
+ *   gather form: one workgroup per low-resolution pixel, fixed order.  mode 1: x is not read (may be NULL).  One launch.
+ *   Replaces F.softmax / F.interpolate and their autograd nodes in front of Discriminator.py:17. */
+int rgda_adv_probs_fwd(const float* x, void* P, int b, int C, int h, int w, int H, int W, int Cp, int mode,
+                       rgda_stream_t stream);
+int rgda_adv_probs_bwd(const void* dP, const float* x, float* dx, int b, int C, int h, int w, int H, int W, int Cp,
+                       int mode, float scale, rgda_stream_t stream);
+
+/* One discriminator layer, nn.Conv2d(Cin, Cout, 4, 2, 1) + LeakyReLU(slope) (Discriminator.py:9-12, 18-25), as an implicit
+ * GEMM on the bf16 MFMA:  y bf16 [N*(H/2)*(W/2)][Cout] = lrelu(conv(x bf16 [N*H*W][Cin]) + bias),  wgt bf16
+ * [Cout][16][Cin] (tap = kh * 4 + kw), bias f32 [Cout] or NULL.  H, W even.  Served: Cin == 16 or Cin % 32 == 0, Cout % 32
+ * == 0 (RGDA_ERR_UNSUPPORTED otherwise).  One launch.
+ * rgda_disc_conv_bwd_data: the data gradient of that layer as four parity sub-convolutions in ONE launch (the output
+ *   pixels of one (row parity, column parity) class read the same 2 x 2 of the 16 taps; no zero tap is multiplied):
+ *   dx bf16 [N*H*W][Cin] = mask * sum dy[src][co] * wt[ci][tap][co],  dy bf16 [N*(H/2)*(W/2)][Cout], wt bf16
+ *   [Cin][16][Cout] (rgda_weight_transpose_bf16 of the [Cout][16][Cin] f32 weights), mask = below > 0 ? 1 : slope read from
+ *   `below` bf16 [N*H*W][Cin], the stored activation of the layer underneath (torch's LeakyReLU convention at 0; NULL: no
+ *   mask, the probability rows).  dx is then the gradient of that layer's PRE-activation: what its own data gradient, its
+ *   weight gradient (rgda_conv2d_wgrad_grouped, kh = kw = 4, stride 2, pad 1) and its bias gradient read.
+ * rgda_disc_bias_lrelu: y bf16 [M][C] = lrelu(y + bias) in place: the epilogue pass behind rgda_conv2d where the generic
+ *   kernel forms a layer's matrix product (measured faster for layers 2-4); C % 32 == 0.  One launch.
+ * rgda_disc_bias_grad: db f32 [C] = the column sums of g bf16 [M][C] in a fixed order (two launches); C % 32 == 0;
+ *   ws: rgda_disc_bias_grad_workspace(M, C) bytes (0: not served), 16-byte aligned. */
+int rgda_disc_conv_fwd(const void* x, const void* wgt, const float* bias, void* y, int N, int H, int W, int Cin, int Cout,
+                       float slope, rgda_stream_t stream);
+int rgda_disc_conv_bwd_data(const void* dy, const void* wt, const void* below, void* dx, int N, int H, int W, int Cin,
+                            int Cout, float slope, rgda_stream_t stream);
+int rgda_disc_bias_lrelu(void* y, const float* bias, int64_t M, int C, float slope, rgda_stream_t stream);
+size_t rgda_disc_bias_grad_workspace(int64_t M, int C);
+int rgda_disc_bias_grad(const void* g, int64_t M, int C, float* db, void* ws, size_t ws_bytes, rgda_stream_t stream);
+
+/* The classifier Conv2d(C, 1, 4, 2, 1) (Discriminator.py:13, 26): a K = 16 C dot product per output pixel.
+ * rgda_disc_head_fwd: z f32 [N*(H/2)*(W/2)] = bias[0] + sum a4[src][c] * w[tap][c];  a4 bf16 [N*H*W][C], w f32 [16][C],
+ *   C % 32 == 0, H and W even.  One wavefront per output.
+ * rgda_disc_head_bwd: from dz f32 [N*(H/2)*(W/2)]: da4 bf16 [N*H*W][C] (masked by a4 > 0 ? 1 : slope: the gradient of the
+ *   last layer's pre-activation; NULL: skipped), dw f32 [16][C] and db f32 [1] (both or neither; written, not
+ *   accumulated).  One launch each for da4 and for (dw, db).
+ * rgda_bce_logits: F.binary_cross_entropy_with_logits(z, full(label)) for a constant label in {0, 1}:
+ *   loss[0] = (accumulate ? loss[0] : 0) + scale * mean(max(z, 0) - label * z + log1p(exp(-|z|))),
+ *   dz (NULL: not wanted) = scale / n * (sigmoid(z) - label).  One workgroup. */
+int rgda_disc_head_fwd(const void* a4, const float* w, const float* bias, float* z, int N, int H, int W, int C,
+                       rgda_stream_t stream);
+int rgda_disc_head_bwd(const float* dz, const void* a4, const float* w, void* da4, float* dw, float* db, int N, int H, int W,
+                       int C, float slope, rgda_stream_t stream);
+int rgda_bce_logits(const float* z, int n, float label, float scale, float* loss, int accumulate, float* dz,
+                    rgda_stream_t stream);
+
 /* Factored form of the PPM heads' tap-shifted bilinear maps (regda/models/Encoder.py:30-51: Upsample(bilinear,
  * align_corners=False) of the s x s branches into the 3x3 / pad 1 conv_last): the map V[(y,x)][(jy,jx),(ky,kx)] =
  * Uy[y+ky-1][jy] * Ux[x+kx-1][jx] is separable, so V and V^T are applied as two short maps (csrc/mix_kernels.hip).

@@ -16,6 +16,8 @@ rank 2), on the same kernel plans as the SSL step (regda_amd/ssl.py):
               (regda/dca_modules.py, multi_layer=True): an extension, tools/train_align_reg.py never calls them]
            [+ saw_weight * 0.5 * (SAW(feat_s) + SAW(feat_t)) with saw_weight > 0 (regda/gast/SAW.py, the prototypes as the
               classifier): an extension, tools/train_align_reg.py never constructs that loss]
+           [+ adv_weight * sum_i head_weights[i] * BCE(D_i(softmax(up(x_i of the target))), source label) with adv_weight >
+              0 (regda/models/Discriminator.py): an extension, no loop of the reference trains that class]
     -> backward -> clip_grad_norm_(32) -> SGD
 
 Differences to the SSL step that matter for the kernels: there is no CE on the target logits (their gradient is
@@ -47,7 +49,16 @@ a selection.  relax_denom defaults to 0 here, not to the reference's 2.0: `feat`
 sigmoids below 1, so each |cov| stays near or below 1 and a group's sum s over its 15 pairs (C = 6) rarely exceeds the
 margin 15 // 2.0 = 7 -- the term would be identically zero: on the features of the CPU oracle's untrained network the mean
 s was 1.3, and even with strongly correlated unit-variance features on the CPU it was 8.2, with 36 % of the groups clamped
-at that margin)."""
+at that margin).
+
+The output-space adversarial term (regda_amd/gast/adversarial.py, AdaptSegNet's recipe on regda/models/Discriminator.py's
+FCDiscriminator) differs from the terms above in that it reaches the network through the logits, not the features: after
+the SAW term, adv_weight * head_weights[i] * BCE(D_i(softmax(up(target logits of head i))), source label) adds its gradient
+onto the TARGET rows of the logit gradients g1 / g2, which are zero otherwise; after the model's update the discriminators
+take one Adam step on the step's own detached logits of both domains.  Its parameters are kept in `step.adv` (a dict:
+head_weights, aligner) and read at every step; `step.loss_adv` and `step.loss_disc` hold the terms.  adv_weight = 0, the
+default, launches nothing.  The discriminators' gradients are not all-reduced: with data-parallel ranks the term raises
+NotImplementedError."""
 import torch
 
 from . import ops
@@ -75,7 +86,14 @@ def saw_selection(class_num, selected_classes):
 
 class AlignStep(SSLStep):
     def __init__(self, model, prototypes, pcl_temperature=8.0, align_domain=False, whiten_weight=0.0, mmd=None,
-                 domain_weight=1.0, contrast_weight=0.0, triplet_weight=0.0, dca_weight=0.0, saw_weight=0.0, **kw):
+                 domain_weight=1.0, contrast_weight=0.0, triplet_weight=0.0, dca_weight=0.0, saw_weight=0.0, adv_weight=0.0,
+                 discriminators=None, **kw):
+        # > 0: + adv_weight * head_weights[i] * BCE(D_i(P_target), source label) on the target logits, then one
+        # discriminator step (regda_amd/gast/adversarial.py); discriminators: one per head or None for a head to skip
+        self.adv_weight = float(adv_weight)
+        if self.adv_weight < 0.0:
+            raise ValueError('AlignStep: adv_weight must be >= 0')
+        self._adv_discriminators = discriminators
         # > 0: + saw_weight * 0.5 * (SAW(feat_s) + SAW(feat_t)), regda/gast/SAW.py on the prototypes (or step.saw['classifier'])
         self.saw_weight = float(saw_weight)
         if self.saw_weight < 0.0:
@@ -122,6 +140,16 @@ class AlignStep(SSLStep):
         self.last_triplet = [None, None]
         self.loss_dca = torch.zeros(1, device=model.device)
         self.loss_saw = torch.zeros(1, device=model.device)
+        self.adv = dict(head_weights=(1.0, 1.0), aligner=None)
+        self.loss_adv = torch.zeros(1, device=model.device)
+        self.loss_disc = torch.zeros(1, device=model.device)
+        if self.adv_weight > 0.0:
+            from .gast.adversarial import AdversarialAligner
+            from .models.Discriminator import FCDiscriminator
+            ds = self._adv_discriminators
+            if ds is None:
+                ds = [FCDiscriminator(self.C).to(model.device) for _ in range(2)]
+            self.adv['aligner'] = AdversarialAligner(ds)
 
     def step(self, images_s, label_s, images_t, regs_t, lr):
         """One stage-2 iteration.  Returns device tensors (loss_seg, loss_align, grad_norm_sq)."""
@@ -130,6 +158,14 @@ class AlignStep(SSLStep):
                              'images per domain')
         if self.saw_weight > 0.0:
             saw_selection(self.C, self.saw['selected_classes'])
+        if self.adv_weight > 0.0:
+            if self.reducer.active:
+                raise NotImplementedError('AlignStep(adv_weight > 0) with data-parallel ranks: the discriminators\' gradients '
+                                          'are not all-reduced')
+            if self.adv['aligner'] is None:
+                raise ValueError("AlignStep: adv_weight was 0 at construction, so no discriminators exist; put an "
+                                 "AdversarialAligner into step.adv['aligner']")
+            self.adv['aligner'].check_served(images_t.shape[0], self.C, tuple(images_t.shape[-2:]))
         self._check_shape(images_s, images_t)
         self.lr_dev.fill_(float(lr))
         with ops.use_stream(torch.cuda.current_stream()):
@@ -241,7 +277,16 @@ class AlignStep(SSLStep):
             for f, _, _, _, rows in sides:
                 ops.saw_loss(f, cls_w, sel, sw['relax_denom'], 0.5 * self.saw_weight, loss=self.loss_saw, dfeat=rows,
                              accumulate=True)
+        if self.adv_weight > 0.0:
+            al, size = self.adv['aligner'], tuple(images_t.shape[-2:])
+            weights = [self.adv_weight * float(hw) for hw in self.adv['head_weights']]
+            self.loss_adv = al.generator_term((t1, t2), (g1[nb:], g2[nb:]), weights, size)
+            if self.keep_debug:     # tests: the step's own logits and the target rows of the logit gradients
+                self.debug = dict(s1=s1.clone(), s2=s2.clone(), t1=t1.clone(), t2=t2.clone(), g1_t=g1[nb:].clone(),
+                                  g2_t=g2[nb:].clone())
         self._backward_and_update(T, main, g1, g2, gfeat=gfeat)
+        if self.adv_weight > 0.0:
+            self.loss_disc = al.discriminator_step((s1, s2), (t1, t2), size)
         self.last_hard, self.last_label_t, self.last_label_s_down = hard, label_t, label_s_down
         return loss_seg, self.loss_align, self.gn
 

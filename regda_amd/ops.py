@@ -1871,3 +1871,146 @@ def aspp_scatter(g1, g2, dz, dbiases, N, h, w, C, dils):
     D = (ctypes.c_int * 4)(*[int(d) for d in dils])
     lib().call('rgda_aspp_scatter', g1.data_ptr(), g2.data_ptr(), dz.data_ptr(), _ld(dz), dz.shape[1],
                ctypes.cast(P, ctypes.c_void_p), N, h, w, C, ctypes.cast(D, ctypes.c_void_p), _stream())
+
+
+# ---------------------------------------------------------------- output-space adversarial alignment (adv_kernels.hip)
+ADV_CP = 16         # channels of a probability row: the classes zero-padded to one K slice of the bf16 MFMA
+DISC_SLOPE = 0.2    # nn.LeakyReLU(negative_slope=0.2), regda/models/Discriminator.py:15
+
+
+def _rows_bf16(t, cols, who):
+    assert t.dtype == torch.bfloat16 and t.dim() == 2 and t.shape[1] == cols and t.is_contiguous(), (who, t.shape, t.dtype)
+    return t
+
+
+def adv_probs(x, size=None, softmax=True, out=None):
+    """x f32 (b, C, h, w) on the GPU -> P bf16 [b*H*W, 16]: softmax over the classes of the bilinear (align_corners=True)
+    upsample to size = (H, W), or with softmax=False the given probabilities packed as they are (size is x's own)."""
+    _need_cuda(x, out)
+    assert x.dim() == 4 and x.dtype == torch.float32 and x.is_contiguous(), 'adv_probs: contiguous f32 (b, C, h, w)'
+    b, C, h, w = x.shape
+    check_class_count(C, 'adv_probs')
+    H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
+    if not softmax and (H, W) != (h, w):
+        raise ValueError('adv_probs: given probabilities are packed at their own size')
+    P = out if out is not None else torch.empty((b * H * W, ADV_CP), dtype=torch.bfloat16, device=x.device)
+    _rows_bf16(P, ADV_CP, 'adv_probs')
+    assert P.shape[0] == b * H * W
+    lib().call('rgda_adv_probs_fwd', x.data_ptr(), P.data_ptr(), b, C, h, w, H, W, ADV_CP, 0 if softmax else 1, _stream())
+    return P
+
+
+def adv_probs_backward(dP, x, dx, size=None, softmax=True, scale=1.0):
+    """dx f32 (b, C, h, w) += scale * (adv_probs' gradient of dP bf16 [b*H*W, 16]); x: the forward's input."""
+    _need_cuda(dP, x, dx)
+    assert dx.dim() == 4 and dx.dtype == torch.float32 and dx.is_contiguous() and x.shape == dx.shape
+    assert x.dtype == torch.float32 and x.is_contiguous()
+    b, C, h, w = dx.shape
+    check_class_count(C, 'adv_probs_backward')
+    H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
+    _rows_bf16(dP, ADV_CP, 'adv_probs_backward')
+    assert dP.shape[0] == b * H * W
+    lib().call('rgda_adv_probs_bwd', dP.data_ptr(), x.data_ptr(), dx.data_ptr(), b, C, h, w, H, W, ADV_CP,
+               0 if softmax else 1, float(scale), _stream())
+    return dx
+
+
+def disc_conv(x, w, bias, N, H, W, slope=DISC_SLOPE, out=None):
+    """One discriminator layer: x bf16 [N*H*W, Cin], w bf16 [Cout, 16, Cin], bias f32 [Cout] or None ->
+    lrelu(conv 4x4 / stride 2 / pad 1 + bias) as bf16 [N*(H/2)*(W/2), Cout]."""
+    _need_cuda(x, w, bias, out)
+    Cout, taps, Cin = w.shape
+    assert taps == 16 and w.dtype == torch.bfloat16 and w.is_contiguous()
+    _rows_bf16(x, Cin, 'disc_conv')
+    assert x.shape[0] == N * H * W and (bias is None or (bias.dtype == torch.float32 and bias.numel() == Cout and bias.is_contiguous()))
+    y = out if out is not None else torch.empty((N * (H // 2) * (W // 2), Cout), dtype=torch.bfloat16, device=x.device)
+    _rows_bf16(y, Cout, 'disc_conv')
+    lib().call('rgda_disc_conv_fwd', x.data_ptr(), w.data_ptr(), _p(bias), y.data_ptr(), N, H, W, Cin, Cout, float(slope), _stream())
+    return y
+
+
+def disc_bias_lrelu(y, bias, slope=DISC_SLOPE):
+    """y bf16 [M, C] = lrelu(y + bias) in place (the epilogue pass behind the generic convolution)."""
+    _need_cuda(y, bias)
+    M, C = y.shape
+    _rows_bf16(y, C, 'disc_bias_lrelu')
+    assert bias.dtype == torch.float32 and bias.numel() == C and bias.is_contiguous()
+    lib().call('rgda_disc_bias_lrelu', y.data_ptr(), bias.data_ptr(), M, C, float(slope), _stream())
+    return y
+
+
+def disc_bias_grad(g):
+    """g bf16 [M, C] -> f32 [C] column sums in a fixed order."""
+    _need_cuda(g)
+    M, C = g.shape
+    _rows_bf16(g, C, 'disc_bias_grad')
+    db = torch.empty(C, dtype=torch.float32, device=g.device)
+    L = lib()
+    ws = _ws(L.size('rgda_disc_bias_grad_workspace', M, C), g.device)
+    L.call('rgda_disc_bias_grad', g.data_ptr(), M, C, db.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    return db
+
+
+def disc_conv_backward(g, x, wt, N, H, W, below=True, need_dx=True, need_dparams=True, slope=DISC_SLOPE):
+    """The gradients of disc_conv from g bf16 [N*(H/2)*(W/2), Cout], the gradient of the layer's PRE-activation.
+    x bf16 [N*H*W, Cin]: the layer's input; wt bf16 [Cin, 16, Cout]: the transposed operand copy.
+    -> (dx, dw, db): dx bf16 [N*H*W, Cin] masked by x's sign where `below` (x is a stored LeakyReLU output) -- the
+    pre-activation gradient of the layer underneath; dw f32 [Cout, 16, Cin] (rgda_conv2d_wgrad_grouped) and db f32 [Cout]."""
+    _need_cuda(g, x, wt)
+    Cin, taps, Cout = wt.shape
+    assert taps == 16 and wt.dtype == torch.bfloat16 and wt.is_contiguous()
+    _rows_bf16(x, Cin, 'disc_conv_backward')
+    _rows_bf16(g, Cout, 'disc_conv_backward')
+    assert x.shape[0] == N * H * W and g.shape[0] == N * (H // 2) * (W // 2)
+    dx = dw = db = None
+    if need_dparams:
+        dw = torch.zeros((Cout, 16, Cin), dtype=torch.float32, device=g.device)
+        conv2d_wgrad_grouped([(x, g, dw, N, H, W, H // 2, W // 2, 4, 4, 2, 1, 1)])
+        db = disc_bias_grad(g)
+    if need_dx:
+        dx = torch.empty_like(x)
+        lib().call('rgda_disc_conv_bwd_data', g.data_ptr(), wt.data_ptr(), x.data_ptr() if below else 0, dx.data_ptr(), N, H, W,
+                   Cin, Cout, float(slope), _stream())
+    return dx, dw, db
+
+
+def disc_head(a4, w, bias, N, H, W):
+    """The classifier: a4 bf16 [N*H*W, C], w f32 [16, C], bias f32 [1] -> z f32 [N, (H/2)*(W/2)]."""
+    _need_cuda(a4, w, bias)
+    C = w.shape[1]
+    assert w.shape == (16, C) and w.dtype == torch.float32 and w.is_contiguous()
+    _rows_bf16(a4, C, 'disc_head')
+    assert a4.shape[0] == N * H * W
+    z = torch.empty((N, (H // 2) * (W // 2)), dtype=torch.float32, device=a4.device)
+    lib().call('rgda_disc_head_fwd', a4.data_ptr(), w.data_ptr(), _p(bias), z.data_ptr(), N, H, W, C, _stream())
+    return z
+
+
+def disc_head_backward(dz, a4, w, N, H, W, need_da=True, need_dparams=True, slope=DISC_SLOPE):
+    """-> (da4 bf16 [N*H*W, C] masked by a4's sign, dw f32 [16, C], db f32 [1]) from dz f32 [N, (H/2)*(W/2)]."""
+    _need_cuda(dz, a4, w)
+    C = w.shape[1]
+    _rows_bf16(a4, C, 'disc_head_backward')
+    assert dz.dtype == torch.float32 and dz.is_contiguous() and dz.numel() == N * (H // 2) * (W // 2)
+    da = torch.empty_like(a4) if need_da else None
+    dw = torch.empty((16, C), dtype=torch.float32, device=a4.device) if need_dparams else None
+    db = torch.empty(1, dtype=torch.float32, device=a4.device) if need_dparams else None
+    lib().call('rgda_disc_head_bwd', dz.data_ptr(), a4.data_ptr(), w.data_ptr(), _p(da), _p(dw), _p(db), N, H, W, C,
+               float(slope), _stream())
+    return da, dw, db
+
+
+def bce_logits(z, label, scale=1.0, loss=None, accumulate=False, want_grad=True):
+    """scale * F.binary_cross_entropy_with_logits(z, full_like(z, label)) for label 0 or 1 -> (loss f32 [1] on the
+    device, dz f32 of z's shape or None).  accumulate: added onto `loss`."""
+    _need_cuda(z, loss)
+    assert z.dtype == torch.float32 and z.is_contiguous()
+    if float(label) not in (0.0, 1.0):
+        raise ValueError('bce_logits: the label is 0 or 1, got %r' % (label,))
+    if loss is None:
+        assert not accumulate
+        loss = torch.empty(1, dtype=torch.float32, device=z.device)
+    dz = torch.empty_like(z) if want_grad else None
+    lib().call('rgda_bce_logits', z.data_ptr(), z.numel(), float(label), float(scale), loss.data_ptr(), int(bool(accumulate)),
+               _p(dz), _stream())
+    return loss, dz

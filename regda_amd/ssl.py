@@ -24,7 +24,9 @@ class SSLStep:
                  process_group=None, overlap_wgrad=True, overlap_comm=True, class_balancer_s=None,
                  class_balancer_t=None, grad_payload='fp32', comm=None, loss_s='CrossEntropy', loss_t='none',
                  uvem_m=0.2, uvem_t=0.7, uvem_g=4.0, gdp_prototype=True, gdp_class_balance=False, ent_weight=0.0,
-                 kld_weight=0.0):
+                 kld_weight=0.0, adv_weight=0.0, discriminators=None):
+        if adv_weight or discriminators is not None:
+            raise NotImplementedError('the adversarial term (adv_weight / discriminators) belongs to the stage-2 step, AlignStep')
         ops.check_class_count(class_num, type(self).__name__)
         self.model = model
         self.C, self.ig = class_num, ignore_label
