@@ -23,51 +23,21 @@ rank 2), on the same kernel plans as the SSL step (regda_amd/ssl.py):
 Differences to the SSL step that matter for the kernels: there is no CE on the target logits (their gradient is
 zero) and the loss reaches the network through the third forward output, the instance-normalised features
 (rgda_pcl_loss writes d loss / d feat pixel-major, `Deeplabv2._backward_plan(gfeat=...)` adds it in the
-instance-norm backward; with align_domain rgda_coral_loss then adds the CORAL gradient of both halves onto it).
-Data-parallel ranks compute CORAL on their local batch (regda_amd/source.py), and so the whitening term
-(rgda_whiten_loss, added onto the same gradient rows after PCL and CORAL), and so the pixel contrast
-(rgda_pixel_contrast_loss, added after those; the predictions are the argmax of the head-2 logits at feature
-resolution, taken inside rgda_pixel_contrast_select; its random draws come from the global CPU generator, which costs
-one host sync per domain and step; a domain without a class of more than max_views labelled pixels contributes 0.  Its
-parameters are the reference's defaults, kept in `step.contrast` (a dict: temperature, base_temperature, max_samples,
-max_views, eps) and read at every step, so assigning `step.contrast['max_views'] = ...` changes them.  The head logits and
-the features of the fused model are f32, so the `.float()` below copies nothing.  `step.last_contrast` holds, per domain,
-the (order, counts, anchors, ranks) the term used, or None), and so the batch-hard triplet term (rgda_triplet_loss,
-added last, on the downscaled labels the whitening term uses, the step's ignore label excluded; its margin is kept in
-`step.triplet` (a dict) and read at every step; `step.loss_triplet` holds the term and `step.last_triplet`, per domain, what the
-kernel left on the device: `stats` (int32: rows in the mean, positive hinges) and the per-row tables of
-ops.triplet_tables), and so the category alignment term (rgda_dca_loss, added after the triplet term: it needs no labels and
-no host draws, its predictions are the step's own head logits at feature resolution, taken as constants; its parameters
-are kept in `step.dca` (a dict: kind 'cov' or 'mse', ccr, icr, ignore_bg) and read at every step; `step.loss_dca` holds the
-term), and so the semantic-aware whitening term (rgda_saw_loss, added after the DCA term; it needs no labels either.  Its
-parameters are kept in `step.saw` (a dict: relax_denom, selected_classes, classifier) and read at every step;
-`step.loss_saw` holds the term.  classifier None: the step's prototypes, after this step's EMA update, as PCL sees them --
-stage 2's PCL is a cosine classifier on `feat` with the prototypes as weights, so they are the (C, k) classifier this model
-has on that tensor; the PPM / ASPP heads have no 2-D weight on `feat`.  A caller's (n_cls, k) tensor or module replaces
-them.  selected_classes None: range(C) where C is one of the served counts 2, 4, 6, 8, 16; any other C (LoveDA's 7) needs
-a selection.  relax_denom defaults to 0 here, not to the reference's 2.0: `feat` is instance-normalised and the weights are
-sigmoids below 1, so each |cov| stays near or below 1 and a group's sum s over its 15 pairs (C = 6) rarely exceeds the
-margin 15 // 2.0 = 7 -- the term would be identically zero: on the features of the CPU oracle's untrained network the mean
-s was 1.3, and even with strongly correlated unit-variance features on the CPU it was 8.2, with 36 % of the groups clamped
-at that margin).
+instance-norm backward).  The bracketed terms are the entries of TERMS below, launched in that order: each adds its
+gradient onto the rows PCL wrote (bf16 accumulation, so the order is part of the result), except the adversarial term,
+which adds onto the target rows of the logit gradients.  Every term is computed on the rank's local batch."""
+from collections import namedtuple
 
-The output-space adversarial term (regda_amd/gast/adversarial.py, AdaptSegNet's recipe on regda/models/Discriminator.py's
-FCDiscriminator) differs from the terms above in that it reaches the network through the logits, not the features: after
-the SAW term, adv_weight * head_weights[i] * BCE(D_i(softmax(up(target logits of head i))), source label) adds its gradient
-onto the TARGET rows of the logit gradients g1 / g2, which are zero otherwise; after the model's update the discriminators
-take one Adam step on the step's own detached logits of both domains.  Its parameters are kept in `step.adv` (a dict:
-head_weights, aligner) and read at every step; `step.loss_adv` and `step.loss_disc` hold the terms.  adv_weight = 0, the
-default, launches nothing.  The discriminators' gradients are not all-reduced: with data-parallel ranks the term raises
-NotImplementedError."""
 import torch
 
 from . import ops
 from .ddp import all_reduce_prototype_statistics
+from .gast.SAW import classifier_weight
+from .gast.adversarial import AdversarialAligner
 from .gast.contrastive import select_and_plan
+from .models.Discriminator import FCDiscriminator
 from .source import domain_kind, domain_loss
 from .ssl import SSLStep
-
-BF = torch.bfloat16
 
 
 def saw_selection(class_num, selected_classes):
@@ -84,88 +54,202 @@ def saw_selection(class_num, selected_classes):
     return sel
 
 
+# One optional loss term, a row of TERMS below.  on: the attribute of the step that switches it on while > 0, read at every
+# step -- its weight, a keyword checked >= 0 (the domain term goes by align_domain).  params: the defaults of `step.<name>`,
+# read at every step too.  launch(step, c), then after_update(step, c) behind the model's update, for a term that is on;
+# check(step, images_s, images_t) before anything is launched; construct(step) once, for a term that is on then
+Term = namedtuple('Term', 'name on params launch check construct after_update', defaults=(None,) * 3)
+# what a term sees of the step: per domain (features, full-size and downscaled labels, head-2 logits, gradient rows), the
+# logits and their gradients, nb source images of n, the feature size, the tile size
+Ctx = namedtuple('Ctx', 'sides s1 s2 t1 t2 g1 g2 nb n h w size')
+
+
+def domain(step, c):
+    """--align-domain 1: + aligner.align_domain(feat_s, feat_t), :188.  rgda_coral_loss (rgda_mmd_loss: regda_amd/source.py)
+    adds the gradient of both halves onto the rows; domain_weight scales it.  Data-parallel ranks compute CORAL on their
+    local batch (regda_amd/source.py)."""
+    step.loss_domain.zero_()
+    (fs, *_, rows_s), (ft, *_, rows_t) = c.sides
+    domain_loss(step.domain_kind, step.mmd, fs, ft, step.domain_weight, loss=step.loss_domain, dfeat_s=rows_s,
+                dfeat_t=rows_t, accumulate=True)
+
+
+def whiten(step, c):
+    """whiten_weight * Aligner.whiten_class_ware(feat_s, label_s, feat_t, label_t) (32 groups, alignment.py:71), on the local
+    batch too: rgda_whiten_loss, added onto the same gradient rows after PCL and CORAL.  `step.loss_white` holds the term."""
+    step.loss_white.zero_()
+    for f, _, lab, _, rows in c.sides:
+        ops.whiten_loss(f, lab, step.C, 32, step.ig, 0.5 * step.whiten_weight, loss=step.loss_white, dfeat=rows,
+                        accumulate=True)
+
+
+def whiten_served(step):
+    k = step.prototypes.shape[-1]
+    if k % 32 or k // 32 not in ops.WHITEN_BLOCKS:
+        raise NotImplementedError(f'AlignStep(whiten_weight > 0): {k} feature channels in 32 groups; served are '
+                                  f'{ops.WHITEN_BLOCKS} channels per group')
+
+
+def contrast(step, c):
+    """PixelContrastLoss, the reference's defaults (rgda_pixel_contrast_loss, added after those above; the predictions are
+    the argmax of the head-2 logits at feature resolution, taken inside rgda_pixel_contrast_select; its random draws come
+    from the global CPU generator, the source side first, which costs one host sync per domain and step; a domain without a
+    class of more than max_views labelled pixels contributes 0).  Its parameters are kept in `step.contrast` and read at
+    every step, so assigning `step.contrast['max_views'] = ...` changes them.  The head logits and the features of the
+    fused model are f32, so the `.float()` below copies nothing.  `step.last_contrast` holds, per domain, the (order,
+    counts, anchors, ranks) the term used, or None."""
+    step.loss_contrast.zero_()
+    pc = step.contrast
+    for side, (f, lab, _, logits, rows) in enumerate(c.sides):
+        lab = lab.reshape(lab.shape[0], *lab.shape[-2:])
+        order, counts, anchors, ranks, _ = select_and_plan(lab, logits.float(), step.C, (c.h, c.w), step.ig,
+                                                           pc['max_samples'], pc['max_views'], None)
+        step.last_contrast[side] = None if anchors is None else (order, counts, anchors, ranks)
+        if anchors is None:        # no class of this domain's batch has more than max_views pixels: the term is 0
+            continue
+        ops.pixel_contrast_loss(f, order, counts, anchors, ranks, pc['temperature'], pc['base_temperature'], pc['eps'],
+                                0.5 * step.contrast_weight, loss=step.loss_contrast, dfeat=rows, accumulate=True)
+
+
+def triplet(step, c):
+    """The batch-hard TripletLoss of regda/gast/triple.py (rgda_triplet_loss, on the downscaled labels the whitening term
+    uses, the step's ignore label excluded); its margin is kept in `step.triplet` and read at every step;
+    `step.loss_triplet` holds the term and `step.last_triplet`, per domain, what the kernel left on the device: `stats`
+    (int32: rows in the mean, positive hinges) and the per-row tables of ops.triplet_tables."""
+    step.loss_triplet.zero_()
+    for side, (f, _, lab, _, rows) in enumerate(c.sides):
+        _, stats, ws = ops.triplet_loss(f, lab, step.triplet['margin'], step.ig, 0.5 * step.triplet_weight,
+                                        loss=step.loss_triplet, dfeat=rows, accumulate=True, return_ws=True)
+        step.last_triplet[side] = dict(ops.triplet_tables(ws, rows.shape[0]), stats=stats)
+
+
+def dca(step, c):
+    """The category alignment of regda/dca_modules.py, multi_layer=True, at the full dca_weight (rgda_dca_loss, added after
+    the triplet term: it needs no labels and no host draws, its predictions are the step's own head logits at feature
+    resolution, taken as constants); its parameters are kept in `step.dca` (kind 'cov' or 'mse', ccr, icr, ignore_bg) and
+    read at every step; `step.loss_dca` holds the term."""
+    step.loss_dca.zero_()
+    dc, hw = step.dca, c.h * c.w
+    (fs, *_, rows_s), (ft, *_, rows_t) = c.sides
+    if dc['ccr']:        # the source side is a constant: the target rows alone receive
+        ops.dca_loss(fs, (c.s1, c.s2), ft, (c.t1, c.t2), 'logits2', dc['kind'], dc['ignore_bg'], step.dca_weight,
+                     loss=step.loss_dca, dfeat_b=rows_t, accumulate=True)
+    if dc['icr']:
+        for f, (p1, p2), rows, bd in ((fs, (c.s1, c.s2), rows_s, c.nb), (ft, (c.t1, c.t2), rows_t, c.n - c.nb)):
+            q = bd // 2
+            ops.dca_loss(f[:q], (p1[:q], p2[:q]), f[q:], (p1[q:], p2[q:]), 'logits2', dc['kind'], dc['ignore_bg'],
+                         step.dca_weight, loss=step.loss_dca, dfeat_a=rows[:q * hw], dfeat_b=rows[q * hw:], accumulate=True)
+
+
+def dca_check(step, images_s, images_t):
+    if step.dca['icr'] and min(images_s.shape[0], images_t.shape[0]) < 2:
+        raise ValueError('AlignStep(dca_weight > 0): icr splits the batch of each domain in two; it needs at least two '
+                         'images per domain')
+
+
+def saw(step, c):
+    """The semantic-aware whitening of regda/gast/SAW.py (rgda_saw_loss, added after the DCA term; it needs no labels
+    either).  Its parameters are kept in `step.saw` and read at every step; `step.loss_saw` holds the term.  classifier
+    None: the step's prototypes, after this step's EMA update, as PCL sees them -- stage 2's PCL is a cosine classifier on
+    `feat` with the prototypes as weights, so they are the (C, k) classifier this model has on that tensor; the PPM / ASPP
+    heads have no 2-D weight on `feat`.  A caller's (n_cls, k) tensor or module replaces them.  selected_classes None:
+    range(C) where C is one of the served counts 2, 4, 6, 8, 16; any other C (LoveDA's 7) needs a selection.  relax_denom
+    defaults to 0 here, not to the reference's 2.0: `feat` is instance-normalised and the weights are sigmoids below 1, so
+    each |cov| stays near or below 1 and a group's sum s over its 15 pairs (C = 6) rarely exceeds the margin 15 // 2.0 = 7
+    -- the term would be identically zero: on the features of the CPU oracle's untrained network the mean s was 1.3, and
+    even with strongly correlated unit-variance features on the CPU it was 8.2, with 36 % of the groups clamped at that
+    margin."""
+    step.loss_saw.zero_()
+    sw = step.saw
+    cls_w = step.prototypes if sw['classifier'] is None else classifier_weight(sw['classifier']).to(step.model.device)
+    sel = saw_selection(step.C, sw['selected_classes'])
+    for f, *_, rows in c.sides:
+        ops.saw_loss(f, cls_w, sel, sw['relax_denom'], 0.5 * step.saw_weight, loss=step.loss_saw, dfeat=rows, accumulate=True)
+
+
+def adv(step, c):
+    """The output-space adversarial term (regda_amd/gast/adversarial.py, AdaptSegNet's recipe on
+    regda/models/Discriminator.py's FCDiscriminator) differs from the terms above in that it reaches the network through
+    the logits, not the features: after the SAW term, adv_weight * head_weights[i] * BCE(D_i(softmax(up(target logits of
+    head i))), source label) adds its gradient onto the TARGET rows of the logit gradients g1 / g2, which are zero
+    otherwise; after the model's update the discriminators (`discriminators=`: one per head or None for a head to skip)
+    take one Adam step on the step's own detached logits of both domains.  Its parameters are kept in `step.adv` and read
+    at every step; `step.loss_adv` and `step.loss_disc` hold the terms.  adv_weight = 0, the default, launches nothing.
+    The discriminators' gradients are not all-reduced: with data-parallel ranks the term raises NotImplementedError."""
+    weights = [step.adv_weight * float(hw) for hw in step.adv['head_weights']]
+    step.loss_adv = step.adv['aligner'].generator_term((c.t1, c.t2), (c.g1[c.nb:], c.g2[c.nb:]), weights, c.size)
+    if step.keep_debug:     # tests: the step's own logits and the target rows of the logit gradients
+        step.debug = dict(s1=c.s1.clone(), s2=c.s2.clone(), t1=c.t1.clone(), t2=c.t2.clone(), g1_t=c.g1[c.nb:].clone(),
+                          g2_t=c.g2[c.nb:].clone())
+
+
+def adv_construct(step):
+    ds = step._adv_discriminators
+    if ds is None:
+        ds = [FCDiscriminator(step.C).to(step.model.device) for _ in range(2)]
+    step.adv['aligner'] = AdversarialAligner(ds)
+
+
+def adv_check(step, images_s, images_t):
+    if step.reducer.active:
+        raise NotImplementedError('AlignStep(adv_weight > 0) with data-parallel ranks: the discriminators\' gradients '
+                                  'are not all-reduced')
+    if step.adv['aligner'] is None:
+        raise ValueError("AlignStep: adv_weight was 0 at construction, so no discriminators exist; put an "
+                         "AdversarialAligner into step.adv['aligner']")
+    step.adv['aligner'].check_served(images_t.shape[0], step.C, tuple(images_t.shape[-2:]))
+
+
+def adv_discriminators(step, c):
+    step.loss_disc = step.adv['aligner'].discriminator_step((c.s1, c.s2), (c.t1, c.t2), c.size)
+
+
+# the order in which the terms add onto the gradient rows, after PCL: part of the result.  A new term goes to the end
+TERMS = (Term('domain', 'align_domain', None, domain),
+         Term('whiten', 'whiten_weight', None, whiten, construct=whiten_served),
+         Term('contrast', 'contrast_weight', dict(temperature=0.1, base_temperature=0.07, max_samples=1024, max_views=100,
+                                                  eps=1e-5), contrast),
+         Term('triplet', 'triplet_weight', dict(margin=0.3), triplet),
+         Term('dca', 'dca_weight', dict(kind='cov', ccr=True, icr=True, ignore_bg=True), dca, dca_check),
+         Term('saw', 'saw_weight', dict(relax_denom=0.0, selected_classes=None, classifier=None), saw,
+              lambda step, *images: saw_selection(step.C, step.saw['selected_classes'])),
+         Term('adv', 'adv_weight', dict(head_weights=(1.0, 1.0), aligner=None), adv, adv_check, adv_construct,
+              adv_discriminators))
+
+
 class AlignStep(SSLStep):
     def __init__(self, model, prototypes, pcl_temperature=8.0, align_domain=False, whiten_weight=0.0, mmd=None,
                  domain_weight=1.0, contrast_weight=0.0, triplet_weight=0.0, dca_weight=0.0, saw_weight=0.0, adv_weight=0.0,
                  discriminators=None, **kw):
-        # > 0: + adv_weight * head_weights[i] * BCE(D_i(P_target), source label) on the target logits, then one
-        # discriminator step (regda_amd/gast/adversarial.py); discriminators: one per head or None for a head to skip
-        self.adv_weight = float(adv_weight)
-        if self.adv_weight < 0.0:
-            raise ValueError('AlignStep: adv_weight must be >= 0')
+        weights = dict(whiten_weight=whiten_weight, contrast_weight=contrast_weight, triplet_weight=triplet_weight,
+                       dca_weight=dca_weight, saw_weight=saw_weight, adv_weight=adv_weight)
+        for t in TERMS:      # before the model is touched
+            if t.on in weights:
+                setattr(self, t.on, float(weights[t.on]))
+                if getattr(self, t.on) < 0.0:
+                    raise ValueError(f'AlignStep: {t.on} must be >= 0')
+            if t.params is not None:
+                setattr(self, t.name, dict(t.params))
         self._adv_discriminators = discriminators
-        # > 0: + saw_weight * 0.5 * (SAW(feat_s) + SAW(feat_t)), regda/gast/SAW.py on the prototypes (or step.saw['classifier'])
-        self.saw_weight = float(saw_weight)
-        if self.saw_weight < 0.0:
-            raise ValueError('AlignStep: saw_weight must be >= 0')
-        self.saw = dict(relax_denom=0.0, selected_classes=None, classifier=None)
-        # > 0: + dca_weight * (CCR(src, tgt) + ICR(src) + ICR(tgt)), regda/dca_modules.py with multi_layer=True
-        self.dca_weight = float(dca_weight)
-        if self.dca_weight < 0.0:
-            raise ValueError('AlignStep: dca_weight must be >= 0')
-        self.dca = dict(kind='cov', ccr=True, icr=True, ignore_bg=True)
-        # > 0: + triplet_weight * 0.5 * (TripletLoss(source rows) + TripletLoss(target rows)), regda/gast/triple.py
-        self.triplet_weight = float(triplet_weight)
-        if self.triplet_weight < 0.0:
-            raise ValueError('AlignStep: triplet_weight must be >= 0')
-        self.triplet = dict(margin=0.3)
-        # > 0: + contrast_weight * 0.5 * (PixelContrastLoss(source) + PixelContrastLoss(target)), the reference's defaults
-        self.contrast_weight = float(contrast_weight)
-        if self.contrast_weight < 0.0:
-            raise ValueError('AlignStep: contrast_weight must be >= 0')
-        self.contrast = dict(temperature=0.1, base_temperature=0.07, max_samples=1024, max_views=100, eps=1e-5)
         self.domain_kind, self.mmd = domain_kind(align_domain, mmd)
         if kw.get('ent_weight') or kw.get('kld_weight'):
             raise NotImplementedError('the IAST regularisers (ent_weight / kld_weight) belong to the SSL step')
         kw.setdefault('proto_decay', 0.999)        # Aligner(decay=0.999), train_align_reg.py:112-113
         kw['ema_decay'] = None
         super().__init__(model, prototypes, **kw)
-        self.pcl_temp = pcl_temperature
-        self.loss_align = torch.zeros(1, device=model.device)
-        self.align_domain = bool(align_domain)     # --align-domain 1: + aligner.align_domain(feat_s, feat_t), :188
-        self.domain_weight = float(domain_weight)
-        self.loss_domain = torch.zeros(1, device=model.device)
-        # > 0: + whiten_weight * Aligner.whiten_class_ware(feat_s, label_s, feat_t, label_t) (32 groups, alignment.py:71)
-        self.whiten_weight = float(whiten_weight)
-        if self.whiten_weight < 0.0:
-            raise ValueError('AlignStep: whiten_weight must be >= 0')
-        k = self.prototypes.shape[-1]
-        if self.whiten_weight > 0.0 and (k % 32 or k // 32 not in ops.WHITEN_BLOCKS):
-            raise NotImplementedError(f'AlignStep(whiten_weight > 0): {k} feature channels in 32 groups; served are '
-                                      f'{ops.WHITEN_BLOCKS} channels per group')
-        self.loss_white = torch.zeros(1, device=model.device)
-        self.loss_contrast = torch.zeros(1, device=model.device)
-        self.last_contrast = [None, None]
-        self.loss_triplet = torch.zeros(1, device=model.device)
-        self.last_triplet = [None, None]
-        self.loss_dca = torch.zeros(1, device=model.device)
-        self.loss_saw = torch.zeros(1, device=model.device)
-        self.adv = dict(head_weights=(1.0, 1.0), aligner=None)
-        self.loss_adv = torch.zeros(1, device=model.device)
-        self.loss_disc = torch.zeros(1, device=model.device)
-        if self.adv_weight > 0.0:
-            from .gast.adversarial import AdversarialAligner
-            from .models.Discriminator import FCDiscriminator
-            ds = self._adv_discriminators
-            if ds is None:
-                ds = [FCDiscriminator(self.C).to(model.device) for _ in range(2)]
-            self.adv['aligner'] = AdversarialAligner(ds)
+        self.pcl_temp, self.align_domain, self.domain_weight = pcl_temperature, bool(align_domain), float(domain_weight)
+        for name in ('align', 'domain', 'white', 'contrast', 'triplet', 'dca', 'saw', 'adv', 'disc'):
+            setattr(self, 'loss_' + name, torch.zeros(1, device=model.device))
+        self.last_contrast, self.last_triplet = [None, None], [None, None]
+        for t in TERMS:
+            if t.construct is not None and getattr(self, t.on) > 0.0:
+                t.construct(self)
 
     def step(self, images_s, label_s, images_t, regs_t, lr):
         """One stage-2 iteration.  Returns device tensors (loss_seg, loss_align, grad_norm_sq)."""
-        if self.dca_weight > 0.0 and self.dca['icr'] and min(images_s.shape[0], images_t.shape[0]) < 2:
-            raise ValueError('AlignStep(dca_weight > 0): icr splits the batch of each domain in two; it needs at least two '
-                             'images per domain')
-        if self.saw_weight > 0.0:
-            saw_selection(self.C, self.saw['selected_classes'])
-        if self.adv_weight > 0.0:
-            if self.reducer.active:
-                raise NotImplementedError('AlignStep(adv_weight > 0) with data-parallel ranks: the discriminators\' gradients '
-                                          'are not all-reduced')
-            if self.adv['aligner'] is None:
-                raise ValueError("AlignStep: adv_weight was 0 at construction, so no discriminators exist; put an "
-                                 "AdversarialAligner into step.adv['aligner']")
-            self.adv['aligner'].check_served(images_t.shape[0], self.C, tuple(images_t.shape[-2:]))
+        for t in TERMS:
+            if t.check is not None and getattr(self, t.on) > 0.0:
+                t.check(self, images_s, images_t)
         self._check_shape(images_s, images_t)
         self.lr_dev.fill_(float(lr))
         with ops.use_stream(torch.cuda.current_stream()):
@@ -209,88 +293,26 @@ class AlignStep(SSLStep):
         else:
             hard = ops.pseudo_select(soft_t, self.top, self.low, self.ig, check=False)
         if self.sam_refine:
-            regs = regs_t.squeeze(1) if regs_t.dim() == 4 else regs_t
-            self._lrh_flag_off = (regs.shape[0] * self.max_regions * (self.C + 1)) * 4
-            need = self._lrh_flag_off + 16
-            if self.lrh_ws is None or self.lrh_ws.numel() < need:
-                self.lrh_ws = torch.empty(need, dtype=torch.uint8, device=m.device)
-            hard = ops.lrh(hard, regs.contiguous(), self.percent, self.C, self.ig, self.max_regions, check=False,
-                           ws=self.lrh_ws)
-        label_t = self._downscale(hard)                                              # aligner.downscale_gt, :180
+            hard = self._lrh(regs_t.squeeze(1) if regs_t.dim() == 4 else regs_t, hard)
+        label_t = ops.downscale_label(hard, self.C, 16, self.ig, 0.75)              # aligner.downscale_gt, :180
         # ---- losses and their gradients: d loss / d logits, the source rows from the loss kernels, the target rows zero
         g1, g2 = torch.zeros_like(x1), torch.zeros_like(x2)
         loss_seg = self._source_loss(s1, s2, label_s, g1[:nb], g2[:nb])
         n, k, h, w = feat.shape
-        gfeat = torch.empty(n * h * w, k, dtype=BF, device=m.device)
-        # per domain: features, full-size and downscaled labels, head-2 logits, its gradient rows.  Every term adds onto
-        # the rows in the order PCL, domain, whitening, contrast, triplet, DCA, SAW (bf16 accumulation depends on it)
+        gfeat = torch.empty(n * h * w, k, dtype=torch.bfloat16, device=m.device)
+        # per domain: features, full-size and downscaled labels, head-2 logits, its gradient rows.  PCL writes the rows
+        # (it is not optional); every term that is on then adds onto them, in the order of TERMS
         sides = ((feat_s, label_s, label_s_down, s2, gfeat[:nb * h * w]), (feat_t, label_t, label_t, t2, gfeat[nb * h * w:]))
         self.loss_align.zero_()
         for f, _, lab, _, rows in sides:
             ops.pcl_loss(f, lab, self.prototypes, self.pcl_temp, self.ig, 0.5, loss=self.loss_align, dfeat=rows)
-        if self.align_domain:
-            self.loss_domain.zero_()
-            domain_loss(self.domain_kind, self.mmd, feat_s, feat_t, self.domain_weight, loss=self.loss_domain,
-                        dfeat_s=sides[0][4], dfeat_t=sides[1][4], accumulate=True)
-        if self.whiten_weight > 0.0:
-            self.loss_white.zero_()
-            for f, _, lab, _, rows in sides:
-                ops.whiten_loss(f, lab, self.C, 32, self.ig, 0.5 * self.whiten_weight, loss=self.loss_white, dfeat=rows,
-                                accumulate=True)
-        if self.contrast_weight > 0.0:
-            self.loss_contrast.zero_()
-            pc = self.contrast
-            for side, (f, lab, _, logits, rows) in enumerate(sides):
-                lab = lab.reshape(lab.shape[0], *lab.shape[-2:])
-                order, counts, anchors, ranks, _ = select_and_plan(lab, logits.float(), self.C, (h, w), self.ig,
-                                                                   pc['max_samples'], pc['max_views'], None)
-                self.last_contrast[side] = None if anchors is None else (order, counts, anchors, ranks)
-                if anchors is None:        # no class of this domain's batch has more than max_views pixels: the term is 0
-                    continue
-                ops.pixel_contrast_loss(f, order, counts, anchors, ranks, pc['temperature'], pc['base_temperature'], pc['eps'],
-                                        0.5 * self.contrast_weight, loss=self.loss_contrast, dfeat=rows, accumulate=True)
-        if self.triplet_weight > 0.0:
-            self.loss_triplet.zero_()
-            for side, (f, _, lab, _, rows) in enumerate(sides):
-                _, stats, ws = ops.triplet_loss(f, lab, self.triplet['margin'], self.ig, 0.5 * self.triplet_weight,
-                                                loss=self.loss_triplet, dfeat=rows, accumulate=True, return_ws=True)
-                self.last_triplet[side] = dict(ops.triplet_tables(ws, rows.shape[0]), stats=stats)
-        if self.dca_weight > 0.0:
-            self.loss_dca.zero_()
-            dc = self.dca
-            dom = ((feat_s, (s1, s2), sides[0][4], nb), (feat_t, (t1, t2), sides[1][4], n - nb))
-            if dc['ccr']:        # the source side is a constant: the target rows alone receive
-                ops.dca_loss(feat_s, (s1, s2), feat_t, (t1, t2), 'logits2', dc['kind'], dc['ignore_bg'], self.dca_weight,
-                             loss=self.loss_dca, dfeat_b=sides[1][4], accumulate=True)
-            if dc['icr']:
-                for f, (p1, p2), rows, bd in dom:
-                    q = bd // 2
-                    ops.dca_loss(f[:q], (p1[:q], p2[:q]), f[q:], (p1[q:], p2[q:]), 'logits2', dc['kind'], dc['ignore_bg'],
-                                 self.dca_weight, loss=self.loss_dca, dfeat_a=rows[:q * h * w], dfeat_b=rows[q * h * w:],
-                                 accumulate=True)
-        if self.saw_weight > 0.0:
-            from .gast.SAW import classifier_weight
-            self.loss_saw.zero_()
-            sw = self.saw
-            cls_w = self.prototypes if sw['classifier'] is None else classifier_weight(sw['classifier']).to(m.device)
-            sel = saw_selection(self.C, sw['selected_classes'])
-            for f, _, _, _, rows in sides:
-                ops.saw_loss(f, cls_w, sel, sw['relax_denom'], 0.5 * self.saw_weight, loss=self.loss_saw, dfeat=rows,
-                             accumulate=True)
-        if self.adv_weight > 0.0:
-            al, size = self.adv['aligner'], tuple(images_t.shape[-2:])
-            weights = [self.adv_weight * float(hw) for hw in self.adv['head_weights']]
-            self.loss_adv = al.generator_term((t1, t2), (g1[nb:], g2[nb:]), weights, size)
-            if self.keep_debug:     # tests: the step's own logits and the target rows of the logit gradients
-                self.debug = dict(s1=s1.clone(), s2=s2.clone(), t1=t1.clone(), t2=t2.clone(), g1_t=g1[nb:].clone(),
-                                  g2_t=g2[nb:].clone())
+        c = Ctx(sides, s1, s2, t1, t2, g1, g2, nb, n, h, w, tuple(images_t.shape[-2:]))
+        on = [t for t in TERMS if getattr(self, t.on) > 0.0]
+        for t in on:
+            t.launch(self, c)
         self._backward_and_update(T, main, g1, g2, gfeat=gfeat)
-        if self.adv_weight > 0.0:
-            self.loss_disc = al.discriminator_step((s1, s2), (t1, t2), size)
+        for t in on:
+            if t.after_update is not None:
+                t.after_update(self, c)
         self.last_hard, self.last_label_t, self.last_label_s_down = hard, label_t, label_s_down
         return loss_seg, self.loss_align, self.gn
-
-    def _downscale(self, hard):
-        b, H, W = hard.shape
-        dummy = torch.zeros((b, 4, H // 16, W // 16), device=hard.device)
-        return ops.proto_update(dummy, hard, torch.zeros((self.C, 4), device=hard.device), 16, self.ig, 0.75, 0.5)

@@ -23,14 +23,7 @@ class DownscaleLabel(torch.nn.Module):
         self.ignore_label, self.min_ratio = ignore_label, min_ratio
 
     def forward(self, label):
-        if label.dim() == 4:
-            label = label.squeeze(1)
-        b, H, W = label.shape
-        s = self.scale_factor
-        # the kernel fuses the downscale with the prototype pass; run it against a dummy feature
-        feat = torch.zeros((b, 4, H // s, W // s), device=label.device)
-        protos = torch.zeros((self.n_classes, 4), device=label.device)
-        return ops.proto_update(feat, label, protos, s, self.ignore_label, self.min_ratio, 0.5)
+        return ops.downscale_label(label, self.n_classes, self.scale_factor, self.ignore_label, self.min_ratio)
 
 
 class Aligner:

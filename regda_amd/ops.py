@@ -310,6 +310,17 @@ def proto_update(feat, label, protos, scale=16, ignore_label=-1, min_ratio=0.75,
     return ds
 
 
+def downscale_label(label, class_num, scale=16, ignore_label=-1, min_ratio=0.75):
+    """DownscaleLabel on its own: (b,H,W) or (b,1,H,W) int64 -> (b,1,H/scale,W/scale) int64.  The kernel fuses the
+    downscale with the prototype pass, so it runs against a dummy 4-channel feature map and dummy prototypes, whose
+    update is thrown away."""
+    if label.dim() == 4:
+        label = label.squeeze(1)
+    b, H, W = label.shape
+    feat = torch.zeros((b, 4, H // scale, W // scale), device=label.device)
+    return proto_update(feat, label, torch.zeros((class_num, 4), device=label.device), scale, ignore_label, min_ratio, 0.5)
+
+
 def proto_stats(feat, label, scale=16, ignore_label=-1, min_ratio=0.75, class_num=6, stats=None, check=False):
     """The sufficient statistics of update_prototype for data-parallel ranks (rgda_proto_stats): returns (stats, ds) --
     `stats` a float32 buffer whose first class_num * k + class_num elements are sums[c][k] and cnt[c] (what the ranks

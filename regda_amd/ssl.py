@@ -367,16 +367,7 @@ class SSLStep:
             self.debug = dict(t1=t1, t2=t2, s1=s1, s2=s2, feat_t=feat_t, feat_s=feat_s, soft_in=soft_t, soft=soft,
                               hard_selected=hard)
         if self.sam_refine:
-            self._lrh_flag_off = (regs.shape[0] * self.max_regions * (self.C + 1)) * 4
-            if fuse_lrh:
-                hard, self.lrh_ws = ops.pseudo_lrh(soft, cm, regs, self.top, self.low, self.percent, self.C, self.ig,
-                                                   self.max_regions, ws=self.lrh_ws)
-            else:
-                need = self._lrh_flag_off + 16
-                if self.lrh_ws is None or self.lrh_ws.numel() < need:
-                    self.lrh_ws = torch.empty(need, dtype=torch.uint8, device=m.device)
-                hard = ops.lrh(hard, regs.contiguous(), self.percent, self.C, self.ig, self.max_regions, check=False,
-                               ws=self.lrh_ws)
+            hard = self._lrh(regs, hard, (soft, cm) if fuse_lrh else None)
         proto_weight = None
         if want_pw:
             proto_weight = ops.proto_pixel_weight(None if sim is not None else feat_t, self.prototypes, hard, sim=sim,
@@ -492,6 +483,19 @@ class SSLStep:
         t.eval()
         x1, x2, _ = t._forward_plan(images_t.contiguous().float(), None)
         return ops.teacher_probs(x1, x2, tuple(images_t.shape[-2:]))
+
+    def _lrh(self, regs, hard, fused=None):
+        """Homogenizer (LRH) of the selected labels `hard` on the step's workspace, which keeps the flag word `lrh_flag()`
+        reads.  fused = (soft, classmax): pseudo_selection + LRH in one pass instead (rgda_pseudo_lrh), `hard` unused."""
+        self._lrh_flag_off = (regs.shape[0] * self.max_regions * (self.C + 1)) * 4
+        if fused is not None:
+            hard, self.lrh_ws = ops.pseudo_lrh(*fused, regs, self.top, self.low, self.percent, self.C, self.ig,
+                                               self.max_regions, ws=self.lrh_ws)
+            return hard
+        need = self._lrh_flag_off + 16
+        if self.lrh_ws is None or self.lrh_ws.numel() < need:
+            self.lrh_ws = torch.empty(need, dtype=torch.uint8, device=self.model.device)
+        return ops.lrh(hard, regs.contiguous(), self.percent, self.C, self.ig, self.max_regions, check=False, ws=self.lrh_ws)
 
     def lrh_flag(self):
         """Deferred check of the LRH kernel's flag word (host sync): region id / label range errors."""

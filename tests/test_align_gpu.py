@@ -60,6 +60,87 @@ def test_pcl_loss_production_shape_weight_and_accumulate():
         ops.pcl_loss(feat.cuda(), lab.cuda(), torch.randn(5, K).cuda())
 
 
+# every optional term of regda_amd.align.TERMS at the weight its own step test uses, and the loss tensors it owns
+TERM_KW = dict(domain=dict(align_domain=True), whiten=dict(whiten_weight=2.0), contrast=dict(contrast_weight=1e-2),
+               triplet=dict(triplet_weight=1.0), dca=dict(dca_weight=100.0), saw=dict(saw_weight=3.0),
+               adv=dict(adv_weight=0.5))
+TERM_LOSSES = dict(domain=('loss_domain',), whiten=('loss_white',), contrast=('loss_contrast',), triplet=('loss_triplet',),
+                   dca=('loss_dca',), saw=('loss_saw',), adv=('loss_adv', 'loss_disc'))
+
+
+@pytest.fixture(scope='module')
+def term_runs():
+    """One stage-2 step per configuration, each from the same initial state, at the smallest shape the stage-2 tests use
+    (resnet17t, 4 + 4 tiles of 128^2: 8 x 8 feature pixels per image): the default step, every optional term alone, and
+    all of them together, twice.  As in the terms' own step tests, max_views is lowered to 8 so that classes qualify for
+    the pixel contrast, and DCA runs its 'mse' kind: the 'cov' kind is NaN on an untrained network (the docstring of
+    tests/test_dca_gpu.py's step test), and a NaN gradient would hide every other term.  The CPU generator the contrast
+    draws from is seeded before every step."""
+    from oracle import model as omodel
+    from regda_amd.align import TERMS, AlignStep
+    from regda_amd.models.Discriminator import FCDiscriminator
+    from regda_amd.models.Encoder import Deeplabv2
+    from regda_amd.synthetic import make_batch
+    assert [t.name for t in TERMS] == list(TERM_KW)
+    rt = 'resnet17t'
+    sd = omodel.init_state_dict(rt, 6, seed=6)
+    g = {k: v.cuda() for k, v in make_batch(b=4, size=128, seed=11, device='cpu').items()}
+    protos = torch.randn(6, 2048, generator=torch.Generator().manual_seed(1))
+    ones = torch.ones(4, 512)
+
+    def run(**kw):
+        m = Deeplabv2(dict(backbone=dict(resnet_type=rt, output_stride=16, pretrained=False), multi_layer=True, cascade=False,
+                           use_ppm=True, ppm=dict(num_classes=6, use_aux=False, fc_dim=2048), inchannels=2048, num_classes=6,
+                           is_ins_norm=True))
+        m.load_state_dict(sd, strict=True)
+        m.set_drop_masks(ones, ones)
+        ds = None
+        if 'adv_weight' in kw:          # as tests/test_adv_step_gpu.py builds them
+            torch.manual_seed(77)
+            ds = [FCDiscriminator(6, ndf=32).cuda() for _ in range(2)]
+        st = AlignStep(m, protos, discriminators=ds, **kw)
+        st.contrast['max_views'], st.dca['kind'] = 8, 'mse'
+        torch.manual_seed(77)
+        loss_seg, _, _ = st.step(g['images_s'], g['label_s'], g['images_t'], g['regs_t'], 1e-3)
+        torch.cuda.synchronize()
+        out = {k: v.clone() for k, v in vars(st).items() if k.startswith('loss_') and torch.is_tensor(v)}
+        out.update(loss_seg=loss_seg.clone(), flat_p=m.flat_p.clone(), flat_g=m.flat_g.clone(), prototypes=st.prototypes.clone(),
+                   last_contrast=list(st.last_contrast),
+                   disc=[p.detach().clone() for d in ds or () for p in d.parameters()])
+        return out
+    everything = {k: v for kw in TERM_KW.values() for k, v in kw.items()}
+    runs = {name: run(**kw) for name, kw in TERM_KW.items()}
+    runs.update(default=run(), all=run(**everything), again=run(**everything))
+    return runs
+
+
+def test_all_terms_in_one_step_leave_each_terms_loss_as_it_is_alone(term_runs):
+    """Every term's loss reads the forward's tensors, the labels and the prototypes, none reads the gradient rows: with
+    all terms on, each loss is bit for bit the one of the step that ran that term alone, and the segmentation and PCL
+    losses are the default step's."""
+    both = term_runs['all']
+    for name, losses in TERM_LOSSES.items():
+        for k in losses:
+            print(name, k, both[k].item(), term_runs[name][k].item())
+            assert both[k].item() != 0.0 and torch.equal(both[k], term_runs[name][k]), (name, k)
+            assert term_runs['default'][k].item() == 0.0, k         # a term that is off does not touch its tensor
+    for k in ('loss_seg', 'loss_align'):
+        assert torch.equal(both[k], term_runs['default'][k]), k
+    assert both['last_contrast'][0] is not None and both['last_contrast'][1] is not None
+
+
+def test_all_terms_in_one_step_accumulate_in_a_fixed_order(term_runs):
+    """Two steps with every term on are bit-identical (weights, gradient, prototypes, discriminators), and their gradient
+    is none of the single terms'."""
+    both, again = term_runs['all'], term_runs['again']
+    for k in ('flat_p', 'flat_g', 'prototypes'):
+        assert torch.equal(both[k], again[k]), k
+    assert len(both['disc']) > 0 and all(torch.equal(a, b) for a, b in zip(both['disc'], again['disc']))
+    assert torch.isfinite(both['flat_g']).all()
+    for name in list(TERM_KW) + ['default']:
+        assert not torch.equal(both['flat_g'], term_runs[name]['flat_g']), name
+
+
 def test_align_step_matches_the_oracle_stage2_step():
     """regda_amd.align.AlignStep (stage 2, tools/train_align_reg.py:144-196) end to end against oracle.step.CpuAlignStep
     on the shallow topology: losses, labels, gradient norm, prototype update, SGD direction."""
