@@ -255,6 +255,24 @@ class AlignStep(SSLStep):
         with ops.use_stream(torch.cuda.current_stream()):
             return self._step(images_s, label_s, images_t, None, regs_t)
 
+    # training state (regda_amd/ssl.py): the adversarial term's discriminators and their Adam moments join the step's own
+    _STATE_EXTRA = ('adv',)
+
+    def _state_extra(self):
+        aligner = self.adv['aligner']
+        return {} if aligner is None else {'adv': aligner.state_dict()}
+
+    def _state_loads(self, sd, strict):
+        loads = super()._state_loads(sd, strict)
+        aligner = self.adv['aligner']
+        if ('adv' in sd) != (aligner is not None) and (strict or 'adv' in sd):
+            raise ValueError(f"state entry 'step.adv': the state has {'an' if 'adv' in sd else 'no'} adversarial aligner, "
+                             f"step.adv['aligner'] is {'set' if aligner is not None else 'None'}")
+        if 'adv' in sd:
+            aligner.check_state_dict(sd['adv'], strict, 'step.adv')
+            loads.append(lambda: aligner.load_state_dict(sd['adv'], strict=strict))
+        return loads
+
     def capture(self, *a, **k):
         raise NotImplementedError('whole-step graph capture is provided for the SSL step only')
 

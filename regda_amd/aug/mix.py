@@ -22,6 +22,31 @@ class DomainMix:
         self.ignore_label = ignore_label
         self.rng = np.random.default_rng(seed)
 
+    # training state (regda_amd/checkpoint.py): where the generator stands.  The 128-bit words of numpy's bit generators
+    # travel as decimal strings, everything else as it is
+    def state_dict(self):
+        def enc(v):
+            if isinstance(v, dict):
+                return {k: enc(x) for k, x in v.items()}
+            return str(v) if isinstance(v, int) and not isinstance(v, bool) and abs(v) >= 2 ** 63 else v
+        return {'rng': enc(self.rng.bit_generator.state)}
+
+    def load_state_dict(self, sd, strict=True):
+        def dec(v):
+            if isinstance(v, dict):
+                return {k: dec(x) for k, x in v.items()}
+            return int(v) if isinstance(v, str) and v.lstrip('-').isdigit() else v
+        if not isinstance(sd, dict) or not isinstance(sd.get('rng'), dict):
+            raise ValueError("state entry 'DomainMix.rng' is missing")
+        own = self.rng.bit_generator.state['bit_generator']
+        if sd['rng'].get('bit_generator') != own:
+            raise ValueError(f"state entry 'DomainMix.rng.bit_generator': {sd['rng'].get('bit_generator')!r}, this "
+                             f'object draws from {own!r}')
+        try:
+            self.rng.bit_generator.state = dec(sd['rng'])      # numpy validates the rest and leaves the state on error
+        except (KeyError, TypeError, ValueError) as e:
+            raise ValueError(f"state entry 'DomainMix.rng': {e}") from None
+
     def draw(self, h, w):
         """One batch's draw for h x w tiles -> None (this batch is not mixed), ('classes', (ids...)) or
         ('box', (y0, y1, x0, x1)): the keyword and value ops.domain_mix takes.  Every call draws the coin first, so the

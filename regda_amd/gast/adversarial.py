@@ -20,6 +20,7 @@ optimizer is torch.optim (ten small tensors per discriminator).  Nothing here sy
 import torch
 
 from .. import ops
+from ..checkpoint import check_module_state, need, plain
 from ..models.Discriminator import backward_rows, forward_rows
 
 
@@ -45,6 +46,44 @@ class AdversarialAligner:
         for d in self.discriminators:
             if d is not None:
                 d.check_served((b, C, size[0], size[1]), 'AdversarialAligner')
+
+    # training state (regda_amd/checkpoint.py)
+    def state_dict(self):
+        """{'discriminators': [state_dict() or None per head], 'optimizer': the optimizer's state_dict()}, plain data"""
+        torch.cuda.synchronize()
+        return plain({'discriminators': [None if d is None else d.state_dict() for d in self.discriminators],
+                      'optimizer': self.optimizer.state_dict()})
+
+    def check_state_dict(self, sd, strict=True, entry='AdversarialAligner'):
+        """ValueError naming the entry where load_state_dict would not take `sd`; writes nothing"""
+        ds = need(sd, 'discriminators', entry)
+        if not isinstance(ds, list) or len(ds) != len(self.discriminators):
+            raise ValueError(f"state entry '{entry}.discriminators': expected a list of {len(self.discriminators)}")
+        for i, (d, s) in enumerate(zip(self.discriminators, ds)):
+            if (d is None) != (s is None):
+                raise ValueError(f"state entry '{entry}.discriminators[{i}]': the state has "
+                                 f"{'none' if s is None else 'one'}, this object has {'none' if d is None else 'one'}")
+            if d is not None:
+                check_module_state(d, s, f'{entry}.discriminators[{i}]', strict)
+        opt = need(sd, 'optimizer', entry)
+        groups, own = need(opt, 'param_groups', entry + '.optimizer'), self.optimizer.state_dict()['param_groups']
+        need(opt, 'state', entry + '.optimizer')
+        if not isinstance(groups, list) or [len(g['params']) for g in groups] != [len(g['params']) for g in own]:
+            raise ValueError(f"state entry '{entry}.optimizer.param_groups': the parameter groups differ from this optimizer's")
+
+    def load_state_dict(self, sd, strict=True):
+        """Validates first, then loads the discriminators (in place), the optimizer's moments, and rebuilds the bf16
+        operand copies.  Nothing of the generator term's cached forward survives."""
+        self.check_state_dict(sd, strict)
+        torch.cuda.synchronize()
+        for d, s in zip(self.discriminators, sd['discriminators']):
+            if d is not None:
+                d.load_state_dict(s, strict=strict)
+        self.optimizer.load_state_dict(sd['optimizer'])
+        self._target = [None] * len(self.discriminators)
+        for d in self.discriminators:
+            if d is not None:
+                d.operands()
 
     def _forward(self, d, x, size):
         b, C = x.shape[:2]

@@ -10,6 +10,7 @@ align_instance are not: their distances end in `.detach()` in the reference, so 
 import torch
 
 from .. import ops
+from ..checkpoint import check_tensor, copy_in_place, need, plain
 from .class_ware_whiten import ClassWareWhitening
 from .coral import CoralLoss
 from .mmd import MMDLoss
@@ -102,6 +103,38 @@ class Aligner:
         if self._avg_stats is None:
             return torch.zeros([self.class_num, self.feat_channels], device='cuda')
         return self._avg_stats[:self.class_num * self.feat_channels].view(self.class_num, self.feat_channels)
+
+    # training state (regda_amd/checkpoint.py)
+    def state_dict(self):
+        """{'prototypes', 'data_sum', 'data_cnt'} as CPU tensors; the two totals are None before the first update_avg."""
+        torch.cuda.synchronize()
+        have = self._avg_stats is not None
+        return {'prototypes': plain(self.prototypes), 'data_sum': plain(self.data_sum) if have else None,
+                'data_cnt': plain(self.data_cnt) if have else None}
+
+    def load_state_dict(self, sd, strict=True):
+        """Validates first (ValueError naming the entry, nothing written), then copies into the tensors this object
+        already holds.  strict=False: entries the state lacks are left as they are."""
+        C, K = self.class_num, self.feat_channels
+        shapes = {'prototypes': (C, K), 'data_sum': (C, K), 'data_cnt': (C, 1)}
+        got = {}
+        for k, shape in shapes.items():
+            if strict or (isinstance(sd, dict) and k in sd):
+                got[k] = need(sd, k, 'Aligner')
+                if got[k] is not None or k == 'prototypes':
+                    check_tensor(got[k], 'Aligner.' + k, shape)
+        if ('data_sum' in got) != ('data_cnt' in got) or (got.get('data_sum') is None) != (got.get('data_cnt') is None):
+            raise ValueError("state entries 'Aligner.data_sum' and 'Aligner.data_cnt' come together")
+        if 'prototypes' in got:
+            copy_in_place(self.prototypes, got['prototypes'])
+        if 'data_sum' in got:
+            if got['data_sum'] is None:
+                self._avg_stats = None
+            else:
+                if self._avg_stats is None:
+                    self._avg_stats = torch.zeros(C * K + C, dtype=torch.float32, device=self.prototypes.device)
+                copy_in_place(self._avg_stats[:C * K], got['data_sum'].reshape(-1))
+                copy_in_place(self._avg_stats[C * K:], got['data_cnt'].reshape(-1))
 
     def update_prototype(self, feat, label):
         """Update global prototypes by source features and labels (alignment.py:86-90)."""

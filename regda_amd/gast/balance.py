@@ -8,6 +8,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from .. import ops
+from ..checkpoint import check_tensor, copy_in_place, need, plain
 
 
 def sync_class_counts(cnt, group=None, comm=None):
@@ -47,6 +48,18 @@ class ClassBalance(nn.Module):
         returned per class (the kernel looks the pixel's class up)."""
         self.ema_update(label)
         return self._get_class_wight().detach()
+
+    # training state (regda_amd/checkpoint.py): the frequency EMA travels in the module's state_dict() as extra state
+    def get_extra_state(self):
+        return {'freq': plain(self.freq)}
+
+    def check_extra_state(self, state, entry='ClassBalance'):
+        check_tensor(need(state, 'freq', entry), entry + '.freq', (self.class_num,))
+
+    def set_extra_state(self, state):
+        self.check_extra_state(state)
+        # ema_update rebinds `freq` at every step, so no launch plan holds its address: assigned, not copied into
+        self.freq = state['freq'].to(self.freq.device).float().clone()
 
     def __str__(self):
         f = self.freq.cpu().numpy()
@@ -172,6 +185,16 @@ class GHMLoss(_FusedLoss):
     def _params(self):
         return dict(acc_sum=self.acc_sum, momentum=float(self.momentum))
 
+    def get_extra_state(self):
+        return {'acc_sum': plain(self.acc_sum)}
+
+    def check_extra_state(self, state, entry='GHMLoss'):
+        check_tensor(need(state, 'acc_sum', entry), entry + '.acc_sum', (self.bins_num,))
+
+    def set_extra_state(self, state):
+        self.check_extra_state(state)
+        copy_in_place(self.acc_sum, state['acc_sum'])      # in place: a recorded step holds the buffer's address
+
     def get_g_distribution(self):
         return self.acc_sum / (self.acc_sum.sum() + 1e-7)
 
@@ -205,6 +228,19 @@ class GDPLoss(_FusedLoss):
         if class_balance:
             self.class_balancer = class_balancer if class_balancer is not None else ClassBalance(
                 class_num=class_num, ignore_label=ignore_label, decay=0.99, temperature=temp)
+
+    def get_extra_state(self):
+        return {'acc_sum': plain(self.acc_sum), 'bins_weight': plain(self.bins_weight)}
+
+    def check_extra_state(self, state, entry='GDPLoss'):
+        for k in ('acc_sum', 'bins_weight'):
+            check_tensor(need(state, k, entry), f'{entry}.{k}', (self.bins_num,))
+
+    def set_extra_state(self, state):
+        # the loss's balancer is a submodule: its frequencies travel under 'class_balancer._extra_state'
+        self.check_extra_state(state)
+        copy_in_place(self.acc_sum, state['acc_sum'])      # in place: a recorded step holds the buffers' addresses
+        copy_in_place(self.bins_weight, state['bins_weight'])
 
     def set_prototype_weight_4pixel(self, weight_prototype):
         """The prototype weights of the NEXT forward call(s): f32, one per label pixel (any shape)."""

@@ -785,6 +785,23 @@ class Deeplabv2(nn.Module):
             }
         return self._mat_cache[key]
 
+    def build_maps(self, H, W):
+        """Make the PPM heads' host-built operand tables for H x W tiles now; otherwise the first forward at that size
+        makes them.  Their contents come from host copies, which a recorded plan does not repeat: made INSIDE a recording
+        they would sit in the plan's memory pool, in blocks that intermediates of earlier launches of the same step had
+        used and released, and the first replay of those launches would overwrite them.  SSLStep.record_plan / capture
+        call this first, so a step may be recorded without an eager step before it (after load_state_dict)."""
+        if self.head_kind != 'ppm':
+            return
+        h, w = H, W
+        for _ in range(4):      # stem, max-pool, layer2, layer3: each ceil(x / 2) (output stride 16)
+            h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        if self.factored_ppm:
+            self._pool_maps(h, w)
+            self._ppm_maps(h, w)
+        else:
+            self._mats(h, w)
+
     def _conv_stats(self, x, w, c, stats, G, N, H, W, Ho, Wo, k, stride, pad, dil, res=None, queue=None):
         """Forward conv (+ `res` added in the epilogue, before the statistics) with BatchNorm statistics per row
         group; falls back to one launch per group when the groups are not a multiple of the pixel tile (tiny PPM

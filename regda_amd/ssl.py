@@ -13,6 +13,8 @@ import torch
 
 from . import ops
 from . import plan
+from .checkpoint import (FORMAT, check_equal, check_format, check_module_state, check_tensor, copy_in_place, need,
+                         plain)
 from .ddp import FlatGradReducer, all_reduce_prototype_statistics
 from .gast.balance import source_loss, target_loss
 
@@ -113,7 +115,8 @@ class SSLStep:
     def capture(self, images_s, label_s, images_t, soft_t, regs_t):
         """Capture one whole step (both streams) into a hipGraph; later `step()` calls replay it.  The step is a
         static launch sequence over fixed shapes, so replay removes the ~20 ms of per-step host launch work.
-        Call after at least one eager step (momentum initialisation is a different kernel variant)."""
+        Call after at least one eager step, or after load_state_dict() of a run that has stepped (momentum
+        initialisation is a different kernel variant)."""
         self._check_shape(images_s, images_t)
         assert not self.first, 'run one eager step before capture()'
         if self.world > 1:
@@ -123,6 +126,7 @@ class SSLStep:
             # address of the pre-capture tensor and never advance the EMA.  record_plan() re-runs it as a host action.
             raise RuntimeError('class balancing (--bcs / --bct) is host-side state: use record_plan(), not capture()')
         self._static = self._static_inputs(images_s, label_s, images_t, soft_t, regs_t)
+        self._build_maps(images_s)
         torch.cuda.synchronize()
         m = self.model
         m._hw_ready = m._wt_ready = None          # everything recorded before the synchronize is complete
@@ -134,6 +138,13 @@ class SSLStep:
                     torch.cuda.current_stream().wait_stream(self.wgrad_stream)     # of the step join the graph
         m._hw_ready = m._wt_ready = None          # (they are events inside the graph now: nothing to wait for outside)
         self._graph = g
+
+    def _build_maps(self, images):
+        """The models' host-built operand tables for these tiles, made before a recording or capture starts
+        (Deeplabv2.build_maps): a step loaded from a saved state may not have run a forward yet."""
+        for net in (self.model, self.teacher):
+            if net is not None:
+                net.build_maps(*images.shape[-2:])
 
     @staticmethod
     def _static_inputs(images_s, label_s, images_t, soft_t, regs_t):
@@ -156,19 +167,133 @@ class SSLStep:
         t.eval()
         return t
 
+    # ------------------------------------------------------------------ training state (regda_amd/checkpoint.py)
+    _STATEFUL = ('class_balancer_s', 'class_balancer_t', 'loss_fn_s', 'loss_fn_t')
+    _STATE_EXTRA = ()       # the entries a subclass adds (_state_extra)
+
+    def _state_config(self):
+        m = self.model
+        return dict(class_num=self.C, ignore_label=self.ig, loss_s=self.loss_fn_s.kind, loss_t=self.loss_fn_t.kind,
+                    ema_decay=self.ema_decay, model=dict(resnet_type=m.resnet_type, head_kind=m.head_kind,
+                                                         num_classes=m.num_classes, n_param=m.flat_p.numel()))
+
+    def _state_extra(self):
+        """What a subclass adds to state_dict()"""
+        return {}
+
+    def state_dict(self, rng=True):
+        """Everything the run needs to continue with the bits of the uninterrupted one, as plain data (nested dicts and
+        lists of CPU tensors, numbers, strings, None: torch.load(weights_only=True) reads a file of it): the model's
+        state_dict(), momentum, the optimizer's `first` flag, prototypes, the teacher's state_dict(), the balancers' and
+        losses' statistics and, with `rng`, torch's CPU and device generator states (the Dropout2d seeds and the contrast
+        term's draws come from the CPU one).  Not state: gradients, the learning rate word, the last_* / loss_* outputs,
+        workspaces, plans, streams, and the parameter dicts the caller sets (step.contrast, ...).  Synchronises the
+        device first: the end of a step leaves work on the side streams."""
+        torch.cuda.synchronize()
+        sd = dict(format=FORMAT, kind=type(self).__name__, config=self._state_config(), model=self.model.state_dict(),
+                  mom=self.mom, first=bool(self.first), prototypes=self.prototypes)
+        if self.teacher is not None:
+            sd['teacher'] = self.teacher.state_dict()
+        for name in self._STATEFUL:
+            obj = getattr(self, name)
+            s = obj.state_dict() if obj is not None else None
+            if s:
+                sd[name] = s
+        sd.update(self._state_extra())
+        if rng:
+            sd['rng'] = dict(cpu=torch.get_rng_state(), cuda=torch.cuda.get_rng_state(self.model.device))
+        return plain(sd)
+
+    def _state_loads(self, sd, strict):
+        """Validate every entry of `sd` against this step (ValueError naming the entry; nothing is written here) and
+        return the writes, in order, as closures for load_state_dict to run once ALL of them are known to be good."""
+        check_format(sd, 'step')
+        check_equal(need(sd, 'kind', 'step'), type(self).__name__, 'step.kind')
+        cfg, own = need(sd, 'config', 'step'), self._state_config()
+        for k in ('class_num', 'ignore_label', 'loss_s', 'loss_t'):
+            check_equal(need(cfg, k, 'step.config'), own[k], 'step.config.' + k)
+        for k, v in own['model'].items():
+            check_equal(need(need(cfg, 'model', 'step.config'), k, 'step.config.model'), v, 'step.config.model.' + k)
+        if ('teacher' in sd) != (self.teacher is not None) and (strict or 'teacher' in sd):
+            raise ValueError(f"state entry 'step.teacher': the state has {'a' if 'teacher' in sd else 'no'} teacher, this "
+                             f"step has {'one' if self.teacher is not None else 'none'} (ema_decay)")
+        known = {'format', 'kind', 'config', 'model', 'mom', 'first', 'prototypes', 'teacher', 'rng', *self._STATEFUL,
+                 *self._STATE_EXTRA}
+        if strict and set(sd) - known:
+            raise ValueError(f'state entries {sorted(set(sd) - known)} of the step are unknown to this {type(self).__name__}')
+        take = lambda k: need(sd, k, 'step') if strict or k in sd else None     # strict=False: what is there
+        loads = []
+        m = self.model
+        if take('model') is not None:
+            check_module_state(m, sd['model'], 'step.model', strict)
+            loads.append(lambda: m.load_state_dict(sd['model'], strict=strict))    # in place; re-syncs the bf16 mirrors
+        for k, dst in (('mom', self.mom), ('prototypes', self.prototypes)):
+            if take(k) is not None:
+                check_tensor(sd[k], 'step.' + k, dst.shape, dst.dtype)
+                loads.append(lambda dst=dst, k=k: copy_in_place(dst, sd[k]))
+        if take('first') is not None:
+            if not isinstance(sd['first'], bool):
+                raise ValueError(f"state entry 'step.first': expected a bool, got {sd['first']!r}")
+            if sd['first'] and self._plan is not None:
+                raise ValueError("state entry 'step.first': the state is that of a run that has not stepped, and this "
+                                 "step holds a recorded plan, which is the optimizer's later variant: release_plan() first")
+            loads.append(lambda: setattr(self, 'first', sd['first']))
+        t = self.teacher
+        if t is not None and 'teacher' in sd:
+            check_module_state(t, sd['teacher'], 'step.teacher', strict)
+
+            def load_teacher():
+                t.load_state_dict(sd['teacher'], strict=strict)
+                t.refresh_from_master()         # flat_pb and _synced_version agree with the shadow again
+            loads.append(load_teacher)
+        for name in self._STATEFUL:
+            obj = getattr(self, name)
+            own_state = obj.state_dict() if obj is not None else None
+            if (name in sd) != bool(own_state) and (strict or name in sd):
+                raise ValueError(f"state entry 'step.{name}': the state has {'one' if name in sd else 'none'}, this step "
+                                 f"has {'one' if own_state else 'none'}")
+            if name in sd:
+                check_module_state(obj, sd[name], 'step.' + name, strict)
+                loads.append(lambda obj=obj, name=name: obj.load_state_dict(sd[name], strict=strict))
+        if 'rng' in sd:
+            cpu, cuda = (need(sd['rng'], k, 'step.rng') for k in ('cpu', 'cuda'))
+            for k, v in (('cpu', cpu), ('cuda', cuda)):
+                check_tensor(v, 'step.rng.' + k, dtype=torch.uint8)
+            loads.append(lambda: (torch.set_rng_state(cpu), torch.cuda.set_rng_state(cuda, m.device)))
+        return loads
+
+    def load_state_dict(self, sd, strict=True):
+        """Continue the run `sd` (a state_dict()) was taken from.  Every entry is validated before the first is written:
+        a mismatch (format, step class, class count, loss kinds, prototype / momentum size, model fingerprint, teacher or
+        not, missing keys) raises ValueError naming the entry and leaves the step untouched and usable.  Each tensor is
+        copied into the storage the step already owns, so a recorded plan (record_plan) stays valid and replays the
+        loaded state.  A captured hipGraph owns generator state that is not restored: RuntimeError -- load first, capture
+        afterwards.  `first` is what was saved: a step loaded from a run that has stepped may record_plan() or capture()
+        at once.  strict=False loads the entries and keys that are there."""
+        if self._graph is not None:
+            raise RuntimeError(f'{type(self).__name__}.load_state_dict: this step holds a captured graph, which owns '
+                               f'generator state that a load cannot restore: load the state first and capture() afterwards')
+        loads = self._state_loads(sd, strict)
+        torch.cuda.synchronize()        # the last step's tail is still writing weights and mirrors on the side streams
+        for load in loads:
+            load()
+        torch.cuda.synchronize()
+
     def record_plan(self, images_s, label_s, images_t, soft_t, regs_t, lr=None):
         """Record one whole step (all streams) as a launch plan (regda_amd/plan.py): its ~750 entry-point calls become
         rows of a table that `rgda_plan_run` walks in C, the torch ops / stream waits between them stay host actions.
         Later `step()` calls replay the plan on the recorded buffers (a private memory pool): same kernels, same
-        streams, same results as the eager step, a fraction of the host time.  Call after at least one eager step
-        (the first step initialises the momentum with another kernel variant).  Inputs are copied into static
-        buffers at every replay; the returned tensors (losses, `last_hard`, ...) are overwritten by the next step."""
+        streams, same results as the eager step, a fraction of the host time.  Call after at least one eager step, or
+        after load_state_dict() of a run that has stepped (the first step initialises the momentum with another kernel
+        variant).  Inputs are copied into static buffers at every replay; the returned tensors (losses, `last_hard`,
+        ...) are overwritten by the next step."""
         self._check_shape(images_s, images_t)
         assert not self.first, 'run one eager step before record_plan()'
         assert self._graph is None and self._plan is None
         self._static = self._static_inputs(images_s, label_s, images_t, soft_t, regs_t)
         if lr is not None:          # recording IS a real step: run it with this learning rate (default: the last one)
             ops.set_f32(self.lr_dev, lr)
+        self._build_maps(images_s)
         torch.cuda.synchronize()
         self._plan_stream = torch.cuda.current_stream()
         p = plan.Plan()
@@ -232,10 +357,14 @@ class SSLStep:
         if balancer is None:
             return None
         cw = torch.empty(2, self.C, device=label.device)
+        here = torch.cuda.current_stream()
 
         def update():
-            for hd in range(2):
-                cw[hd].copy_(balancer.next_class_weight(label))
+            # a replay runs this on `here` as torch's stream, but with the library's stream set to the plan's: the count
+            # kernel and the torch arithmetic on its result must share one (the source side runs on the second stream)
+            with ops.use_stream(here):
+                for hd in range(2):
+                    cw[hd].copy_(balancer.next_class_weight(label))
         plan.host(update)
         return cw
 

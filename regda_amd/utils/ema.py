@@ -23,6 +23,34 @@ class ExponentialMovingAverage:
     def register(self):
         self.shadow = {n: p.detach().clone() for n, p in self._trainable()}
 
+    # training state (regda_amd/checkpoint.py): the averaged weights; `backup` lives only between apply_shadow / restore
+    def state_dict(self):
+        return {'shadow': {n: v.detach().to('cpu', copy=True) for n, v in self.shadow.items()}}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd, strict=True):
+        """Validates first (ValueError naming the entry, nothing written), then copies into the shadow tensors this
+        object holds, creating those it lacks.  strict=False: names the state lacks are left as they are."""
+        shadow = sd.get('shadow') if isinstance(sd, dict) else None
+        if not isinstance(shadow, dict):
+            raise ValueError("state entry 'ExponentialMovingAverage.shadow' is missing")
+        params = dict(self._trainable())
+        missing = [n for n in params if n not in shadow]
+        extra = [n for n in shadow if n not in params]
+        if strict and (missing or extra):
+            raise ValueError(f"state entry 'ExponentialMovingAverage.shadow': missing {missing[:4]}, unexpected {extra[:4]}")
+        for n, v in shadow.items():
+            if n in params and (not isinstance(v, torch.Tensor) or v.shape != params[n].shape):
+                raise ValueError(f"state entry 'ExponentialMovingAverage.shadow.{n}': expected a tensor of shape "
+                                 f'{tuple(params[n].shape)}')
+        for n, v in shadow.items():
+            if n not in params:
+                continue
+            if n in self.shadow:
+                self.shadow[n].copy_(v)
+            else:
+                self.shadow[n] = v.to(device=params[n].device, dtype=params[n].dtype, copy=True)
+
     @torch.no_grad()
     def update(self):
         d = self.decay

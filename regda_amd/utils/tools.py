@@ -380,6 +380,18 @@ class IASTSelector:
         self.n_class, self.alpha, self.beta, self.gamma = n_class, pl_alpha, pl_beta, pl_gamma
         self.cls_thresh = np.ones(n_class) * 0.9
 
+    # training state (regda_amd/checkpoint.py): the thresholds, as the float64 they are
+    def state_dict(self):
+        return {'cls_thresh': torch.from_numpy(np.array(self.cls_thresh, dtype=np.float64))}
+
+    def load_state_dict(self, sd, strict=True):
+        if not isinstance(sd, dict) or 'cls_thresh' not in sd:
+            raise ValueError("state entry 'IASTSelector.cls_thresh' is missing")
+        t = sd['cls_thresh']
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or tuple(t.shape) != (self.n_class,):
+            raise ValueError(f"state entry 'IASTSelector.cls_thresh': expected a float64 tensor of {self.n_class} thresholds")
+        self.cls_thresh = t.detach().cpu().numpy().copy()
+
     def quantiles(self):
         """q_c of np.percentile(arr, 100 * (1 - alpha * w_c ** gamma)), scalar by scalar as ias_thresh computes them."""
         w = self.cls_thresh
