@@ -1280,6 +1280,47 @@ int rgda_disc_head_bwd(const float* dz, const void* a4, const float* w, void* da
 int rgda_bce_logits(const float* z, int n, float label, float scale, float* loss, int accumulate, float* dz,
                     rgda_stream_t stream);
 
+/* ------------------------------------------------ feature-space adversarial alignment (csrc/fada_kernels.hip)
+ * PixelDiscriminator (regda/models/Discriminator.py:60-78: D = Conv2d(input_nc, ndf, 3, 1, 1) + LeakyReLU(0.2) +
+ * Conv2d(ndf, ndf/2, 3, 1, 1) + LeakyReLU(0.2), then cls1 and cls2 = Conv2d(ndf/2, num_classes, 3, 1, 1), concatenated:
+ * FADA's class-level discriminator, Wang et al. 2020) on pixel-major DENSE bf16 rows.  D.0 and D.2 run on rgda_conv2d
+ * (mode 0 / mode 1 on the transposed operand), rgda_disc_bias_lrelu, rgda_conv2d_wgrad_grouped and rgda_disc_bias_grad; the
+ * entry points below are what those do not provide.  Stored activations are post-LeakyReLU, stored gradients are
+ * gradients of pre-activations.  Deterministic: fixed summation orders, no floating-point atomics.  Every check comes
+ * before any launch; every row buffer must stay below 2^31 bytes (RGDA_ERR_UNSUPPORTED).
+ *
+ * rgda_feat_pack_rows: x f32, image n / channel c / pixel p at x[n * ldb + c * ldc + p] (a strided NCHW view: NCHW, a
+ *   channel slice, a batch slice) -> rows bf16 [b*hw][ld], columns 0 .. k-1 written (round to nearest even), the others
+ *   untouched.  ld >= k, ld % 8 == 0, rows 16-byte aligned.  A 64 x 64 transpose through LDS: loads coalesced along the
+ *   pixels, stores along the channels.  Replaces the permute + cast in front of Discriminator.py:72.  One launch.
+ * rgda_feat_unpack_rows: the inverse, dx[n * ldb + c * ldc + p] = (accumulate ? dx : 0) + scale * rows[n * hw + p][c].
+ * rgda_fada_head: the two heads (Discriminator.py:70-71, 75-77) as ONE 3 x 3 / pad 1 convolution to 32 columns on
+ *   v_mfma_f32_32x32x16_bf16: a2 bf16 [N*H*W][Ch], wh bf16 [32][9][Ch] (cls1 rows 0 .. nc-1, cls2 rows nc .. 2nc-1, zero
+ *   rows beyond; tap = kh * 3 + kw), bias f32 [32].  Ch % 32 == 0, 1 <= nc <= 16.  Two uses, one or both per call:
+ *   z != NULL : z f32 [N*H*W][32] is stored.
+ *   x2 != NULL: (z need not be stored) x2 f32 (N, nc, H, W) are logits; with a[k] = min(softmax_k(x2 / T), clip), S = sum_k
+ *     a[k], logp = log_softmax(z[0 .. 2nc)), M = N*H*W and side in {0, 1}:
+ *       loss[0] += scale / M * sum_p -sum_k a[k] logp[side * nc + k]   (per-workgroup partials in ws, then one fixed-order sum)
+ *       dz bf16 [N*H*W][32] = scale / M * (S * softmax(z)_j - a'_j), a' = a in that side's half; columns >= 2nc zero.
+ *     T > 0, clip > 0; ws: rgda_fada_head_workspace(M) bytes.  Two launches.
+ * rgda_fada_head_bwd_data: da bf16 [N*H*W][Ch] = mask * sum dz[(y + 1 - kh, x + 1 - kw)][j] * wt[c][tap][j] from dz bf16
+ *   [N*H*W][32] and wt bf16 [Ch][9][32] (rgda_weight_transpose_bf16 of wh); mask = below > 0 ? 1 : slope from `below` bf16
+ *   [N*H*W][Ch], the stored activation.  Also D.2's data gradient where ndf / 2 == 32.  One launch.
+ *   The heads' weight and bias gradients are rgda_conv2d_wgrad_grouped and rgda_disc_bias_grad with 32 columns.
+ * rgda_lrelu_mask_rows: g bf16 [M][C] *= (a > 0 ? 1 : slope) in place, a bf16 [M][C]; C % 8 == 0: the pass behind the
+ *   generic data gradient (rgda_conv2d mode 1) of D.2.  One launch. */
+int rgda_feat_pack_rows(const float* x, int b, int hw, int64_t ldc, int64_t ldb, int k, void* rows, int ld,
+                        rgda_stream_t stream);
+int rgda_feat_unpack_rows(const void* rows, int ld, float* dx, int b, int hw, int64_t ldc, int64_t ldb, int k, float scale,
+                          int accumulate, rgda_stream_t stream);
+size_t rgda_fada_head_workspace(int64_t M);
+int rgda_fada_head(const void* a2, const void* wh, const float* bias, int N, int H, int W, int Ch, int nc, float* z,
+                   const float* x2, int side, float T, float clip, float scale, float* loss, void* dz, void* ws,
+                   size_t ws_bytes, rgda_stream_t stream);
+int rgda_fada_head_bwd_data(const void* dz, const void* wt, const void* below, void* da, int N, int H, int W, int Ch,
+                            float slope, rgda_stream_t stream);
+int rgda_lrelu_mask_rows(void* g, const void* a, int64_t M, int C, float slope, rgda_stream_t stream);
+
 /* Factored form of the PPM heads' tap-shifted bilinear maps (regda/models/Encoder.py:30-51: Upsample(bilinear,
  * align_corners=False) of the s x s branches into the 3x3 / pad 1 conv_last): the map V[(y,x)][(jy,jx),(ky,kx)] =
  * Uy[y+ky-1][jy] * Ux[x+kx-1][jx] is separable, so V and V^T are applied as two short maps (csrc/mix_kernels.hip).

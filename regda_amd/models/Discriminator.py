@@ -11,7 +11,8 @@ deterministic weight gradient and the fixed-order bias sums.  The bf16 operand c
 are rebuilt when a parameter's `_version` has moved, e.g. after an optimizer step.
 
 Served: f32 inputs on the GPU, 6 <= num_classes <= 16, H % 32 == 0 and W % 32 == 0, ndf % 32 == 0; anything else raises
-with the cause.  Not provided: FCDiscriminator_Local (a 2048 + C channel input), PixelDiscriminator.
+with the cause.  Not provided: FCDiscriminator_Local (a 2048 + C channel input).  PixelDiscriminator lives in its own module,
+regda_amd/models/PixelDiscriminator.py.
 """
 import torch
 import torch.nn as nn

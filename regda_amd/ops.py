@@ -2025,3 +2025,120 @@ def bce_logits(z, label, scale=1.0, loss=None, accumulate=False, want_grad=True)
     lib().call('rgda_bce_logits', z.data_ptr(), z.numel(), float(label), float(scale), loss.data_ptr(), int(bool(accumulate)),
                _p(dz), _stream())
     return loss, dz
+
+
+# ---------------------------------------------------------------- feature-space adversarial alignment (fada_kernels.hip)
+FADA_CP = 32            # columns of a head row of PixelDiscriminator: 2 * num_classes <= 32
+FADA_MAX_CLASSES = 16
+
+
+def check_fada_classes(nc, who='num_classes'):
+    """ValueError unless 1 <= nc <= FADA_MAX_CLASSES (the two heads share one 32-column tile)."""
+    if not 1 <= int(nc) <= FADA_MAX_CLASSES:
+        raise ValueError(f'{who}: {nc} classes; the head kernel serves 1 <= num_classes <= {FADA_MAX_CLASSES}')
+
+
+def feat_pack_rows(x, out=None):
+    """x f32 (b, k, h, w) on the GPU (read in place through its channel and image strides where the pixels of an image
+    are contiguous) -> bf16 rows [b*h*w, ld] with columns 0 .. k-1 written; `out` gives a wider, caller-filled buffer."""
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError(f'feat_pack_rows: f32 (b, k, h, w) features, got {x.dtype} {tuple(x.shape)}')
+    _need_cuda(x, out)
+    x, b, hw, ldc, ldb, k = _feat_rows(x, 'feat_pack_rows')
+    if out is None:
+        if k % 8:
+            raise ValueError(f'feat_pack_rows: {k} channels; dense rows need k % 8 == 0 (or a wider `out`)')
+        out = torch.empty((b * hw, k), dtype=torch.bfloat16, device=x.device)
+    _rows_bf16(out, out.shape[1], 'feat_pack_rows')
+    assert out.shape[0] == b * hw and out.shape[1] >= k
+    lib().call('rgda_feat_pack_rows', x.data_ptr(), b, hw, ldc, ldb, k, out.data_ptr(), out.shape[1], _stream())
+    return out
+
+
+def feat_unpack_rows(rows, dx, scale=1.0, accumulate=False):
+    """dx f32 (b, k, h, w) (a strided view as in feat_pack_rows) = (accumulate ? dx : 0) + scale * rows[:, :k]"""
+    _need_cuda(rows, dx)
+    assert dx.dim() == 4 and dx.dtype == torch.float32
+    b, k, h, w = dx.shape
+    ldb, ldc = dx.stride(0), dx.stride(1)
+    assert (w == 1 or dx.stride(3) == 1) and (h == 1 or dx.stride(2) == w) and ldc >= h * w and (b == 1 or ldb >= ldc * k), \
+        'feat_unpack_rows: the pixels of one image must be contiguous'
+    _rows_bf16(rows, rows.shape[1], 'feat_unpack_rows')
+    assert rows.shape[0] == b * h * w and rows.shape[1] >= k
+    lib().call('rgda_feat_unpack_rows', rows.data_ptr(), rows.shape[1], dx.data_ptr(), b, h * w, ldc, ldb, k, float(scale),
+               int(bool(accumulate)), _stream())
+    return dx
+
+
+def _fada_head_operands(a2, wh, bias, N, H, W, who):
+    _need_cuda(a2, wh, bias)
+    rows, taps, Ch = wh.shape
+    assert rows == FADA_CP and taps == 9 and wh.dtype == torch.bfloat16 and wh.is_contiguous(), who
+    assert bias.dtype == torch.float32 and bias.numel() == FADA_CP and bias.is_contiguous(), who
+    _rows_bf16(a2, Ch, who)
+    assert a2.shape[0] == N * H * W
+    return Ch
+
+
+def fada_head(a2, wh, bias, N, H, W, nc):
+    """The two heads of PixelDiscriminator: a2 bf16 [N*H*W, Ch], wh bf16 [32, 9, Ch], bias f32 [32] -> z f32 [N*H*W, 32]
+    (columns 0 .. 2 nc - 1 live)."""
+    check_fada_classes(nc, 'fada_head')
+    Ch = _fada_head_operands(a2, wh, bias, N, H, W, 'fada_head')
+    z = torch.empty((N * H * W, FADA_CP), dtype=torch.float32, device=a2.device)
+    lib().call('rgda_fada_head', a2.data_ptr(), wh.data_ptr(), bias.data_ptr(), N, H, W, Ch, int(nc), z.data_ptr(), 0, 0, 1.0,
+               1.0, 0.0, 0, 0, 0, 0, _stream())
+    return z
+
+
+def fada_loss(a2, wh, bias, x2, side, temperature=1.8, clip=0.9, scale=1.0, loss=None, want_z=False):
+    """The fused head + loss: with z = head(a2), a = min(softmax(x2 / temperature), clip) (x2 f32 (N, nc, H, W) logits, no
+    gradient) and M = N*H*W, loss (f32 [1], accumulating) += scale * l(z, a, side) and dz bf16 [M, 32] = scale * dl/dz.
+    -> (loss, dz, z or None)."""
+    if x2.dim() != 4 or x2.dtype != torch.float32:
+        raise ValueError(f'fada_loss: f32 (N, nc, H, W) logits, got {x2.dtype} {tuple(x2.shape)}')
+    N, nc, H, W = x2.shape
+    check_fada_classes(nc, 'fada_loss')
+    if side not in (0, 1):
+        raise ValueError(f'fada_loss: side is 0 (source) or 1 (target), got {side!r}')
+    if not temperature > 0 or not clip > 0:
+        raise ValueError(f'fada_loss: temperature and clip must be positive, got {temperature!r} and {clip!r}')
+    _need_cuda(x2, loss)
+    Ch = _fada_head_operands(a2, wh, bias, N, H, W, 'fada_loss')
+    x2 = x2.contiguous()
+    loss = _loss_out(loss, a2.device)
+    M = N * H * W
+    dz = torch.empty((M, FADA_CP), dtype=torch.bfloat16, device=a2.device)
+    z = torch.empty((M, FADA_CP), dtype=torch.float32, device=a2.device) if want_z else None
+    L = lib()
+    ws = _ws(L.size('rgda_fada_head_workspace', M), a2.device)
+    L.call('rgda_fada_head', a2.data_ptr(), wh.data_ptr(), bias.data_ptr(), N, H, W, Ch, nc, _p(z), x2.data_ptr(), int(side),
+           float(temperature), float(clip), float(scale), loss.data_ptr(), dz.data_ptr(), ws.data_ptr(), ws.numel(), _stream())
+    return loss, dz, z
+
+
+def fada_head_backward_data(dz, wt, below, N, H, W, slope=DISC_SLOPE):
+    """da bf16 [N*H*W, Ch] from dz bf16 [N*H*W, 32] and wt bf16 [Ch, 9, 32], masked by the sign of `below` bf16 [N*H*W, Ch],
+    the stored activation."""
+    _need_cuda(dz, wt, below)
+    Ch, taps, cp = wt.shape
+    assert taps == 9 and cp == FADA_CP and wt.dtype == torch.bfloat16 and wt.is_contiguous()
+    _rows_bf16(dz, FADA_CP, 'fada_head_backward_data')
+    assert dz.shape[0] == N * H * W
+    _rows_bf16(below, Ch, 'fada_head_backward_data')
+    assert below.shape[0] == N * H * W
+    da = torch.empty((N * H * W, Ch), dtype=torch.bfloat16, device=dz.device)
+    lib().call('rgda_fada_head_bwd_data', dz.data_ptr(), wt.data_ptr(), below.data_ptr(), da.data_ptr(), N, H, W, Ch, float(slope),
+               _stream())
+    return da
+
+
+def lrelu_mask_rows(g, a, slope=DISC_SLOPE):
+    """g bf16 [M, C] *= (a > 0 ? 1 : slope) in place (a: the stored activation, same shape)"""
+    _need_cuda(g, a)
+    M, C = g.shape
+    _rows_bf16(g, C, 'lrelu_mask_rows')
+    _rows_bf16(a, C, 'lrelu_mask_rows')
+    assert a.shape[0] == M
+    lib().call('rgda_lrelu_mask_rows', g.data_ptr(), a.data_ptr(), M, C, float(slope), _stream())
+    return g

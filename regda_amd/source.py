@@ -14,11 +14,23 @@ align_domain='mmd' / 'mmd_linear' puts the MMD of regda/gast/mmd.py (rgda_mmd_lo
 `self.mmd`, alignment.py:68) in CORAL's place, on the same gradient rows; `mmd=dict(kernel_mul=, kernel_num=, fix_sigma=)`
 sets its kernel parameters and `domain_weight` scales either domain term.
 
+fada_weight > 0 adds the feature-space, class-level adversarial term of regda_amd/gast/fada.py (FADA's recipe on
+regda/models/Discriminator.py:60-78's PixelDiscriminator) onto the same rows: after CORAL / MMD,
+fada_weight * l(D(feat_t), a_t, source side) adds its gradient onto the TARGET rows (there is no adversarial term on the
+source features); after the model's update the discriminator (`pixel_discriminator=`, default
+PixelDiscriminator(2048, 512, class_num)) takes one Adam step on the step's own detached features and head-2 logits of
+both domains.  Both domains then run as two BatchNorm groups even without align_domain (the rows start at zero).
+`step.fada = dict(aligner=, temperature=, clip=)` is read at every step; `step.loss_fada` and `step.loss_fada_disc` hold
+the terms.  fada_weight = 0, the default, launches exactly what the step launched before.  The discriminator's gradients
+are not all-reduced: with data-parallel ranks the term raises NotImplementedError.
+
 Data-parallel ranks compute CORAL / MMD on their local batch (the rank's own source and target pixels),
 the same per-rank semantics as the per-GPU BatchNorm statistics: there is no extra collective."""
 import torch
 
 from . import ops
+from .gast.fada import FeatureAdversarialAligner
+from .models.PixelDiscriminator import PixelDiscriminator
 from .ssl import SSLStep
 
 BF = torch.bfloat16
@@ -46,7 +58,10 @@ def domain_loss(kind, mmd, feat_s, feat_t, weight, **kw):
 
 class SourceStep(SSLStep):
     def __init__(self, model, class_balancer_s=None, align_domain=False, class_num=6, loss_s='CrossEntropy', mmd=None,
-                 domain_weight=1.0, **kw):
+                 domain_weight=1.0, fada_weight=0.0, pixel_discriminator=None, **kw):
+        self.fada_weight = float(fada_weight)
+        if not self.fada_weight >= 0.0:         # before the model is touched
+            raise ValueError('SourceStep: fada_weight must be >= 0')
         self.domain_kind, self.mmd = domain_kind(align_domain, mmd)
         if kw.get('ent_weight') or kw.get('kld_weight'):
             raise NotImplementedError('the IAST regularisers (ent_weight / kld_weight) belong to the SSL step')
@@ -58,17 +73,61 @@ class SourceStep(SSLStep):
         self.align_domain = bool(align_domain)
         self.domain_weight = float(domain_weight)
         self.loss_domain = torch.zeros(1, device=model.device)
+        self.loss_fada = torch.zeros(1, device=model.device)
+        self.loss_fada_disc = torch.zeros(1, device=model.device)
+        self.fada = dict(aligner=None, temperature=1.8, clip=0.9)
+        if self.fada_weight > 0.0:
+            d = pixel_discriminator
+            if d is None:
+                d = PixelDiscriminator(2048, 512, class_num).to(model.device)
+            self.fada['aligner'] = FeatureAdversarialAligner(d)
 
     @torch.no_grad()
     def step(self, images_s, label_s, images_t, lr):
         """One stage-1 iteration.  Returns device tensors (loss_seg, loss_domain, grad_norm_sq); loss_domain stays 0
-        without align_domain.  images_t may be None when align_domain is off (no target forward then)."""
+        without align_domain.  images_t may be None when align_domain and fada_weight are off (no target forward then)."""
         if self.align_domain and images_t is None:
             raise ValueError('SourceStep(align_domain=True) needs the target images')
-        self._check_shape(images_s, images_t if self.align_domain else None)
+        if self.fada_weight > 0.0:
+            self._fada_check(images_s, images_t)
+        self._check_shape(images_s, images_t if self.align_domain or self.fada_weight > 0.0 else None)
         ops.set_f32(self.lr_dev, lr)
         with ops.use_stream(torch.cuda.current_stream()):
             return self._step(images_s, label_s, images_t)
+
+    def _fada_check(self, images_s, images_t):
+        if images_t is None:
+            raise ValueError('SourceStep(fada_weight > 0) needs the target images')
+        if self.reducer.active:
+            raise NotImplementedError('SourceStep(fada_weight > 0) with data-parallel ranks: the discriminator\'s gradients '
+                                      'are not all-reduced')
+        aligner = self.fada['aligner']
+        if aligner is None:
+            raise ValueError("SourceStep: fada_weight was 0 at construction, so no discriminator exists; put a "
+                             "FeatureAdversarialAligner into step.fada['aligner']")
+        T, clip = float(self.fada['temperature']), float(self.fada['clip'])
+        if not T > 0.0 or not 0.0 < clip <= 1.0:
+            raise ValueError(f"SourceStep: step.fada needs temperature > 0 and 0 < clip <= 1, got {T!r} and {clip!r}")
+        h, w = ((int(v) + 15) // 16 for v in images_t.shape[-2:])      # the feature map lies at output stride 16
+        aligner.check_served((images_t.shape[0], 2048, h, w), (images_t.shape[0], self.C, h, w))
+
+    # training state (regda_amd/ssl.py): the adversarial term's discriminator and its Adam moments join the step's own
+    _STATE_EXTRA = ('fada',)
+
+    def _state_extra(self):
+        aligner = self.fada['aligner']
+        return {} if aligner is None else {'fada': aligner.state_dict()}
+
+    def _state_loads(self, sd, strict):
+        loads = super()._state_loads(sd, strict)
+        aligner = self.fada['aligner']
+        if ('fada' in sd) != (aligner is not None) and (strict or 'fada' in sd):
+            raise ValueError(f"state entry 'step.fada': the state has {'a' if 'fada' in sd else 'no'} feature-adversarial "
+                             f"aligner, step.fada['aligner'] is {'set' if aligner is not None else 'None'}")
+        if 'fada' in sd:
+            aligner.check_state_dict(sd['fada'], strict, 'step.fada')
+            loads.append(lambda: aligner.load_state_dict(sd['fada'], strict=strict))
+        return loads
 
     def capture(self, *a, **k):
         raise NotImplementedError('whole-step graph capture is provided for the SSL step only')
@@ -84,7 +143,8 @@ class SourceStep(SSLStep):
         ops.fill_zero(m.flat_g)
         nb = images_s.shape[0]
         main = torch.cuda.current_stream()
-        if self.align_domain:
+        fada = self.fada_weight > 0.0
+        if self.align_domain or fada:
             T = m.new_tape(groups=2)
             x1, x2, feat = m._forward_plan([images_s.contiguous().float(), images_t.contiguous().float()], T)
         else:
@@ -100,5 +160,19 @@ class SourceStep(SSLStep):
             gfeat = torch.empty(n * h * w, k, dtype=BF, device=m.device)
             domain_loss(self.domain_kind, self.mmd, feat[:nb], feat[nb:], self.domain_weight, loss=self.loss_domain,
                         dfeat_s=gfeat[:nb * h * w], dfeat_t=gfeat[nb * h * w:])
+        if fada:
+            aligner = self.fada['aligner']
+            aligner.temperature, aligner.clip = float(self.fada['temperature']), float(self.fada['clip'])
+            n, k, h, w = feat.shape
+            if gfeat is None:       # no domain term: the rows start at zero
+                gfeat = torch.zeros(n * h * w, k, dtype=BF, device=m.device)
+            feat_s, feat_t, rows_t = feat[:nb], feat[nb:], gfeat[nb * h * w:]
+            before = rows_t.clone() if self.keep_debug else None
+            self.loss_fada = aligner.generator_term(feat_t, x2[nb:], rows_t, self.fada_weight)
+            if self.keep_debug:     # tests: the step's own features and head-2 logits, the target rows before and after
+                self.debug = dict(feat_s=feat_s.clone(), feat_t=feat_t.clone(), s2=x2[:nb].clone(), t2=x2[nb:].clone(),
+                                  rows_t_before=before, rows_t=rows_t.clone())
         self._backward_and_update(T, main, g1, g2, gfeat=gfeat)
+        if fada:
+            self.loss_fada_disc = aligner.discriminator_step(feat_s, x2[:nb], feat_t, x2[nb:])
         return loss_seg, self.loss_domain, self.gn
