@@ -288,6 +288,46 @@ int rgda_iast_percentile(const double* prepend, const double* q, float* out, int
 int rgda_iast_label(const double* cls_thresh, uint8_t* label, int n, int c, int H, int W, const void* ws,
                     size_t ws_bytes, rgda_stream_t stream);
 
+/* analysis_pseudo_labels + range_static: entropy-binned accuracy tables   regda/gast/pseudo_generation.py:158-235
+ * The reference makes R = 100 passes per image over the (C, H, W) soft label; here one pass bins every pixel.
+ * rgda_pseudo_analysis: soft NCHW f32 (b,c,H,W), gt int64 (b,H,W), lo / hi: device f32[R], the bin edges as the reference
+ *   compares them (f32(1.0 * i * step), f32(1.0 * i * step + step), step = log(c) / R).  Per pixel
+ *     pseudo      the decision of rgda_pseudo_select (threshold max(classmax * cutoff_top, cutoff_low) in f32, strict >,
+ *                 exactly one passing class).  The per-image per-class maxima are NOT an argument: the call runs the
+ *                 maximum pass of rgda_pseudo_select itself, into the tail of `tables`.
+ *     entropy     sum_c -p_c * log(p_c) in fp64 in class order, rounded once to f32 (:185 sums in f32); NaN where a
+ *                 probability is exactly 0, as in the reference
+ *     difficulty  1 - p[gt] in f32, 1 where gt == ignore_label (:188-191); always a multiple of 2^-24
+ *   and the pixel is counted in every bin i with lo[i] <= entropy < hi[i] (the candidate bin and both neighbours are
+ *   tested: the rounded edges of some (c, R) overlap or gap by an ulp); a NaN entropy is counted in row R instead (the
+ *   reference keeps such a pixel in every bin's used / true / difficulty sums, :226, :232, but in no bin's pixel count,
+ *   :233; the fold adds row R accordingly).  tables, written by the call (cleared first), per image T = (R + 1) * (2 * c + 2)
+ *   int64:   used[R + 1][c] (pixels whose pseudo label is class k) | hit[R + 1][c] (of those, pseudo == gt) |
+ *            inbin[R + 1] | diff24[R + 1] (the sum of difficulty * 2^24: exact)
+ *   then, after the b images, int32 flag (bit 0: a probability outside [0, 1] or not finite, :71; bit 1: a gt outside
+ *   [0, c) that is not ignore_label, :189; such pixels are skipped), int32 pad, f32 classmax[b][c].
+ *   rgda_pseudo_analysis_workspace(b, c, R): the bytes of `tables` (0 = bad arguments); 8-byte aligned.
+ * rgda_pseudo_analysis_fold: one workgroup adds a batch's tables to a running state, image after image (:195-207):
+ *     acc = cnt_true / (cnt_used + 1e-7), acc_cnt += (cnt_used != 0)       cnt_* = the sums over the classes, row R added
+ *     diffi = (diff24 / 2^24) / (inbin + 1e-7), diffi_cnt += (diff24 != 0)  diff24 with row R added, inbin without
+ *   both quotients in fp64 from the exact integers (the reference: f32).  state, rgda_pseudo_analysis_fold_workspace(c, R)
+ *   bytes, zeroed by the caller before the first batch, 8-byte aligned:
+ *     int64 total[T] (as one image's tables, row R kept apart) | f64 acc_sum[R] | f64 diffi_sum[R] | int64 images |
+ *     int32 acc_cnt[R] | int32 diffi_cnt[R] | int32 flag (the batches' flags or-ed) | padding to 8 bytes.
+ * soft needs 4-byte alignment only: where it, gt or H * W rule out 16-byte loads, both passes take scalar loads.
+ * 6 <= c <= 16 (RGDA_ERR_UNSUPPORTED); 1 <= R <= 256, b * H * W < 2^31, H * W <= 2^31 - 16384 (the passes' int steps),
+ * b * c <= 65535 (grid y of the maximum pass), null or misaligned pointers (RGDA_ERR_ARG); a short
+ * buffer (RGDA_ERR_WORKSPACE); all before any launch.  Integer atomics only and a fixed image order: deterministic, and
+ * nothing is read back. */
+#define RGDA_ANALYSIS_MAX_BINS 256
+size_t rgda_pseudo_analysis_workspace(int b, int c, int R);
+int rgda_pseudo_analysis(const float* soft, const int64_t* gt, const float* lo, const float* hi, int b, int c, int H, int W,
+                         int R, float cutoff_top, float cutoff_low, int ignore_label, void* tables, size_t tables_bytes,
+                         rgda_stream_t stream);
+size_t rgda_pseudo_analysis_fold_workspace(int c, int R);
+int rgda_pseudo_analysis_fold(const void* tables, size_t tables_bytes, int b, int c, int R, void* state, size_t state_bytes,
+                              rgda_stream_t stream);
+
 /* Aligner.get_prototype_weight_4pixel(feats, label_hard)   regda/gast/alignment.py:267-281 (+ _pearson_dist :396-423).
  * feat NCHW f32 (b,k,h,w); protos (c,k) f32; label (b,H,W) int64; out f32[b*H*W]:
  *   sim = 1 / pearson_dist(feat, protos) at (b,c,h,w) -> bilinear align_corners=True to (H,W) -> softmax over the classes

@@ -581,6 +581,68 @@ def iast_label(ws, cls_thresh, n, H, W, out=None):
     return out
 
 
+ANALYSIS_MAX_BINS = 256     # RGDA_ANALYSIS_MAX_BINS
+
+
+def analysis_views(tables, b, c, R):
+    """The pieces of a rgda_pseudo_analysis buffer -> (used int64 [b, R + 1, c], hit [b, R + 1, c], inbin [b, R + 1],
+    diff24 [b, R + 1], flag int32 [1]).  Row R holds the pixels whose entropy is NaN."""
+    rows = R + 1
+    T = rows * (2 * c + 2)
+    t = tables[:b * T * 8].view(torch.int64).view(b, T)
+    return (t[:, :rows * c].view(b, rows, c), t[:, rows * c:2 * rows * c].view(b, rows, c),
+            t[:, 2 * rows * c:2 * rows * c + rows], t[:, 2 * rows * c + rows:], tables[b * T * 8:b * T * 8 + 4].view(torch.int32))
+
+
+def pseudo_analysis(soft, gt, lo, hi, cutoff_top, cutoff_low, ignore_label, tables=None):
+    """soft f32 (b, c, H, W), gt int64 (b, H, W), lo / hi f32 [R] (the bin edges) -> the buffer holding the batch's
+    per-image entropy-binned tables (rgda_pseudo_analysis; analysis_views reads them).  soft may be a contiguous view
+    that starts anywhere in its buffer."""
+    _need_cuda(soft, gt, lo, hi)
+    assert soft.dim() == 4 and soft.dtype == torch.float32 and gt.dtype == torch.int64
+    assert lo.dtype == hi.dtype == torch.float32 and lo.shape == hi.shape and lo.dim() == 1
+    soft, gt, lo, hi = soft.contiguous(), gt.contiguous(), lo.contiguous(), hi.contiguous()
+    b, c, H, W = soft.shape
+    assert gt.shape == (b, H, W), 'gt must be (b, H, W) for soft (b, c, H, W)'
+    check_class_count(c, 'pseudo_analysis')
+    L = lib()
+    need = L.size('rgda_pseudo_analysis_workspace', b, c, lo.numel())
+    if tables is None or tables.numel() < need:
+        tables = _ws(need, soft.device)
+    L.call('rgda_pseudo_analysis', soft.data_ptr(), gt.data_ptr(), lo.data_ptr(), hi.data_ptr(), b, c, H, W, lo.numel(),
+           cutoff_top, cutoff_low, ignore_label, tables.data_ptr(), tables.numel(), _stream())
+    return tables
+
+
+def pseudo_analysis_state(c, R, device):
+    """A zeroed running state for pseudo_analysis_fold (rgda_pseudo_analysis_fold_workspace bytes)."""
+    check_class_count(c, 'pseudo_analysis')
+    return torch.zeros(lib().size('rgda_pseudo_analysis_fold_workspace', c, R), dtype=torch.uint8, device=device)
+
+
+def pseudo_analysis_fold(tables, b, c, R, state):
+    """Adds the b images of a pseudo_analysis buffer to the running state, in image order (rgda_pseudo_analysis_fold)."""
+    _need_cuda(tables, state)
+    lib().call('rgda_pseudo_analysis_fold', tables.data_ptr(), tables.numel(), b, c, R, state.data_ptr(), state.numel(),
+               _stream())
+    return state
+
+
+def pseudo_analysis_state_views(state, c, R):
+    """The pieces of a running state (any device) -> dict of total_used / total_hit [R + 1, c], total_inbin /
+    total_diff24 [R + 1], acc_sum / diffi_sum f64 [R], images, acc_cnt / diffi_cnt int32 [R], flag."""
+    rows = R + 1
+    T = rows * (2 * c + 2)
+    o = T * 8
+    tot = state[:o].view(torch.int64)
+    f = state[o:o + 16 * R].view(torch.float64)
+    i = state[o + 16 * R + 8:o + 16 * R + 8 + 8 * R + 4].view(torch.int32)
+    return dict(total_used=tot[:rows * c].view(rows, c), total_hit=tot[rows * c:2 * rows * c].view(rows, c),
+                total_inbin=tot[2 * rows * c:2 * rows * c + rows], total_diff24=tot[2 * rows * c + rows:],
+                acc_sum=f[:R], diffi_sum=f[R:], images=state[o + 16 * R:o + 16 * R + 8].view(torch.int64),
+                acc_cnt=i[:R], diffi_cnt=i[R:2 * R], flag=i[2 * R:])
+
+
 def proto_pixel_weight(feat, protos, label, sim=None, ignore_label=-1, out=None):
     """Aligner.get_prototype_weight_4pixel (rgda_proto_pixel_weight; alignment.py:267-281) -> f32 [b*H*W]: the prototype
     agreement of every label pixel with its own label, 0 where the label is ignored.  feat (b,k,h,w), protos (c,k),
