@@ -500,7 +500,9 @@ __global__ void __launch_bounds__(256) loss_grad_kernel(const float* __restrict_
                     // (1 - pt)^gamma * ce, pt = exp(-ce); d/d ce = (1 - pt)^gamma + gamma (1 - pt)^(gamma - 1) pt ce
                     const float pt = expf(-ce), q = 1.f - pt;
                     const float qg = prm.gamma == 2.f ? q * q : powf(q, prm.gamma);
-                    const float qg1 = prm.gamma == 2.f ? q : powf(q, prm.gamma - 1.f);
+                    // gamma == 0 is the plain CE: the second term is 0 for every q, also at q == 0 (a CE of exactly 0),
+                    // where powf(0, -1) = inf would make it 0 * inf; torch's pow backward gives 0 there too
+                    const float qg1 = prm.gamma == 2.f ? q : (prm.gamma == 0.f ? 0.f : powf(q, prm.gamma - 1.f));
                     lp = qg * ce;
                     dce = (qg + prm.gamma * qg1 * pt * ce) * inv_d;
                 } else if constexpr (KIND == RGDA_LOSS_GHM) {

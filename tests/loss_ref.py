@@ -43,7 +43,7 @@ def ghm_g(p, label, ig=-1):
     """|p_y - 1| per pixel, -1 where the label is ignored."""
     prob = torch.softmax(p.detach(), 1).permute(0, 2, 3, 1).reshape(-1, p.shape[1])
     lab = label.reshape(-1)
-    py = prob.gather(1, lab.clamp(min=0)[:, None])[:, 0]
+    py = prob.gather(1, torch.where(lab == ig, torch.zeros_like(lab), lab)[:, None])[:, 0]
     return torch.where(lab == ig, torch.full_like(py, -1.0), (py - 1.0).abs())
 
 
