@@ -839,6 +839,58 @@ int rgda_domain_mix(const float* img_s, const int64_t* label_s, float* img_t, in
                     int64_t* regs_t, int N, int C, int H, int W, int mode, uint32_t class_bits, int y0, int y1, int x0,
                     int x1, int ignore_label, int* flag, rgda_stream_t stream);
 
+/* rgda_domain_mix with the predicate of every image read from a device table, and the image written out of place: the
+ * mix a training step does on its own inputs (DACS: the student sees the mixed tile, the teacher the clean one), where
+ * the arguments of a recorded launch are frozen and the table is not.
+ *   table int32 [N][RGDA_MIX_TABLE_COLS], 16-byte aligned: row n = {class_bits, y0, y1, x0, x1, 0, 0, 0}, the predicate
+ *     of image n as rgda_domain_mix takes it; `mode` says which columns are read and stays a launch argument.
+ *   img_in f32 [N][3][H][W] (read only), img_out f32 [N][3][H][W]: img_out[n] = cond ? img_s[n] : img_in[n], EVERY pixel
+ *     written (img_out may be img_in: the in-place mix).  Both NULL: no image work, the call that pastes labels.
+ *   label_t int64 [N][H][W], soft_t f32 [N][C][H][W], each or NULL: pasted in place, as rgda_domain_mix does.
+ * cond, the pasted values, the flag, the 16-byte route (W % 4 == 0 and every given pointer 16-byte aligned) and its
+ * element fallback are those of rgda_domain_mix with row n's values, image by image: a row with class_bits == 0 or an
+ * empty box pastes nothing, reads no label and sets no flag.  The rows are read on the device and cannot be refused
+ * before the launch: a class bit at or above C selects nothing, and a box is cut to the tile by construction (only the
+ * tile's pixels are visited), so no row makes the kernel leave its tensors.
+ * Errors before any launch (RGDA_ERR_ARG): null img_s / label_s; null or misaligned table; N, H or W < 1; C outside
+ * 1..32; an unknown mode; img_in without img_out or img_out without img_in. */
+#define RGDA_MIX_TABLE_COLS 8
+int rgda_domain_mix_table(const float* img_s, const int64_t* label_s, const float* img_in, float* img_out,
+                          int64_t* label_t, float* soft_t, const int32_t* table, int N, int C, int H, int W, int mode,
+                          int ignore_label, int* flag, rgda_stream_t stream);
+
+/* The DACS draw on the device (half of the classes that OCCUR in each source label map): writes table[n][0], the
+ * class_bits of image n, and leaves the other columns alone.
+ *   label_s int64 [N][H][W]; ranks uint8 [N][C], row n a permutation of 0..C-1 (the host's draw, rgda_mix_write_table)
+ *   present(n) = the classes of [0, C) that occur in label_s[n], P = |present(n)|
+ *   selected(n) = the (P + 1) / 2 (integer division) classes of present(n) with the smallest ranks[n][c]; P = 0: none.
+ *     Equal ranks (not a permutation) are ordered by class id, and a rank at or above C never selects its class: a row
+ *     of 255s is how a step says "no mix for this batch" without changing its launch sequence.
+ *   ws: workspace of N uint32 words (4-byte aligned), the presence sets; zeroed BY the call, any contents on entry.
+ * A label that is neither in [0, C) nor ignore_label sets *flag (optional, device int) to 1 and is otherwise skipped.
+ * Three launches: clear ws; presence (many workgroups per image, 16-byte loads where H * W is even and label_s is
+ * 16-byte aligned, an OR per wave, per workgroup, then one atomic OR per workgroup); the choice (C threads per image).
+ * Presence is an OR, so the result does not depend on the order of anything: two runs are bit-identical.
+ * Errors before any launch (RGDA_ERR_ARG): null label_s / ranks / ws; null or misaligned table; N, H or W < 1; C
+ * outside 1..32. */
+int rgda_mix_select_classes(const int64_t* label_s, const uint8_t* ranks, int32_t* table, uint32_t* ws, int N, int C,
+                            int H, int W, int ignore_label, int* flag, rgda_stream_t stream);
+
+/* The host's draw -> device, carried IN THE KERNEL ARGUMENTS of one launch (as rgda_set_f32 carries the learning rate):
+ * nothing is staged in host memory that a later call could overwrite before the device has read it, so a host that runs
+ * a step ahead of the device is safe.
+ *   table int32 [N][RGDA_MIX_TABLE_COLS], 16-byte aligned: every row becomes {class_bits, y0, y1, x0, x1, 0, 0, 0}
+ *     (all zero: the empty table, which pastes nothing in either mode)
+ *   ranks uint8 [N][C] on the device and ranks_host, N * C bytes of HOST memory read during the call, both or neither:
+ *     ranks = ranks_host (what rgda_mix_select_classes reads).  A recorded plan must not table this call with a host
+ *     pointer; the step calls it from a host action.
+ * N above RGDA_MIX_WRITE_MAX_IMAGES (the images the argument block holds): RGDA_ERR_UNSUPPORTED.  RGDA_ERR_ARG: null or
+ * misaligned table; N < 1; C outside 1..32; a bit of class_bits at or above C; a box that is not 0 <= y0 <= y1,
+ * 0 <= x0 <= x1; ranks without ranks_host or the reverse. */
+#define RGDA_MIX_WRITE_MAX_IMAGES 16
+int rgda_mix_write_table(int32_t* table, uint8_t* ranks, const uint8_t* ranks_host, int N, int C, uint32_t class_bits,
+                         int y0, int y1, int x0, int x1, rgda_stream_t stream);
+
 /* ------------------------------------------------------------- region maps without SAM */
 
 /* The region maps rgda_lrh and rgda_label_refine_sup read, generated from the raw tile.

@@ -234,7 +234,9 @@ class AlignStep(SSLStep):
         self.domain_kind, self.mmd = domain_kind(align_domain, mmd)
         if kw.get('ent_weight') or kw.get('kld_weight'):
             raise NotImplementedError('the IAST regularisers (ent_weight / kld_weight) belong to the SSL step')
-        kw.setdefault('proto_decay', 0.999)        # Aligner(decay=0.999), train_align_reg.py:112-113
+        if kw.get('mix') is not None:
+            raise NotImplementedError('the in-step cross-domain mix (mix=) belongs to the SSL step')
+        kw.setdefault('proto_decay', 0.999)       # Aligner(decay=0.999), train_align_reg.py:112-113
         kw['ema_decay'] = None
         super().__init__(model, prototypes, **kw)
         self.pcl_temp, self.align_domain, self.domain_weight = pcl_temperature, bool(align_domain), float(domain_weight)

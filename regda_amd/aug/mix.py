@@ -1,5 +1,6 @@
 """The host side of cross-domain mixing: what to paste from the source batch over the target batch,
-drawn per batch; ops.domain_mix / rgda_domain_mix does the pasting (DevicePrefetcher(mix=...) on its copy stream)."""
+drawn per batch; ops.domain_mix / rgda_domain_mix does the pasting (DevicePrefetcher(mix=...) on its copy stream), or,
+inside a training step, ops.domain_mix_table / rgda_domain_mix_table from `draw_step` (SSLStep(mix=...))."""
 import numpy as np
 
 from ..utils.cutmix import box_from_draw
@@ -8,12 +9,15 @@ from ..utils.cutmix import box_from_draw
 class DomainMix:
     """kind 'class': ClassMix, int(class_num * ratio) classes of a permutation (regda/utils/classmix.py:42);
     kind 'box': CutMix, one box from lam ~ Beta(alpha, alpha) and a uniform centre (regda/utils/cutmix.py:17-27).
+    kind 'dacs': DACS, per image half of the classes that occur in its source label map -- the labels live on the device,
+    so the host draws one permutation per image (the classes' ranks) and rgda_mix_select_classes chooses; only a training
+    step can use it (`draw_step`).
     prob: the probability that a batch is mixed at all.  The draws come from this object's own numpy Generator
     (seed), never from a global one, so a run is reproducible from the seed whatever else draws."""
 
     def __init__(self, kind, class_num, ratio=0.5, alpha=1.0, prob=1.0, ignore_label=-1, seed=None):
-        if kind not in ('class', 'box'):
-            raise ValueError("DomainMix: kind must be 'class' or 'box', got %r" % (kind,))
+        if kind not in ('class', 'box', 'dacs'):
+            raise ValueError("DomainMix: kind must be 'class', 'box' or 'dacs', got %r" % (kind,))
         if not 1 <= int(class_num) <= 32:
             raise ValueError('DomainMix: %r classes; rgda_domain_mix serves 1..32' % (class_num,))
         if not 0.0 <= ratio <= 1.0 or not 0.0 <= prob <= 1.0 or not alpha > 0:
@@ -51,6 +55,9 @@ class DomainMix:
         """One batch's draw for h x w tiles -> None (this batch is not mixed), ('classes', (ids...)) or
         ('box', (y0, y1, x0, x1)): the keyword and value ops.domain_mix takes.  Every call draws the coin first, so the
         sequence of a seed does not depend on h and w except through the box itself."""
+        if self.kind == 'dacs':
+            raise ValueError("DomainMix('dacs') chooses among the classes of each source label map, on the device: it is "
+                             "drawn by a training step (SSLStep(mix=...)), not per batch on the host")
         if self.rng.random() >= self.prob:
             return None
         if self.kind == 'class':
@@ -60,3 +67,15 @@ class DomainMix:
         cx = self.rng.uniform(0, w)
         cy = self.rng.uniform(0, h)
         return 'box', box_from_draw(lam, cx, cy, h, w)
+
+    def draw_step(self, n, h, w):
+        """What a training step needs for one batch of n images of h x w -> None (not mixed), ('classes', ids) or
+        ('box', box), one draw for all n images and the same values `draw` gives for this seed, or, for kind 'dacs',
+        ('ranks', uint8 [n][class_num]): one rng.permutation(class_num) per image, image by image, row i the ranks of image
+        i's classes (rgda_mix_select_classes keeps the present classes of smallest rank).  The coin comes first, as in
+        `draw`."""
+        if self.kind != 'dacs':
+            return self.draw(h, w)
+        if self.rng.random() >= self.prob:
+            return None
+        return 'ranks', np.stack([self.rng.permutation(self.class_num) for _ in range(int(n))]).astype(np.uint8)

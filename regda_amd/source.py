@@ -65,6 +65,8 @@ class SourceStep(SSLStep):
         self.domain_kind, self.mmd = domain_kind(align_domain, mmd)
         if kw.get('ent_weight') or kw.get('kld_weight'):
             raise NotImplementedError('the IAST regularisers (ent_weight / kld_weight) belong to the SSL step')
+        if kw.get('mix') is not None:
+            raise NotImplementedError('the in-step cross-domain mix (mix=) belongs to the SSL step')
         kw['ema_decay'] = None
         kw.setdefault('sam_refine', False)
         kw.setdefault('refine_label', False)

@@ -9,6 +9,9 @@ clip + SGD (+ EMA shadow + bf16 weight mirror) kernel.  Optionally the soft targ
 online EMA teacher (regda/utils/ema.py semantics: parameters averaged, BN buffers shared) instead of
 the offline `.pt` files of the reference (BASELINE.json north_star; SURVEY.md header table).
 """
+import copy
+
+import numpy as np
 import torch
 
 from . import ops
@@ -26,7 +29,7 @@ class SSLStep:
                  process_group=None, overlap_wgrad=True, overlap_comm=True, class_balancer_s=None,
                  class_balancer_t=None, grad_payload='fp32', comm=None, loss_s='CrossEntropy', loss_t='none',
                  uvem_m=0.2, uvem_t=0.7, uvem_g=4.0, gdp_prototype=True, gdp_class_balance=False, ent_weight=0.0,
-                 kld_weight=0.0, adv_weight=0.0, discriminators=None):
+                 kld_weight=0.0, adv_weight=0.0, discriminators=None, mix=None):
         if adv_weight or discriminators is not None:
             raise NotImplementedError('the adversarial term (adv_weight / discriminators) belongs to the stage-2 step, AlignStep')
         ops.check_class_count(class_num, type(self).__name__)
@@ -79,6 +82,14 @@ class SSLStep:
         # rgda_upsample_reg call behind the target loss that adds its gradient onto that loss's.  Both 0: no launch.
         self.ent_weight, self.kld_weight = float(ent_weight), float(kld_weight)
         self.loss_ent = self.loss_kld = None    # the unscaled terms of the last step (device tensors)
+        # mix: a regda_amd.aug.mix.DomainMix (kind 'class', 'box' or 'dacs') -- DACS inside the step: the
+        # student's target tile is the source batch pasted over images_t, the teacher (or the offline soft labels) labels
+        # the clean tile, and the source labels are pasted onto the pseudo labels after selection and LRH.  None: no launch.
+        if mix is not None and mix.class_num != class_num:
+            raise ValueError(f'{type(self).__name__}: mix draws among {mix.class_num} classes, the step has {class_num}')
+        self.mix = mix
+        self.mix_flag = torch.zeros(1, dtype=torch.int32, device=dev) if mix is not None else None
+        self.last_mix = self.last_mix_table = None      # the last step's draw (host) and the table its kernels read
         self._graph = None
         self._plan = None
         self._proto_ready = None
@@ -125,6 +136,10 @@ class SSLStep:
             # ClassBalance.next_class_weight rebinds its frequency tensor and is host arithmetic: a graph would keep the
             # address of the pre-capture tensor and never advance the EMA.  record_plan() re-runs it as a host action.
             raise RuntimeError('class balancing (--bcs / --bct) is host-side state: use record_plan(), not capture()')
+        if self.mix is not None:
+            # the draws come from the DomainMix's generator on the host and travel as kernel arguments, which a graph
+            # freezes: record_plan() re-runs the draw and the table write as a host action
+            raise RuntimeError('the cross-domain mix (mix=) draws on the host: use record_plan(), not capture()')
         self._static = self._static_inputs(images_s, label_s, images_t, soft_t, regs_t)
         self._build_maps(images_s)
         torch.cuda.synchronize()
@@ -199,6 +214,8 @@ class SSLStep:
             s = obj.state_dict() if obj is not None else None
             if s:
                 sd[name] = s
+        if self.mix is not None:
+            sd['mix'] = self.mix.state_dict()        # where its generator stands: a resumed run continues the draws
         sd.update(self._state_extra())
         if rng:
             sd['rng'] = dict(cpu=torch.get_rng_state(), cuda=torch.cuda.get_rng_state(self.model.device))
@@ -217,7 +234,7 @@ class SSLStep:
         if ('teacher' in sd) != (self.teacher is not None) and (strict or 'teacher' in sd):
             raise ValueError(f"state entry 'step.teacher': the state has {'a' if 'teacher' in sd else 'no'} teacher, this "
                              f"step has {'one' if self.teacher is not None else 'none'} (ema_decay)")
-        known = {'format', 'kind', 'config', 'model', 'mom', 'first', 'prototypes', 'teacher', 'rng', *self._STATEFUL,
+        known = {'format', 'kind', 'config', 'model', 'mom', 'first', 'prototypes', 'teacher', 'rng', 'mix', *self._STATEFUL,
                  *self._STATE_EXTRA}
         if strict and set(sd) - known:
             raise ValueError(f'state entries {sorted(set(sd) - known)} of the step are unknown to this {type(self).__name__}')
@@ -255,6 +272,15 @@ class SSLStep:
             if name in sd:
                 check_module_state(obj, sd[name], 'step.' + name, strict)
                 loads.append(lambda obj=obj, name=name: obj.load_state_dict(sd[name], strict=strict))
+        if ('mix' in sd) != (self.mix is not None) and (strict or 'mix' in sd):
+            raise ValueError(f"state entry 'step.mix': the state has {'one' if 'mix' in sd else 'none'}, this step has "
+                             f"{'one' if self.mix is not None else 'none'}")
+        if 'mix' in sd:
+            try:
+                copy.deepcopy(self.mix).load_state_dict(sd['mix'])      # validated on a copy: nothing is written here
+            except ValueError as e:
+                raise ValueError(f"state entry 'step.mix': {e}") from None
+            loads.append(lambda: self.mix.load_state_dict(sd['mix']))
         if 'rng' in sd:
             cpu, cuda = (need(sd['rng'], k, 'step.rng') for k in ('cpu', 'cuda'))
             for k, v in (('cpu', cpu), ('cuda', cuda)):
@@ -434,7 +460,14 @@ class SSLStep:
                 ops.fill_zero(m.flat_g)
         else:
             ops.fill_zero(m.flat_g)
-        x1, x2, feat = m._forward_plan([images_s.contiguous().float(), images_t.contiguous().float()], T)
+        student_t = images_t
+        if self.mix is not None:
+            # the teacher above reads the caller's images_t; the student gets the mixed tile, a buffer of the step's own
+            images_s, label_s, mix_table, mix_mode = self._mix_draw(images_s, label_s)
+            student_t = ops.domain_mix_table(images_s, label_s, mix_table, mix_mode, images_in=images_t.contiguous().float(),
+                                             images_out=torch.empty(images_t.shape, dtype=torch.float32, device=images_t.device),
+                                             class_num=self.C, ignore_label=self.ig, flag=self.mix_flag)[0]
+        x1, x2, feat = m._forward_plan([images_s.contiguous().float(), student_t.contiguous().float()], T)
         self._mark('student forward done')
         s1, t1, s2, t2 = x1[:nb], x1[nb:], x2[:nb], x2[nb:]
         # d(loss) / d(logits) of both heads, source rows then target rows: the two loss kernels write their halves in place
@@ -497,6 +530,21 @@ class SSLStep:
                               hard_selected=hard)
         if self.sam_refine:
             hard = self._lrh(regs, hard, (soft, cm) if fuse_lrh else None)
+        if self.mix is not None:
+            # the source labels go onto the FINAL pseudo labels: selection thresholds, label_refine and LRH have seen the
+            # teacher's view of the clean tile only.  The refined soft label is pasted only where the target loss reads it,
+            # and never in the caller's tensor or last_soft_t (refine_label=False makes `soft` that tensor itself)
+            paste_soft = self.loss_fn_t.kind in ('ups', 'uvem')
+            if paste_soft and (soft is soft_t or self.keep_debug):
+                clean, soft = soft, torch.empty(soft.shape, dtype=torch.float32, device=soft.device)
+                plan.host(lambda dst=soft, src=clean: dst.copy_(src))       # a torch op: re-run at every replay
+            if self.keep_debug:
+                self.debug.update(hard_clean=hard)      # the pseudo labels of the clean tile, before the paste
+                hard = hard.clone()
+            ops.domain_mix_table(images_s, label_s, mix_table, mix_mode, label_t=hard, soft_t=soft if paste_soft else None,
+                                 class_num=self.C, ignore_label=self.ig, flag=self.mix_flag)
+            if self.keep_debug:
+                self.debug.update(soft_loss=soft)
         proto_weight = None
         if want_pw:
             proto_weight = ops.proto_pixel_weight(None if sim is not None else feat_t, self.prototypes, hard, sim=sim,
@@ -539,6 +587,44 @@ class SSLStep:
         self._backward_and_update(T, main, g1, g2)
         self.last_hard = hard
         return loss_s, loss_t, self.gn
+
+    def _mix_draw(self, images_s, label_s):
+        """This batch's draw of `self.mix` on the device -> (images_s, label_s as the mixing kernels read them, the table
+        int32 [N][8], the mode).  The draw and the launch that carries it (rgda_mix_write_table: values in the kernel
+        arguments, nothing staged in host memory) are ONE host action, re-run at every replay of a recorded step; a batch
+        whose coin says "no mix" writes the empty table, so the launch sequence never changes.  kind 'dacs': the host
+        draws the classes' ranks and rgda_mix_select_classes chooses among the classes present in each label map."""
+        mx = self.mix
+        images_s, label_s = images_s.contiguous().float(), label_s.contiguous()
+        n, _, h, w = images_s.shape
+        dev = images_s.device
+        dacs = mx.kind == 'dacs'
+        table = torch.empty(n, ops.MIX_TABLE_COLS, dtype=torch.int32, device=dev)
+        ranks = torch.empty(n, self.C, dtype=torch.uint8, device=dev) if dacs else None
+        here = torch.cuda.current_stream()
+
+        def draw():
+            d = mx.draw_step(n, h, w)
+            bits, box, host = 0, (0, 0, 0, 0), None
+            if dacs:        # a rank of 255 never selects its class: the batch that is not mixed
+                host = d[1] if d is not None else np.full((n, self.C), 255, np.uint8)
+            elif d is not None and d[0] == 'classes':
+                bits = ops.mix_class_bits(d[1], self.C)
+            elif d is not None:
+                box = d[1]
+            self.last_mix = d
+            with ops.use_stream(here):      # (a replay runs host actions with the library's stream set to the plan's)
+                ops.mix_write_table(table, self.C, bits, box, ranks, host)
+        plan.host(draw)
+        if dacs:
+            ops.mix_select_classes(label_s, ranks, table, ignore_label=self.ig, flag=self.mix_flag)
+        self.last_mix_table = table
+        return images_s, label_s, table, ops.MIX_BOX if mx.kind == 'box' else ops.MIX_CLASS
+
+    def mix_flag_value(self):
+        """Deferred check of the mixing kernels' flag word (host sync): a source label that is neither a class nor the
+        ignore label."""
+        return 0 if self.mix_flag is None else int(self.mix_flag.item())
 
     def _proto_local(self, feat_s, label_s, exchange):
         """update_prototype on this rank's source batch: the whole update (one rank), or its sufficient statistics only
