@@ -1372,6 +1372,45 @@ int rgda_disc_head_bwd(const float* dz, const void* a4, const float* w, void* da
 int rgda_bce_logits(const float* z, int n, float label, float scale, float* loss, int accumulate, float* dz,
                     rgda_stream_t stream);
 
+/* ------------------------------------------------ category-level adversarial alignment (csrc/clan_kernels.hip)
+ * CLAN (Luo et al., CVPR 2019) around the discriminator above: ONE discriminator reads softmax(up x1 + up x2) of the two
+ * heads, its output is upsampled to the tile, and the BCE there is weighted per pixel by alpha + beta * wmap, wmap the
+ * cosine distance of the two heads' probabilities.  `up` is loss_calc's bilinear map (align_corners=True) everywhere.
+ * Deterministic: fixed summation orders, no floating-point atomics.  Every check comes before any launch; 6 <= C <= 16,
+ * Cp = 16 and every row buffer below 2^31 bytes, or RGDA_ERR_UNSUPPORTED; NULL or misaligned pointers RGDA_ERR_ARG.
+ *
+ * rgda_clan_probs_fwd: x1, x2 f32 (b, C, h, w).  Per pixel of the H x W tile, with u_i = up(x_i), p_i = softmax(u_i):
+ *     P bf16 [b*H*W][Cp] = softmax(u1 + u2), channels C .. Cp-1 zero (rgda_adv_probs_fwd's layout, 16-byte aligned);
+ *     wmap f32 [b*H*W]   = 1 - <p1, p2> / (|p1|_2 |p2|_2)     (no clamp, no epsilon: |softmax|_2 >= 1 / sqrt(C)).
+ *   One launch, one thread per pixel.  Replaces two F.interpolate, three F.softmax, the cosine similarity and their
+ *   autograd nodes.
+ * rgda_clan_probs_bwd: dx1, dx2 f32 (b, C, h, w) += scale * (the transpose of that map), from dP bf16 [b*H*W][Cp], the
+ *   discriminator's gradient, and gw f32 [b*H*W], the gradient with respect to wmap (NULL: none, the weight is a
+ *   constant).  Per pixel, p1, p2 and q = softmax(u1 + u2) recomputed in f32:
+ *     both heads receive  q (dP - <q, dP>);
+ *     head 1 adds  p1 (g1 - <p1, g1>),  g1 = -gw (p2 / (n1 n2) - s p1 / (n1^3 n2)),  s = <p1, p2>, n_i = |p_i|_2;
+ *     head 2 its mirror;
+ *   then the transpose of the bilinear map in gather form: one workgroup per low-resolution pixel over its footprint, 2 C
+ *   accumulators, a fixed two-level sum in LDS.  One launch.
+ * rgda_wbce_logits: WeightedBCEWithLogitsLoss (regda/loss.py:60-85) on an upsampled map.  z f32 [b*hz*wz], zu = up(z) to
+ *   H x W (hz == H and wz == W: the identity); t = target[p] (f32 [b*H*W]) or, target NULL, the constant label in {0, 1};
+ *     l = max(zu, 0) - t zu + log1p(exp(-|zu|)),    k = wmap ? alpha + beta * wmap[p] : 1      (`weighted()`, :66-79)
+ *     loss[0] = (accumulate ? loss[0] : 0) + scale * r * sum_p k l,   r = mean ? 1 / n : 1,  n = b*H*W:  per-workgroup
+ *       partials in ws, then one fixed-order sum;
+ *     dz f32 [b*hz*wz] (NULL: not wanted) = the transpose of `up` applied to scale * r * k (sigmoid(zu) - t), in gather
+ *       form, one workgroup per pixel of z: written, never scattered;
+ *     gw f32 [b*H*W] (NULL: not wanted; needs wmap) = scale * r * beta * l, the gradient with respect to wmap.
+ *   At most three launches.  ws: rgda_wbce_logits_workspace(b, H, W) bytes (0: not served), 16-byte aligned, or
+ *   RGDA_ERR_WORKSPACE. */
+int rgda_clan_probs_fwd(const float* x1, const float* x2, void* P, float* wmap, int b, int C, int h, int w, int H, int W,
+                        int Cp, rgda_stream_t stream);
+int rgda_clan_probs_bwd(const void* dP, const float* gw, const float* x1, const float* x2, float* dx1, float* dx2, int b,
+                        int C, int h, int w, int H, int W, int Cp, float scale, rgda_stream_t stream);
+size_t rgda_wbce_logits_workspace(int b, int H, int W);
+int rgda_wbce_logits(const float* z, int b, int hz, int wz, int H, int W, const float* target, float label, const float* wmap,
+                     float alpha, float beta, float scale, int mean, float* loss, int accumulate, float* dz, float* gw,
+                     void* ws, size_t ws_bytes, rgda_stream_t stream);
+
 /* ------------------------------------------------ feature-space adversarial alignment (csrc/fada_kernels.hip)
  * PixelDiscriminator (regda/models/Discriminator.py:60-78: D = Conv2d(input_nc, ndf, 3, 1, 1) + LeakyReLU(0.2) +
  * Conv2d(ndf, ndf/2, 3, 1, 1) + LeakyReLU(0.2), then cls1 and cls2 = Conv2d(ndf/2, num_classes, 3, 1, 1), concatenated:

@@ -17,7 +17,9 @@ rank 2), on the same kernel plans as the SSL step (regda_amd/ssl.py):
            [+ saw_weight * 0.5 * (SAW(feat_s) + SAW(feat_t)) with saw_weight > 0 (regda/gast/SAW.py, the prototypes as the
               classifier): an extension, tools/train_align_reg.py never constructs that loss]
            [+ adv_weight * sum_i head_weights[i] * BCE(D_i(softmax(up(x_i of the target))), source label) with adv_weight >
-              0 (regda/models/Discriminator.py): an extension, no loop of the reference trains that class]
+              0 (regda/models/Discriminator.py): an extension, no loop of the reference trains that class;
+              adv_kind='clan': adv_weight * wBCE(up(D(softmax(up x1_t + up x2_t))), source label, 1 - cos(softmax(up x1_t),
+              softmax(up x2_t)), epsilon, lambda_local) in its place (regda/loss.py:60-85, regda_amd/gast/clan.py)]
     -> backward -> clip_grad_norm_(32) -> SGD
 
 Differences to the SSL step that matter for the kernels: there is no CE on the target logits (their gradient is
@@ -34,6 +36,7 @@ from . import ops
 from .ddp import all_reduce_prototype_statistics
 from .gast.SAW import classifier_weight
 from .gast.adversarial import AdversarialAligner
+from .gast.clan import CategoryAdversarialAligner
 from .gast.contrastive import select_and_plan
 from .models.Discriminator import FCDiscriminator
 from .source import domain_kind, domain_loss
@@ -175,8 +178,19 @@ def adv(step, c):
     otherwise; after the model's update the discriminators (`discriminators=`: one per head or None for a head to skip)
     take one Adam step on the step's own detached logits of both domains.  Its parameters are kept in `step.adv` and read
     at every step; `step.loss_adv` and `step.loss_disc` hold the terms.  adv_weight = 0, the default, launches nothing.
-    The discriminators' gradients are not all-reduced: with data-parallel ranks the term raises NotImplementedError."""
-    weights = [step.adv_weight * float(hw) for hw in step.adv['head_weights']]
+    The discriminators' gradients are not all-reduced: with data-parallel ranks the term raises NotImplementedError.
+    kind 'clan' (AlignStep(adv_kind='clan')): the category-level form of regda_amd/gast/clan.py in its place -- one
+    discriminator on softmax(up x1 + up x2), its output upsampled to the tile, the BCE weighted per pixel by epsilon +
+    lambda_local * (1 - cos of the two heads' probabilities), at the full adv_weight; head_weights is not read.  epsilon,
+    lambda_local, preheat_steps and weight_grad of `step.adv` are the step's only source for them: they are checked (in
+    adv_check, before anything is launched) and handed to the aligner at every step, over whatever was set on the aligner
+    itself; a resumed state puts the saved three back into `step.adv`.  While the aligner has taken fewer than preheat_steps steps both losses are
+    the plain BCE on the upsampled map."""
+    if step.adv['kind'] == 'clan':
+        step.adv['aligner'].set_hyper(*(step.adv[k] for k in ('epsilon', 'lambda_local', 'preheat_steps', 'weight_grad')))
+        weights = step.adv_weight
+    else:
+        weights = [step.adv_weight * float(hw) for hw in step.adv['head_weights']]
     step.loss_adv = step.adv['aligner'].generator_term((c.t1, c.t2), (c.g1[c.nb:], c.g2[c.nb:]), weights, c.size)
     if step.keep_debug:     # tests: the step's own logits and the target rows of the logit gradients
         step.debug = dict(s1=c.s1.clone(), s2=c.s2.clone(), t1=c.t1.clone(), t2=c.t2.clone(), g1_t=c.g1[c.nb:].clone(),
@@ -185,6 +199,16 @@ def adv(step, c):
 
 def adv_construct(step):
     ds = step._adv_discriminators
+    if step.adv['kind'] == 'clan':
+        live = [] if ds is None else [d for d in ds if d is not None]
+        if ds is not None and len(live) != 1:
+            raise ValueError(f"AlignStep(adv_kind='clan'): one discriminator reads softmax(x1 + x2); discriminators= holds "
+                             f"{len(live)}")
+        d = live[0] if live else FCDiscriminator(step.C).to(step.model.device)
+        a = step.adv
+        step.adv['aligner'] = CategoryAdversarialAligner(d, epsilon=a['epsilon'], lambda_local=a['lambda_local'],
+                                                         preheat_steps=a['preheat_steps'], weight_grad=a['weight_grad'])
+        return
     if ds is None:
         ds = [FCDiscriminator(step.C).to(step.model.device) for _ in range(2)]
     step.adv['aligner'] = AdversarialAligner(ds)
@@ -197,6 +221,9 @@ def adv_check(step, images_s, images_t):
     if step.adv['aligner'] is None:
         raise ValueError("AlignStep: adv_weight was 0 at construction, so no discriminators exist; put an "
                          "AdversarialAligner into step.adv['aligner']")
+    if step.adv['kind'] == 'clan':
+        CategoryAdversarialAligner.check_hyper(step.adv['epsilon'], step.adv['lambda_local'], step.adv['preheat_steps'],
+                                               "AlignStep(adv_kind='clan'): step.adv")
     step.adv['aligner'].check_served(images_t.shape[0], step.C, tuple(images_t.shape[-2:]))
 
 
@@ -213,14 +240,16 @@ TERMS = (Term('domain', 'align_domain', None, domain),
          Term('dca', 'dca_weight', dict(kind='cov', ccr=True, icr=True, ignore_bg=True), dca, dca_check),
          Term('saw', 'saw_weight', dict(relax_denom=0.0, selected_classes=None, classifier=None), saw,
               lambda step, *images: saw_selection(step.C, step.saw['selected_classes'])),
-         Term('adv', 'adv_weight', dict(head_weights=(1.0, 1.0), aligner=None), adv, adv_check, adv_construct,
+         Term('adv', 'adv_weight', dict(head_weights=(1.0, 1.0), aligner=None, kind='adaptsegnet', epsilon=0.4,
+                                        lambda_local=40.0, preheat_steps=0, weight_grad=True), adv, adv_check, adv_construct,
               adv_discriminators))
+ADV_KINDS = ('adaptsegnet', 'clan')
 
 
 class AlignStep(SSLStep):
     def __init__(self, model, prototypes, pcl_temperature=8.0, align_domain=False, whiten_weight=0.0, mmd=None,
                  domain_weight=1.0, contrast_weight=0.0, triplet_weight=0.0, dca_weight=0.0, saw_weight=0.0, adv_weight=0.0,
-                 discriminators=None, **kw):
+                 discriminators=None, adv_kind='adaptsegnet', **kw):
         weights = dict(whiten_weight=whiten_weight, contrast_weight=contrast_weight, triplet_weight=triplet_weight,
                        dca_weight=dca_weight, saw_weight=saw_weight, adv_weight=adv_weight)
         for t in TERMS:      # before the model is touched
@@ -230,6 +259,9 @@ class AlignStep(SSLStep):
                     raise ValueError(f'AlignStep: {t.on} must be >= 0')
             if t.params is not None:
                 setattr(self, t.name, dict(t.params))
+        if adv_kind not in ADV_KINDS:
+            raise ValueError(f'AlignStep: adv_kind is one of {ADV_KINDS}, got {adv_kind!r}')
+        self.adv['kind'] = adv_kind
         self._adv_discriminators = discriminators
         self.domain_kind, self.mmd = domain_kind(align_domain, mmd)
         if kw.get('ent_weight') or kw.get('kld_weight'):
@@ -273,6 +305,9 @@ class AlignStep(SSLStep):
         if 'adv' in sd:
             aligner.check_state_dict(sd['adv'], strict, 'step.adv')
             loads.append(lambda: aligner.load_state_dict(sd['adv'], strict=strict))
+            if 'clan' in sd['adv']:             # validated with the aligner's entry above
+                loads.append(lambda: self.adv.update({k: sd['adv']['clan'][k] for k in ('epsilon', 'lambda_local',
+                                                                                      'preheat_steps')}))
         return loads
 
     def capture(self, *a, **k):

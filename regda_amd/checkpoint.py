@@ -2,9 +2,9 @@
 
 The fused steps (regda_amd/ssl.py, source.py, align.py) own what the reference keeps in a torch.optim.SGD and a handful of
 Python objects: momentum, the optimizer's `first` flag, the EMA teacher, the prototypes, class frequencies, loss
-statistics, discriminators, generator state.  `step.state_dict()` hands all of it out as plain data, `step.load_state_dict()`
-puts it back IN PLACE (a recorded plan holds device addresses), and because every step is bit-reproducible a resumed run
-continues with the bits of the uninterrupted one.
+statistics, discriminators (and the step counter CLAN's preheat goes by), generator state.  `step.state_dict()` hands all
+of it out as plain data, `step.load_state_dict()` puts it back IN PLACE (a recorded plan holds device addresses), and
+because every step is bit-reproducible a resumed run continues with the bits of the uninterrupted one.
 
     save_training_state(path, step, iteration, **named)     named: further objects with a state_dict() (DomainMix, ...)
     load_training_state(path, step, **named) -> iteration

@@ -12,35 +12,10 @@
 // The data gradient runs as four parity sub-convolutions in one launch (blockIdx.z): the output pixels of one (row
 // parity, column parity) class see the same 2 x 2 subset of the 16 taps, so no zero tap reaches the matrix pipe.
 // Every reduction runs in a fixed order; nothing here uses floating-point atomics.
-#include "common.h"
-
-#define ADV_CP 16
-#define ADV_BYTES_MAX 0x7fffffffLL       // row buffers are addressed below 2^31 bytes
-
-static inline bool adv_fits(long long rows, long long cols, long long elem) { return rows * cols * elem <= ADV_BYTES_MAX; }
+#include "adv_rows.h"
 
 // ---------------------------------------------------------------------------------------------- probabilities
 // one thread per full-resolution pixel: C interpolated logits, softmax, Cp bf16 values (32 bytes)
-template <int C>
-static __device__ __forceinline__ void adv_probs_at(const float* __restrict__ xb, int h, int w, const Lerp& ly, const Lerp& lx,
-                                                    float (&p)[C]) {
-    float mx = -INFINITY;
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        const float* q = xb + (size_t)c * h * w;
-        const float top = q[ly.i0 * w + lx.i0] * lx.l0 + q[ly.i0 * w + lx.i1] * lx.l1;
-        const float bot = q[ly.i1 * w + lx.i0] * lx.l0 + q[ly.i1 * w + lx.i1] * lx.l1;
-        p[c] = top * ly.l0 + bot * ly.l1;
-        mx = fmaxf(mx, p[c]);
-    }
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < C; ++c) { p[c] = expf(p[c] - mx); s += p[c]; }
-    const float inv = 1.f / s;
-#pragma unroll
-    for (int c = 0; c < C; ++c) p[c] *= inv;
-}
-
 template <int C, int MODE>
 __global__ void __launch_bounds__(256) adv_probs_fwd_kernel(const float* __restrict__ x, bf16_t* __restrict__ P, int b, int h,
                                                             int w, int H, int W) {
@@ -62,18 +37,6 @@ __global__ void __launch_bounds__(256) adv_probs_fwd_kernel(const float* __restr
     uint4* dst = (uint4*)(P + (size_t)m * ADV_CP);
     dst[0] = uint4{o[0], o[1], o[2], o[3]};
     dst[1] = uint4{o[4], o[5], o[6], o[7]};
-}
-
-// the source rows (columns) of an align_corners=True map that touch low-resolution index i: a conservative range, the
-// exact weight is taken from lerp_ac per candidate
-static __device__ __forceinline__ void adv_footprint(int i, int in, int out, int& lo, int& hi) {
-    if (in <= 1 || out <= 1) { lo = 0; hi = out - 1; return; }
-    const float inv = (float)(out - 1) / (float)(in - 1);
-    lo = max(0, (int)floorf((float)(i - 1) * inv) - 1);
-    hi = min(out - 1, (int)ceilf((float)(i + 1) * inv) + 1);
-}
-static __device__ __forceinline__ float adv_weight_of(const Lerp& l, int i) {
-    return (l.i0 == i ? l.l0 : 0.f) + (l.i1 == i ? l.l1 : 0.f);
 }
 
 // gather form: one workgroup per low-resolution pixel sums, over the full-resolution pixels whose bilinear footprint

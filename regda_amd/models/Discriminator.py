@@ -11,7 +11,8 @@ deterministic weight gradient and the fixed-order bias sums.  The bf16 operand c
 are rebuilt when a parameter's `_version` has moved, e.g. after an optimizer step.
 
 Served: f32 inputs on the GPU, 6 <= num_classes <= 16, H % 32 == 0 and W % 32 == 0, ndf % 32 == 0; anything else raises
-with the cause.  Not provided: FCDiscriminator_Local (a 2048 + C channel input).  PixelDiscriminator lives in its own module,
+with the cause.  Not provided: FCDiscriminator_Local (a 2048 + C channel input; CLAN's upsampled-output role is served by
+this class and rgda_wbce_logits' fused upsample, regda_amd/gast/clan.py).  PixelDiscriminator lives in its own module,
 regda_amd/models/PixelDiscriminator.py.
 """
 import torch

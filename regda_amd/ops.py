@@ -2190,6 +2190,81 @@ def bce_logits(z, label, scale=1.0, loss=None, accumulate=False, want_grad=True)
     return loss, dz
 
 
+# ---------------------------------------------------------------- category-level adversarial alignment (clan_kernels.hip)
+def _pair_logits(x1, x2, who):
+    _need_cuda(x1, x2)
+    assert x1.dim() == 4 and x1.dtype == torch.float32 and x1.is_contiguous(), who + ': contiguous f32 (b, C, h, w)'
+    assert x2.shape == x1.shape and x2.dtype == torch.float32 and x2.is_contiguous(), who + ': x2 as x1'
+    check_class_count(x1.shape[1], who)
+    return x1.shape
+
+
+def clan_probs(x1, x2, size=None):
+    """The two heads' logits x1, x2 f32 (b, C, h, w) -> (P bf16 [b*H*W, 16] = softmax(up x1 + up x2), what the
+    discriminator reads, and wmap f32 (b, H, W) = 1 - cos(softmax(up x1), softmax(up x2))); `up`: bilinear,
+    align_corners=True, to size = (H, W)."""
+    b, C, h, w = _pair_logits(x1, x2, 'clan_probs')
+    H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
+    P = torch.empty((b * H * W, ADV_CP), dtype=torch.bfloat16, device=x1.device)
+    wmap = torch.empty((b, H, W), dtype=torch.float32, device=x1.device)
+    lib().call('rgda_clan_probs_fwd', x1.data_ptr(), x2.data_ptr(), P.data_ptr(), wmap.data_ptr(), b, C, h, w, H, W, ADV_CP,
+               _stream())
+    return P, wmap
+
+
+def clan_probs_backward(dP, gw, x1, x2, dx1, dx2, size=None, scale=1.0):
+    """dx1, dx2 f32 (b, C, h, w) += scale * (clan_probs' gradient of dP bf16 [b*H*W, 16] and of gw f32 (b, H, W), the
+    gradient with respect to wmap; gw None: the weight map is a constant); x1, x2: the forward's inputs."""
+    b, C, h, w = _pair_logits(x1, x2, 'clan_probs_backward')
+    _need_cuda(dP, gw, dx1, dx2)
+    for dx in (dx1, dx2):
+        assert dx.shape == x1.shape and dx.dtype == torch.float32 and dx.is_contiguous()
+    H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
+    _rows_bf16(dP, ADV_CP, 'clan_probs_backward')
+    assert dP.shape[0] == b * H * W
+    assert gw is None or (gw.dtype == torch.float32 and gw.is_contiguous() and gw.numel() == b * H * W)
+    lib().call('rgda_clan_probs_bwd', dP.data_ptr(), _p(gw), x1.data_ptr(), x2.data_ptr(), dx1.data_ptr(), dx2.data_ptr(), b, C,
+               h, w, H, W, ADV_CP, float(scale), _stream())
+    return dx1, dx2
+
+
+def wbce_logits(z, size, target, wmap=None, alpha=1.0, beta=0.0, scale=1.0, mean=True, loss=None, accumulate=False,
+                want_dz=True, want_gw=False):
+    """WeightedBCEWithLogitsLoss (regda/loss.py:60-85) on z f32 (b, hz, wz) upsampled (bilinear, align_corners=True) to
+    size = (H, W): scale * mean-or-sum over the pixels of (alpha + beta * wmap) * BCE(up z, target); wmap f32 (b, H, W) or
+    None for the plain loss; target a tensor f32 (b, H, W) or the constant label 0 / 1.
+    -> (loss f32 [1] on the device, dz f32 of z's shape or None, gw f32 (b, H, W), the gradient for wmap, or None)."""
+    _need_cuda(z, wmap, loss)
+    assert z.dim() == 3 and z.dtype == torch.float32 and z.is_contiguous(), 'wbce_logits: contiguous f32 (b, hz, wz)'
+    b, hz, wz = z.shape
+    H, W = int(size[0]), int(size[1])
+    label = 0.0
+    if isinstance(target, torch.Tensor):
+        _need_cuda(target)
+        assert target.dtype == torch.float32 and target.is_contiguous() and target.numel() == b * H * W
+    else:
+        if float(target) not in (0.0, 1.0):
+            raise ValueError('wbce_logits: a constant label is 0 or 1, got %r' % (target,))
+        label, target = float(target), None
+    assert wmap is None or (wmap.dtype == torch.float32 and wmap.is_contiguous() and wmap.numel() == b * H * W)
+    if want_gw and wmap is None:
+        raise ValueError('wbce_logits: no weight map, no gradient with respect to it')
+    if loss is None:
+        assert not accumulate
+        loss = torch.empty(1, dtype=torch.float32, device=z.device)
+    dz = torch.empty_like(z) if want_dz else None
+    gw = torch.empty((b, H, W), dtype=torch.float32, device=z.device) if want_gw else None
+    L = lib()
+    nbytes = L.size('rgda_wbce_logits_workspace', b, H, W)
+    if not nbytes:
+        raise ValueError(f'wbce_logits: {b} x {H} x {W} pixels are not served')
+    ws = _ws(nbytes, z.device)
+    L.call('rgda_wbce_logits', z.data_ptr(), b, hz, wz, H, W, _p(target), label, _p(wmap), float(alpha), float(beta),
+           float(scale), int(bool(mean)), loss.data_ptr(), int(bool(accumulate)), _p(dz), _p(gw), ws.data_ptr(), ws.numel(),
+           _stream())
+    return loss, dz, gw
+
+
 # ---------------------------------------------------------------- feature-space adversarial alignment (fada_kernels.hip)
 FADA_CP = 32            # columns of a head row of PixelDiscriminator: 2 * num_classes <= 32
 FADA_MAX_CLASSES = 16
