@@ -891,6 +891,62 @@ int rgda_mix_select_classes(const int64_t* label_s, const uint8_t* ranks, int32_
 int rgda_mix_write_table(int32_t* table, uint8_t* ranks, const uint8_t* ranks_host, int N, int C, uint32_t class_bits,
                          int y0, int y1, int x0, int x1, rgda_stream_t stream);
 
+/* ------------------------------------------------------------- strong (photometric) augmentation of the student's tile */
+
+/* Colour jitter and Gaussian blur of normalised tiles, image by image from a device table: the perturbation of the
+ * student's view in consistency training (mean teacher, DACS).  The reference has no such pass; the semantics are this
+ * library's and tests/strong_ref.py restates them in fp64.
+ *   img_in  f32 [N][3][H][W] (read only): v = (raw - mean_c) / std_c with raw in 0..255, as the training step sees tiles
+ *   img_out f32 [N][3][H][W], every pixel written.  OUT OF PLACE ONLY: a blurred pixel reads its neighbours' inputs, which
+ *     other workgroups would already have overwritten, so img_out overlapping img_in is refused (RGDA_ERR_ARG).
+ *   table   f32 [N][RGDA_STRONG_TABLE_COLS], 16-byte aligned, DEVICE memory: row n = {fb, fc, fs, theta, sigma, flags, 0, 0};
+ *     flags (an integer value) bit 0: jitter on, bit 1: blur on.
+ *   mean_*, std_* (r, g, b): the normalisation the tiles carry; std_* > 0.
+ * An image with both bits clear is copied bit for bit (16-byte moves where the route allows): no arithmetic touches it, so
+ * NaN and inf pass through.  Otherwise, per pixel, u = (v * std_c + mean_c) / 255, clamp = clamp to [0, 1], and
+ *   1. brightness  u <- clamp(u * fb)
+ *   2. contrast    m = the mean over the WHOLE image of grey(u) = 0.299 r + 0.587 g + 0.114 b, taken after step 1;
+ *                  u <- clamp((u - m) * fc + m)
+ *   3. saturation  g = grey(u) of the pixel; u <- clamp((u - g) * fs + g)
+ *   4. hue         u <- clamp(M u), M = T^-1 R(theta) T, nine entries built once per image (in fp64, rounded once):
+ *                  T = {{0.299, 0.587, 0.114}, {0.596, -0.274, -0.322}, {0.211, -0.523, 0.312}} (RGB -> YIQ), T^-1 its
+ *                  inverse to double precision, R(theta) the rotation of (I, Q) by theta radians:
+ *                  I' = cos(theta) I - sin(theta) Q, Q' = sin(theta) I + cos(theta) Q
+ *   5. blur, bit 1: a separable Gaussian of standard deviation sigma and radius R = ceil(3 * sigma) (that product in fp32);
+ *                  taps exp(-d^2 / (2 sigma^2)), d = -R..R, normalised to sum 1 (built in fp64, rounded once); the
+ *                  horizontal pass, then the vertical one; borders by reflection without repeating the edge pixel
+ *                  (x[-1] -> x[1], x[W] -> x[W-2]).  It acts on the values after step 4, or on u itself when bit 0 is clear
+ *   6. v' = (255 u - mean_c) / std_c
+ * Steps 1 to 4 run only with bit 0, always in this order.  Every halo pixel gets the same pointwise steps as an interior
+ * pixel.  Served: 0 < sigma <= 4 (R <= RGDA_STRONG_MAX_RADIUS), H > R and W > R; rgda_strong_write_table refuses rows
+ * outside that.  The rows are read on the device and cannot be refused here: a row that asks for a blur outside the served
+ * range is copied unchanged and sets *flag (optional, device int) to 1; every source index is cut to the image.
+ * m is order-independent: every grey value is rounded to a multiple of 2^-24 and the image's total is a 64-bit integer sum
+ * (integer atomics), so two runs give identical bits.
+ *   ws: rgda_strong_augment_workspace(N) bytes (128 per image), 8-byte aligned; rewritten BY the call, any contents on entry.
+ * Three launches whatever the table holds: each image's constants into ws (switches, radius, M and the taps, built once
+ * per image by one thread, and its cleared sum); the grey sums (workgroups of images without bit 0 leave at once); the
+ * transform (a 32 x 32 tile per workgroup, tile + halo of the three channels in LDS, both blur passes there).
+ * 16-byte stores where W % 4 == 0 and img_out is 16-byte aligned (the copy also needs img_in aligned), element stores otherwise.
+ * Errors before any launch (RGDA_ERR_ARG): null img_in / img_out / ws; null or misaligned table; misaligned ws; N, H or
+ * W < 1; a std that is not positive; overlapping img_in and img_out.  N > 65535 or H * W >= 2^31: RGDA_ERR_UNSUPPORTED. */
+#define RGDA_STRONG_TABLE_COLS 8
+#define RGDA_STRONG_MAX_RADIUS 12
+size_t rgda_strong_augment_workspace(int N);
+int rgda_strong_augment(const float* img_in, float* img_out, const float* table, void* ws, int N, int H, int W,
+                        float mean_r, float mean_g, float mean_b, float std_r, float std_g, float std_b, int* flag,
+                        rgda_stream_t stream);
+
+/* The host's table -> device, carried IN THE KERNEL ARGUMENTS of one launch, as rgda_mix_write_table carries its draw:
+ * nothing is staged in host memory, so the call can be a host action of a recorded plan.
+ *   table f32 [N][RGDA_STRONG_TABLE_COLS] on the device, 16-byte aligned <- host, N * 8 floats of HOST memory read during
+ *     the call; columns 6 and 7 are written as 0.
+ *   H, W: the tiles the table is for (the blur radius is checked against them).
+ * RGDA_ERR_ARG: null table / host; misaligned table; N, H or W < 1; a value of fb, fc, fs, theta or sigma that is not
+ * finite; fb, fc or fs below 0; flags not one of 0, 1, 2, 3.  RGDA_ERR_UNSUPPORTED: N above RGDA_MIX_WRITE_MAX_IMAGES; a
+ * row with bit 1 whose sigma is outside (0, 4] or whose radius R is not below both H and W. */
+int rgda_strong_write_table(float* table, const float* host, int N, int H, int W, rgda_stream_t stream);
+
 /* ------------------------------------------------------------- region maps without SAM */
 
 /* The region maps rgda_lrh and rgda_label_refine_sup read, generated from the raw tile.

@@ -268,6 +268,8 @@ class AlignStep(SSLStep):
             raise NotImplementedError('the IAST regularisers (ent_weight / kld_weight) belong to the SSL step')
         if kw.get('mix') is not None:
             raise NotImplementedError('the in-step cross-domain mix (mix=) belongs to the SSL step')
+        if kw.get('strong') is not None:
+            raise NotImplementedError('the strong augmentation of the student tile (strong=) belongs to the SSL step')
         kw.setdefault('proto_decay', 0.999)       # Aligner(decay=0.999), train_align_reg.py:112-113
         kw['ema_decay'] = None
         super().__init__(model, prototypes, **kw)

@@ -6,6 +6,34 @@ import numpy as np
 from ..utils.cutmix import box_from_draw
 
 
+def rng_state_dict(rng):
+    """Where a numpy Generator stands, as a training state entry (DomainMix, StrongAugment).  The 128-bit words of
+    numpy's bit generators travel as decimal strings, everything else as it is."""
+    def enc(v):
+        if isinstance(v, dict):
+            return {k: enc(x) for k, x in v.items()}
+        return str(v) if isinstance(v, int) and not isinstance(v, bool) and abs(v) >= 2 ** 63 else v
+    return {'rng': enc(rng.bit_generator.state)}
+
+
+def load_rng_state_dict(rng, sd, who):
+    """The inverse of rng_state_dict: validated first, nothing written on error (ValueError naming `who`)."""
+    def dec(v):
+        if isinstance(v, dict):
+            return {k: dec(x) for k, x in v.items()}
+        return int(v) if isinstance(v, str) and v.lstrip('-').isdigit() else v
+    if not isinstance(sd, dict) or not isinstance(sd.get('rng'), dict):
+        raise ValueError(f"state entry '{who}.rng' is missing")
+    own = rng.bit_generator.state['bit_generator']
+    if sd['rng'].get('bit_generator') != own:
+        raise ValueError(f"state entry '{who}.rng.bit_generator': {sd['rng'].get('bit_generator')!r}, this "
+                         f'object draws from {own!r}')
+    try:
+        rng.bit_generator.state = dec(sd['rng'])      # numpy validates the rest and leaves the state on error
+    except (KeyError, TypeError, ValueError) as e:
+        raise ValueError(f"state entry '{who}.rng': {e}") from None
+
+
 class DomainMix:
     """kind 'class': ClassMix, int(class_num * ratio) classes of a permutation (regda/utils/classmix.py:42);
     kind 'box': CutMix, one box from lam ~ Beta(alpha, alpha) and a uniform centre (regda/utils/cutmix.py:17-27).
@@ -26,30 +54,12 @@ class DomainMix:
         self.ignore_label = ignore_label
         self.rng = np.random.default_rng(seed)
 
-    # training state (regda_amd/checkpoint.py): where the generator stands.  The 128-bit words of numpy's bit generators
-    # travel as decimal strings, everything else as it is
+    # training state (regda_amd/checkpoint.py): where the generator stands
     def state_dict(self):
-        def enc(v):
-            if isinstance(v, dict):
-                return {k: enc(x) for k, x in v.items()}
-            return str(v) if isinstance(v, int) and not isinstance(v, bool) and abs(v) >= 2 ** 63 else v
-        return {'rng': enc(self.rng.bit_generator.state)}
+        return rng_state_dict(self.rng)
 
     def load_state_dict(self, sd, strict=True):
-        def dec(v):
-            if isinstance(v, dict):
-                return {k: dec(x) for k, x in v.items()}
-            return int(v) if isinstance(v, str) and v.lstrip('-').isdigit() else v
-        if not isinstance(sd, dict) or not isinstance(sd.get('rng'), dict):
-            raise ValueError("state entry 'DomainMix.rng' is missing")
-        own = self.rng.bit_generator.state['bit_generator']
-        if sd['rng'].get('bit_generator') != own:
-            raise ValueError(f"state entry 'DomainMix.rng.bit_generator': {sd['rng'].get('bit_generator')!r}, this "
-                             f'object draws from {own!r}')
-        try:
-            self.rng.bit_generator.state = dec(sd['rng'])      # numpy validates the rest and leaves the state on error
-        except (KeyError, TypeError, ValueError) as e:
-            raise ValueError(f"state entry 'DomainMix.rng': {e}") from None
+        load_rng_state_dict(self.rng, sd, 'DomainMix')
 
     def draw(self, h, w):
         """One batch's draw for h x w tiles -> None (this batch is not mixed), ('classes', (ids...)) or

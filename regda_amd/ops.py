@@ -1494,6 +1494,70 @@ def mix_write_table(table, class_num, class_bits=0, box=(0, 0, 0, 0), ranks=None
     return table
 
 
+# ----------------------------------------------------------------------------- strong augmentation of the student's tile
+STRONG_TABLE_COLS = 8           # RGDA_STRONG_TABLE_COLS: {fb, fc, fs, theta, sigma, flags, 0, 0} per image
+STRONG_MAX_RADIUS = 12          # RGDA_STRONG_MAX_RADIUS: sigma <= 4
+
+
+def _strong_table_check(who, table, n):
+    if table.dtype != torch.float32 or tuple(table.shape) != (n, STRONG_TABLE_COLS) or not table.is_contiguous():
+        raise ValueError('%s: table must be contiguous torch.float32 (%d, %d), got %s %s'
+                         % (who, n, STRONG_TABLE_COLS, table.dtype, tuple(table.shape)))
+
+
+def strong_write_table(table, host, size):
+    """rgda_strong_write_table: table (f32 (N, 8) on the device, N <= 16) <- host (a float32 numpy array of that shape:
+    fb, fc, fs, theta, sigma, flags, 0, 0 per image -- StrongAugment.draw), carried in the launch's arguments: the host
+    buffer is read before this returns.  size = (H, W) of the tiles the table is for.  A row the transform does not serve
+    (sigma outside (0, 4] with the blur bit, a radius that does not fit the tile, values that are not finite) is a
+    ValueError before any launch."""
+    import numpy as np
+    _need_cuda(table)
+    n = table.shape[0]
+    _strong_table_check('strong_write_table', table, n)
+    host = np.ascontiguousarray(host, dtype=np.float32)
+    if host.shape != (n, STRONG_TABLE_COLS):
+        raise ValueError('strong_write_table: host must be float32 (%d, %d), got %s' % (n, STRONG_TABLE_COLS, host.shape))
+    h, w = (int(v) for v in size)
+    lib().call('rgda_strong_write_table', table.data_ptr(), host.ctypes.data, n, h, w, _stream())
+    return table
+
+
+def strong_augment(images, table, mean, std, out=None, ws=None, flag=None):
+    """rgda_strong_augment: colour jitter and Gaussian blur of normalised tiles, image n as row n of `table` (f32 (N, 8)
+    on the device) says; include/rgda_hip.h carries the semantics.  images f32 (N,3,H,W), never written; out: the
+    result (allocated unless given), a different buffer -- the blur reads neighbours, so in place is refused.  mean, std:
+    three values each, the normalisation the tiles carry.  ws: workspace of rgda_strong_augment_workspace(N) bytes, a
+    uint8 tensor (allocated unless given; the call rewrites it: each image's constants and its grey sum).  flag: optional device int32, set to 1 by a row whose blur is outside the served range (that image
+    is copied).  -> out."""
+    _need_cuda(images, table, out, ws, flag)
+    if images.dim() != 4 or images.shape[1] != 3 or images.dtype != torch.float32:
+        raise ValueError('strong_augment: images must be torch.float32 (N,3,H,W), got %s %s'
+                         % (images.dtype, tuple(images.shape)))
+    n, _, h, w = images.shape
+    _strong_table_check('strong_augment', table, n)
+    mean, std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+    if len(mean) != 3 or len(std) != 3 or not all(v > 0 for v in std):
+        raise ValueError('strong_augment: mean and std are three values each, std positive')
+    if out is None:
+        out = torch.empty(images.shape, dtype=torch.float32, device=images.device)
+    if out.dtype != torch.float32 or tuple(out.shape) != tuple(images.shape) or not out.is_contiguous():
+        raise ValueError('strong_augment: out is written and must be contiguous torch.float32 %s' % (tuple(images.shape),))
+    need = lib().size('rgda_strong_augment_workspace', n)
+    if ws is None:
+        ws = _ws(need, images.device)
+    if ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous():
+        raise ValueError('strong_augment: ws must be contiguous torch.uint8 with at least %d bytes' % need)
+    if n * h * w == 0:
+        return out
+    src = images.contiguous()
+    if src.data_ptr() == out.data_ptr():
+        raise ValueError('strong_augment: out must not be the input (the blur reads neighbouring pixels)')
+    lib().call('rgda_strong_augment', src.data_ptr(), out.data_ptr(), table.data_ptr(), ws.data_ptr(), n, h, w, *mean, *std,
+               _p(flag) or None, _stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- region maps without SAM
 def superpixels_max_regions(h, w, min_area):
     """The exclusive bound on the region ids rgda_superpixels writes for an h x w image: R <= h * w // min_area, so

@@ -67,6 +67,8 @@ class SourceStep(SSLStep):
             raise NotImplementedError('the IAST regularisers (ent_weight / kld_weight) belong to the SSL step')
         if kw.get('mix') is not None:
             raise NotImplementedError('the in-step cross-domain mix (mix=) belongs to the SSL step')
+        if kw.get('strong') is not None:
+            raise NotImplementedError('the strong augmentation of the student tile (strong=) belongs to the SSL step')
         kw['ema_decay'] = None
         kw.setdefault('sam_refine', False)
         kw.setdefault('refine_label', False)

@@ -29,7 +29,7 @@ class SSLStep:
                  process_group=None, overlap_wgrad=True, overlap_comm=True, class_balancer_s=None,
                  class_balancer_t=None, grad_payload='fp32', comm=None, loss_s='CrossEntropy', loss_t='none',
                  uvem_m=0.2, uvem_t=0.7, uvem_g=4.0, gdp_prototype=True, gdp_class_balance=False, ent_weight=0.0,
-                 kld_weight=0.0, adv_weight=0.0, discriminators=None, mix=None):
+                 kld_weight=0.0, adv_weight=0.0, discriminators=None, mix=None, strong=None):
         if adv_weight or discriminators is not None:
             raise NotImplementedError('the adversarial term (adv_weight / discriminators) belongs to the stage-2 step, AlignStep')
         ops.check_class_count(class_num, type(self).__name__)
@@ -90,6 +90,12 @@ class SSLStep:
         self.mix = mix
         self.mix_flag = torch.zeros(1, dtype=torch.int32, device=dev) if mix is not None else None
         self.last_mix = self.last_mix_table = None      # the last step's draw (host) and the table its kernels read
+        # strong: a regda_amd.aug.strong.StrongAugment -- colour jitter and Gaussian blur of the student's target tile, after
+        # the mix where there is one: the teacher, the caller's images_t, soft_t and the source tile are
+        # never touched, the result is a buffer of the step's own.  None: no launch.
+        self.strong = strong
+        self.strong_flag = torch.zeros(1, dtype=torch.int32, device=dev) if strong is not None else None
+        self.last_strong = None     # the last step's table as drawn on the host, f32 (N, 8)
         self._graph = None
         self._plan = None
         self._proto_ready = None
@@ -140,6 +146,9 @@ class SSLStep:
             # the draws come from the DomainMix's generator on the host and travel as kernel arguments, which a graph
             # freezes: record_plan() re-runs the draw and the table write as a host action
             raise RuntimeError('the cross-domain mix (mix=) draws on the host: use record_plan(), not capture()')
+        if self.strong is not None:
+            # the same: the table is drawn on the host and travels as kernel arguments
+            raise RuntimeError('the strong augmentation (strong=) draws on the host: use record_plan(), not capture()')
         self._static = self._static_inputs(images_s, label_s, images_t, soft_t, regs_t)
         self._build_maps(images_s)
         torch.cuda.synchronize()
@@ -216,6 +225,8 @@ class SSLStep:
                 sd[name] = s
         if self.mix is not None:
             sd['mix'] = self.mix.state_dict()        # where its generator stands: a resumed run continues the draws
+        if self.strong is not None:
+            sd['strong'] = self.strong.state_dict()
         sd.update(self._state_extra())
         if rng:
             sd['rng'] = dict(cpu=torch.get_rng_state(), cuda=torch.cuda.get_rng_state(self.model.device))
@@ -234,8 +245,8 @@ class SSLStep:
         if ('teacher' in sd) != (self.teacher is not None) and (strict or 'teacher' in sd):
             raise ValueError(f"state entry 'step.teacher': the state has {'a' if 'teacher' in sd else 'no'} teacher, this "
                              f"step has {'one' if self.teacher is not None else 'none'} (ema_decay)")
-        known = {'format', 'kind', 'config', 'model', 'mom', 'first', 'prototypes', 'teacher', 'rng', 'mix', *self._STATEFUL,
-                 *self._STATE_EXTRA}
+        known = {'format', 'kind', 'config', 'model', 'mom', 'first', 'prototypes', 'teacher', 'rng', 'mix', 'strong',
+                 *self._STATEFUL, *self._STATE_EXTRA}
         if strict and set(sd) - known:
             raise ValueError(f'state entries {sorted(set(sd) - known)} of the step are unknown to this {type(self).__name__}')
         take = lambda k: need(sd, k, 'step') if strict or k in sd else None     # strict=False: what is there
@@ -272,15 +283,16 @@ class SSLStep:
             if name in sd:
                 check_module_state(obj, sd[name], 'step.' + name, strict)
                 loads.append(lambda obj=obj, name=name: obj.load_state_dict(sd[name], strict=strict))
-        if ('mix' in sd) != (self.mix is not None) and (strict or 'mix' in sd):
-            raise ValueError(f"state entry 'step.mix': the state has {'one' if 'mix' in sd else 'none'}, this step has "
-                             f"{'one' if self.mix is not None else 'none'}")
-        if 'mix' in sd:
-            try:
-                copy.deepcopy(self.mix).load_state_dict(sd['mix'])      # validated on a copy: nothing is written here
-            except ValueError as e:
-                raise ValueError(f"state entry 'step.mix': {e}") from None
-            loads.append(lambda: self.mix.load_state_dict(sd['mix']))
+        for name, obj in (('mix', self.mix), ('strong', self.strong)):      # the host generators of the step's draws
+            if (name in sd) != (obj is not None) and (strict or name in sd):
+                raise ValueError(f"state entry 'step.{name}': the state has {'one' if name in sd else 'none'}, this step "
+                                 f"has {'one' if obj is not None else 'none'}")
+            if name in sd:
+                try:
+                    copy.deepcopy(obj).load_state_dict(sd[name])        # validated on a copy: nothing is written here
+                except ValueError as e:
+                    raise ValueError(f"state entry 'step.{name}': {e}") from None
+                loads.append(lambda obj=obj, name=name: obj.load_state_dict(sd[name]))
         if 'rng' in sd:
             cpu, cuda = (need(sd['rng'], k, 'step.rng') for k in ('cpu', 'cuda'))
             for k, v in (('cpu', cpu), ('cuda', cuda)):
@@ -467,6 +479,11 @@ class SSLStep:
             student_t = ops.domain_mix_table(images_s, label_s, mix_table, mix_mode, images_in=images_t.contiguous().float(),
                                              images_out=torch.empty(images_t.shape, dtype=torch.float32, device=images_t.device),
                                              class_num=self.C, ignore_label=self.ig, flag=self.mix_flag)[0]
+        if self.strong is not None:
+            # out of place: the mixed tile above, or the caller's images_t, is read; the student's tile is a new buffer
+            n_t, _, h_t, w_t = images_t.shape
+            student_t = ops.strong_augment(student_t.contiguous().float(), self._strong_draw(n_t, h_t, w_t, images_t.device),
+                                           self.strong.mean, self.strong.std, flag=self.strong_flag)
         x1, x2, feat = m._forward_plan([images_s.contiguous().float(), student_t.contiguous().float()], T)
         self._mark('student forward done')
         s1, t1, s2, t2 = x1[:nb], x1[nb:], x2[:nb], x2[nb:]
@@ -527,7 +544,7 @@ class SSLStep:
             source_done = source_prototypes()
         if self.keep_debug:
             self.debug = dict(t1=t1, t2=t2, s1=s1, s2=s2, feat_t=feat_t, feat_s=feat_s, soft_in=soft_t, soft=soft,
-                              hard_selected=hard)
+                              hard_selected=hard, student_t=student_t)
         if self.sam_refine:
             hard = self._lrh(regs, hard, (soft, cm) if fuse_lrh else None)
         if self.mix is not None:
@@ -620,6 +637,24 @@ class SSLStep:
             ops.mix_select_classes(label_s, ranks, table, ignore_label=self.ig, flag=self.mix_flag)
         self.last_mix_table = table
         return images_s, label_s, table, ops.MIX_BOX if mx.kind == 'box' else ops.MIX_CLASS
+
+    def _strong_draw(self, n, h, w, dev):
+        """This batch's table of `self.strong` on the device, f32 [n][8].  The draw and the launch that carries it
+        (rgda_strong_write_table: values in the kernel arguments) are ONE host action, re-run at every replay of a
+        recorded step, like `_mix_draw`."""
+        table = torch.empty(n, ops.STRONG_TABLE_COLS, dtype=torch.float32, device=dev)
+        here = torch.cuda.current_stream()
+
+        def draw():
+            self.last_strong = self.strong.draw(n)
+            with ops.use_stream(here):      # (a replay runs host actions with the library's stream set to the plan's)
+                ops.strong_write_table(table, self.last_strong, (h, w))
+        plan.host(draw)
+        return table
+
+    def strong_flag_value(self):
+        """Deferred check of the strong augmentation's flag word (host sync): a table row outside the served range."""
+        return 0 if self.strong_flag is None else int(self.strong_flag.item())
 
     def mix_flag_value(self):
         """Deferred check of the mixing kernels' flag word (host sync): a source label that is neither a class nor the
