@@ -1,5 +1,6 @@
 """The stage-2 ("align") inner loop of tools/train_align_reg.py:144-196 as one fused, sync-free step (SURVEY.md 8f
-rank 2), on the same kernel plans as the SSL step (regda_amd/ssl.py):
+rank 2): a PseudoLabelStep (regda_amd/step.py) on the same kernel plans as the SSL step, without its teacher, target loss,
+mix / strong and plan replay:
 
     model(src) -> update_prototype -> model(tgt) -> the student's own (softmax(up x1) + softmax(up x2)) / 2 as soft
     labels -> label_refine -> pseudo_selection -> Homogenizer (LRH) -> DownscaleLabel
@@ -40,7 +41,7 @@ from .gast.clan import CategoryAdversarialAligner
 from .gast.contrastive import select_and_plan
 from .models.Discriminator import FCDiscriminator
 from .source import domain_kind, domain_loss
-from .ssl import SSLStep
+from .step import Part, PseudoLabelStep
 
 
 def saw_selection(class_num, selected_classes):
@@ -246,10 +247,10 @@ TERMS = (Term('domain', 'align_domain', None, domain),
 ADV_KINDS = ('adaptsegnet', 'clan')
 
 
-class AlignStep(SSLStep):
+class AlignStep(PseudoLabelStep):
     def __init__(self, model, prototypes, pcl_temperature=8.0, align_domain=False, whiten_weight=0.0, mmd=None,
                  domain_weight=1.0, contrast_weight=0.0, triplet_weight=0.0, dca_weight=0.0, saw_weight=0.0, adv_weight=0.0,
-                 discriminators=None, adv_kind='adaptsegnet', **kw):
+                 discriminators=None, adv_kind='adaptsegnet', proto_decay=0.999, **kw):
         weights = dict(whiten_weight=whiten_weight, contrast_weight=contrast_weight, triplet_weight=triplet_weight,
                        dca_weight=dca_weight, saw_weight=saw_weight, adv_weight=adv_weight)
         for t in TERMS:      # before the model is touched
@@ -264,15 +265,8 @@ class AlignStep(SSLStep):
         self.adv['kind'] = adv_kind
         self._adv_discriminators = discriminators
         self.domain_kind, self.mmd = domain_kind(align_domain, mmd)
-        if kw.get('ent_weight') or kw.get('kld_weight'):
-            raise NotImplementedError('the IAST regularisers (ent_weight / kld_weight) belong to the SSL step')
-        if kw.get('mix') is not None:
-            raise NotImplementedError('the in-step cross-domain mix (mix=) belongs to the SSL step')
-        if kw.get('strong') is not None:
-            raise NotImplementedError('the strong augmentation of the student tile (strong=) belongs to the SSL step')
-        kw.setdefault('proto_decay', 0.999)       # Aligner(decay=0.999), train_align_reg.py:112-113
-        kw['ema_decay'] = None
-        super().__init__(model, prototypes, **kw)
+        # proto_decay: Aligner(decay=0.999), train_align_reg.py:112-113
+        super().__init__(model, prototypes, proto_decay=proto_decay, **self._refuse_ssl_only(kw))
         self.pcl_temp, self.align_domain, self.domain_weight = pcl_temperature, bool(align_domain), float(domain_weight)
         for name in ('align', 'domain', 'white', 'contrast', 'triplet', 'dca', 'saw', 'adv', 'disc'):
             setattr(self, 'loss_' + name, torch.zeros(1, device=model.device))
@@ -281,68 +275,38 @@ class AlignStep(SSLStep):
             if t.construct is not None and getattr(self, t.on) > 0.0:
                 t.construct(self)
 
+    @torch.no_grad()
     def step(self, images_s, label_s, images_t, regs_t, lr):
         """One stage-2 iteration.  Returns device tensors (loss_seg, loss_align, grad_norm_sq)."""
         for t in TERMS:
             if t.check is not None and getattr(self, t.on) > 0.0:
                 t.check(self, images_s, images_t)
         self._check_shape(images_s, images_t)
-        self.lr_dev.fill_(float(lr))
+        ops.set_f32(self.lr_dev, lr)
         with ops.use_stream(torch.cuda.current_stream()):
-            return self._step(images_s, label_s, images_t, None, regs_t)
+            return self._step(images_s, label_s, images_t, regs_t)
 
-    # training state (regda_amd/ssl.py): the adversarial term's discriminators and their Adam moments join the step's own
-    _STATE_EXTRA = ('adv',)
+    def _state_parts(self):
+        """+ the adversarial aligner; CLAN's three saved parameters go back into `step.adv`, the step's only source for them"""
+        def clan(saved):
+            self.adv.update({k: saved['clan'][k] for k in ('epsilon', 'lambda_local', 'preheat_steps') if 'clan' in saved})
+        return [*super()._state_parts(), Part('adv', self.adv['aligner'], after=clan, hint=" (step.adv['aligner'])")]
 
-    def _state_extra(self):
-        aligner = self.adv['aligner']
-        return {} if aligner is None else {'adv': aligner.state_dict()}
-
-    def _state_loads(self, sd, strict):
-        loads = super()._state_loads(sd, strict)
-        aligner = self.adv['aligner']
-        if ('adv' in sd) != (aligner is not None) and (strict or 'adv' in sd):
-            raise ValueError(f"state entry 'step.adv': the state has {'an' if 'adv' in sd else 'no'} adversarial aligner, "
-                             f"step.adv['aligner'] is {'set' if aligner is not None else 'None'}")
-        if 'adv' in sd:
-            aligner.check_state_dict(sd['adv'], strict, 'step.adv')
-            loads.append(lambda: aligner.load_state_dict(sd['adv'], strict=strict))
-            if 'clan' in sd['adv']:             # validated with the aligner's entry above
-                loads.append(lambda: self.adv.update({k: sd['adv']['clan'][k] for k in ('epsilon', 'lambda_local',
-                                                                                      'preheat_steps')}))
-        return loads
-
-    def capture(self, *a, **k):
-        raise NotImplementedError('whole-step graph capture is provided for the SSL step only')
-
-    def record_plan(self, *a, **k):
-        raise NotImplementedError('plan replay is provided for the SSL step only (the stage-2 step has host actions that '
-                                  'are not marked for recording)')
-
-    def _step(self, images_s, label_s, images_t, soft_t, regs_t):
+    def _step(self, images_s, label_s, images_t, regs_t):
         m = self.model
-        if not m.training:
-            m.train()
-        m._maybe_sync()
-        m.flat_g.zero_()
         nb = images_s.shape[0]
-        T = m.new_tape(groups=2)
-        main = torch.cuda.current_stream()
-        x1, x2, feat = m._forward_plan([images_s.contiguous().float(), images_t.contiguous().float()], T)
+        T, main, x1, x2, feat = self._forward_domains(images_s, images_t)
         s1, t1, s2, t2 = x1[:nb], x1[nb:], x2[:nb], x2[nb:]
         feat_s, feat_t = feat[:nb], feat[nb:]
         # ema-updating prototypes comes first here (train_align_reg.py:157): the target branch sees the new ones
+        label_s_down = self._proto_local(feat_s, label_s, self.reducer.active)
         if self.reducer.active:
-            # data-parallel ranks (or RGDA_FORCE_DDP at world 1, as in SSLStep): all-reduce the sufficient statistics
-            # (per-class feature sums, pixel counts) and apply the totals -- the prototypes of the concatenated global
-            # batch, identical on every rank.  Through the step's communicator when it has one (`comm=`: the torch-free
-            # route), else through torch.distributed on `process_group`
-            self.proto_stats, label_s_down = ops.proto_stats(feat_s, label_s, 16, self.ig, 0.75, self.C, stats=self.proto_stats)
+            # data-parallel ranks (or RGDA_FORCE_DDP at world 1, as in SSLStep): all-reduce the statistics and apply the
+            # totals -- the prototypes of the concatenated global batch, identical on every rank.  Through the step's
+            # communicator when it has one (`comm=`: the torch-free route), else through torch.distributed
             all_reduce_prototype_statistics(self.proto_stats, self.C, self.prototypes.shape[1], self.group, self.comm,
                                             world=self.world)
             ops.proto_apply(self.prototypes, self.proto_stats, self.pdecay)
-        else:
-            label_s_down = ops.proto_update(feat_s, label_s, self.prototypes, 16, self.ig, 0.75, self.pdecay)
         soft_t = ops.teacher_probs(t1, t2, tuple(images_t.shape[-2:]))             # :164-166
         if self.refine_label:
             soft, cm = ops.label_refine(feat_t, self.prototypes, t1, t2, soft_t, self.temp, return_ws=True)

@@ -1,6 +1,6 @@
 """Saving and resuming a training run (INTEGRATION.md "Stopping and resuming a run").
 
-The fused steps (regda_amd/ssl.py, source.py, align.py) own what the reference keeps in a torch.optim.SGD and a handful of
+The fused steps (regda_amd/step.py) own what the reference keeps in a torch.optim.SGD and a handful of
 Python objects: momentum, the optimizer's `first` flag, the EMA teacher, the prototypes, class frequencies, loss
 statistics, discriminators (and the step counter CLAN's preheat goes by), generator state.  `step.state_dict()` hands all
 of it out as plain data, `step.load_state_dict()` puts it back IN PLACE (a recorded plan holds device addresses), and

@@ -28,7 +28,7 @@ _LDS_LOSS_ROW, _LDS_PCL, _LDS_REFINE = 0, 1, 2      # rgda_class_lds `which` (in
 def check_step_shape(c, k, H, W, who='step'):
     """ValueError where a training step at c classes, k prototype channels and H x W tiles (logits at output stride 16)
     would reach a kernel that cannot serve it -- so that a step refuses before its first launch, never halfway.  The
-    LDS needs and limits are the library's own (rgda_class_lds)."""
+    LDS needs and limits are the library's own (rgda_class_lds).  k None: a step without prototypes, the row pass only."""
     check_class_count(c, who)
     L = lib()
     w = (int(W) + 15) // 16
@@ -36,6 +36,8 @@ def check_step_shape(c, k, H, W, who='step'):
     if row > lim:
         raise ValueError(f'{who}: {c} classes at {W}-pixel rows need {row} B of LDS in the fused upsample + loss row pass, '
                          f'above its limit of {lim} B (16 classes: W <= 1008; 1024 x 1024 tiles serve up to 15)')
+    if k is None:
+        return
     for which, name in ((_LDS_PCL, 'PrototypeContrastiveLoss'), (_LDS_REFINE, 'label_refine')):
         need, lim = L.size('rgda_class_lds', which, c, k, 0), L.size('rgda_class_lds_limit', which)
         if need > lim:

@@ -1,5 +1,5 @@
 """The stage-1 ("source") inner loop of tools/train_src.py:117-140 as one fused, sync-free step, on the same kernel
-plans as the SSL step (regda_amd/ssl.py):
+plans as the SSL step; a FusedStep (regda_amd/step.py), so the optimizer tail, the source loss and the state are shared:
 
     model(src) [-> model(tgt)] -> loss = loss_calc(src) [+ CORAL(feat_s, feat_t)  with --align-domain 1]
     -> backward -> clip_grad_norm_(32) -> SGD
@@ -31,7 +31,7 @@ import torch
 from . import ops
 from .gast.fada import FeatureAdversarialAligner
 from .models.PixelDiscriminator import PixelDiscriminator
-from .ssl import SSLStep
+from .step import FusedStep, Part
 
 BF = torch.bfloat16
 
@@ -56,24 +56,17 @@ def domain_loss(kind, mmd, feat_s, feat_t, weight, **kw):
     return ops.mmd_loss(feat_s, feat_t, weight, 'linear' if kind == 'mmd_linear' else 'rbf', **mmd, **kw)
 
 
-class SourceStep(SSLStep):
+class SourceStep(FusedStep):
+    _STATE_LEGACY = ('prototypes',)     # states written while this class derived from SSLStep carry a zero tensor
+
     def __init__(self, model, class_balancer_s=None, align_domain=False, class_num=6, loss_s='CrossEntropy', mmd=None,
                  domain_weight=1.0, fada_weight=0.0, pixel_discriminator=None, **kw):
         self.fada_weight = float(fada_weight)
         if not self.fada_weight >= 0.0:         # before the model is touched
             raise ValueError('SourceStep: fada_weight must be >= 0')
         self.domain_kind, self.mmd = domain_kind(align_domain, mmd)
-        if kw.get('ent_weight') or kw.get('kld_weight'):
-            raise NotImplementedError('the IAST regularisers (ent_weight / kld_weight) belong to the SSL step')
-        if kw.get('mix') is not None:
-            raise NotImplementedError('the in-step cross-domain mix (mix=) belongs to the SSL step')
-        if kw.get('strong') is not None:
-            raise NotImplementedError('the strong augmentation of the student tile (strong=) belongs to the SSL step')
-        kw['ema_decay'] = None
-        kw.setdefault('sam_refine', False)
-        kw.setdefault('refine_label', False)
-        super().__init__(model, torch.zeros(class_num, 2048), class_num=class_num, class_balancer_s=class_balancer_s,
-                         loss_s=loss_s, **kw)
+        super().__init__(model, class_num=class_num, class_balancer_s=class_balancer_s, loss_s=loss_s,
+                         **self._refuse_ssl_only(kw))
         self.align_domain = bool(align_domain)
         self.domain_weight = float(domain_weight)
         self.loss_domain = torch.zeros(1, device=model.device)
@@ -115,45 +108,16 @@ class SourceStep(SSLStep):
         h, w = ((int(v) + 15) // 16 for v in images_t.shape[-2:])      # the feature map lies at output stride 16
         aligner.check_served((images_t.shape[0], 2048, h, w), (images_t.shape[0], self.C, h, w))
 
-    # training state (regda_amd/ssl.py): the adversarial term's discriminator and its Adam moments join the step's own
-    _STATE_EXTRA = ('fada',)
-
-    def _state_extra(self):
-        aligner = self.fada['aligner']
-        return {} if aligner is None else {'fada': aligner.state_dict()}
-
-    def _state_loads(self, sd, strict):
-        loads = super()._state_loads(sd, strict)
-        aligner = self.fada['aligner']
-        if ('fada' in sd) != (aligner is not None) and (strict or 'fada' in sd):
-            raise ValueError(f"state entry 'step.fada': the state has {'a' if 'fada' in sd else 'no'} feature-adversarial "
-                             f"aligner, step.fada['aligner'] is {'set' if aligner is not None else 'None'}")
-        if 'fada' in sd:
-            aligner.check_state_dict(sd['fada'], strict, 'step.fada')
-            loads.append(lambda: aligner.load_state_dict(sd['fada'], strict=strict))
-        return loads
-
-    def capture(self, *a, **k):
-        raise NotImplementedError('whole-step graph capture is provided for the SSL step only')
-
-    def record_plan(self, *a, **k):
-        raise NotImplementedError('plan replay is provided for the SSL step only')
+    def _state_parts(self):
+        """+ the adversarial term's discriminator and its Adam moments"""
+        return [*super()._state_parts(), Part('fada', self.fada['aligner'], hint=" (step.fada['aligner'])")]
 
     def _step(self, images_s, label_s, images_t):
         m = self.model
-        if not m.training:
-            m.train()
-        m._maybe_sync()
-        ops.fill_zero(m.flat_g)
         nb = images_s.shape[0]
-        main = torch.cuda.current_stream()
         fada = self.fada_weight > 0.0
-        if self.align_domain or fada:
-            T = m.new_tape(groups=2)
-            x1, x2, feat = m._forward_plan([images_s.contiguous().float(), images_t.contiguous().float()], T)
-        else:
-            T = m.new_tape(groups=1)
-            x1, x2, feat = m._forward_plan(images_s.contiguous().float(), T)
+        # both domains run as two BatchNorm groups where a term reads the target features; else the source batch alone
+        T, main, x1, x2, feat = self._forward_domains(*((images_s, images_t) if self.align_domain or fada else (images_s,)))
         # d(loss) / d(logits): the source rows from the CE kernel, the target rows (when there are any) zero
         g1, g2 = torch.zeros_like(x1), torch.zeros_like(x2)
         loss_seg = self._source_loss(x1[:nb], x2[:nb], label_s, g1[:nb], g2[:nb])

@@ -8,69 +8,34 @@ flat gradient buffer, bucketed RCCL all-reduce overlapped with the second backwa
 clip + SGD (+ EMA shadow + bf16 weight mirror) kernel.  Optionally the soft target labels come from an
 online EMA teacher (regda/utils/ema.py semantics: parameters averaged, BN buffers shared) instead of
 the offline `.pt` files of the reference (BASELINE.json north_star; SURVEY.md header table).
+SSLStep is a PseudoLabelStep (regda_amd/step.py: the optimizer tail, the gradient exchange, the source loss, the state walk,
+prototypes and LRH live there); its own are the teacher, the target loss, mix / strong and the recorded plans and graphs.
 """
-import copy
-
 import numpy as np
 import torch
 
 from . import ops
 from . import plan
-from .checkpoint import (FORMAT, check_equal, check_format, check_module_state, check_tensor, copy_in_place, need,
-                         plain)
-from .ddp import FlatGradReducer, all_reduce_prototype_statistics
-from .gast.balance import source_loss, target_loss
+from .ddp import all_reduce_prototype_statistics
+from .gast.balance import target_loss
+from .checkpoint import check_module_state
+from .step import Part, PseudoLabelStep, check_generator
 
 
-class SSLStep:
-    def __init__(self, model, prototypes, class_num=6, ignore_label=-1, momentum=0.9, weight_decay=5e-4,
-                 max_norm=32.0, cutoff_top=0.8, cutoff_low=0.6, percent=0.5, proto_decay=0.996, refine_temp=2.0,
-                 sam_refine=True, refine_label=True, ema_decay=None, max_regions=4096, bucket_elems=12 << 20,
-                 process_group=None, overlap_wgrad=True, overlap_comm=True, class_balancer_s=None,
-                 class_balancer_t=None, grad_payload='fp32', comm=None, loss_s='CrossEntropy', loss_t='none',
-                 uvem_m=0.2, uvem_t=0.7, uvem_g=4.0, gdp_prototype=True, gdp_class_balance=False, ent_weight=0.0,
-                 kld_weight=0.0, adv_weight=0.0, discriminators=None, mix=None, strong=None):
+class SSLStep(PseudoLabelStep):
+    def __init__(self, model, prototypes, ema_decay=None, class_balancer_t=None, loss_t='none', uvem_m=0.2, uvem_t=0.7,
+                 uvem_g=4.0, gdp_prototype=True, gdp_class_balance=False, ent_weight=0.0, kld_weight=0.0, adv_weight=0.0,
+                 discriminators=None, mix=None, strong=None, **kw):
         if adv_weight or discriminators is not None:
             raise NotImplementedError('the adversarial term (adv_weight / discriminators) belongs to the stage-2 step, AlignStep')
-        ops.check_class_count(class_num, type(self).__name__)
-        self.model = model
-        self.C, self.ig = class_num, ignore_label
-        self._shape_ok = None
-        self.momentum, self.wd, self.max_norm = momentum, weight_decay, max_norm
-        self.top, self.low, self.percent = cutoff_top, cutoff_low, percent
-        self.pdecay, self.temp = proto_decay, refine_temp
-        self.sam_refine, self.refine_label = sam_refine, refine_label
-        self.max_regions = max_regions
-        dev = model.device
-        self.prototypes = prototypes.to(dev).float().contiguous().clone()
-        self.mom = torch.zeros_like(model.flat_p)
-        self.lr_dev = torch.zeros(1, device=dev)
-        self.gn = torch.zeros(1, device=dev)
-        self.gn_ws = torch.zeros(1024, device=dev)
-        self.first = True
-        self.lrh_ws = None
+        super().__init__(model, prototypes, **kw)
+        class_num, ignore_label, dev = self.C, self.ig, model.device
         self.ema_decay = ema_decay
-        self.teacher = None
         if ema_decay is not None:
             self.teacher = model.make_teacher()
-        bounds = model.param_boundaries()
-        # grad_payload: 'fp32' = bucketed all-reduce of the fp32 gradient; 'bf16' = all-to-all + fp32 accumulation +
-        # all-gather of bf16 payloads, half the bytes on every link (regda_amd/ddp.py)
-        # comm: a regda_amd.ddp.RcclComm -- the gradient buckets and the prototype statistics then go through the library's
-        # own RCCL entry points (rgda_comm_*) instead of torch.distributed
-        self.comm = comm
-        self.reducer = FlatGradReducer(model.flat_g, bounds, bucket_elems, process_group, payload=grad_payload, comm=comm)
-        self.measure_comm = False   # bench: HIP events around the main stream's wait for the gradient exchange
-        self.comm_events = None
-        self.bwd_start_event = None
-        self.wgrad_stream = torch.cuda.Stream(device=dev) if overlap_wgrad else None
-        self.source_side = overlap_wgrad    # source half of the label path on the second stream
-        # --bcs / --bct of tools/train_ssl_reg.py:54-58,125-158: regda_amd.gast.balance.ClassBalance objects whose
-        # frequency EMA re-weights the source / target cross-entropy per class (None = plain CE, the default)
-        self.class_balancer_s, self.class_balancer_t = class_balancer_s, class_balancer_t
-        # --ls / --lt (+ --uvem-m/-t/-g) of tools/train_ssl_reg.py:52-63,134-158: regda_amd.gast.balance losses whose
-        # fused kernels (rgda_upsample_ce / rgda_upsample_loss) the step launches directly
-        self.loss_fn_s = source_loss(loss_s, class_balancer_s, ignore_label)
+        self.source_side = self.wgrad_stream is not None    # source half of the label path on the second stream
+        # --bct, --lt (+ --uvem-m/-t/-g) of tools/train_ssl_reg.py:52-63,125-158, as --bcs and --ls in regda_amd/step.py
+        self.class_balancer_t = class_balancer_t
         # loss_t='gdp': GDPLoss (balance.py:218-303).  gdp_prototype adds the prototype weight of every pseudo-labelled
         # pixel (Aligner.get_prototype_weight_4pixel on feat_t and the step's final pseudo labels, from the prototypes as
         # label_refine reads them), gdp_class_balance the class weight (class_balancer_t if given, else the loss's own)
@@ -96,16 +61,7 @@ class SSLStep:
         self.strong = strong
         self.strong_flag = torch.zeros(1, dtype=torch.int32, device=dev) if strong is not None else None
         self.last_strong = None     # the last step's table as drawn on the host, f32 (N, 8)
-        self._graph = None
-        self._plan = None
-        self._proto_ready = None
-        self.proto_stats = None     # data-parallel ranks: sums[c][k], cnt[c] of update_prototype (all-reduced per step)
-        self.marks = None           # set to [] to collect (name, event) phase marks of the next step (bench --phases)
-        self.overlap_comm = overlap_comm
-        self.keep_debug = False     # tests: keep the step's target logits / features / refined soft labels (`self.debug`)
-        self.debug = None
-        self.world = self.reducer.world
-        self.group = process_group
+        self._graph = self._plan = None
 
     # ------------------------------------------------------------------
     @torch.no_grad()
@@ -120,14 +76,6 @@ class SSLStep:
         ops.set_f32(self.lr_dev, lr)
         with ops.use_stream(torch.cuda.current_stream()):
             return self._step(images_s, label_s, images_t, soft_t, regs_t)
-
-    def _check_shape(self, *images):
-        """ValueError before the first launch where a kernel of the step cannot serve these tiles (ops.check_step_shape)."""
-        for x in images:
-            if x is None or tuple(x.shape[-2:]) == self._shape_ok:
-                continue
-            ops.check_step_shape(self.C, self.prototypes.shape[-1], x.shape[-2], x.shape[-1], type(self).__name__)
-            self._shape_ok = tuple(x.shape[-2:])
 
     def capture(self, images_s, label_s, images_t, soft_t, regs_t):
         """Capture one whole step (both streams) into a hipGraph; later `step()` calls replay it.  The step is a
@@ -191,131 +139,28 @@ class SSLStep:
         t.eval()
         return t
 
-    # ------------------------------------------------------------------ training state (regda_amd/checkpoint.py)
-    _STATEFUL = ('class_balancer_s', 'class_balancer_t', 'loss_fn_s', 'loss_fn_t')
-    _STATE_EXTRA = ()       # the entries a subclass adds (_state_extra)
+    # ------------------------------------------------------------------ training state (regda_amd/step.py)
+    _STATE_CONFIG_FREE = ('ema_decay',)     # recorded; whether there is a teacher is what a load compares
 
     def _state_config(self):
-        m = self.model
-        return dict(class_num=self.C, ignore_label=self.ig, loss_s=self.loss_fn_s.kind, loss_t=self.loss_fn_t.kind,
-                    ema_decay=self.ema_decay, model=dict(resnet_type=m.resnet_type, head_kind=m.head_kind,
-                                                         num_classes=m.num_classes, n_param=m.flat_p.numel()))
+        return dict(super()._state_config(), loss_t=self.loss_fn_t.kind, ema_decay=self.ema_decay)
 
-    def _state_extra(self):
-        """What a subclass adds to state_dict()"""
-        return {}
-
-    def state_dict(self, rng=True):
-        """Everything the run needs to continue with the bits of the uninterrupted one, as plain data (nested dicts and
-        lists of CPU tensors, numbers, strings, None: torch.load(weights_only=True) reads a file of it): the model's
-        state_dict(), momentum, the optimizer's `first` flag, prototypes, the teacher's state_dict(), the balancers' and
-        losses' statistics and, with `rng`, torch's CPU and device generator states (the Dropout2d seeds and the contrast
-        term's draws come from the CPU one).  Not state: gradients, the learning rate word, the last_* / loss_* outputs,
-        workspaces, plans, streams, and the parameter dicts the caller sets (step.contrast, ...).  Synchronises the
-        device first: the end of a step leaves work on the side streams."""
-        torch.cuda.synchronize()
-        sd = dict(format=FORMAT, kind=type(self).__name__, config=self._state_config(), model=self.model.state_dict(),
-                  mom=self.mom, first=bool(self.first), prototypes=self.prototypes)
-        if self.teacher is not None:
-            sd['teacher'] = self.teacher.state_dict()
-        for name in self._STATEFUL:
-            obj = getattr(self, name)
-            s = obj.state_dict() if obj is not None else None
-            if s:
-                sd[name] = s
-        if self.mix is not None:
-            sd['mix'] = self.mix.state_dict()        # where its generator stands: a resumed run continues the draws
-        if self.strong is not None:
-            sd['strong'] = self.strong.state_dict()
-        sd.update(self._state_extra())
-        if rng:
-            sd['rng'] = dict(cpu=torch.get_rng_state(), cuda=torch.cuda.get_rng_state(self.model.device))
-        return plain(sd)
+    def _state_parts(self):
+        t = self.teacher    # behind its load, flat_pb and _synced_version agree with the shadow again
+        return [Part('teacher', t, check_module_state, lambda saved: t.refresh_from_master(), ' (ema_decay)'),
+                *super()._state_parts(), Part('class_balancer_t', self.class_balancer_t, check_module_state),
+                Part('loss_fn_t', self.loss_fn_t, check_module_state), Part('mix', self.mix, check_generator),
+                Part('strong', self.strong, check_generator)]
 
     def _state_loads(self, sd, strict):
-        """Validate every entry of `sd` against this step (ValueError naming the entry; nothing is written here) and
-        return the writes, in order, as closures for load_state_dict to run once ALL of them are known to be good."""
-        check_format(sd, 'step')
-        check_equal(need(sd, 'kind', 'step'), type(self).__name__, 'step.kind')
-        cfg, own = need(sd, 'config', 'step'), self._state_config()
-        for k in ('class_num', 'ignore_label', 'loss_s', 'loss_t'):
-            check_equal(need(cfg, k, 'step.config'), own[k], 'step.config.' + k)
-        for k, v in own['model'].items():
-            check_equal(need(need(cfg, 'model', 'step.config'), k, 'step.config.model'), v, 'step.config.model.' + k)
-        if ('teacher' in sd) != (self.teacher is not None) and (strict or 'teacher' in sd):
-            raise ValueError(f"state entry 'step.teacher': the state has {'a' if 'teacher' in sd else 'no'} teacher, this "
-                             f"step has {'one' if self.teacher is not None else 'none'} (ema_decay)")
-        known = {'format', 'kind', 'config', 'model', 'mom', 'first', 'prototypes', 'teacher', 'rng', 'mix', 'strong',
-                 *self._STATEFUL, *self._STATE_EXTRA}
-        if strict and set(sd) - known:
-            raise ValueError(f'state entries {sorted(set(sd) - known)} of the step are unknown to this {type(self).__name__}')
-        take = lambda k: need(sd, k, 'step') if strict or k in sd else None     # strict=False: what is there
-        loads = []
-        m = self.model
-        if take('model') is not None:
-            check_module_state(m, sd['model'], 'step.model', strict)
-            loads.append(lambda: m.load_state_dict(sd['model'], strict=strict))    # in place; re-syncs the bf16 mirrors
-        for k, dst in (('mom', self.mom), ('prototypes', self.prototypes)):
-            if take(k) is not None:
-                check_tensor(sd[k], 'step.' + k, dst.shape, dst.dtype)
-                loads.append(lambda dst=dst, k=k: copy_in_place(dst, sd[k]))
-        if take('first') is not None:
-            if not isinstance(sd['first'], bool):
-                raise ValueError(f"state entry 'step.first': expected a bool, got {sd['first']!r}")
-            if sd['first'] and self._plan is not None:
-                raise ValueError("state entry 'step.first': the state is that of a run that has not stepped, and this "
-                                 "step holds a recorded plan, which is the optimizer's later variant: release_plan() first")
-            loads.append(lambda: setattr(self, 'first', sd['first']))
-        t = self.teacher
-        if t is not None and 'teacher' in sd:
-            check_module_state(t, sd['teacher'], 'step.teacher', strict)
-
-            def load_teacher():
-                t.load_state_dict(sd['teacher'], strict=strict)
-                t.refresh_from_master()         # flat_pb and _synced_version agree with the shadow again
-            loads.append(load_teacher)
-        for name in self._STATEFUL:
-            obj = getattr(self, name)
-            own_state = obj.state_dict() if obj is not None else None
-            if (name in sd) != bool(own_state) and (strict or name in sd):
-                raise ValueError(f"state entry 'step.{name}': the state has {'one' if name in sd else 'none'}, this step "
-                                 f"has {'one' if own_state else 'none'}")
-            if name in sd:
-                check_module_state(obj, sd[name], 'step.' + name, strict)
-                loads.append(lambda obj=obj, name=name: obj.load_state_dict(sd[name], strict=strict))
-        for name, obj in (('mix', self.mix), ('strong', self.strong)):      # the host generators of the step's draws
-            if (name in sd) != (obj is not None) and (strict or name in sd):
-                raise ValueError(f"state entry 'step.{name}': the state has {'one' if name in sd else 'none'}, this step "
-                                 f"has {'one' if obj is not None else 'none'}")
-            if name in sd:
-                try:
-                    copy.deepcopy(obj).load_state_dict(sd[name])        # validated on a copy: nothing is written here
-                except ValueError as e:
-                    raise ValueError(f"state entry 'step.{name}': {e}") from None
-                loads.append(lambda obj=obj, name=name: obj.load_state_dict(sd[name]))
-        if 'rng' in sd:
-            cpu, cuda = (need(sd['rng'], k, 'step.rng') for k in ('cpu', 'cuda'))
-            for k, v in (('cpu', cpu), ('cuda', cuda)):
-                check_tensor(v, 'step.rng.' + k, dtype=torch.uint8)
-            loads.append(lambda: (torch.set_rng_state(cpu), torch.cuda.set_rng_state(cuda, m.device)))
-        return loads
-
-    def load_state_dict(self, sd, strict=True):
-        """Continue the run `sd` (a state_dict()) was taken from.  Every entry is validated before the first is written:
-        a mismatch (format, step class, class count, loss kinds, prototype / momentum size, model fingerprint, teacher or
-        not, missing keys) raises ValueError naming the entry and leaves the step untouched and usable.  Each tensor is
-        copied into the storage the step already owns, so a recorded plan (record_plan) stays valid and replays the
-        loaded state.  A captured hipGraph owns generator state that is not restored: RuntimeError -- load first, capture
-        afterwards.  `first` is what was saved: a step loaded from a run that has stepped may record_plan() or capture()
-        at once.  strict=False loads the entries and keys that are there."""
-        if self._graph is not None:
+        if self._graph is not None:     # (a recorded plan stays valid: it replays the loaded state)
             raise RuntimeError(f'{type(self).__name__}.load_state_dict: this step holds a captured graph, which owns '
                                f'generator state that a load cannot restore: load the state first and capture() afterwards')
-        loads = self._state_loads(sd, strict)
-        torch.cuda.synchronize()        # the last step's tail is still writing weights and mirrors on the side streams
-        for load in loads:
-            load()
-        torch.cuda.synchronize()
+        loads = super()._state_loads(sd, strict)
+        if sd.get('first') and self._plan is not None:
+            raise ValueError("state entry 'step.first': the state is that of a run that has not stepped, and this "
+                             "step holds a recorded plan, which is the optimizer's later variant: release_plan() first")
+        return loads
 
     def record_plan(self, images_s, label_s, images_t, soft_t, regs_t, lr=None):
         """Record one whole step (all streams) as a launch plan (regda_amd/plan.py): its ~750 entry-point calls become
@@ -388,32 +233,9 @@ class SSLStep:
         self._graph.replay()
         return self._out
 
-    def _class_weights(self, balancer, label):
-        """Per-class CE weights of the two heads [2, C] (or None): loss_calc(multi=True) calls the loss once per head
-        and every call EMA-updates the balancer (regda/gast/balance.py:27-35), so the heads see consecutive states.
-        A host action of a recorded step: the counts and the 6-element arithmetic are re-run at every replay."""
-        if balancer is None:
-            return None
-        cw = torch.empty(2, self.C, device=label.device)
-        here = torch.cuda.current_stream()
-
-        def update():
-            # a replay runs this on `here` as torch's stream, but with the library's stream set to the plan's: the count
-            # kernel and the torch arithmetic on its result must share one (the source side runs on the second stream)
-            with ops.use_stream(here):
-                for hd in range(2):
-                    cw[hd].copy_(balancer.next_class_weight(label))
-        plan.host(update)
-        return cw
-
     def _host_balancers(self):
         """Whether a ClassBalance takes part in the step's losses (ohem, focal and ghm targets take none)."""
-        return self.loss_fn_s.class_balancer is not None or self.loss_fn_t.class_balancer is not None
-
-    def _source_loss(self, s1, s2, label_s, g1, g2):
-        """loss_calc(source, loss_fn_s): its value; d loss / d logits written into g1, g2."""
-        f = self.loss_fn_s
-        return f.launch(s1, s2, label_s, class_weight=self._class_weights(f.class_balancer, label_s), g1=g1, g2=g2)[0]
+        return super()._host_balancers() or self.loss_fn_t.class_balancer is not None
 
     def _target_loss(self, t1, t2, hard, soft, g1, g2, proto_weight=None):
         """loss_calc / loss_calc_uvem(target, loss_fn_t) on the pseudo labels (ups / uvem also read the refined soft label,
@@ -435,12 +257,6 @@ class SSLStep:
         reg = ops.upsample_reg(t1, t2, hard, terms=terms, lambda_ent=self.ent_weight, lambda_kld=self.kld_weight,
                                ignore_label=self.ig, g1=g1, g2=g2, accumulate=True, empty_is_zero=True)[0]
         self.loss_ent, self.loss_kld = reg[0], reg[1]
-
-    def _mark(self, name, stream=None):
-        if self.marks is not None:
-            ev = torch.cuda.Event(enable_timing=True)
-            ev.record(stream if stream is not None else torch.cuda.current_stream())
-            self.marks.append((name, ev))
 
     def _step(self, images_s, label_s, images_t, soft_t, regs_t):
         m = self.model
@@ -661,65 +477,6 @@ class SSLStep:
         ignore label."""
         return 0 if self.mix_flag is None else int(self.mix_flag.item())
 
-    def _proto_local(self, feat_s, label_s, exchange):
-        """update_prototype on this rank's source batch: the whole update (one rank), or its sufficient statistics only
-        (data-parallel ranks: `_step` all-reduces them and applies the totals)."""
-        if exchange:
-            self.proto_stats, _ = ops.proto_stats(feat_s, label_s, 16, self.ig, 0.75, self.C, stats=self.proto_stats)
-        else:
-            ops.proto_update(feat_s, label_s, self.prototypes, 16, self.ig, 0.75, self.pdecay)
-
-    def _backward_and_update(self, T, main, g1, g2, gfeat=None):
-        """Backward (both domains in one pass; all-reduce buckets are released as it moves down the net), then clip +
-        SGD (+ EMA) in one pass over the flat buffers."""
-        m = self.model
-        plan.host(self.reducer.reset)
-        if self.measure_comm and self.reducer.active:
-            def mark_backward_start():
-                self.reducer.measure = True
-                self.bwd_start_event = torch.cuda.Event(enable_timing=True)
-                self.bwd_start_event.record()
-            plan.host(mark_backward_start)
-        T['wgrad_stream'] = self.wgrad_stream
-        T['main_stream'] = main
-        T['mark'] = self._mark if self.marks is not None else None
-
-        def progress(offset):
-            if (self.world > 1 or self.reducer.force) and self.overlap_comm:
-                if self.wgrad_stream is not None:
-                    # a bucket needs the weight gradients (second stream) AND the BN gradients (main stream) of its
-                    # layers: issue it from the second stream once that has caught up with this point of the main
-                    # stream, so the critical path never waits for communication
-                    plan.wait_event(self.wgrad_stream, plan.record_event(main))
-                    with ops.use_stream(self.wgrad_stream):
-                        plan.host(lambda: self.reducer.ready_down_to(offset))
-                else:
-                    plan.host(lambda: self.reducer.ready_down_to(offset))
-        m._backward_plan(T, g1, g2, on_progress=progress, gfeat=gfeat)
-        self._mark('backward done (streams joined)')
-        def finish_exchange():
-            # everything the main stream still has to wait for here is EXPOSED communication (the buckets were issued
-            # while backward ran); with measure_comm the stall is bracketed by events (bench.py: comm_exposed_ms)
-            if self.measure_comm and self.reducer.active:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                self.reducer.finish()
-                e1.record()
-                self.comm_events = (e0, e1)
-            else:
-                self.reducer.finish()
-        plan.host(finish_exchange)
-        # ---- clip + SGD (+ EMA) in one pass over the flat buffers
-        ops.sumsq(m.flat_g, self.gn, self.gn_ws)
-        shadow = self.teacher.flat_p if self.teacher is not None else None
-        ops.sgd_step(m.flat_p, m.flat_g, self.mom, shadow, m.flat_pb, self.gn, self.lr_dev, self.momentum, self.wd,
-                     self.max_norm, self.reducer.gscale, self.ema_decay if shadow is not None else 0.0, self.first,
-                     shadow_bf16=self.teacher.flat_pb if shadow is not None else None)   # teacher mirror stays fresh
-        self.first = False
-        m.sync_derived_weights(self.wgrad_stream)
-        m._synced_version = m.flat_p._version
-        self._mark('optimizer + weight mirrors done')
-
     @torch.no_grad()
     def teacher_probs(self, images_t, snapshot=True):
         """Eval-mode forward of the EMA teacher (Encoder.py:152-155 on the shadow weights; BatchNorm buffers = the
@@ -733,23 +490,3 @@ class SSLStep:
         t.eval()
         x1, x2, _ = t._forward_plan(images_t.contiguous().float(), None)
         return ops.teacher_probs(x1, x2, tuple(images_t.shape[-2:]))
-
-    def _lrh(self, regs, hard, fused=None):
-        """Homogenizer (LRH) of the selected labels `hard` on the step's workspace, which keeps the flag word `lrh_flag()`
-        reads.  fused = (soft, classmax): pseudo_selection + LRH in one pass instead (rgda_pseudo_lrh), `hard` unused."""
-        self._lrh_flag_off = (regs.shape[0] * self.max_regions * (self.C + 1)) * 4
-        if fused is not None:
-            hard, self.lrh_ws = ops.pseudo_lrh(*fused, regs, self.top, self.low, self.percent, self.C, self.ig,
-                                               self.max_regions, ws=self.lrh_ws)
-            return hard
-        need = self._lrh_flag_off + 16
-        if self.lrh_ws is None or self.lrh_ws.numel() < need:
-            self.lrh_ws = torch.empty(need, dtype=torch.uint8, device=self.model.device)
-        return ops.lrh(hard, regs.contiguous(), self.percent, self.C, self.ig, self.max_regions, check=False, ws=self.lrh_ws)
-
-    def lrh_flag(self):
-        """Deferred check of the LRH kernel's flag word (host sync): region id / label range errors."""
-        if self.lrh_ws is None:
-            return 0
-        o = self._lrh_flag_off
-        return int(self.lrh_ws[o:o + 4].view(torch.int32).item())

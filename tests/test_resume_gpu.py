@@ -335,42 +335,85 @@ def test_align_step_with_adversarial_and_contrast_terms_resumes_bit_for_bit(batc
     assert_same([], align_final(a), [], align_final(c), 'stage 2: after the refusals')
 
 
-def test_source_step_with_domain_alignment_resumes_bit_for_bit(batches, tmp_path):
-    from regda_amd.checkpoint import load_training_state, save_training_state
+def source_step(init_seed=12, torch_seed=77):
     from regda_amd.gast.balance import ClassBalance
     from regda_amd.source import SourceStep
+    m = build()
+    m.load_state_dict(init_sd(init_seed), strict=True)
+    torch.manual_seed(torch_seed)
+    return SourceStep(m, class_balancer_s=ClassBalance(class_num=6, ignore_label=-1, decay=0.99, temperature=0.5),
+                      align_domain=True)
 
-    def source_step(init_seed=12, torch_seed=77):
-        m = build()
-        m.load_state_dict(init_sd(init_seed), strict=True)
-        torch.manual_seed(torch_seed)
-        return SourceStep(m, class_balancer_s=ClassBalance(class_num=6, ignore_label=-1, decay=0.99, temperature=0.5),
-                          align_domain=True)
 
-    def steps(st, which):
-        out = []
-        for i in which:
-            b = batches[i]
-            r = st.step(b['images_s'], b['label_s'], b['images_t'], LRS[i])
-            out.append(dict(loss_seg=r[0].clone(), loss_domain=r[1].clone(), gn=r[2].clone()))
-        torch.cuda.synchronize()
-        return out
+def source_steps(st, batches, which):
+    out = []
+    for i in which:
+        b = batches[i]
+        r = st.step(b['images_s'], b['label_s'], b['images_t'], LRS[i])
+        out.append(dict(loss_seg=r[0].clone(), loss_domain=r[1].clone(), gn=r[2].clone()))
+    torch.cuda.synchronize()
+    return out
 
-    def final(st):
-        return dict(p=st.model.flat_p.clone(), buf=st.model.flat_buf.clone(), mom=st.mom.clone(),
-                    freq=st.class_balancer_s.freq.clone())
+
+def source_final(st):
+    return dict(p=st.model.flat_p.clone(), buf=st.model.flat_buf.clone(), mom=st.mom.clone(),
+                freq=st.class_balancer_s.freq.clone())
+
+
+def test_source_step_with_domain_alignment_resumes_bit_for_bit(batches, tmp_path):
+    from regda_amd.checkpoint import load_training_state, save_training_state
     a = source_step()
-    A = steps(a, range(3))
+    A = source_steps(a, batches, range(3))
     assert all(s['loss_domain'].item() != 0.0 for s in A)
     b = source_step()
-    steps(b, range(1))
+    source_steps(b, batches, range(1))
     path = os.path.join(tmp_path, 'source.pth')
     save_training_state(path, b, 1)
     c = source_step(init_seed=99, torch_seed=5)
     assert load_training_state(path, c) == 1
-    assert_same(A[1:], final(a), steps(c, (1, 2)), final(c), 'stage 1: resumed')
+    assert_same(A[1:], source_final(a), source_steps(c, batches, (1, 2)), source_final(c), 'stage 1: resumed')
     with pytest.raises(ValueError, match='kind'):
         ssl_step('plain').load_state_dict(torch.load(path, weights_only=True)['step'])
+
+
+# ------------------------------------------------------- format-1 states written while both steps derived from SSLStep
+def test_a_source_step_has_no_prototypes_and_loads_a_state_that_carries_them(batches):
+    """Such a state holds the zero tensor that stood in for prototypes and the SSL step's two config keys: it loads under
+    strict=True, the entries are ignored, and the run continues with the bits of one that loaded today's form."""
+    a = source_step()
+    assert not hasattr(a, 'prototypes') and not hasattr(a, 'loss_fn_t') and a.teacher is None
+    source_steps(a, batches, range(1))
+    sd = a.state_dict()
+    assert 'prototypes' not in sd and 'loss_t' not in sd['config'] and 'ema_decay' not in sd['config']
+    old = dict(sd, prototypes=torch.zeros(6, 2048), config=dict(sd['config'], loss_t='none', ema_decay=None))
+    b, c = source_step(init_seed=99, torch_seed=5), source_step(init_seed=99, torch_seed=6)
+    b.load_state_dict(sd, strict=True)          # (the generators a state restores are global: load, then run, one by one)
+    new_form = source_steps(b, batches, (1, 2))
+    with pytest.raises(ValueError, match='no_such_entry'):
+        c.load_state_dict(dict(old, no_such_entry=torch.zeros(1)), strict=True)
+    c.load_state_dict(old, strict=True)
+    assert not hasattr(c, 'prototypes') and 'prototypes' not in c.state_dict()
+    assert_same(new_form, source_final(b), source_steps(c, batches, (1, 2)), source_final(c),
+                'stage 1: the earlier form of the state')
+
+
+def test_an_align_step_loads_a_state_that_carries_the_ssl_config_keys(batches):
+    a = align_step()
+    assert not hasattr(a, 'loss_fn_t') and a.teacher is None
+    align_steps(a, batches, range(1))
+    sd = a.state_dict()
+    assert 'loss_t' not in sd['config'] and 'ema_decay' not in sd['config'] and 'prototypes' in sd
+    # built on a second copy of the state: a load may keep what it is given (torch's Adam keeps the CPU `step` tensors)
+    old = a.state_dict()
+    old = dict(old, config=dict(old['config'], loss_t='none', ema_decay=None))
+    b, c = align_step(init_seed=99, torch_seed=5, proto_seed=6), align_step(init_seed=99, torch_seed=6, proto_seed=7)
+    b.load_state_dict(sd, strict=True)
+    new_form = align_steps(b, batches, (1, 2))
+    with pytest.raises(ValueError, match='no_such_entry'):
+        c.load_state_dict(dict(old, no_such_entry=torch.zeros(1)), strict=True)
+    c.load_state_dict(old, strict=True)
+    assert_same(new_form, align_final(b), align_steps(c, batches, (1, 2)), align_final(c),
+                'stage 2: the earlier form of the state')
 
 
 # ------------------------------------------------------------------------------------------ the helpers a script holds
