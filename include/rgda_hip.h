@@ -947,6 +947,57 @@ int rgda_strong_augment(const float* img_in, float* img_out, const float* table,
  * row with bit 1 whose sigma is outside (0, 4] or whose radius R is not below both H and W. */
 int rgda_strong_write_table(float* table, const float* host, int N, int H, int W, rgda_stream_t stream);
 
+/* ------------------------------------------------------------- Fourier style transfer of the source tile */
+
+/* Fourier Domain Adaptation (Yang and Soatto, CVPR 2020) of normalised source tiles, image by image from a device table:
+ * the low-frequency amplitude spectrum of a source image is replaced with that of a target image, the source's phase is
+ * kept.  The reference has no such pass; the semantics are this library's and tests/fourier_ref.py restates them in fp64
+ * through a full FFT.
+ *   img_s f32 [N][3][H][W], img_t f32 [M][3][H][W] (read only), out f32 [N][3][H][W], every pixel written, OUT OF PLACE.
+ *   table int32 [N][RGDA_STYLE_TABLE_COLS], 16-byte aligned, DEVICE memory: row n = {partner in [0, M), b, on, 0}.
+ *   mean_s*, std_s*, mean_t*, std_t* (r, g, b): the normalisations the source and the target tiles carry; std > 0.
+ * Per channel, on the raw grey scale: S = x_s std_s + mean_s, T = x_t std_t + mean_t of the row's partner.
+ *   1. F_S = DFT2(S), F_T = DFT2(T).
+ *   2. On every frequency pair (ky, kx) with |ky| <= b and |kx| <= b (signed frequencies, DC at (0, 0): the published
+ *      window [c - b, c + b] around c = floor(size / 2) of the fft-shifted spectrum, for even and odd sizes alike) the
+ *      amplitude |F_S| is replaced by |F_T| and the source's phase is kept; where |F_S(k)| is exactly 0 the phase is 0.
+ *   3. The real part of the inverse transform, normalised as the source is: out = (. - mean_s) / std_s.  No clamp.
+ * b = 0 swaps the channel mean; T == S with equal normalisations returns S up to rounding.  A row with on == 0 is COPIED
+ * bit for bit (no arithmetic touches it; NaN and inf pass through).  b comes from the host (b = floor(min(H, W) beta)).
+ * No full FFT: only (2b + 1)^2 bins change, so out_raw = S + (1 / HW) Re sum_k D(k) e^{+2 pi i (ky y / H + kx x / W)} with
+ * D(k) = (|F_T(k)| - |F_S(k)|) F_S(k) / |F_S(k)|, a pruned separable DFT (kx in [0, b] suffices: the images are real).
+ * Six launches whatever the table holds: the rows as served and the twiddle tables e^{2 pi i p / W}, e^{2 pi i p / H}
+ * (p = (k x) mod size reduced in integers, sincospi in fp64, rounded once); the row transform of the source and the
+ * needed target images; the column transform; D; the column synthesis; the row synthesis, which reads the source tile
+ * once, adds the correction and writes the normalised output (or copies an off row).  fp32 arithmetic, every sum in a
+ * fixed order (a fixed sequence per lane, then a fixed tree): no atomics, two runs give identical bits.
+ * Served: b <= RGDA_STYLE_MAX_B, 2 b + 1 <= min(H, W), N and M in 1..RGDA_STYLE_MAX_IMAGES, H, W <= 4096.
+ * rgda_fourier_style_write_table refuses rows outside that.  The rows are read on the device and cannot be refused here:
+ * a row with a partner outside [0, M), b < 0, a b that does not fit, or on outside {0, 1} is copied unchanged and sets
+ * *flag (optional, device int) to 1.
+ *   ws: rgda_fourier_style_workspace(N, M, H, W) bytes (0 for a shape that is not served), sized for the largest b the
+ *     tile admits, 16-byte aligned; rewritten BY the call, any contents on entry.
+ * Errors before any launch (RGDA_ERR_ARG): null img_s / img_t / out / ws; null or misaligned table; misaligned ws; N, M,
+ * H or W < 1; a std that is not positive and finite, a mean that is not finite; out overlapping img_s or img_t.  N or M
+ * above RGDA_STYLE_MAX_IMAGES, H or W above 4096: RGDA_ERR_UNSUPPORTED. */
+#define RGDA_STYLE_TABLE_COLS 4
+#define RGDA_STYLE_MAX_B 64
+#define RGDA_STYLE_MAX_IMAGES 16
+size_t rgda_fourier_style_workspace(int N, int M, int H, int W);
+int rgda_fourier_style(const float* img_s, const float* img_t, float* out, const int32_t* table, void* ws, int N, int M,
+                       int H, int W, float mean_sr, float mean_sg, float mean_sb, float std_sr, float std_sg, float std_sb,
+                       float mean_tr, float mean_tg, float mean_tb, float std_tr, float std_tg, float std_tb, int* flag,
+                       rgda_stream_t stream);
+
+/* The host's table -> device, carried IN THE KERNEL ARGUMENTS of one launch, as rgda_strong_write_table carries its draw.
+ *   table int32 [N][RGDA_STYLE_TABLE_COLS] on the device, 16-byte aligned <- host, N * 4 int32 of HOST memory read during
+ *     the call; column 3 is written as 0.
+ *   M: the target images the partners index; H, W: the tiles the table is for.
+ * RGDA_ERR_ARG: null table / host; misaligned table; N, M, H or W < 1; a partner outside [0, M); b < 0; on not 0 or 1.
+ * RGDA_ERR_UNSUPPORTED: N or M above RGDA_STYLE_MAX_IMAGES; b above RGDA_STYLE_MAX_B; 2 b + 1 > min(H, W).  (b is checked
+ * on rows that are switched off too: the table says what was drawn.) */
+int rgda_fourier_style_write_table(int32_t* table, const int32_t* host, int N, int M, int H, int W, rgda_stream_t stream);
+
 /* ------------------------------------------------------------- region maps without SAM */
 
 /* The region maps rgda_lrh and rgda_label_refine_sup read, generated from the raw tile.

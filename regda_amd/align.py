@@ -295,6 +295,7 @@ class AlignStep(PseudoLabelStep):
     def _step(self, images_s, label_s, images_t, regs_t):
         m = self.model
         nb = images_s.shape[0]
+        images_s = self._style_source(images_s, images_t)       # the caller's tile itself without style=
         T, main, x1, x2, feat = self._forward_domains(images_s, images_t)
         s1, t1, s2, t2 = x1[:nb], x1[nb:], x2[:nb], x2[nb:]
         feat_s, feat_t = feat[:nb], feat[nb:]
@@ -336,4 +337,5 @@ class AlignStep(PseudoLabelStep):
             if t.after_update is not None:
                 t.after_update(self, c)
         self.last_hard, self.last_label_t, self.last_label_s_down = hard, label_t, label_s_down
+        self._keep_source(images_s)
         return loss_seg, self.loss_align, self.gn

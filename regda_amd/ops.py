@@ -1560,6 +1560,91 @@ def strong_augment(images, table, mean, std, out=None, ws=None, flag=None):
     return out
 
 
+# ----------------------------------------------------------------------------- Fourier style transfer of the source tile
+STYLE_TABLE_COLS = 4            # RGDA_STYLE_TABLE_COLS: {partner, b, on, 0} per source image
+STYLE_MAX_B = 64                # RGDA_STYLE_MAX_B
+STYLE_MAX_IMAGES = 16           # RGDA_STYLE_MAX_IMAGES
+
+
+def _style_table_check(who, table, n):
+    if table.dtype != torch.int32 or tuple(table.shape) != (n, STYLE_TABLE_COLS) or not table.is_contiguous():
+        raise ValueError('%s: table must be contiguous torch.int32 (%d, %d), got %s %s'
+                         % (who, n, STYLE_TABLE_COLS, table.dtype, tuple(table.shape)))
+
+
+def fourier_style_write_table(table, host, n_targets, size):
+    """rgda_fourier_style_write_table: table (int32 (N, 4) on the device, N <= 16) <- host (an int32 numpy array of that
+    shape: partner, b, on, 0 per source image -- FourierStyle.draw), carried in the launch's arguments: the host buffer is
+    read before this returns.  n_targets: the target images the partners index; size = (H, W) of the tiles.  A row the
+    transform does not serve (a partner outside [0, n_targets), b above 64 or 2 b + 1 above min(H, W), on not 0 or 1) is a
+    ValueError before any launch."""
+    import numpy as np
+    _need_cuda(table)
+    n = table.shape[0]
+    _style_table_check('fourier_style_write_table', table, n)
+    host = np.ascontiguousarray(host, dtype=np.int32)
+    if host.shape != (n, STYLE_TABLE_COLS):
+        raise ValueError('fourier_style_write_table: host must be int32 (%d, %d), got %s' % (n, STYLE_TABLE_COLS, host.shape))
+    h, w = (int(v) for v in size)
+    lib().call('rgda_fourier_style_write_table', table.data_ptr(), host.ctypes.data, n, int(n_targets), h, w, _stream())
+    return table
+
+
+def fourier_style_workspace(n, m, h, w, device):
+    """A workspace for ops.fourier_style(ws=) at n source and m target tiles of h x w: a uint8 tensor of
+    rgda_fourier_style_workspace(n, m, h, w) bytes; ValueError for a shape that is not served."""
+    need = lib().size('rgda_fourier_style_workspace', int(n), int(m), int(h), int(w))
+    if need == 0:
+        raise ValueError('fourier_style: %d + %d tiles of %d x %d are not served (1..%d images of each, H, W <= 4096)'
+                         % (n, m, h, w, STYLE_MAX_IMAGES))
+    return _ws(need, device)
+
+
+def fourier_style(images_s, images_t, table, mean_s, std_s, mean_t, std_t, out=None, ws=None, flag=None):
+    """rgda_fourier_style: Fourier Domain Adaptation of normalised source tiles -- the amplitudes of the (2 b + 1)^2 lowest
+    frequencies of source image n are replaced with those of its partner target image, as row n of `table` (int32 (N, 4)
+    on the device: partner, b, on, 0) says; include/rgda_hip.h carries the semantics.  images_s f32 (N,3,H,W) and
+    images_t f32 (M,3,H,W), N, M <= 16, never written; out: the result (allocated unless given), a different buffer.
+    mean_*, std_*: three values each, the normalisation the source and the target tiles carry.  ws: workspace of
+    rgda_fourier_style_workspace(N, M, H, W) bytes, a uint8 tensor (allocated unless given; the call rewrites it).  flag:
+    optional device int32, set to 1 by a row that is not served (that image is copied).  -> out."""
+    _need_cuda(images_s, images_t, table, out, ws, flag)
+    for name, x in (('images_s', images_s), ('images_t', images_t)):
+        if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32:
+            raise ValueError('fourier_style: %s must be torch.float32 (N,3,H,W), got %s %s' % (name, x.dtype, tuple(x.shape)))
+    n, _, h, w = images_s.shape
+    m = images_t.shape[0]
+    if tuple(images_t.shape[-2:]) != (h, w):
+        raise ValueError('fourier_style: source and target tiles must have one size, got %s and %s'
+                         % (tuple(images_s.shape[-2:]), tuple(images_t.shape[-2:])))
+    if not 1 <= n <= STYLE_MAX_IMAGES or not 1 <= m <= STYLE_MAX_IMAGES:
+        raise ValueError('fourier_style: %d source and %d target images; the kernels serve 1..%d of each'
+                         % (n, m, STYLE_MAX_IMAGES))
+    _style_table_check('fourier_style', table, n)
+    norms = [tuple(float(v) for v in t) for t in (mean_s, std_s, mean_t, std_t)]
+    if any(len(t) != 3 for t in norms) or not all(v > 0 for v in norms[1] + norms[3]):
+        raise ValueError('fourier_style: mean and std are three values each, std positive')
+    if out is None:
+        out = torch.empty(images_s.shape, dtype=torch.float32, device=images_s.device)
+    if out.dtype != torch.float32 or tuple(out.shape) != tuple(images_s.shape) or not out.is_contiguous():
+        raise ValueError('fourier_style: out is written and must be contiguous torch.float32 %s' % (tuple(images_s.shape),))
+    if h * w == 0:
+        return out
+    need = lib().size('rgda_fourier_style_workspace', n, m, h, w)
+    if need == 0:
+        raise ValueError('fourier_style: %d x %d tiles are not served (H, W <= 4096)' % (h, w))
+    if ws is None:
+        ws = _ws(need, images_s.device)
+    if ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_contiguous():
+        raise ValueError('fourier_style: ws must be contiguous torch.uint8 with at least %d bytes' % need)
+    src, tgt = images_s.contiguous(), images_t.contiguous()
+    if out.data_ptr() in (src.data_ptr(), tgt.data_ptr()):
+        raise ValueError('fourier_style: out must not be an input (the transform is out of place)')
+    lib().call('rgda_fourier_style', src.data_ptr(), tgt.data_ptr(), out.data_ptr(), table.data_ptr(), ws.data_ptr(), n, m, h, w,
+               *norms[0], *norms[1], *norms[2], *norms[3], _p(flag) or None, _stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- region maps without SAM
 def superpixels_max_regions(h, w, min_area):
     """The exclusive bound on the region ids rgda_superpixels writes for an h x w image: R <= h * w // min_area, so

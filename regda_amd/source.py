@@ -82,9 +82,12 @@ class SourceStep(FusedStep):
     @torch.no_grad()
     def step(self, images_s, label_s, images_t, lr):
         """One stage-1 iteration.  Returns device tensors (loss_seg, loss_domain, grad_norm_sq); loss_domain stays 0
-        without align_domain.  images_t may be None when align_domain and fada_weight are off (no target forward then)."""
+        without align_domain.  images_t may be None when align_domain, fada_weight and style are off (no target forward
+        then; style= reads the target tiles' spectra and needs them even without a target forward)."""
         if self.align_domain and images_t is None:
             raise ValueError('SourceStep(align_domain=True) needs the target images')
+        if self.style is not None and images_t is None:
+            raise ValueError('SourceStep(style=) needs the target images')
         if self.fada_weight > 0.0:
             self._fada_check(images_s, images_t)
         self._check_shape(images_s, images_t if self.align_domain or self.fada_weight > 0.0 else None)
@@ -116,6 +119,7 @@ class SourceStep(FusedStep):
         m = self.model
         nb = images_s.shape[0]
         fada = self.fada_weight > 0.0
+        images_s = self._style_source(images_s, images_t)       # the caller's tile itself without style=
         # both domains run as two BatchNorm groups where a term reads the target features; else the source batch alone
         T, main, x1, x2, feat = self._forward_domains(*((images_s, images_t) if self.align_domain or fada else (images_s,)))
         # d(loss) / d(logits): the source rows from the CE kernel, the target rows (when there are any) zero
@@ -143,4 +147,5 @@ class SourceStep(FusedStep):
         self._backward_and_update(T, main, g1, g2, gfeat=gfeat)
         if fada:
             self.loss_fada_disc = aligner.discriminator_step(feat_s, x2[:nb], feat_t, x2[nb:])
+        self._keep_source(images_s)
         return loss_seg, self.loss_domain, self.gn

@@ -9,7 +9,8 @@ clip + SGD (+ EMA shadow + bf16 weight mirror) kernel.  Optionally the soft targ
 online EMA teacher (regda/utils/ema.py semantics: parameters averaged, BN buffers shared) instead of
 the offline `.pt` files of the reference (BASELINE.json north_star; SURVEY.md header table).
 SSLStep is a PseudoLabelStep (regda_amd/step.py: the optimizer tail, the gradient exchange, the source loss, the state walk,
-prototypes and LRH live there); its own are the teacher, the target loss, mix / strong and the recorded plans and graphs.
+prototypes and LRH live there, and style=, the Fourier style transfer of the source tile); its own are the teacher, the
+target loss, mix / strong and the recorded plans and graphs.
 """
 import numpy as np
 import torch
@@ -97,6 +98,8 @@ class SSLStep(PseudoLabelStep):
         if self.strong is not None:
             # the same: the table is drawn on the host and travels as kernel arguments
             raise RuntimeError('the strong augmentation (strong=) draws on the host: use record_plan(), not capture()')
+        if self.style is not None:
+            raise RuntimeError('the Fourier style transfer (style=) draws on the host: use record_plan(), not capture()')
         self._static = self._static_inputs(images_s, label_s, images_t, soft_t, regs_t)
         self._build_maps(images_s)
         torch.cuda.synchronize()
@@ -277,6 +280,9 @@ class SSLStep(PseudoLabelStep):
             # the main stream, before the student's forward rewrites them) -- the same view whether its forward then
             # runs next to the student's on the second stream or after it
             self.teacher.adopt_buffers(m)
+        # style, then mix, then strong: the mix below pastes the stylised source pixels; the teacher sees the clean images_t
+        # (ahead of the teacher's launch or behind it: the step time was the same)
+        images_s = self._style_source(images_s, images_t)
         if teacher_on_side:
             # the EMA teacher's forward is independent of the student's: it runs on the second stream, next to it
             plan.wait_stream(self.wgrad_stream, main)
@@ -361,6 +367,7 @@ class SSLStep(PseudoLabelStep):
         if self.keep_debug:
             self.debug = dict(t1=t1, t2=t2, s1=s1, s2=s2, feat_t=feat_t, feat_s=feat_s, soft_in=soft_t, soft=soft,
                               hard_selected=hard, student_t=student_t)
+            self._keep_source(images_s)
         if self.sam_refine:
             hard = self._lrh(regs, hard, (soft, cm) if fuse_lrh else None)
         if self.mix is not None:

@@ -1,6 +1,7 @@
 """What the three fused training steps share:
 
-    FusedStep               the model, the optimizer tail, the gradient exchange, the source loss, the training state
+    FusedStep               the model, the optimizer tail, the gradient exchange, the source loss, the training state,
+                            style= (the Fourier style transfer of the source tile)
       +-- SourceStep        stage 1 (regda_amd/source.py)
       +-- PseudoLabelStep   + prototypes, the selection thresholds, LRH
             +-- SSLStep     the self-training step: teacher, target loss, mix / strong, plans and graphs (regda_amd/ssl.py)
@@ -24,7 +25,7 @@ from .gast.balance import source_loss
 Part = namedtuple('Part', 'name obj check after hint', defaults=(None, None, ''))
 
 
-def check_generator(obj, saved, entry, strict):     # the host generators (DomainMix, StrongAugment): load a copy
+def check_generator(obj, saved, entry, strict):     # the host generators (DomainMix, StrongAugment, FourierStyle): load a copy
     try:
         copy.deepcopy(obj).load_state_dict(saved)
     except ValueError as e:
@@ -36,7 +37,7 @@ class FusedStep:
 
     def __init__(self, model, class_num=6, ignore_label=-1, momentum=0.9, weight_decay=5e-4, max_norm=32.0,
                  bucket_elems=12 << 20, process_group=None, overlap_wgrad=True, overlap_comm=True, class_balancer_s=None,
-                 grad_payload='fp32', comm=None, loss_s='CrossEntropy'):
+                 grad_payload='fp32', comm=None, loss_s='CrossEntropy', style=None):
         ops.check_class_count(class_num, type(self).__name__)
         self.model = model
         self.C, self.ig = class_num, ignore_label
@@ -69,6 +70,50 @@ class FusedStep:
         self.keep_debug = False     # tests: keep intermediate tensors of the step (`self.debug`)
         self.debug = None
         self.world, self.group = self.reducer.world, process_group
+        # style: a regda_amd.aug.fourier.FourierStyle -- Fourier style transfer of the source tile ahead of the forward
+        # (DESIGN.md 4.2j): the low-frequency amplitudes of each source image become those of a target image of the batch.
+        # The caller's tensors are never written, the result is a buffer of the step's own.  None: no launch.
+        self.style = style
+        self.style_flag = torch.zeros(1, dtype=torch.int32, device=dev) if style is not None else None
+        self.last_style = None      # the last step's table as drawn on the host, int32 (N, 4)
+        self._style_ws = None       # (shape, the transform's workspace): kept from step to step, like the flag word
+
+    def _style_source(self, images_s, images_t):
+        """The source tile the network sees: `images_s` itself without `style=`, else its Fourier style transfer towards
+        this batch's target tiles, out of place.  The draw and the launch that carries it (rgda_fourier_style_write_table:
+        values in the kernel arguments) are ONE host action, re-run at every replay of a recorded step."""
+        st = self.style
+        if st is None:
+            return images_s
+        if images_t is None:
+            raise ValueError(f'{type(self).__name__}(style=) needs the target images')
+        if images_s.dim() != 4 or images_t.dim() != 4 or tuple(images_s.shape[1:]) != tuple(images_t.shape[1:]):
+            raise ValueError(f'{type(self).__name__}(style=): source and target tiles must have one size, got '
+                             f'{tuple(images_s.shape)} and {tuple(images_t.shape)}')
+        images_s = images_s.contiguous().float()
+        n, _, h, w = images_s.shape
+        m = images_t.shape[0]
+        table = torch.empty(n, ops.STYLE_TABLE_COLS, dtype=torch.int32, device=images_s.device)
+        if self._style_ws is None or self._style_ws[0] != (n, m, h, w):
+            self._style_ws = ((n, m, h, w), ops.fourier_style_workspace(n, m, h, w, images_s.device))
+        here = torch.cuda.current_stream()
+
+        def draw():
+            self.last_style = st.draw(n, m, h, w)
+            with ops.use_stream(here):      # (a replay runs host actions with the library's stream set to the plan's)
+                ops.fourier_style_write_table(table, self.last_style, m, (h, w))
+        plan.host(draw)
+        return ops.fourier_style(images_s, images_t.contiguous().float(), table, st.mean_s, st.std_s, st.mean_t, st.std_t,
+                                 ws=self._style_ws[1], flag=self.style_flag)
+
+    def _keep_source(self, source_s):
+        """keep_debug: the source tile as the network saw it, next to whatever the step kept"""
+        if self.keep_debug and self.style is not None:
+            self.debug = dict(self.debug or {}, source_s=source_s)
+
+    def style_flag_value(self):
+        """Deferred check of the style transfer's flag word (host sync): a table row outside the served range."""
+        return 0 if self.style_flag is None else int(self.style_flag.item())
 
     @staticmethod
     def _refuse_ssl_only(kw):
@@ -211,7 +256,7 @@ class FusedStep:
     def _state_parts(self):
         return [Part('model', self.model, check_module_state),      # loaded in place; re-syncs the bf16 mirrors
                 Part('class_balancer_s', self.class_balancer_s, check_module_state),
-                Part('loss_fn_s', self.loss_fn_s, check_module_state)]
+                Part('loss_fn_s', self.loss_fn_s, check_module_state), Part('style', self.style, check_generator)]
 
     def state_dict(self, rng=True):
         """Everything the run needs to continue with the bits of the uninterrupted one, as plain data (nested dicts and
