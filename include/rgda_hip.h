@@ -813,6 +813,36 @@ int rgda_augment_tiles(const uint8_t* img, const uint8_t* label, const float* so
                        const int32_t* label_lut, float* img_out, int64_t* label_out, float* soft_out, int64_t* regs_out,
                        int* flag, rgda_stream_t stream);
 
+/* Random scale and rotation of the same raw tiles: every plane of sample n is warped by ONE affine map, one launch per
+ * batch of one domain.  This project's own specification (the reference has no such transform), restated in integers
+ * by tests/affine_ref.py.  Inputs, outputs and tables as rgda_augment_tiles, except 1 <= C <= 16 (the soft planes are
+ * gathered, not staged) and Ho, Wo may exceed Hi, Wi (zooming out fills).
+ *   params int32 [N][8] (cy, cx, a00, a01, a10, a11, fill, 0) per sample, DEVICE memory; fill = r | g << 8 | b << 16.
+ * With u = 2i + 1 - Ho, v = 2j + 1 - Wo, output pixel (i, j) has the source coordinate, in 1/65536 pixel and int64,
+ *   Y = cy + a00 u + a01 v,  X = cx + a10 u + a11 v
+ * where a_kl = round(M_kl * 32768) for the output-to-source linear map M in centred coordinates and
+ * cy = round((y0 + Ho/2) * 65536) is the crop's centre in the raw tile (pixel centre k at k + 0.5; cx likewise).
+ *   image:   Yp = Y - 32768, y = Yp >> 16 (arithmetic), fy = (Yp & 0xFFFF) >> 8; x, fx likewise from X;
+ *            byte = ((256-fx)(256-fy) p00 + fx (256-fy) p01 + (256-fx) fy p10 + fx fy p11 + 32768) >> 16 per channel with
+ *            p00 = img[y][x], p01 = img[y][x+1], p10 = img[y+1][x], p11 = img[y+1][x+1]; a tap outside the input is the
+ *            channel's fill byte; img_out = lut[channel][byte].  No floating-point arithmetic.
+ *   label:   label_lut[label[Y >> 16][X >> 16]]; outside the input, ignore_label (not through the table).
+ *   regions: regs[Y >> 16][X >> 16] widened; outside the input, 0 ("no region", which LRH leaves alone).
+ *   soft:    the image's taps and weights in f32, (w00 p00 + w01 p01 + w10 p10 + w11 p11) * 2^-16 summed in that order; a
+ *            tap outside contributes 0, so an out-of-frame pixel is all zero and pseudo_selection never selects it.
+ * A row whose M is a signed permutation with an integer crop has fx = fy = 0 everywhere and gives rgda_augment_tiles'
+ * outputs for the matching (y0, x0, d) bit for bit.  No atomics.  Errors before any launch: null img / params / lut /
+ * img_out, a size below 1, a label without label_lut / label_out, soft with C < 1 or without soft_out, regs without
+ * regs_out, a misaligned input (RGDA_ERR_ARG); Hi or Wi above 16384, Ho or Wo above 8192, C > 16, N > 65535 (one grid row
+ * per sample) (RGDA_ERR_UNSUPPORTED).  Checked on the device, per row: |a_kl| <= 131072 (a scale inside [1/4, 4]), cy in
+ * [0, Hi * 65536], cx in [0, Wi * 65536], column 7 zero, fill below 2^24; the outputs of a row that fails are not
+ * written and *flag (optional, device int) is set to 1.  Every tap is bounds-checked, so no row reads outside the
+ * input. */
+int rgda_augment_affine(const uint8_t* img, const uint8_t* label, const float* soft, const int32_t* regs,
+                        const int32_t* params, int N, int Hi, int Wi, int C, int Ho, int Wo, const float* lut,
+                        const int32_t* label_lut, int ignore_label, float* img_out, int64_t* label_out, float* soft_out,
+                        int64_t* regs_out, int* flag, rgda_stream_t stream);
+
 /* ------------------------------------------------------------- cross-domain mixing */
 
 /* ClassMix and CutMix across the domains (regda/utils/classmix.py:17-53, regda/utils/cutmix.py:15-31): the pixels of the

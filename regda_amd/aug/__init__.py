@@ -2,12 +2,15 @@
 
 augmentation: the reference's regda/aug/augmentation.py (target domain, `st.regda.*` TARGET_DATA_CONFIG);
 albu: the albumentations pipeline of the source domain and evaluation (configs/To*.py).
-`from_config(data_config)` builds the right one from the declarative transform lists of configs/."""
+`from_config(data_config)` builds the right one from the declarative transform lists of configs/.  Random scale and
+rotation (`RandomScaleRotate`, albu's `ShiftScaleRotate`; `rgda_augment_affine`, DESIGN.md 4.2h.1) are this project's
+addition: a list entry `('RandomScaleRotate', dict(scale=(0.5, 2.0), degrees=15, prob=0.5))`."""
 from . import albu, augmentation
 
-_MAG = {'RandomCrop', 'RandomHorizontalFlip', 'RandomVerticalFlip', 'RandomRotate90', 'Normalize'}
-_ALBU = {'RandomCrop', 'OneOf', 'HorizontalFlip', 'VerticalFlip', 'RandomRotate90', 'Normalize', 'ToTensor'}
-_ALBU_ONLY = {'OneOf', 'HorizontalFlip', 'VerticalFlip', 'ToTensor'}
+_MAG = {'RandomCrop', 'RandomHorizontalFlip', 'RandomVerticalFlip', 'RandomRotate90', 'RandomScaleRotate', 'Normalize'}
+_ALBU = {'RandomCrop', 'OneOf', 'HorizontalFlip', 'VerticalFlip', 'RandomRotate90', 'ShiftScaleRotate', 'Normalize',
+         'ToTensor'}
+_ALBU_ONLY = {'OneOf', 'HorizontalFlip', 'VerticalFlip', 'ShiftScaleRotate', 'ToTensor'}
 
 
 def _is_albu(transforms):
@@ -55,6 +58,8 @@ def from_config(data_config, rng=None, generator=None, offset=0, num_class=6, ig
                 out.append(albu.Normalize(**t[1], always_apply=True))
             elif name == 'ToTensor':
                 out.append(albu.ToTensor())
+            elif name == 'ShiftScaleRotate':
+                out.append(albu.ShiftScaleRotate(**t[1]))
             else:
                 out.append(one(name))
         return albu.Compose(out, rng=rng, **lab)
@@ -65,6 +70,8 @@ def from_config(data_config, rng=None, generator=None, offset=0, num_class=6, ig
             raise ValueError('unknown transform %r' % (name,))
         if name == 'Normalize':
             out.append(augmentation.Normalize(**t[1]))
+        elif name == 'RandomScaleRotate':
+            out.append(augmentation.RandomScaleRotate(**t[1]))
         else:
             out.append(getattr(augmentation, name)(t[1]))
     return augmentation.Compose(out, rng=rng, generator=generator, **lab)

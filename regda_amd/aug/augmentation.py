@@ -59,10 +59,24 @@ def identity_table():
     return torch.arange(256, dtype=torch.float32).expand(3, 256).contiguous()
 
 
+def affine_row(y0, x0, m, b, ho, wo, h, w, fill=(0, 0, 0)):
+    """One row (cy, cx, a00, a01, a10, a11, fill, 0) of rgda_augment_affine's table: the crop at (y0, x0) of an h x w tile,
+    the output-to-source map p -> m p + b in the crop's centred coordinates (b in pixels), the fill colour.  A centre
+    that b moves off the tile is clamped to its edge."""
+    cy = min(max((2 * y0 + ho) * 32768 + int(round(float(b[0]) * 65536)), 0), h * 65536)
+    cx = min(max((2 * x0 + wo) * 32768 + int(round(float(b[1]) * 65536)), 0), w * 65536)
+    a = [int(round(float(v) * 32768)) for v in (m[0][0], m[0][1], m[1][0], m[1][1])]
+    return [cy, cx] + a + [int(fill[0]) | int(fill[1]) << 8 | int(fill[2]) << 16, 0]
+
+
 class _Pipeline:
-    """Crop size, composed dihedral draws and the two tables of one pipeline; the launch is shared by both pipelines.
-    Subclasses implement `sample(h, w) -> (y0, x0, d)` and `table()`; `crop` is the output size (None: the input's)."""
+    """Crop size, composed geometric draws and the two tables of one pipeline; the launch is shared by both pipelines.
+    Subclasses implement `sample(h, w) -> (y0, x0, d)` and `table()`; `crop` is the output size (None: the input's).
+    A pipeline that holds a scale / rotation transform (`affine`) implements `sample_affine(h, w) -> (y0, x0, m, b)`
+    instead, has `param_cols = 8` and launches rgda_augment_affine."""
     crop = None
+    affine = None
+    param_cols = 4
 
     def __init__(self, offset=0, num_class=6, ignore_label=-1):
         self.offset, self.num_class, self.ignore_label = offset, num_class, ignore_label
@@ -82,16 +96,38 @@ class _Pipeline:
         return tuple(self.crop) if self.crop is not None else (h, w)
 
     def params(self, n, h, w):
-        """int32 [n][4] (y0, x0, d, 0): the draws of n consecutive samples of h x w inputs, in order."""
+        """int32 [n][4] (y0, x0, d, 0): the draws of n consecutive samples of h x w inputs, in order.  With a scale /
+        rotation transform: int32 [n][8] (cy, cx, a00, a01, a10, a11, fill, 0), the rows of rgda_augment_affine."""
+        if self.param_cols == 8:
+            ho, wo = self.out_size(h, w)
+            rows = []
+            for i in range(n):
+                y0, x0, m, b = self.sample_affine(h, w)
+                rows.append(affine_row(y0, x0, m, b, ho, wo, h, w, self.affine.fill))
+            return torch.tensor(rows, dtype=torch.int32)
         p = torch.zeros(n, 4, dtype=torch.int32)
         for i in range(n):
             p[i, :3] = torch.tensor(self.sample(h, w), dtype=torch.int32)
         return p
 
+    def check_params(self, params, h, w):
+        """Host-side check of a CPU table of `params()` for h x w inputs; raises ValueError."""
+        if self.param_cols == 8:
+            ops.check_affine_params(params, h, w)
+        else:
+            ops.check_augment_params(params, h, w, *self.out_size(h, w))
+
+    def launch(self, img, params, lut, size, label=None, label_lut=None, soft=None, regs=None, out=None):
+        """The pipeline's one launch on device tensors: rgda_augment_tiles, or rgda_augment_affine for [N][8] rows."""
+        if self.param_cols == 8:
+            return ops.augment_affine(img, params, lut, size, label=label, label_lut=label_lut,
+                                      ignore_label=self.ignore_label, soft=soft, regs=regs, out=out)
+        return ops.augment_tiles(img, params, lut, size, label=label, label_lut=label_lut, soft=soft, regs=regs, out=out)
+
     def batch(self, images_u8, mask=None, soft=None, mask_sup=None, out=None, params=None):
         """images_u8 uint8 [N][H][W][3]; mask uint8 [N][H][W] class labels (through the label table); soft f32
         [N][C][H][W]; mask_sup int32 [N][H][W] region ids.  Tensors on the host are copied to the current device.
-        Draws each sample's parameters in order (or takes `params`, int32 [N][4]) and issues one launch.
+        Draws each sample's parameters in order (or takes `params`, int32 [N][param_cols]) and issues one launch.
         -> {'image': f32 [N][3][Ho][Wo], 'mask': int64 [N][Ho][Wo], 'soft': f32 [N][C][Ho][Wo],
             'mask_sup': int64 [N][1][Ho][Wo]} (None where the input is None)."""
         dev = torch.device('cuda', torch.cuda.current_device())
@@ -104,8 +140,7 @@ class _Pipeline:
         lut, llut = self.device_tables(images_u8.device)
         names = dict(image='image', label='mask', soft='soft', regs='mask_sup')
         o = None if out is None else {k: out.get(v) for k, v in names.items()}
-        r = ops.augment_tiles(images_u8, params, lut, (ho, wo), label=mask, label_lut=llut, soft=soft, regs=mask_sup,
-                              out=o)
+        r = self.launch(images_u8, params, lut, (ho, wo), label=mask, label_lut=llut, soft=soft, regs=mask_sup, out=o)
         return {v: r[k] for k, v in names.items()}
 
     def __call__(self, image, mask=None, mask_sup=None):
@@ -179,11 +214,44 @@ class Normalize:
         return v.contiguous()
 
 
+class RandomScaleRotate:
+    """Random rescaling and rotation about the crop's centre (this project's own transform; rgda_augment_affine).  With
+    probability `prob` the crop is magnified by s, uniform in scale = (lo, hi), and turned by theta, uniform in
+    [-degrees, degrees]: the output-to-source matrix is (1/s) [[cos, -sin], [sin, cos]] on centred (row, column)
+    coordinates.  Pixels whose source lies outside the raw tile take `fill` (r, g, b bytes), the ignore label, region 0
+    and an all-zero soft label."""
+
+    def __init__(self, scale=(1.0, 1.0), degrees=0.0, prob=0.5, fill=(0, 0, 0)):
+        lo, hi = scale
+        if not 0.25 <= lo <= hi <= 4:
+            raise ValueError('RandomScaleRotate: scale=(lo, hi) needs 0.25 <= lo <= hi <= 4, got %r' % (scale,))
+        if not 0 <= degrees <= 180:
+            raise ValueError('RandomScaleRotate: degrees must lie in [0, 180], got %r' % (degrees,))
+        if len(fill) != 3 or any(int(v) != v or not 0 <= v <= 255 for v in fill):
+            raise ValueError('RandomScaleRotate: fill is three bytes (r, g, b), got %r' % (fill,))
+        self.scale, self.degrees, self.prob, self.fill = (lo, hi), degrees, prob, tuple(int(v) for v in fill)
+
+    def draw(self, rng):
+        """Three draws whatever the coin says (the coin, s, theta) -> the 2 x 2 matrix, or None when the coin fails."""
+        coin, s, theta = rng.random(), rng.uniform(*self.scale), rng.uniform(-self.degrees, self.degrees)
+        if coin >= self.prob:
+            return None
+        return rotation(s, theta)
+
+
+def rotation(s, theta):
+    """(1/s) [[cos, -sin], [sin, cos]], theta in degrees: the output-to-source matrix of a magnification by s and a turn
+    by theta."""
+    c, sn = np.cos(np.deg2rad(theta)), np.sin(np.deg2rad(theta))
+    return np.array([[c, -sn], [sn, c]]) / s
+
+
 _GEOM = (RandomHorizontalFlip, RandomVerticalFlip, RandomRotate90)
 
 
 class Compose(_Pipeline):
-    """Compose([RandomCrop?, flips / rotation..., Normalize?]) of the reference (mag) pipeline.
+    """Compose([RandomCrop?, flips / rotation..., Normalize?]) of the reference (mag) pipeline; at most one
+    RandomScaleRotate among the flips.
     rng: random.Random for the flip / rotation draws (default: the `random` module); generator: torch.Generator for
     the crop (default: torch's global generator).  offset / num_class / ignore_label: the label table (IsprsDA's)."""
 
@@ -198,12 +266,18 @@ class Compose(_Pipeline):
                 raise ValueError('RandomCrop must come first')
             if isinstance(t, Normalize) and i != len(self.transforms) - 1:
                 raise ValueError('Normalize must come last')
-            if not isinstance(t, (RandomCrop, Normalize) + _GEOM):
+            if not isinstance(t, (RandomCrop, Normalize, RandomScaleRotate) + _GEOM):
                 raise ValueError('unsupported transform %r' % (t,))
         self.crop = tuple(self.transforms[0].size) if kinds and kinds[0] is RandomCrop else None
         self.norm = self.transforms[-1] if kinds and kinds[-1] is Normalize else None
+        warps = [t for t in self.transforms if isinstance(t, RandomScaleRotate)]
+        if len(warps) > 1:
+            raise ValueError('at most one RandomScaleRotate')
+        if warps:
+            self.affine, self.param_cols = warps[0], 8
 
-    def sample(self, h, w):
+    def sample_affine(self, h, w):
+        """-> (y0, x0, m, b): the crop origin and the composed output-to-source map p -> m p + b (b = 0 here)."""
         y0 = x0 = 0
         m = IDENTITY
         for t in self.transforms:
@@ -212,6 +286,14 @@ class Compose(_Pipeline):
             elif isinstance(t, _GEOM):
                 if self.rng.random() < t.prob:
                     m = m @ t.m
+            elif isinstance(t, RandomScaleRotate):
+                mt = t.draw(self.rng)
+                if mt is not None:
+                    m = m @ mt
+        return y0, x0, m, (0.0, 0.0)
+
+    def sample(self, h, w):
+        y0, x0, m, _ = self.sample_affine(h, w)
         return y0, x0, code(m)
 
     def table(self):

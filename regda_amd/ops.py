@@ -1329,6 +1329,69 @@ def augment_tiles(img, params, lut, size, label=None, label_lut=None, soft=None,
     return res
 
 
+AFFINE_A_MAX = 131072           # |a_kl| <= 4 * 32768: rgda_augment_affine takes scales inside [1/4, 4]
+
+
+def check_affine_params(params, hi, wi):
+    """Host-side check of a CPU int32 [N][8] (cy, cx, a00, a01, a10, a11, fill, 0) table, the device-side row check of
+    rgda_augment_affine: |a_kl| <= 131072, the centre inside [0, hi * 65536] x [0, wi * 65536], fill below 2^24 and
+    column 7 zero.  Raises ValueError."""
+    p = params.numpy()
+    if p.ndim != 2 or p.shape[1] != 8:
+        raise ValueError('affine params must be [N][8], got %s' % (tuple(p.shape),))
+    if (abs(p[:, 2:6].astype('int64')) > AFFINE_A_MAX).any():
+        raise ValueError('affine matrix entry outside +-%d (a scale outside [1/4, 4])' % AFFINE_A_MAX)
+    if (p[:, 0] < 0).any() or (p[:, 0] > hi * 65536).any() or (p[:, 1] < 0).any() or (p[:, 1] > wi * 65536).any():
+        raise ValueError('affine crop centre outside the %d x %d input' % (hi, wi))
+    if (p[:, 6] < 0).any() or (p[:, 6] >> 24).any() or (p[:, 7] != 0).any():
+        raise ValueError('affine fill must be r | g << 8 | b << 16 and column 7 zero')
+
+
+def augment_affine(img, params, lut, size, label=None, label_lut=None, ignore_label=-1, soft=None, regs=None, out=None,
+                   flag=None):
+    """rgda_augment_affine: one affine warp per sample (random scale / rotation) + normalisation / label tables of N raw
+    tiles, one launch.  Arguments as augment_tiles, except params int32 [N][8] (cy, cx, a00, a01, a10, a11, fill, 0) (a
+    CPU tensor is checked by check_affine_params), up to 16 soft planes, a size that may exceed the input, and
+    ignore_label: the label of a pixel whose source lies outside the input (its regions are 0, its soft label all 0,
+    its image the fill colour).
+    -> {'image': f32 [N][3][Ho][Wo], 'label': int64 [N][Ho][Wo], 'soft': f32 [N][C][Ho][Wo], 'regs': int64 [N][1][Ho][Wo]}
+    (None where the input is None)."""
+    _need_cuda(img, label, soft, regs, lut, label_lut)
+    n, hi, wi, three = img.shape
+    ho, wo = size
+    if three != 3 or img.dtype != torch.uint8:
+        raise ValueError('augment_affine: img must be uint8 [N][H][W][3]')
+    want = dict(label=(label, torch.uint8, (n, hi, wi)), regs=(regs, torch.int32, (n, hi, wi)),
+                soft=(soft, torch.float32, (n, soft.shape[1] if soft is not None else 0, hi, wi)))
+    for k, (t, dt, shape) in want.items():
+        if t is not None and (t.dtype != dt or tuple(t.shape) != shape):
+            raise ValueError('augment_affine: %s must be %s %s, got %s %s' % (k, dt, shape, t.dtype, tuple(t.shape)))
+    if label is not None and label_lut is None:
+        raise ValueError('augment_affine: a label needs label_lut')
+    if not params.is_cuda:
+        check_affine_params(params, hi, wi)
+        params = params.to(img.device, torch.int32, non_blocking=True)
+    assert params.dtype == torch.int32 and tuple(params.shape) == (n, 8)
+    c = soft.shape[1] if soft is not None else 0
+    shapes = dict(image=((n, 3, ho, wo), torch.float32, img), label=((n, ho, wo), torch.int64, label),
+                  soft=((n, c, ho, wo), torch.float32, soft), regs=((n, 1, ho, wo), torch.int64, regs))
+    res = {}
+    for k, (shape, dt, src) in shapes.items():
+        t = None if out is None else out.get(k)
+        if src is None:
+            res[k] = None
+            continue
+        if t is None:
+            t = torch.empty(shape, dtype=dt, device=img.device)
+        assert tuple(t.shape) == shape and t.dtype == dt and t.is_contiguous(), k
+        res[k] = t
+    ptr = lambda t: None if t is None else t.contiguous().data_ptr()
+    lib().call('rgda_augment_affine', ptr(img), ptr(label), ptr(soft), ptr(regs), ptr(params), n, hi, wi, c, ho, wo,
+               ptr(lut), ptr(label_lut), int(ignore_label), ptr(res['image']), ptr(res['label']), ptr(res['soft']),
+               ptr(res['regs']), ptr(flag), _stream())
+    return res
+
+
 # ----------------------------------------------------------------------------- cross-domain mixing
 MIX_CLASS, MIX_BOX = 0, 1       # rgda_mix_mode (include/rgda_hip.h)
 MIX_MAX_CLASSES = 32            # one bit of class_bits per class

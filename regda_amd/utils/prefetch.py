@@ -74,7 +74,7 @@ class DevicePrefetcher:
                 raw['sup_count'] = torch.empty((n,), dtype=torch.int32, device=self.device)
                 regions.reserve(n, h, w, self.device)
             tables = pipe.device_tables(self.device)
-            prm = torch.empty(n, 4, dtype=torch.int32, device=self.device)
+            prm = torch.empty(n, pipe.param_cols, dtype=torch.int32, device=self.device)
             self.augment.append((pipe, roles, raw, tables, prm, gen))
         if into is not None:
             depth = 1
@@ -153,7 +153,7 @@ class DevicePrefetcher:
                     done.add(gen)
                 n, h, w, _ = raw['image'].shape
                 p = pipe.params(n, h, w)
-                ops.check_augment_params(p, h, w, *pipe.out_size(h, w))
+                pipe.check_params(p, h, w)
                 prm.copy_(p.pin_memory(), non_blocking=True)
             if self.consumed[slot] is not None:
                 self.copy_stream.wait_event(self.consumed[slot])
@@ -164,8 +164,8 @@ class DevicePrefetcher:
             for pipe, roles, raw, (lut, llut), prm, gen in self.augment:
                 out = {'image': dst[roles['image']], 'label': dst.get(roles.get('mask')), 'soft': dst.get(roles.get('soft')),
                        'regs': dst.get(roles.get('mask_sup', gen))}
-                ops.augment_tiles(raw['image'], prm, lut, tuple(out['image'].shape[2:]), label=raw.get('mask'),
-                                  label_lut=llut, soft=raw.get('soft'), regs=raw.get('mask_sup'), out=out)
+                pipe.launch(raw['image'], prm, lut, tuple(out['image'].shape[2:]), label=raw.get('mask'),
+                            label_lut=llut, soft=raw.get('soft'), regs=raw.get('mask_sup'), out=out)
             self._mix(slot)
             self.copied[slot] = self.copy_stream.record_event()
 

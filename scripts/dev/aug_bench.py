@@ -2,8 +2,11 @@
 crops: HIP-event time per batch (source: image + label; target: image + region map, and + soft labels offline),
 algorithmic bytes and their share of the 8 TB/s peak, bytes staged raw against prepared, the torch CPU restatement's
 time per target tile, and the step time of a recorded SSLStep fed by DevicePrefetcher(augment=...) against resident
-inputs, alternated.
-    python scripts/dev/aug_bench.py [--no-step] [--size 512] [--input 512]"""
+inputs, alternated.  --affine: rgda_augment_affine against rgda_augment_tiles on the same inputs,
+alternated, at 512 -> 512 and 1024 -> 512: dihedral rows (the same work as rgda_augment_tiles) and drawn scale /
+rotation rows.
+    python scripts/dev/aug_bench.py [--no-step] [--size 512] [--input 512]
+    python scripts/dev/aug_bench.py --affine"""
 import argparse
 import os
 import random
@@ -77,6 +80,45 @@ def kernel(b, size, hw):
               ' (%4.1f %% of peak, %.2f TB/s)  staged raw %.1f MB vs prepared %.1f MB' % (
                   'offline' if offline else 'online', b, b, hw, size, t, nb / 1e6, nb / PEAK * 1e6,
                   100 * nb / PEAK * 1e6 / t, nb / t / 1e6, staged_raw / 1e6, staged_prep / 1e6), flush=True)
+
+
+def affine(b, size, hw, rounds=5):
+    """One 8 + 8 batch (source: image + label; target: image + soft labels + region map), three tables over the same
+    crops: rgda_augment_tiles' (y0, x0, d), the same rows through rgda_augment_affine, and RandomScaleRotate's draws
+    (scale 0.5 - 2, +-30 degrees, every coin fires).  The launches alternate inside every round; the median round
+    counts.  Bytes: each output pixel once (the dihedral kernel's count), so the warped rows' taps come on top."""
+    ps, pt = pipes(size)
+    raw = {k: v.cuda() for k, v in raw_batch(b, hw).items()}
+    (ls, lls), (lt, llt) = ps.device_tables('cuda'), pt.device_tables('cuda')
+    tile_s, tile_t = ps.params(b, hw, hw), pt.params(b, hw, hw)
+    rows = lambda t, m=None: torch.tensor([A.affine_row(y0, x0, A.matrix(d) if m is None else m(), (0, 0), size, size,
+                                                         hw, hw) for y0, x0, d, _ in t.tolist()], dtype=torch.int32).cuda()
+    rng = random.Random(2)
+    warp = lambda: A.rotation(rng.uniform(0.5, 2.0), rng.uniform(-30, 30))
+    tabs = {'tiles': (tile_s.cuda(), tile_t.cuda()), 'affine, dihedral rows': (rows(tile_s), rows(tile_t)),
+            'affine, scale 0.5-2 +-30 deg': (rows(tile_s, warp), rows(tile_t, warp))}
+    c = raw['soft_t'].shape[1]
+
+    def run(name):
+        prm_s, prm_t = tabs[name]
+        if name == 'tiles':
+            ops.augment_tiles(raw['images_s'], prm_s, ls, (size, size), label=raw['label_s'], label_lut=lls)
+            ops.augment_tiles(raw['images_t'], prm_t, lt, (size, size), soft=raw['soft_t'], regs=raw['regs_t'])
+        else:
+            ops.augment_affine(raw['images_s'], prm_s, ls, (size, size), label=raw['label_s'], label_lut=lls)
+            ops.augment_affine(raw['images_t'], prm_t, lt, (size, size), soft=raw['soft_t'], regs=raw['regs_t'])
+    times = {k: [] for k in tabs}
+    for _ in range(rounds):
+        for name in tabs:
+            times[name].append(t_of(lambda: run(name), reps=100))
+    px = b * size * size
+    nb = px * (3 + 1 + 12 + 8) + px * (3 + 4 + 4 * c + 12 + 8 + 4 * c)
+    for name, v in times.items():
+        v = sorted(v)
+        med = v[len(v) // 2]
+        print('%d + %d x %d^2 -> %d  %-30s %6.1f us per batch (min %.1f, max %.1f; 2 launches)  %.1f MB, floor %.1f us at '
+              '8 TB/s: %4.1f %% of peak' % (b, b, hw, size, name, med, v[0], v[-1], nb / 1e6, nb / PEAK * 1e6,
+                                            100 * nb / PEAK * 1e6 / med), flush=True)
 
 
 def cpu_restatement(size, threads=16):
@@ -169,7 +211,12 @@ if __name__ == '__main__':
     ap.add_argument('--no-step', action='store_true')
     ap.add_argument('--no-cpu', action='store_true')
     ap.add_argument('--kernel-only', action='store_true')
+    ap.add_argument('--affine', action='store_true')
     a = ap.parse_args()
+    if a.affine:
+        for hw in (512, 1024):
+            affine(a.batch, 512, hw)
+        sys.exit(0)
     kernel(a.batch, a.size, a.input)
     if a.kernel_only:
         sys.exit(0)
