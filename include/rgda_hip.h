@@ -268,6 +268,38 @@ int rgda_upsample_reg(int heads, const float* p1, const float* p2, const int64_t
                       int empty_is_zero, float* loss, float* g1, float* g2, int b, int c, int h, int w, int H, int W,
                       int ignore_label, void* ws, size_t ws_bytes, rgda_stream_t stream);
 
+/* PyCDA region pyramid term (Lian et al., ICCV 2019, "Constructing Self-motivated Pyramid Curriculums"): at every level of
+ * a pyramid of square regions the student's mean prediction over a region must match the teacher's label distribution
+ * of that region.  Forward + d / d(logits) on the upsample-loss pipeline.  The reference has no such code; this is the
+ * contract (restated in float64 by tests/pycda_ref.py).
+ * Inputs: p1, p2 student logits NCHW f32 (b,c,h,w); soft teacher probabilities NCHW f32 (b,c,H,W), every value finite
+ *   and in [0, 1]: a value outside is clamped into it, NaN counts as 0, and either raises bit 0 of *flag (device int32,
+ *   may be NULL; never cleared here).
+ * Levels: sizes, a HOST int array of `levels` entries (1 <= levels <= 6), read during the call: finite sizes are powers
+ *   of two in [2, 256], strictly increasing, optionally followed by one 0 = the whole image; so every coarser region is
+ *   a union of whole cells of the finest level.  At size s image n is cut into ceil(H/s) x ceil(W/s) squares anchored at
+ *   (0, 0), border squares clipped; |r| is a region's real pixel count.
+ * Targets (exact integers): Tfix_r(c) = sum_{i in r} rint(soft_i(c) * 2^24) as int64; class c is active in r iff
+ *   Tfix_r(c) > rint(thresh * 2^24) * |r| (strict, in integers; 0 <= thresh <= 1); T_r(c) = Tfix_r(c) / (|r| * 2^24);
+ *   n_l = the regions of level l, over the batch, with at least one active class.
+ * Predictions: per head q = softmax of the logits upsampled bilinearly (align_corners=True, the arithmetic of
+ *   rgda_upsample_ce); Q_r(c) = mean_{i in r} q_i(c).
+ * Loss: L_{l,hd} = sum_{r, active c} -T_r(c) log(Q_r(c) + 1e-7) / max(n_l, 1); level[l] = the mean of L_{l,hd} over the
+ *   heads; total = sum_l level_weight[l] * level[l].  level_weight: a HOST f32 array of `levels` entries, or NULL = 1 /
+ *   levels each.  A level without an active region is exactly 0 with a gradient of exactly 0.  Targets carry no gradient.
+ * Outputs: loss f32[1 + levels] = total, then the levels, all unscaled; n_active int32[levels]; g1, g2: NULL or NCHW f32
+ *   (b,c,h,w), per head the gradient of 0.5 * weight * total_hd; heads 1: p2 == p1, g1 + g2 is the gradient, no 0.5 (the
+ *   convention of rgda_upsample_reg).  accumulate 0: written, 1: added onto what they hold (one f32 addition of the
+ *   finished value).
+ * Limits: 6 <= c <= 16 and the row-LDS limit of rgda_upsample_ce, with gradients (RGDA_ERR_UNSUPPORTED); b * H * W <
+ *   2^31; b <= 65535.  ws: rgda_upsample_pycda_workspace bytes (0 = bad arguments).  Every check comes before anything
+ *   touches the GPU.  Deterministic: no float atomics, every sum in a fixed order or in integers; nothing is read back. */
+size_t rgda_upsample_pycda_workspace(int b, int c, int h, int w, int H, int W, const int* sizes, int levels);
+int rgda_upsample_pycda(int heads, const float* p1, const float* p2, const float* soft, const int* sizes,
+                        const float* level_weight, int levels, double thresh, float weight, int accumulate, float* loss,
+                        int* n_active, float* g1, float* g2, int* flag, int b, int c, int h, int w, int H, int W, void* ws,
+                        size_t ws_bytes, rgda_stream_t stream);
+
 /* IAST, instance-adaptive pseudo-labels: ias_thresh and the loop body of generate_pseudo   regda/utils/tools.py:323-373
  * Three stages over one workspace of rgda_iast_workspace(n, c, H, W) bytes (0 = bad arguments), laid out as
  *   int32 hist[c][RGDA_IAST_BINS] | f32 maxp[n*H*W] | uint8 arg[n*H*W], each piece starting on a 256-byte boundary.

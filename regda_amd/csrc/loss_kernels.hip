@@ -25,6 +25,7 @@
 // IAST's entropy / KLD region regularisers (rgda_upsample_reg; regda/utils/tools.py:376-398) are a row pass of their own
 // on the same staging, contraction and reduction, behind a count pass for their two denominators (at the end of this file).
 #include "common.h"
+#include <cmath>
 
 namespace {
 
@@ -866,6 +867,394 @@ static int run_reg(const RegCall& a, rgda_stream_t stream) {
     return RGDA_OK;
 }
 
+// ------------------------------------------------------------------------ PyCDA region pyramid term (rgda_upsample_pycda)
+// The student's mean prediction over every square region of a pyramid must match the teacher's label distribution of
+// that region (the contract: include/rgda_hip.h).  Every level's regions are unions of whole base cells, squares of
+// min(sizes[0], 8) pixels, so the per-pixel work happens once and the pyramid is sums of cells:
+//   cell     one workgroup per band of base-cell rows and 256 columns: q = softmax(upsampled logits) per head and the
+//            clamped soft label in 2^24 fixed point, summed over each cell's pixels: across the cell's lanes by DPP, down
+//            its rows in the registers of the cell's owner lane, written once with plain stores
+//   pyramid  one launch per step of the chain base -> sizes[...] -> image (steps of at most x4, so a region sums at most 16
+//            children, in row-major order, one thread per sum): f64 sums of q, int64 sums of the targets
+//   count    n_l, the regions with an active class: integer compares, integer atomics
+//   coef     per (region, head, class): the loss term and a = -w_l T / (max(n_l, 1) |r| (Q + 1e-7)), both in f64;
+//            per-workgroup loss partials by a fixed tree
+//   push     A[cell][head][class] = sum_l a_l[the cell's region], levels in order
+//   reduce   the partials in a fixed order -> loss[1 + L]
+//   grad     the row pass again: dz_k = q_k (A_k - sum_c A_c q_c) * 0.5 weight, contracted horizontally; col as above.
+// No float atomics; nothing is read back.
+constexpr int PY_MAX_LEVELS = 6;
+constexpr int PY_MAX_CHAIN = 24;          // base, <= 6 sizes, the x4 steps between them up to an image side of 2^30
+constexpr double PY_FIX = 16777216.0;     // 2^24
+constexpr double PY_EPS = 1e-7;
+
+struct PyGeom {
+    int b, H, W, nk, L;
+    int size[PY_MAX_CHAIN], ry[PY_MAX_CHAIN], rx[PY_MAX_CHAIN];     // the chain: side, regions down and across one image
+    long long off[PY_MAX_CHAIN];          // first region of the chain level in lvq / lvt
+    int map[PY_MAX_LEVELS];               // level l of the caller -> chain index
+    long long coff[PY_MAX_LEVELS];        // first region of level l in coef
+    float lw[PY_MAX_LEVELS];
+    long long thr_fix;                    // rint(thresh * 2^24)
+};
+
+// pixels of region (ry, rx) of a level of side s: border squares are clipped
+__device__ __forceinline__ long long py_area(int s, int ry, int rx, int H, int W) {
+    const long long y0 = (long long)ry * s, x0 = (long long)rx * s;
+    const long long y1 = min(y0 + s, (long long)H), x1 = min(x0 + s, (long long)W);
+    return (y1 - y0) * (x1 - x0);
+}
+
+// v summed over the aligned group of S = 2 / 4 / 8 lanes, the same bits in every lane of the group (f32 and integer
+// addition commute): quad permutes, then the mirror of each half row
+template <int CTRL>
+__device__ __forceinline__ float dpp_f(float v) {
+    return __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), CTRL, 0xf, 0xf, false));
+}
+template <int CTRL>
+__device__ __forceinline__ int dpp_i(int v) {
+    return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false);
+}
+__device__ __forceinline__ float group_sum(float v, int S) {
+    v += dpp_f<0xB1>(v);                  // quad_perm [1, 0, 3, 2]
+    if (S >= 4) v += dpp_f<0x4E>(v);      // quad_perm [2, 3, 0, 1]
+    if (S >= 8) v += dpp_f<0x141>(v);     // row_half_mirror
+    return v;
+}
+__device__ __forceinline__ int group_sum(int v, int S) {
+    v += dpp_i<0xB1>(v);
+    if (S >= 4) v += dpp_i<0x4E>(v);
+    if (S >= 8) v += dpp_i<0x141>(v);
+    return v;
+}
+
+// one workgroup per (band of S rows, image, chunk of 256 columns); a cell's sums live in the registers of its owner lane
+template <int C>
+__global__ void __launch_bounds__(256) pycda_cell_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
+                                                         const float* __restrict__ soft, double* __restrict__ lvq,
+                                                         long long* __restrict__ lvt, int* flag, int* n_active,
+                                                         int levels, int h, int w, int H, int W, int S, int ncx) {
+    extern __shared__ float rows[];
+    // the counters of the count pass, which runs behind this one
+    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x < levels) n_active[threadIdx.x] = 0;
+    const int band = blockIdx.x, b = blockIdx.y;
+    const int X = blockIdx.z * 256 + threadIdx.x;
+    const bool in = X < W;
+    const bool owner = (threadIdx.x & (S - 1)) == 0;      // 256 % S == 0: X % S == threadIdx.x % S
+    const Lerp lx = lerp_ac(in ? X : W - 1, w, W);
+    float accq[2][C];
+    long long acct[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) accq[0][c] = accq[1][c] = 0.f, acct[c] = 0;
+    bool bad = false;
+    for (int r = 0; r < S; ++r) {
+        const int Y = band * S + r;
+        if (Y >= H) break;
+        const Lerp ly = row_lerp<false>(Y, h, H);
+        __syncthreads();                  // the row before is consumed
+        stage_rows<C>(rows, p1, p2, b, ly.i0, ly.i1, h, w);
+        __syncthreads();
+        const float* sp = soft + (((size_t)b * C) * H + Y) * W + (in ? X : 0);
+        // every lane of a cell takes part in its sum: lanes past the row's end add 0
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            int t = 0;
+            if (in) {
+                const float s = sp[(size_t)c * H * W];
+                bad |= !(s >= 0.f && s <= 1.f);
+                t = (int)rintf(__fmul_rn(fminf(fmaxf(s, 0.f), 1.f), 16777216.f));      // fmaxf(NaN, 0) = 0
+            }
+            acct[c] += group_sum(t, S);
+        }
+#pragma unroll
+        for (int hd = 0; hd < 2; ++hd) {
+            float m, e[C], se, zl;
+            up_softmax<C>(rows, w, hd, ly, lx, 0, m, e, se, zl);
+#pragma unroll
+            for (int c = 0; c < C; ++c) accq[hd][c] += group_sum(in ? e[c] / se : 0.f, S);
+        }
+    }
+    if (bad && flag) atomicOr(flag, 1);
+    if (!(owner && in)) return;
+    const size_t cell = ((size_t)b * gridDim.x + band) * ncx + X / S;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        lvq[cell * 2 * C + c] = (double)accq[0][c];
+        lvq[cell * 2 * C + C + c] = (double)accq[1][c];
+        lvt[cell * C + c] = acct[c];
+    }
+}
+
+// chain level k from k - 1: one thread per (region, value), value = 2 C sums of q, then C sums of the targets
+__global__ void __launch_bounds__(256) pycda_pyramid_kernel(double* __restrict__ lvq, long long* __restrict__ lvt, PyGeom g,
+                                                            int k, int C) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int rxk = g.rx[k], ryk = g.ry[k], rxp = g.rx[k - 1], ryp = g.ry[k - 1];
+    if (i >= (long long)g.b * ryk * rxk * 3 * C) return;
+    const int j = (int)(i % (3 * C));
+    const long long r = i / (3 * C);
+    const int rx = (int)(r % rxk), ry = (int)((r / rxk) % ryk), bb = (int)(r / ((long long)rxk * ryk));
+    const int f = g.size[k] / g.size[k - 1];
+    const int cy1 = (int)min((long long)(ry + 1) * f, (long long)ryp), cx1 = (int)min((long long)(rx + 1) * f, (long long)rxp);
+    if (j < 2 * C) {
+        const double* src = lvq + g.off[k - 1] * 2 * C + j;
+        double s = 0.0;
+        for (int cy = ry * f; cy < cy1; ++cy)
+            for (int cx = rx * f; cx < cx1; ++cx) s += src[(((long long)bb * ryp + cy) * rxp + cx) * 2 * C];
+        lvq[(g.off[k] + r) * 2 * C + j] = s;
+    } else {
+        const long long* src = lvt + g.off[k - 1] * C + (j - 2 * C);
+        long long s = 0;
+        for (int cy = ry * f; cy < cy1; ++cy)
+            for (int cx = rx * f; cx < cx1; ++cx) s += src[(((long long)bb * ryp + cy) * rxp + cx) * C];
+        lvt[(g.off[k] + r) * C + (j - 2 * C)] = s;
+    }
+}
+
+// n_active[l]: grid (blocks, L), one thread per region
+__global__ void __launch_bounds__(256) pycda_count_kernel(const long long* __restrict__ lvt, PyGeom g, int C, int* n_active) {
+    __shared__ int s_cnt;
+    if (threadIdx.x == 0) s_cnt = 0;
+    __syncthreads();
+    const int l = blockIdx.y, k = g.map[l];
+    const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (r < (long long)g.b * g.ry[k] * g.rx[k]) {
+        const int rx = (int)(r % g.rx[k]), ry = (int)((r / g.rx[k]) % g.ry[k]);
+        const long long bound = g.thr_fix * py_area(g.size[k], ry, rx, g.H, g.W);
+        bool any = false;
+        for (int c = 0; c < C; ++c) any |= lvt[(g.off[k] + r) * C + c] > bound;
+        if (any) atomicAdd(&s_cnt, 1);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0 && s_cnt) atomicAdd(&n_active[l], s_cnt);
+}
+
+// grid (blocks, L), one thread per (region, head, class): coef and the workgroup's two loss partials (head 1, head 2)
+__global__ void __launch_bounds__(256) pycda_coef_kernel(const double* __restrict__ lvq, const long long* __restrict__ lvt,
+                                                         PyGeom g, int C, const int* __restrict__ n_active,
+                                                         float* __restrict__ coef, double* __restrict__ ploss) {
+    __shared__ double red[2][256];
+    const int l = blockIdx.y, k = g.map[l];
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    double term = 0.0;
+    int hd = 0;
+    if (i < (long long)g.b * g.ry[k] * g.rx[k] * 2 * C) {
+        const int hc = (int)(i % (2 * C)), c = hc % C;
+        hd = hc / C;
+        const long long r = i / (2 * C);
+        const int rx = (int)(r % g.rx[k]), ry = (int)((r / g.rx[k]) % g.ry[k]);
+        const long long area = py_area(g.size[k], ry, rx, g.H, g.W);
+        const long long tf = lvt[(g.off[k] + r) * C + c];
+        float a = 0.f;
+        if (tf > g.thr_fix * area) {
+            const double T = (double)tf / ((double)area * PY_FIX);
+            const double Q = lvq[(g.off[k] + r) * 2 * C + hc] / (double)area + PY_EPS;
+            const double n = (double)max(n_active[l], 1);
+            term = -T * log(Q);
+            a = (float)(-(double)g.lw[l] * T / (n * (double)area * Q));
+        }
+        coef[(g.coff[l] + r) * 2 * C + hc] = a;
+    }
+    red[0][threadIdx.x] = hd == 0 ? term : 0.0;
+    red[1][threadIdx.x] = hd == 1 ? term : 0.0;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) { red[0][threadIdx.x] += red[0][threadIdx.x + o]; red[1][threadIdx.x] += red[1][threadIdx.x + o]; }
+        __syncthreads();
+    }
+    if (threadIdx.x < 2) ploss[((size_t)l * gridDim.x + blockIdx.x) * 2 + threadIdx.x] = red[threadIdx.x][0];
+}
+
+// A[cell][head][class]: one thread per value, the levels added in order
+__global__ void __launch_bounds__(256) pycda_push_kernel(const float* __restrict__ coef, PyGeom g, int C, float* __restrict__ A) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)g.b * g.ry[0] * g.rx[0] * 2 * C) return;
+    const int hc = (int)(i % (2 * C));
+    const long long cell = i / (2 * C);
+    const int cx = (int)(cell % g.rx[0]), cy = (int)((cell / g.rx[0]) % g.ry[0]), bb = (int)(cell / ((long long)g.rx[0] * g.ry[0]));
+    float acc = 0.f;
+    for (int l = 0; l < g.L; ++l) {
+        const int k = g.map[l], f = g.size[k] / g.size[0];
+        const long long r = ((long long)bb * g.ry[k] + cy / f) * g.rx[k] + cx / f;
+        acc += coef[(g.coff[l] + r) * 2 * C + hc];
+    }
+    A[i] = acc;
+}
+
+// loss[0] = total, loss[1 + l] = level l: the partials in a fixed order, / max(n_l, 1), the mean over the heads
+__global__ void __launch_bounds__(256) pycda_reduce_kernel(const double* __restrict__ ploss, const int* __restrict__ n_active,
+                                                           PyGeom g, int nblk, float* loss) {
+    __shared__ double red[2][256];
+    __shared__ double s_level[PY_MAX_LEVELS];
+    for (int l = 0; l < g.L; ++l) {
+        double s0 = 0.0, s1 = 0.0;
+        for (int i = threadIdx.x; i < nblk; i += 256) { s0 += ploss[((size_t)l * nblk + i) * 2]; s1 += ploss[((size_t)l * nblk + i) * 2 + 1]; }
+        red[0][threadIdx.x] = s0; red[1][threadIdx.x] = s1;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if (threadIdx.x < o) { red[0][threadIdx.x] += red[0][threadIdx.x + o]; red[1][threadIdx.x] += red[1][threadIdx.x + o]; }
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) {
+            const double n = (double)max(n_active[l], 1);
+            s_level[l] = 0.5 * (red[0][0] / n + red[1][0] / n);
+            loss[1 + l] = (float)s_level[l];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        double tot = 0.0;
+        for (int l = 0; l < g.L; ++l) tot += (double)g.lw[l] * s_level[l];
+        loss[0] = (float)tot;
+    }
+}
+
+template <int C>
+__global__ void __launch_bounds__(256) pycda_grad_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
+                                                         const float* __restrict__ A, float* T, int h, int w, int H, int W,
+                                                         int S, int ncx, int ncy, float gs) {
+    extern __shared__ float lds[];
+    float* rows = lds;
+    float* G = lds + 2 * C * 2 * w;
+    int* lxi = (int*)(G + 2 * C * W);
+    float* lxl = (float*)(lxi + W);
+    const int b = blockIdx.y, Y = blockIdx.x;
+    const Lerp ly = row_lerp<false>(Y, h, H);
+    stage_rows<C>(rows, p1, p2, b, ly.i0, ly.i1, h, w);
+    __syncthreads();
+    for (int X = threadIdx.x; X < W; X += 256) {
+        const Lerp lx = lerp_ac(X, w, W);
+        lxi[X] = lx.i0;
+        lxl[X] = lx.l1;
+        const float* a = A + (((size_t)b * ncy + Y / S) * ncx + X / S) * 2 * C;
+#pragma unroll
+        for (int hd = 0; hd < 2; ++hd) {
+            float m, e[C], se, zl;
+            up_softmax<C>(rows, w, hd, ly, lx, 0, m, e, se, zl);
+            float ac[C], dot = 0.f;
+#pragma unroll
+            for (int c = 0; c < C; ++c) { e[c] = e[c] / se; ac[c] = a[hd * C + c]; dot += ac[c] * e[c]; }
+#pragma unroll
+            for (int c = 0; c < C; ++c) G[(hd * C + c) * W + X] = e[c] * (ac[c] - dot) * gs;
+        }
+    }
+    __syncthreads();
+    contract_row<C>(G, lxi, lxl, T, b, Y, w, H, W);
+}
+
+// the chain and the workspace layout of one call; false: sizes outside the contract
+struct PyLayout {
+    PyGeom g;
+    size_t lvq, lvt, coef, A, ploss, T, total;      // byte offsets
+    int nblk;                             // workgroups of the coef pass per level
+    long long most;                       // regions of the largest level
+};
+
+static bool py_layout(int b, int c, int h, int w, int H, int W, const int* sizes, int L, PyLayout& o) {
+    if (!sizes || L < 1 || L > PY_MAX_LEVELS || b <= 0 || c <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return false;
+    if ((long long)b * H * W >= (1ll << 31)) return false;
+    PyGeom& g = o.g;
+    g = PyGeom{};
+    g.b = b, g.H = H, g.W = W, g.L = L;
+    if (max(H, W) > (1 << 30)) return false;
+    int img = 2;                          // the image level: the smallest power of two that covers the image
+    while (img < max(H, W)) img <<= 1;
+    int nk = 0;
+    for (int l = 0; l < L; ++l) {
+        int s = sizes[l];
+        if (s == 0) {
+            if (l != L - 1) return false;
+            s = img;
+        } else {
+            if (s < 2 || s > 256 || (s & (s - 1))) return false;
+            if (l > 0 && s <= sizes[l - 1]) return false;
+        }
+        if (nk == 0) g.size[nk++] = min(s, 8);
+        while (g.size[nk - 1] < s) {      // steps of at most x4
+            if (nk >= PY_MAX_CHAIN) return false;
+            g.size[nk] = (int)min((long long)g.size[nk - 1] * 4, (long long)s);
+            ++nk;
+        }
+        g.map[l] = nk - 1;                // an image level no larger than the last finite size is that level
+    }
+    g.nk = nk;
+    long long regions = 0, cregions = 0;
+    for (int k = 0; k < nk; ++k) {
+        g.ry[k] = (H + g.size[k] - 1) / g.size[k], g.rx[k] = (W + g.size[k] - 1) / g.size[k];
+        g.off[k] = regions;
+        regions += (long long)b * g.ry[k] * g.rx[k];
+    }
+    long long most = 0;
+    for (int l = 0; l < L; ++l) {
+        const long long r = (long long)b * g.ry[g.map[l]] * g.rx[g.map[l]];
+        g.coff[l] = cregions;
+        cregions += r;
+        most = max(most, r);
+    }
+    o.most = most;
+    o.nblk = cdiv(most * 2 * c, 256);
+    size_t at = 0;
+    o.lvq = at, at += align256_((size_t)regions * 2 * c * 8);
+    o.lvt = at, at += align256_((size_t)regions * c * 8);
+    o.coef = at, at += align256_((size_t)cregions * 2 * c * 4);
+    o.A = at, at += align256_((size_t)b * g.ry[0] * g.rx[0] * 2 * c * 4);
+    o.ploss = at, at += align256_((size_t)L * o.nblk * 2 * 8);
+    o.T = at, at += (size_t)b * H * 2 * c * w * 4;
+    o.total = at;
+    return true;
+}
+
+struct PyCall {
+    const float *p1, *p2, *soft;
+    float *loss, *g1, *g2;
+    int *n_active, *flag;
+    char* ws;
+    int h, w, accumulate;
+    float gs;
+};
+
+template <int C>
+static int run_pycda(const PyCall& a, const PyLayout& lay, rgda_stream_t stream) {
+    hipStream_t st = to_stream(stream);
+    const PyGeom& g = lay.g;
+    double* lvq = (double*)(a.ws + lay.lvq);
+    long long* lvt = (long long*)(a.ws + lay.lvt);
+    float* coef = (float*)(a.ws + lay.coef);
+    float* A = (float*)(a.ws + lay.A);
+    double* ploss = (double*)(a.ws + lay.ploss);
+    float* T = (float*)(a.ws + lay.T);
+    const size_t clds = (size_t)2 * C * 2 * a.w * 4;      // the staged rows: within the gradient pass's need, checked there
+    if (lds_attr((const void*)pycda_cell_kernel<C>, clds) != RGDA_OK) return RGDA_ERR_LAUNCH;
+    pycda_cell_kernel<C><<<dim3(g.ry[0], g.b, cdiv(g.W, 256)), 256, clds, st>>>(a.p1, a.p2, a.soft, lvq, lvt, a.flag, a.n_active,
+                                                                               g.L, a.h, a.w, g.H, g.W, g.size[0], g.rx[0]);
+    RGDA_CHECK_LAUNCH();
+    for (int k = 1; k < g.nk; ++k) {
+        pycda_pyramid_kernel<<<cdiv((long long)g.b * g.ry[k] * g.rx[k] * 3 * C, 256), 256, 0, st>>>(lvq, lvt, g, k, C);
+        RGDA_CHECK_LAUNCH();
+    }
+    pycda_count_kernel<<<dim3(cdiv(lay.most, 256), g.L), 256, 0, st>>>(lvt, g, C, a.n_active);
+    RGDA_CHECK_LAUNCH();
+    pycda_coef_kernel<<<dim3(lay.nblk, g.L), 256, 0, st>>>(lvq, lvt, g, C, a.n_active, coef, ploss);
+    RGDA_CHECK_LAUNCH();
+    pycda_reduce_kernel<<<1, 256, 0, st>>>(ploss, a.n_active, g, lay.nblk, a.loss);
+    RGDA_CHECK_LAUNCH();
+    if (!a.g1) return RGDA_OK;
+    pycda_push_kernel<<<cdiv((long long)g.b * g.ry[0] * g.rx[0] * 2 * C, 256), 256, 0, st>>>(coef, g, C, A);
+    RGDA_CHECK_LAUNCH();
+    const size_t lds = grad_lds(C, a.w, g.W, true);
+    if (lds_attr((const void*)pycda_grad_kernel<C>, lds) != RGDA_OK) return RGDA_ERR_LAUNCH;
+    pycda_grad_kernel<C><<<dim3(g.H, g.b), 256, lds, st>>>(a.p1, a.p2, A, T, a.h, a.w, g.H, g.W, g.size[0], g.rx[0], g.ry[0],
+                                                        a.gs);
+    RGDA_CHECK_LAUNCH();
+    const int blocks = cdiv((long long)2 * g.b * C * a.h * a.w, 256);
+    if (a.accumulate)
+        loss_col_kernel<C, true><<<blocks, 256, 0, st>>>(T, a.g1, a.g2, g.b, a.h, a.w, g.H);
+    else
+        loss_col_kernel<C, false><<<blocks, 256, 0, st>>>(T, a.g1, a.g2, g.b, a.h, a.w, g.H);
+    RGDA_CHECK_LAUNCH();
+    return RGDA_OK;
+}
+
 }  // namespace
 
 size_t loss_row_lds_bytes(int c, int w, int W, bool want) { return grad_lds(c, w, W, want); }
@@ -1016,4 +1405,36 @@ extern "C" int rgda_upsample_reg(int heads, const float* p1, const float* p2, co
     a.prm.terms = terms, a.prm.empty_is_zero = empty_is_zero != 0, a.prm.ignore_label = ignore_label;
     a.prm.se = 0.5f * lambda_ent, a.prm.sk = 0.5f * lambda_kld;
     return with_classes(c, [&](auto cc) { return run_reg<decltype(cc)::value>(a, stream); });
+}
+
+extern "C" size_t rgda_upsample_pycda_workspace(int b, int c, int h, int w, int H, int W, const int* sizes, int levels) {
+    PyLayout lay;
+    return py_layout(b, c, h, w, H, W, sizes, levels, lay) ? lay.total : 0;
+}
+
+extern "C" int rgda_upsample_pycda(int heads, const float* p1, const float* p2, const float* soft, const int* sizes,
+                                   const float* level_weight, int levels, double thresh, float weight, int accumulate,
+                                   float* loss, int* n_active, float* g1, float* g2, int* flag, int b, int c, int h, int w,
+                                   int H, int W, void* ws, size_t ws_bytes, rgda_stream_t stream) {
+    if (heads != 1 && heads != 2) return RGDA_ERR_ARG;
+    if (!p1 || !p2 || !soft || !sizes || !loss || !n_active || !ws || ((g1 == nullptr) != (g2 == nullptr))) return RGDA_ERR_ARG;
+    if (heads == 1 && p2 != p1) return RGDA_ERR_ARG;
+    if (!(thresh >= 0.0 && thresh <= 1.0) || !std::isfinite(weight)) return RGDA_ERR_ARG;
+    if (b <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return RGDA_ERR_ARG;
+    if (!class_count_ok(c)) return RGDA_ERR_UNSUPPORTED;
+    PyLayout lay;
+    if (!py_layout(b, c, h, w, H, W, sizes, levels, lay)) return RGDA_ERR_ARG;
+    for (int l = 0; l < levels; ++l) {
+        lay.g.lw[l] = level_weight ? level_weight[l] : 1.f / (float)levels;
+        if (!std::isfinite(lay.g.lw[l])) return RGDA_ERR_ARG;
+    }
+    if (ws_bytes < lay.total) return RGDA_ERR_WORKSPACE;
+    if (b > 65535) return RGDA_ERR_UNSUPPORTED;                             // grid y of the row passes
+    if (grad_lds(c, w, W, true) > MAX_ROW_LDS) return RGDA_ERR_UNSUPPORTED;
+    lay.g.thr_fix = llrint(thresh * PY_FIX);
+    PyCall a{};
+    a.p1 = p1, a.p2 = p2, a.soft = soft, a.loss = loss, a.g1 = g1, a.g2 = g2, a.n_active = n_active, a.flag = flag;
+    a.ws = (char*)ws, a.h = h, a.w = w, a.accumulate = accumulate != 0;
+    a.gs = 0.5f * weight;
+    return with_classes(c, [&](auto cc) { return run_pycda<decltype(cc)::value>(a, lay, stream); });
 }

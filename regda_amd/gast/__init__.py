@@ -1,1 +1,2 @@
 from .triple import TripletLoss  # noqa: F401
+from .pycda import PyramidCurriculumLoss  # noqa: F401

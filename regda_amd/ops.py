@@ -526,6 +526,87 @@ def upsample_reg(p1, p2, label=None, w_ent=None, w_kld=None, terms=REG_ENT | REG
     return loss, g1, g2
 
 
+PYCDA_MAX_LEVELS = 6
+
+
+def pycda_sizes(sizes):
+    """The level sizes of upsample_pycda as a tuple of ints; ValueError unless they are 1 to 6 powers of two in [2, 256],
+    strictly increasing, optionally followed by one 0 (the whole image) -- what rgda_upsample_pycda refuses."""
+    try:
+        sizes = tuple(int(s) for s in sizes)
+    except TypeError:
+        raise ValueError(f'pycda sizes: {sizes!r} is not a sequence of ints') from None
+    if not 1 <= len(sizes) <= PYCDA_MAX_LEVELS:
+        raise ValueError(f'pycda sizes: {len(sizes)} levels; 1 to {PYCDA_MAX_LEVELS}')
+    finite = sizes[:-1] if sizes[-1] == 0 else sizes
+    for i, s in enumerate(finite):
+        if s < 2 or s > 256 or s & (s - 1):
+            raise ValueError(f'pycda sizes: {s}; a finite size is a power of two in [2, 256], 0 (the image) comes last')
+        if i and s <= finite[i - 1]:
+            raise ValueError(f'pycda sizes: {sizes} are not strictly increasing')
+    return sizes
+
+
+def upsample_pycda_workspace(p, soft_shape, sizes):
+    """The workspace of upsample_pycda for logits like `p` and soft labels of shape `soft_shape`: a step allocates it
+    once per shape and passes it as `ws=`."""
+    sizes = pycda_sizes(sizes)
+    b, c, h, w = p.shape
+    H, W = (int(v) for v in soft_shape[-2:])
+    arr = (ctypes.c_int * len(sizes))(*sizes)
+    n = lib().size('rgda_upsample_pycda_workspace', b, c, h, w, H, W, arr, len(sizes))
+    if n == 0:
+        raise ValueError(f'upsample_pycda: no workspace for logits {tuple(p.shape)}, soft labels {tuple(soft_shape)}, sizes {sizes}')
+    return _ws(n, p.device)
+
+
+def upsample_pycda(p1, p2, soft, sizes, thresh=0.5, level_weight=None, weight=1.0, g1=None, g2=None, accumulate=False,
+                   flag=None, want_grad=True, heads=2, loss=None, n_active=None, ws=None):
+    """PyCDA's region pyramid term on the upsampled logits (rgda_upsample_pycda, include/rgda_hip.h)
+    -> (loss f32[1 + L] = total, then the levels, unscaled; n_active int32[L]; g1; g2).  soft: the teacher's
+    probabilities (b, c, H, W); sizes: the levels' region sides, powers of two in [2, 256], strictly increasing, optionally
+    followed by 0 = the whole image; level_weight: L floats (default 1 / L each).  g1 / g2 receive (accumulate: are added)
+    the gradient of 0.5 * weight * total per head.  flag: a device int32 word whose bit 0 is raised by a soft value
+    outside [0, 1].  heads=1: one prediction (p2 must be p1; the gradient is then g1 + g2).  ValueError for what the
+    entry point refuses."""
+    _need_cuda(p1, p2, soft, flag)
+    sizes = pycda_sizes(sizes)
+    p1, p2 = p1.contiguous().float(), p2.contiguous().float()
+    b, c, h, w = p1.shape
+    if soft.dim() != 4 or soft.dtype != torch.float32 or tuple(soft.shape[:2]) != (b, c):
+        raise ValueError(f'upsample_pycda: soft {soft.dtype} {tuple(soft.shape)}, expected float32 ({b}, {c}, H, W)')
+    soft = soft.contiguous()
+    H, W = soft.shape[-2:]
+    nl = len(sizes)
+    lw = None
+    if level_weight is not None:
+        if len(level_weight) != nl:
+            raise ValueError(f'upsample_pycda: {len(level_weight)} level weights for {nl} levels')
+        lw = (ctypes.c_float * nl)(*(float(v) for v in level_weight))
+    if flag is not None:
+        assert flag.dtype == torch.int32 and flag.numel() >= 1
+    loss = torch.empty(1 + nl, dtype=torch.float32, device=p1.device) if loss is None else loss
+    n_active = torch.empty(nl, dtype=torch.int32, device=p1.device) if n_active is None else n_active
+    assert loss.dtype == torch.float32 and loss.numel() == 1 + nl and n_active.dtype == torch.int32 and n_active.numel() == nl
+    if want_grad:
+        assert not accumulate or (g1 is not None and g2 is not None), 'accumulate adds onto given gradients'
+        g1 = torch.empty_like(p1) if g1 is None else g1
+        g2 = torch.empty_like(p2) if g2 is None else g2
+        assert g1.is_contiguous() and g2.is_contiguous() and g1.shape == p1.shape and g2.shape == p2.shape
+    else:
+        g1 = g2 = None
+    L = lib()
+    arr = (ctypes.c_int * nl)(*sizes)
+    if ws is None:
+        ws = _ws(L.size('rgda_upsample_pycda_workspace', b, c, h, w, H, W, arr, nl), p1.device)
+    if heads == 1:
+        p2 = p1
+    L.call('rgda_upsample_pycda', heads, p1.data_ptr(), p2.data_ptr(), soft.data_ptr(), arr, lw, nl, float(thresh),
+           float(weight), int(bool(accumulate)), loss.data_ptr(), n_active.data_ptr(), _p(g1), _p(g2), _p(flag), b, c, h, w,
+           H, W, ws.data_ptr(), ws.numel(), _stream())
+    return loss, n_active, g1, g2
+
+
 IAST_BINS = 0x7C01      # RGDA_IAST_BINS: the non-negative fp16 bit patterns 0 .. 0x7C00
 
 

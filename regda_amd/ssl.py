@@ -26,9 +26,17 @@ from .step import Part, PseudoLabelStep, check_generator
 class SSLStep(PseudoLabelStep):
     def __init__(self, model, prototypes, ema_decay=None, class_balancer_t=None, loss_t='none', uvem_m=0.2, uvem_t=0.7,
                  uvem_g=4.0, gdp_prototype=True, gdp_class_balance=False, ent_weight=0.0, kld_weight=0.0, adv_weight=0.0,
-                 discriminators=None, mix=None, strong=None, **kw):
+                 discriminators=None, mix=None, strong=None, pycda_weight=0.0, pycda_sizes=(8, 16, 32, 64, 0),
+                 pycda_thresh=0.5, **kw):
         if adv_weight or discriminators is not None:
             raise NotImplementedError('the adversarial term (adv_weight / discriminators) belongs to the stage-2 step, AlignStep')
+        # PyCDA's region pyramid term (regda_amd/gast/pycda.py) on the target logits and the label path's
+        # soft label: one rgda_upsample_pycda call behind the target loss and its regularisers that adds its gradient onto
+        # theirs.  Weight 0: no launch.  Checked before the model is touched.
+        self.pycda_weight, self.pycda_sizes = float(pycda_weight), ops.pycda_sizes(pycda_sizes)
+        self.pycda_thresh = float(pycda_thresh)
+        if not self.pycda_weight >= 0.0 or not 0.0 <= self.pycda_thresh <= 1.0:
+            raise ValueError(f'{type(self).__name__}: pycda_weight must be >= 0 and pycda_thresh in [0, 1]')
         super().__init__(model, prototypes, **kw)
         class_num, ignore_label, dev = self.C, self.ig, model.device
         self.ema_decay = ema_decay
@@ -48,6 +56,9 @@ class SSLStep(PseudoLabelStep):
         # rgda_upsample_reg call behind the target loss that adds its gradient onto that loss's.  Both 0: no launch.
         self.ent_weight, self.kld_weight = float(ent_weight), float(kld_weight)
         self.loss_ent = self.loss_kld = None    # the unscaled terms of the last step (device tensors)
+        self.loss_pycda = self.pycda_active = None      # f32 [1 + L]: the unscaled total and levels of the last step; int32 [L]
+        self.pycda_flag = torch.zeros(1, dtype=torch.int32, device=dev) if self.pycda_weight > 0.0 else None
+        self._pycda_bufs = {}       # shape -> (workspace, loss, n_active): allocated once
         # mix: a regda_amd.aug.mix.DomainMix (kind 'class', 'box' or 'dacs') -- DACS inside the step: the
         # student's target tile is the source batch pasted over images_t, the teacher (or the offline soft labels) labels
         # the clean tile, and the source labels are pasted onto the pseudo labels after selection and LRH.  None: no launch.
@@ -261,6 +272,27 @@ class SSLStep(PseudoLabelStep):
                                ignore_label=self.ig, g1=g1, g2=g2, accumulate=True, empty_is_zero=True)[0]
         self.loss_ent, self.loss_kld = reg[0], reg[1]
 
+    def _target_pyramid(self, t1, t2, soft, g1, g2):
+        """PyCDA's region term: the student's mean prediction over the squares of every level against the soft label's
+        mean there (the label path's soft label: refined, and with mix= the pasted copy); its gradient is added onto the
+        target loss's in g1, g2.  Ranks of a data-parallel run use their local region counts."""
+        if not self.pycda_weight > 0.0:
+            return
+        key = (tuple(t1.shape), tuple(soft.shape))
+        if key not in self._pycda_bufs:
+            nl = len(self.pycda_sizes)
+            self._pycda_bufs[key] = (ops.upsample_pycda_workspace(t1, soft.shape, self.pycda_sizes),
+                                     torch.zeros(1 + nl, dtype=torch.float32, device=t1.device),
+                                     torch.zeros(nl, dtype=torch.int32, device=t1.device))
+        ws, loss, n_active = self._pycda_bufs[key]
+        ops.upsample_pycda(t1, t2, soft, self.pycda_sizes, thresh=self.pycda_thresh, weight=self.pycda_weight, g1=g1, g2=g2,
+                           accumulate=True, flag=self.pycda_flag, loss=loss, n_active=n_active, ws=ws)
+        self.loss_pycda, self.pycda_active = loss, n_active
+
+    def pycda_flag_value(self):
+        """Deferred check of the pyramid term's flag word (host sync): bit 0 = a soft-label value outside [0, 1]."""
+        return 0 if self.pycda_flag is None else int(self.pycda_flag.item())
+
     def _step(self, images_s, label_s, images_t, soft_t, regs_t):
         m = self.model
         if not m.training:
@@ -372,9 +404,9 @@ class SSLStep(PseudoLabelStep):
             hard = self._lrh(regs, hard, (soft, cm) if fuse_lrh else None)
         if self.mix is not None:
             # the source labels go onto the FINAL pseudo labels: selection thresholds, label_refine and LRH have seen the
-            # teacher's view of the clean tile only.  The refined soft label is pasted only where the target loss reads it,
-            # and never in the caller's tensor or last_soft_t (refine_label=False makes `soft` that tensor itself)
-            paste_soft = self.loss_fn_t.kind in ('ups', 'uvem')
+            # teacher's view of the clean tile only.  The refined soft label is pasted only where the target loss or the
+            # pyramid term reads it, and never in the caller's tensor or last_soft_t (refine_label=False makes `soft` that tensor itself)
+            paste_soft = self.loss_fn_t.kind in ('ups', 'uvem') or self.pycda_weight > 0.0
             if paste_soft and (soft is soft_t or self.keep_debug):
                 clean, soft = soft, torch.empty(soft.shape, dtype=torch.float32, device=soft.device)
                 plan.host(lambda dst=soft, src=clean: dst.copy_(src))       # a torch op: re-run at every replay
@@ -416,6 +448,7 @@ class SSLStep(PseudoLabelStep):
             loss_s = self._source_loss(s1, s2, label_s, g1[:nb], g2[:nb])
         loss_t = self._target_loss(t1, t2, hard, soft, g1[nb:], g2[nb:], proto_weight)
         self._target_regularisers(t1, t2, hard, g1[nb:], g2[nb:])
+        self._target_pyramid(t1, t2, soft, g1[nb:], g2[nb:])
         if self.keep_debug:
             self.debug.update(g1_t=g1[nb:].clone(), g2_t=g2[nb:].clone())
         if side is not None:

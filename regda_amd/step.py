@@ -122,6 +122,10 @@ class FusedStep:
         ent, kld = kw.pop('ent_weight', 0.0), kw.pop('kld_weight', 0.0)
         if ent or kld:
             raise NotImplementedError('the IAST regularisers (ent_weight / kld_weight) belong to the SSL step')
+        pycda = kw.pop('pycda_weight', 0.0)
+        kw.pop('pycda_sizes', None), kw.pop('pycda_thresh', None)
+        if pycda:
+            raise NotImplementedError('the PyCDA region pyramid term (pycda_weight) belongs to the SSL step')
         if kw.pop('mix', None) is not None:
             raise NotImplementedError('the in-step cross-domain mix (mix=) belongs to the SSL step')
         if kw.pop('strong', None) is not None:
