@@ -300,6 +300,37 @@ int rgda_upsample_pycda(int heads, const float* p1, const float* p2, const float
                         int* n_active, float* g1, float* g2, int* flag, int b, int c, int h, int w, int H, int W, void* ws,
                         size_t ws_bytes, rgda_stream_t stream);
 
+/* Region-overlap term (Dice / soft Jaccard / Tversky, Salehi et al. 2017 / focal-Tversky, Abraham & Khan 2019) of the
+ * upsampled logits against hard labels.  Forward + d / d(logits) on the upsample-loss pipeline.  The reference has no
+ * such code; this is the contract (restated in float64 by tests/overlap_ref.py).
+ * Inputs: p1, p2 logits NCHW f32 (b,c,h,w); label int64 (b,H,W).  A pixel is valid iff label != ignore_label; a valid
+ *   label outside [0, c) counts as ignored and raises bit 0 of *flag (device int32, may be NULL; never cleared here).
+ * Predictions: per head q = softmax of the logits upsampled bilinearly (align_corners=True, the arithmetic of
+ *   rgda_upsample_ce) to (H, W); h == H, w == W is the plain call on full-resolution logits.
+ * Sums over the valid pixels i of the whole batch, per head and class, each one a sum of non-negative terms:
+ *   TP_c = sum q_i(c) [y_i == c];  FP_c = sum q_i(c) [y_i != c];  FN_c = sum (1 - q_i(c)) [y_i == c];
+ *   Y_c = #{y_i == c} (an exact integer).
+ * Index and loss: N_c = TP_c + smooth; M_c = alpha FP_c + beta FN_c + 1e-7; T_c = N_c / (N_c + M_c); class c is present
+ *   iff Y_c > 0, n = #present; loss_hd = (1 / n) sum_{present c} (M_c / (N_c + M_c))^gamma; the loss is the mean over the
+ *   heads.  alpha = beta = 0.5: Dice; alpha = beta = 1: soft Jaccard; gamma > 1: focal-Tversky.  Labels carry no
+ *   gradient.  n == 0 (everything ignored): a loss of exactly 0 and a gradient of exactly 0; with accumulate = 1 the
+ *   gradient buffers are then left untouched.
+ * Parameters: alpha, beta, smooth finite and >= 0; 1 <= gamma <= 8; weight finite and >= 0; anything else is
+ *   RGDA_ERR_ARG.
+ * Outputs: loss f32[1], unscaled; index f32[heads][c] (may be NULL) = T_c, 0 for an absent class; present int32[c] (may
+ *   be NULL) = Y_c; g1, g2: NULL or NCHW f32 (b,c,h,w), per head the gradient of 0.5 * weight * loss_hd; heads 1: p2 ==
+ *   p1, g1 + g2 is the gradient, no 0.5 (the convention of rgda_upsample_reg / _pycda).  accumulate 0: written, 1: added
+ *   onto what they hold (one f32 addition of the finished value).
+ * Limits: 6 <= c <= 16 and the row-LDS limit of rgda_upsample_ce (RGDA_ERR_UNSUPPORTED); b * H * W < 2^31; b <= 65535.
+ *   ws: rgda_upsample_overlap_workspace bytes (0 = bad arguments).  Every check comes before anything touches the GPU.
+ * Deterministic: no float atomics, Y_c summed in integers, the float sums combined in a fixed order that does not
+ *   depend on workgroup scheduling; two calls give identical bits; nothing is read back. */
+size_t rgda_upsample_overlap_workspace(int b, int c, int h, int w, int H, int W);
+int rgda_upsample_overlap(int heads, const float* p1, const float* p2, const int64_t* label, double alpha, double beta,
+                          double gamma, double smooth, float weight, int accumulate, float* loss, float* index,
+                          int* present, float* g1, float* g2, int* flag, int b, int c, int h, int w, int H, int W,
+                          int ignore_label, void* ws, size_t ws_bytes, rgda_stream_t stream);
+
 /* IAST, instance-adaptive pseudo-labels: ias_thresh and the loop body of generate_pseudo   regda/utils/tools.py:323-373
  * Three stages over one workspace of rgda_iast_workspace(n, c, H, W) bytes (0 = bad arguments), laid out as
  *   int32 hist[c][RGDA_IAST_BINS] | f32 maxp[n*H*W] | uint8 arg[n*H*W], each piece starting on a 256-byte boundary.

@@ -547,9 +547,9 @@ __global__ void __launch_bounds__(256) loss_grad_kernel(const float* __restrict_
 
 // vertical contraction T -> g[head][b][c][y][x]; ACC (rgda_upsample_reg, accumulate): one f32 add of the finished value
 // onto what g holds
-template <int C, bool ACC = false>
-__global__ void __launch_bounds__(256) loss_col_kernel(const float* __restrict__ T, float* g1, float* g2, int b_n, int h,
-                                                       int w, int H) {
+template <int C, bool ACC>
+__device__ __forceinline__ void col_contract(const float* __restrict__ T, float* g1, float* g2, int b_n, int h, int w,
+                                             int H) {
     int i = blockIdx.x * 256 + threadIdx.x;
     int total = 2 * b_n * C * h * w;
     if (i >= total) return;
@@ -565,6 +565,18 @@ __global__ void __launch_bounds__(256) loss_col_kernel(const float* __restrict__
     }
     float* g = (hd ? g2 : g1) + (((size_t)b * C + c) * h + y) * w + x;
     *g = ACC ? __fadd_rn(*g, acc) : acc;
+}
+template <int C, bool ACC = false>
+__global__ void __launch_bounds__(256) loss_col_kernel(const float* __restrict__ T, float* g1, float* g2, int b_n, int h,
+                                                       int w, int H) {
+    col_contract<C, ACC>(T, g1, g2, b_n, h, w, H);
+}
+// the accumulate variant behind a device-side gate: *live == 0 leaves g1, g2 untouched (x + 0 is not x for x = -0)
+template <int C>
+__global__ void __launch_bounds__(256) loss_col_gated_kernel(const float* __restrict__ T, float* g1, float* g2, int b_n,
+                                                             int h, int w, int H, const int* __restrict__ live) {
+    if (*live == 0) return;
+    col_contract<C, true>(T, g1, g2, b_n, h, w, H);
 }
 
 // per head: the row partials in a fixed order in double, / the head's denominator -- CE (no header): * 1 / #pixels,
@@ -1255,6 +1267,246 @@ static int run_pycda(const PyCall& a, const PyLayout& lay, rgda_stream_t stream)
     return RGDA_OK;
 }
 
+// ------------------------------------------------------------------------ region-overlap term (rgda_upsample_overlap)
+// Dice / soft Jaccard / Tversky / focal-Tversky of the upsampled logits against hard labels (the contract:
+// include/rgda_hip.h): three sums per head and class over the whole batch, and a per-pixel gradient whose two
+// coefficients per head and class are functions of those sums.  No per-pixel scratch:
+//   stat     one workgroup per output row: q = softmax(upsampled logits) per head in registers, TP / FP / FN per head and
+//            class summed per thread, across the wave by DPP (a fixed butterfly), across the four waves in order; one
+//            partial of 6 C floats per row with plain stores.  1 - q_y is taken as the sum of the other classes' q: no
+//            cancellation.  Y_c per row: integer LDS atomics, plain stores
+//   stage    one workgroup: every value's row partials in double, rows in order within contiguous chunks and the chunks
+//            in order; T_c, the loss, and per head and class the two coefficients dL/dq for pixels with y == c and for
+//            the others, with 0.5 * weight folded in (f64, rounded once)
+//   grad     the row pass again: u_c from the coefficient table (scalar loads: SGPR-resident), dz_k = q_k (u_k - sum_c
+//            q_c u_c) over valid pixels, contracted horizontally; col as above (accumulate: behind the n > 0 gate).
+// No float atomics; nothing is read back.
+constexpr int OV_STAGE_THREADS = 1024;
+constexpr double OV_EPS = 1e-7;
+
+struct OvParams {
+    double alpha, beta, gamma, smooth, gs;
+    int heads;
+};
+
+// v summed over the wave, the same bits in every lane, without the LDS crossbar
+__device__ __forceinline__ float wave_sum_dpp(float v) {
+    return xor_add<32>(xor_add<16>(xor_add<8>(group_sum(v, 8))));
+}
+
+template <int C>
+__global__ void __launch_bounds__(256) overlap_stat_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
+                                                           const int64_t* __restrict__ label, float* __restrict__ partial,
+                                                           int* __restrict__ ycnt, int* flag, int h, int w, int H, int W,
+                                                           int ignore_label) {
+    extern __shared__ float rows[];
+    __shared__ int s_cnt[C];
+    __shared__ float red[4][6 * C];
+    const int b = blockIdx.y, Y = blockIdx.x;
+    const Lerp ly = row_lerp<false>(Y, h, H);
+    if (threadIdx.x < C) s_cnt[threadIdx.x] = 0;
+    stage_rows<C>(rows, p1, p2, b, ly.i0, ly.i1, h, w);
+    __syncthreads();
+    float acc[2][3][C];                   // head x (TP, FP, FN) x class
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int c = 0; c < C; ++c) acc[i / 3][i % 3][c] = 0.f;
+    bool bad = false;
+    for (int X = threadIdx.x; X < W; X += 256) {
+        const long long lab = label[((size_t)b * H + Y) * W + X];
+        const bool inr = lab >= 0 && lab < C;
+        bad |= lab != ignore_label && !inr;
+        if (lab == ignore_label || !inr) continue;
+        const int li = (int)lab;
+        atomicAdd(&s_cnt[li], 1);
+        const Lerp lx = lerp_ac(X, w, W);
+#pragma unroll
+        for (int hd = 0; hd < 2; ++hd) {
+            float m, e[C], se, zl;
+            up_softmax<C>(rows, w, hd, ly, lx, li, m, e, se, zl);
+            const float inv_se = 1.f / se;
+            float others = 0.f;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const float q = e[c] * inv_se;
+                acc[hd][0][c] += (c == li) ? q : 0.f;
+                acc[hd][1][c] += (c == li) ? 0.f : q;
+                others += (c == li) ? 0.f : q;
+            }
+#pragma unroll
+            for (int c = 0; c < C; ++c) acc[hd][2][c] += (c == li) ? others : 0.f;
+        }
+    }
+    if (bad && flag) atomicOr(flag, 1);
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const float v = wave_sum_dpp(acc[i / 3][i % 3][c]);
+            if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][i * C + c] = v;
+        }
+    __syncthreads();
+    const size_t row = (size_t)b * H + Y;
+    if (threadIdx.x < 6 * C)
+        partial[row * 6 * C + threadIdx.x] =
+            red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+    if (threadIdx.x < C) ycnt[row * C + threadIdx.x] = s_cnt[threadIdx.x];
+}
+
+// coef f32[2 heads][C][2] = dL/dq of a pixel with y == c, of the others (times 0.5 * weight); *live = n, the present classes
+__global__ void __launch_bounds__(OV_STAGE_THREADS) overlap_stage_kernel(const float* __restrict__ partial,
+                                                                         const int* __restrict__ ycnt, int nrows, int C,
+                                                                         OvParams prm, float* __restrict__ coef, int* live,
+                                                                         float* loss, float* index, int* present) {
+    __shared__ double s_part[OV_STAGE_THREADS];
+    __shared__ double s_tot[7 * RGDA_MAX_CLASSES];
+    __shared__ double s_term[2 * RGDA_MAX_CLASSES];
+    const int t = threadIdx.x, nv = 7 * C, nchunk = OV_STAGE_THREADS / nv;      // nv <= 112: at least 9 chunks
+    const int j = t % nv, k = t / nv;
+    if (k < nchunk) {
+        const int r0 = (int)((long long)k * nrows / nchunk), r1 = (int)((long long)(k + 1) * nrows / nchunk);
+        double s = 0.0;
+        if (j < 6 * C)
+            for (int r = r0; r < r1; ++r) s += (double)partial[(size_t)r * 6 * C + j];
+        else
+            for (int r = r0; r < r1; ++r) s += (double)ycnt[(size_t)r * C + (j - 6 * C)];      // integers: exact
+        s_part[k * nv + j] = s;
+    }
+    __syncthreads();
+    if (t < nv) {
+        double s = 0.0;
+        for (int i = 0; i < nchunk; ++i) s += s_part[i * nv + t];
+        s_tot[t] = s;
+    }
+    __syncthreads();
+    int n = 0;
+    for (int c = 0; c < C; ++c) n += s_tot[6 * C + c] > 0.0;
+    if (t < 2 * C) {
+        const int hd = t / C, c = t % C;
+        const double TP = s_tot[(hd * 3 + 0) * C + c], FP = s_tot[(hd * 3 + 1) * C + c], FN = s_tot[(hd * 3 + 2) * C + c];
+        const bool on = s_tot[6 * C + c] > 0.0;
+        const double N = TP + prm.smooth, M = prm.alpha * FP + prm.beta * FN + OV_EPS, D = N + M, r = M / D;
+        const double kc = on ? prm.gamma * pow(r, prm.gamma - 1.0) / (double)n * prm.gs : 0.0;
+        s_term[t] = on ? pow(r, prm.gamma) : 0.0;
+        coef[t * 2] = (float)(-kc * (D - (1.0 - prm.beta) * N) / (D * D));
+        coef[t * 2 + 1] = (float)(kc * prm.alpha * N / (D * D));
+        if (index && hd < prm.heads) index[t] = on ? (float)(N / D) : 0.f;
+    }
+    if (present && t < C) present[t] = (int)s_tot[6 * C + t];
+    __syncthreads();
+    if (t == 0) {
+        double l0 = 0.0, l1 = 0.0;
+        for (int c = 0; c < C; ++c) { l0 += s_term[c]; l1 += s_term[C + c]; }
+        const double tot = prm.heads == 2 ? 0.5 * (l0 + l1) : l0;
+        loss[0] = n > 0 ? (float)(tot / (double)n) : 0.f;
+        *live = n;
+    }
+}
+
+template <int C>
+__global__ void __launch_bounds__(256) overlap_grad_kernel(const float* __restrict__ p1, const float* __restrict__ p2,
+                                                           const int64_t* __restrict__ label,
+                                                           const float* __restrict__ coef, float* T, int h, int w, int H,
+                                                           int W, int ignore_label) {
+    extern __shared__ float lds[];
+    float* rows = lds;
+    float* G = lds + 2 * C * 2 * w;
+    int* lxi = (int*)(G + 2 * C * W);
+    float* lxl = (float*)(lxi + W);
+    const int b = blockIdx.y, Y = blockIdx.x;
+    const Lerp ly = row_lerp<false>(Y, h, H);
+    stage_rows<C>(rows, p1, p2, b, ly.i0, ly.i1, h, w);
+    float ua[2][C], ub[2][C];             // uniform addresses: scalar loads
+#pragma unroll
+    for (int i = 0; i < 2 * C; ++i) { ua[i / C][i % C] = coef[2 * i]; ub[i / C][i % C] = coef[2 * i + 1]; }
+    __syncthreads();
+    for (int X = threadIdx.x; X < W; X += 256) {
+        const Lerp lx = lerp_ac(X, w, W);
+        lxi[X] = lx.i0;
+        lxl[X] = lx.l1;
+        const long long lab = label[((size_t)b * H + Y) * W + X];
+        const bool valid = lab != ignore_label && lab >= 0 && lab < C;
+        const int li = valid ? (int)lab : 0;
+#pragma unroll
+        for (int hd = 0; hd < 2; ++hd) {
+            float m, e[C], se, zl, u[C], dot = 0.f;
+            up_softmax<C>(rows, w, hd, ly, lx, li, m, e, se, zl);
+            const float inv_se = 1.f / se;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                e[c] *= inv_se;
+                u[c] = (c == li) ? ua[hd][c] : ub[hd][c];
+                dot += e[c] * u[c];
+            }
+#pragma unroll
+            for (int c = 0; c < C; ++c) G[(hd * C + c) * W + X] = valid ? e[c] * (u[c] - dot) : 0.f;
+        }
+    }
+    __syncthreads();
+    contract_row<C>(G, lxi, lxl, T, b, Y, w, H, W);
+}
+
+// the workspace of one call: byte offsets
+struct OvLayout {
+    size_t partial, ycnt, coef, T, total;
+};
+
+static OvLayout ov_layout(int b, int c, int h, int w, int H) {
+    (void)h;
+    OvLayout o;
+    const size_t nrows = (size_t)b * H;
+    size_t at = 0;
+    o.partial = at, at += align256_(nrows * 6 * c * 4);
+    o.ycnt = at, at += align256_(nrows * c * 4);
+    o.coef = at, at += align256_((size_t)4 * c * 4 + 4);      // the table, then n
+    o.T = at, at += nrows * 2 * c * w * 4;
+    o.total = at;
+    return o;
+}
+
+struct OvCall {
+    const float *p1, *p2;
+    const int64_t* label;
+    float *loss, *index, *g1, *g2;
+    int *present, *flag;
+    char* ws;
+    int b, h, w, H, W, ignore_label, accumulate;
+    OvParams prm;
+};
+
+template <int C>
+static int run_overlap(const OvCall& a, rgda_stream_t stream) {
+    hipStream_t st = to_stream(stream);
+    const OvLayout lay = ov_layout(a.b, C, a.h, a.w, a.H);
+    float* partial = (float*)(a.ws + lay.partial);
+    int* ycnt = (int*)(a.ws + lay.ycnt);
+    float* coef = (float*)(a.ws + lay.coef);
+    int* live = (int*)(coef + 4 * C);
+    float* T = (float*)(a.ws + lay.T);
+    const dim3 rows_grid(a.H, a.b);
+    const size_t slds = (size_t)2 * C * 2 * a.w * 4;      // the staged rows: within the gradient pass's need
+    if (lds_attr((const void*)overlap_stat_kernel<C>, slds) != RGDA_OK) return RGDA_ERR_LAUNCH;
+    overlap_stat_kernel<C><<<rows_grid, 256, slds, st>>>(a.p1, a.p2, a.label, partial, ycnt, a.flag, a.h, a.w, a.H, a.W,
+                                                        a.ignore_label);
+    RGDA_CHECK_LAUNCH();
+    overlap_stage_kernel<<<1, OV_STAGE_THREADS, 0, st>>>(partial, ycnt, a.b * a.H, C, a.prm, coef, live, a.loss, a.index,
+                                                        a.present);
+    RGDA_CHECK_LAUNCH();
+    if (!a.g1) return RGDA_OK;
+    const size_t lds = grad_lds(C, a.w, a.W, true);
+    if (lds_attr((const void*)overlap_grad_kernel<C>, lds) != RGDA_OK) return RGDA_ERR_LAUNCH;
+    overlap_grad_kernel<C><<<rows_grid, 256, lds, st>>>(a.p1, a.p2, a.label, coef, T, a.h, a.w, a.H, a.W, a.ignore_label);
+    RGDA_CHECK_LAUNCH();
+    const int blocks = cdiv((long long)2 * a.b * C * a.h * a.w, 256);
+    if (a.accumulate)
+        loss_col_gated_kernel<C><<<blocks, 256, 0, st>>>(T, a.g1, a.g2, a.b, a.h, a.w, a.H, live);
+    else
+        loss_col_kernel<C, false><<<blocks, 256, 0, st>>>(T, a.g1, a.g2, a.b, a.h, a.w, a.H);
+    RGDA_CHECK_LAUNCH();
+    return RGDA_OK;
+}
+
 }  // namespace
 
 size_t loss_row_lds_bytes(int c, int w, int W, bool want) { return grad_lds(c, w, W, want); }
@@ -1437,4 +1689,36 @@ extern "C" int rgda_upsample_pycda(int heads, const float* p1, const float* p2, 
     a.ws = (char*)ws, a.h = h, a.w = w, a.accumulate = accumulate != 0;
     a.gs = 0.5f * weight;
     return with_classes(c, [&](auto cc) { return run_pycda<decltype(cc)::value>(a, lay, stream); });
+}
+
+extern "C" size_t rgda_upsample_overlap_workspace(int b, int c, int h, int w, int H, int W) {
+    if (b <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0 || !class_count_ok(c)) return 0;
+    if ((long long)b * H * W >= (1ll << 31)) return 0;
+    return ov_layout(b, c, h, w, H).total;
+}
+
+extern "C" int rgda_upsample_overlap(int heads, const float* p1, const float* p2, const int64_t* label, double alpha,
+                                     double beta, double gamma, double smooth, float weight, int accumulate, float* loss,
+                                     float* index, int* present, float* g1, float* g2, int* flag, int b, int c, int h, int w,
+                                     int H, int W, int ignore_label, void* ws, size_t ws_bytes, rgda_stream_t stream) {
+    if (heads != 1 && heads != 2) return RGDA_ERR_ARG;
+    if (!p1 || !p2 || !label || !loss || !ws || ((g1 == nullptr) != (g2 == nullptr))) return RGDA_ERR_ARG;
+    if (heads == 1 && p2 != p1) return RGDA_ERR_ARG;
+    if (!(std::isfinite(alpha) && alpha >= 0.0) || !(std::isfinite(beta) && beta >= 0.0)) return RGDA_ERR_ARG;
+    if (!(std::isfinite(smooth) && smooth >= 0.0) || !(gamma >= 1.0 && gamma <= 8.0)) return RGDA_ERR_ARG;
+    if (!(std::isfinite(weight) && weight >= 0.f)) return RGDA_ERR_ARG;
+    if (b <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0) return RGDA_ERR_ARG;
+    if ((long long)b * H * W >= (1ll << 31)) return RGDA_ERR_ARG;         // the class counts: 32 bits
+    if (!class_count_ok(c)) return RGDA_ERR_UNSUPPORTED;
+    if (ws_bytes < ov_layout(b, c, h, w, H).total) return RGDA_ERR_WORKSPACE;
+    if (b > 65535) return RGDA_ERR_UNSUPPORTED;                             // grid y of the row passes
+    const bool want = g1 != nullptr;      // without gradients the rows alone are staged
+    if (grad_lds(c, w, W, want) > MAX_ROW_LDS) return RGDA_ERR_UNSUPPORTED;
+    OvCall a{};
+    a.p1 = p1, a.p2 = p2, a.label = label, a.loss = loss, a.index = index, a.present = present, a.g1 = g1, a.g2 = g2;
+    a.flag = flag, a.ws = (char*)ws, a.b = b, a.h = h, a.w = w, a.H = H, a.W = W, a.ignore_label = ignore_label;
+    a.accumulate = accumulate != 0;
+    a.prm.alpha = alpha, a.prm.beta = beta, a.prm.gamma = gamma, a.prm.smooth = smooth, a.prm.heads = heads;
+    a.prm.gs = 0.5 * (double)weight;
+    return with_classes(c, [&](auto cc) { return run_overlap<decltype(cc)::value>(a, stream); });
 }

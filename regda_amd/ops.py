@@ -5,6 +5,7 @@ Everything here takes/returns CUDA(ROCm) torch tensors, enqueues on
 (device memory + streams); the arithmetic is in librgda_hip.so.
 """
 import ctypes
+import math
 
 import torch
 
@@ -605,6 +606,84 @@ def upsample_pycda(p1, p2, soft, sizes, thresh=0.5, level_weight=None, weight=1.
            float(weight), int(bool(accumulate)), loss.data_ptr(), n_active.data_ptr(), _p(g1), _p(g2), _p(flag), b, c, h, w,
            H, W, ws.data_ptr(), ws.numel(), _stream())
     return loss, n_active, g1, g2
+
+
+def overlap_params(alpha=0.5, beta=0.5, gamma=1.0, smooth=0.0, who='upsample_overlap'):
+    """The four parameters of the overlap term as floats; ValueError unless alpha, beta, smooth are finite and >= 0 and
+    1 <= gamma <= 8 -- what rgda_upsample_overlap refuses."""
+    try:
+        alpha, beta, gamma, smooth = float(alpha), float(beta), float(gamma), float(smooth)
+    except (TypeError, ValueError):
+        raise ValueError(f'{who}: alpha, beta, gamma, smooth must be numbers') from None
+    for name, v in (('alpha', alpha), ('beta', beta), ('smooth', smooth)):
+        if not (math.isfinite(v) and v >= 0.0):
+            raise ValueError(f'{who}: {name} {v!r}; finite and >= 0')
+    if not 1.0 <= gamma <= 8.0:
+        raise ValueError(f'{who}: gamma {gamma!r} outside [1, 8]')
+    return alpha, beta, gamma, smooth
+
+
+def upsample_overlap_workspace(p, label_shape):
+    """The workspace of upsample_overlap for logits like `p` and labels of shape `label_shape`: a step allocates it once
+    per shape and passes it as `ws=`."""
+    b, c, h, w = p.shape
+    H, W = (int(v) for v in label_shape[-2:])
+    n = lib().size('rgda_upsample_overlap_workspace', b, c, h, w, H, W)
+    if n == 0:
+        raise ValueError(f'upsample_overlap: no workspace for logits {tuple(p.shape)}, labels {tuple(label_shape)}')
+    return _ws(n, p.device)
+
+
+def upsample_overlap(p1, p2, label, alpha=.5, beta=.5, gamma=1., smooth=0., weight=1., heads=2, ignore_label=-1, g1=None,
+                     g2=None, accumulate=False, want_grad=True, loss=None, index=None, present=None, flag=None, ws=None):
+    """The Dice / soft Jaccard / Tversky / focal-Tversky overlap term of the upsampled logits against hard labels
+    (rgda_upsample_overlap, include/rgda_hip.h) -> (loss f32[1], unscaled; index f32 [heads, c] = the per-class soft
+    overlap index T_c, 0 for an absent class; present int32 [c] = the class's valid pixels; g1; g2).  With N = TP + smooth
+    and M = alpha FP + beta FN + 1e-7 summed over the valid pixels of the batch, T = N / (N + M) and the loss is the mean
+    of (1 - T)^gamma over the classes that occur, then over the heads.  alpha = beta = 0.5: Dice, 1: Jaccard.  g1 / g2
+    receive (accumulate: are added) the gradient of 0.5 * weight * loss per head.  flag: a device int32 word whose bit 0 is
+    raised by a label outside [0, c) that is not ignore_label (it counts as ignored).  heads=1: one prediction (p2 must
+    be p1; the gradient is then g1 + g2).  ValueError for what the entry point refuses."""
+    _need_cuda(p1, p2, label, flag)
+    alpha, beta, gamma, smooth = overlap_params(alpha, beta, gamma, smooth)
+    weight = float(weight)
+    if not (math.isfinite(weight) and weight >= 0.0):
+        raise ValueError(f'upsample_overlap: weight {weight!r}; finite and >= 0')
+    if heads not in (1, 2):
+        raise ValueError(f'upsample_overlap: heads {heads!r}; 1 or 2')
+    if p1.dim() != 4 or p2.shape != p1.shape:
+        raise ValueError(f'upsample_overlap: logits {tuple(p1.shape)} and {tuple(p2.shape)}, expected two (b, c, h, w)')
+    p1, p2 = p1.contiguous().float(), p2.contiguous().float()
+    b, c, h, w = p1.shape
+    if label.dim() != 3 or label.dtype != torch.int64 or label.shape[0] != b:
+        raise ValueError(f'upsample_overlap: label {label.dtype} {tuple(label.shape)}, expected int64 ({b}, H, W)')
+    label = label.contiguous()
+    H, W = label.shape[-2:]
+    dev = p1.device
+    if flag is not None:
+        assert flag.dtype == torch.int32 and flag.numel() >= 1
+    loss = torch.empty(1, dtype=torch.float32, device=dev) if loss is None else loss
+    index = torch.empty(heads, c, dtype=torch.float32, device=dev) if index is None else index
+    present = torch.empty(c, dtype=torch.int32, device=dev) if present is None else present
+    assert loss.dtype == torch.float32 and loss.numel() == 1
+    assert index.dtype == torch.float32 and index.is_contiguous() and tuple(index.shape) == (heads, c)
+    assert present.dtype == torch.int32 and present.is_contiguous() and present.numel() == c
+    if want_grad:
+        assert not accumulate or (g1 is not None and g2 is not None), 'accumulate adds onto given gradients'
+        g1 = torch.empty_like(p1) if g1 is None else g1
+        g2 = torch.empty_like(p2) if g2 is None else g2
+        assert g1.is_contiguous() and g2.is_contiguous() and g1.shape == p1.shape and g2.shape == p2.shape
+    else:
+        g1 = g2 = None
+    L = lib()
+    if ws is None:
+        ws = upsample_overlap_workspace(p1, label.shape)
+    if heads == 1:
+        p2 = p1
+    L.call('rgda_upsample_overlap', heads, p1.data_ptr(), p2.data_ptr(), label.data_ptr(), alpha, beta, gamma, smooth,
+           weight, int(bool(accumulate)), loss.data_ptr(), index.data_ptr(), present.data_ptr(), _p(g1), _p(g2), _p(flag), b,
+           c, h, w, H, W, int(ignore_label), ws.data_ptr(), ws.numel(), _stream())
+    return loss, index, present, g1, g2
 
 
 IAST_BINS = 0x7C01      # RGDA_IAST_BINS: the non-negative fp16 bit patterns 0 .. 0x7C00

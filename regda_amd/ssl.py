@@ -27,7 +27,7 @@ class SSLStep(PseudoLabelStep):
     def __init__(self, model, prototypes, ema_decay=None, class_balancer_t=None, loss_t='none', uvem_m=0.2, uvem_t=0.7,
                  uvem_g=4.0, gdp_prototype=True, gdp_class_balance=False, ent_weight=0.0, kld_weight=0.0, adv_weight=0.0,
                  discriminators=None, mix=None, strong=None, pycda_weight=0.0, pycda_sizes=(8, 16, 32, 64, 0),
-                 pycda_thresh=0.5, **kw):
+                 pycda_thresh=0.5, overlap_weight_t=0.0, **kw):
         if adv_weight or discriminators is not None:
             raise NotImplementedError('the adversarial term (adv_weight / discriminators) belongs to the stage-2 step, AlignStep')
         # PyCDA's region pyramid term (regda_amd/gast/pycda.py) on the target logits and the label path's
@@ -37,6 +37,10 @@ class SSLStep(PseudoLabelStep):
         self.pycda_thresh = float(pycda_thresh)
         if not self.pycda_weight >= 0.0 or not 0.0 <= self.pycda_thresh <= 1.0:
             raise ValueError(f'{type(self).__name__}: pycda_weight must be >= 0 and pycda_thresh in [0, 1]')
+        # The overlap term (FusedStep: overlap_weight_s, overlap=) on the student's target logits against the step's final
+        # pseudo labels (with mix= the pasted copy; unlabelled pixels are ignored): one rgda_upsample_overlap call behind
+        # the pyramid term that adds its gradient onto the target loss's.  Weight 0: no launch.
+        self.overlap_weight_t = self._overlap_weight(overlap_weight_t, 'overlap_weight_t')
         super().__init__(model, prototypes, **kw)
         class_num, ignore_label, dev = self.C, self.ig, model.device
         self.ema_decay = ema_decay
@@ -449,10 +453,13 @@ class SSLStep(PseudoLabelStep):
         loss_t = self._target_loss(t1, t2, hard, soft, g1[nb:], g2[nb:], proto_weight)
         self._target_regularisers(t1, t2, hard, g1[nb:], g2[nb:])
         self._target_pyramid(t1, t2, soft, g1[nb:], g2[nb:])
+        self._overlap_term('t', self.overlap_weight_t, t1, t2, hard, g1[nb:], g2[nb:])
         if self.keep_debug:
             self.debug.update(g1_t=g1[nb:].clone(), g2_t=g2[nb:].clone())
         if side is not None:
             plan.wait_event(main, source_done)       # source loss, its logit gradients, the new prototypes
+        if self.keep_debug:
+            self.debug.update(g1_s=g1[:nb].clone(), g2_s=g2[:nb].clone())
         self._mark('label path + losses done')
         # from here on the step no longer reads its input tensors (images: stem im2col of student and teacher; labels,
         # soft labels and region maps: the label path and the losses): an input prefetcher may overwrite them

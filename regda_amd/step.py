@@ -37,8 +37,14 @@ class FusedStep:
 
     def __init__(self, model, class_num=6, ignore_label=-1, momentum=0.9, weight_decay=5e-4, max_norm=32.0,
                  bucket_elems=12 << 20, process_group=None, overlap_wgrad=True, overlap_comm=True, class_balancer_s=None,
-                 grad_payload='fp32', comm=None, loss_s='CrossEntropy', style=None):
+                 grad_payload='fp32', comm=None, loss_s='CrossEntropy', style=None, overlap_weight_s=0.0, overlap=None):
         ops.check_class_count(class_num, type(self).__name__)
+        # The region-overlap term (Dice by default; regda_amd/gast/overlap.py) on the source logits and
+        # the true labels: one rgda_upsample_overlap call behind the source loss that adds its gradient onto that loss's.
+        # overlap: a dict of alpha, beta, gamma, smooth, read at every step.  Weight 0: no launch.  Checked before the model
+        # is touched.
+        self.overlap_weight_s = self._overlap_weight(overlap_weight_s, 'overlap_weight_s')
+        self.overlap = self._overlap_dict(overlap)
         self.model = model
         self.C, self.ig = class_num, ignore_label
         self._shape_ok = None
@@ -77,6 +83,53 @@ class FusedStep:
         self.style_flag = torch.zeros(1, dtype=torch.int32, device=dev) if style is not None else None
         self.last_style = None      # the last step's table as drawn on the host, int32 (N, 4)
         self._style_ws = None       # (shape, the transform's workspace): kept from step to step, like the flag word
+        # the overlap term's outputs of the last step (device tensors; None while the weight is 0): the unscaled loss f32
+        # [1], the per-class soft overlap index f32 [2, C], the classes' pixel counts int32 [C]; _t: the SSL step's target side
+        self.loss_overlap_s = self.overlap_index_s = self.overlap_present_s = None
+        self.loss_overlap_t = self.overlap_index_t = self.overlap_present_t = None
+        self.overlap_flag = None    # bit 0: a label outside [0, C) that is not ignore_label (made at the first launch)
+        self._overlap_bufs = {}     # (side, shapes) -> (workspace, loss, index, present): allocated once
+
+    def _overlap_weight(self, v, name):
+        v = float(v)
+        if not (v >= 0.0 and v != float('inf')):
+            raise ValueError(f'{type(self).__name__}: {name} must be finite and >= 0, got {v!r}')
+        return v
+
+    def _overlap_dict(self, d):
+        d = dict(d or {})
+        if set(d) - {'alpha', 'beta', 'gamma', 'smooth'}:
+            raise ValueError(f"{type(self).__name__}: overlap= takes alpha, beta, gamma, smooth; got {sorted(d)}")
+        ops.overlap_params(**d, who=f'{type(self).__name__}(overlap=)')
+        return d
+
+    def _overlap_term(self, side, weight, x1, x2, label, g1, g2):
+        """The overlap term of logits x1, x2 against `label`: its gradient, times `weight`, is added onto g1, g2 (one
+        launch sequence on the current stream, nothing read back) and its outputs become loss_overlap_<side>,
+        overlap_index_<side>, overlap_present_<side>.  The sums run over this rank's batch: ranks of a data-parallel
+        run use their local sums, like every other loss of the step."""
+        if not weight > 0.0:
+            return
+        prm = ops.overlap_params(**self.overlap, who=f'{type(self).__name__}.overlap')
+        key = (side, tuple(x1.shape), tuple(label.shape))
+        if key not in self._overlap_bufs:
+            dev = x1.device
+            self._overlap_bufs[key] = (ops.upsample_overlap_workspace(x1, label.shape),
+                                       torch.zeros(1, dtype=torch.float32, device=dev),
+                                       torch.zeros(2, x1.shape[1], dtype=torch.float32, device=dev),
+                                       torch.zeros(x1.shape[1], dtype=torch.int32, device=dev))
+        if self.overlap_flag is None:
+            self.overlap_flag = torch.zeros(1, dtype=torch.int32, device=x1.device)
+        ws, loss, index, present = self._overlap_bufs[key]
+        ops.upsample_overlap(x1, x2, label, *prm, weight=weight, ignore_label=self.ig, g1=g1, g2=g2, accumulate=True,
+                             loss=loss, index=index, present=present, flag=self.overlap_flag, ws=ws)
+        setattr(self, 'loss_overlap_' + side, loss)
+        setattr(self, 'overlap_index_' + side, index)
+        setattr(self, 'overlap_present_' + side, present)
+
+    def overlap_flag_value(self):
+        """Deferred check of the overlap term's flag word (host sync): bit 0 = a label outside [0, C)."""
+        return 0 if self.overlap_flag is None else int(self.overlap_flag.item())
 
     def _style_source(self, images_s, images_t):
         """The source tile the network sees: `images_s` itself without `style=`, else its Fourier style transfer towards
@@ -126,6 +179,9 @@ class FusedStep:
         kw.pop('pycda_sizes', None), kw.pop('pycda_thresh', None)
         if pycda:
             raise NotImplementedError('the PyCDA region pyramid term (pycda_weight) belongs to the SSL step')
+        if kw.pop('overlap_weight_t', 0.0):
+            raise NotImplementedError('the overlap term on the target logits (overlap_weight_t) belongs to the SSL step; '
+                                      'overlap_weight_s is served here')
         if kw.pop('mix', None) is not None:
             raise NotImplementedError('the in-step cross-domain mix (mix=) belongs to the SSL step')
         if kw.pop('strong', None) is not None:
@@ -185,9 +241,13 @@ class FusedStep:
         return self.loss_fn_s.class_balancer is not None
 
     def _source_loss(self, s1, s2, label_s, g1, g2):
-        """loss_calc(source, loss_fn_s): its value; d loss / d logits written into g1, g2."""
+        """loss_calc(source, loss_fn_s): its value; d loss / d logits written into g1, g2.  With overlap_weight_s the
+        overlap term against the true labels follows on the same stream and adds its gradient onto them; the value
+        returned stays the plain loss."""
         f = self.loss_fn_s
-        return f.launch(s1, s2, label_s, class_weight=self._class_weights(f.class_balancer, label_s), g1=g1, g2=g2)[0]
+        loss = f.launch(s1, s2, label_s, class_weight=self._class_weights(f.class_balancer, label_s), g1=g1, g2=g2)[0]
+        self._overlap_term('s', self.overlap_weight_s, s1, s2, label_s, g1, g2)
+        return loss
 
     def _mark(self, name, stream=None):
         if self.marks is not None:
