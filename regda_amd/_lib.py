@@ -6,11 +6,11 @@ the ABI.  Fails loudly when the shared library has not been built
 """
 import ctypes
 import os
-import re
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, 'csrc', 'librgda_hip.so')
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'rgda_hip.h')
+from . import _header
+from ._header import HEADER_PATH
+
+LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc', 'librgda_hip.so')
 
 _CT = {
     'int': ctypes.c_int, 'float': ctypes.c_float, 'int64_t': ctypes.c_int64, 'size_t': ctypes.c_size_t,
@@ -21,23 +21,10 @@ _CT = {
 
 def parse_header(path=HEADER_PATH):
     """-> {name: (restype, [argtypes])} for every function declared in the header."""
-    src = open(path).read()
-    src = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
-    src = re.sub(r'//[^\n]*', '', src)
     protos = {}
-    for m in re.finditer(r'\b(int|size_t|const char\s*\*)\s+(rgda_\w+)\s*\(([^;{]*?)\)\s*;', src, flags=re.S):
-        ret, name, args = m.group(1), m.group(2), m.group(3)
-        restype = {'int': ctypes.c_int, 'size_t': ctypes.c_size_t}.get(ret.strip(), ctypes.c_char_p)
-        argtypes = []
-        args = args.strip()
-        if args and args != 'void':
-            for a in args.split(','):
-                a = a.strip()
-                if '*' in a:
-                    argtypes.append(ctypes.c_void_p)
-                else:
-                    ty = a.replace('const ', '').split()[0]
-                    argtypes.append(_CT[ty])
+    for ret, name, args in _header.prototypes(path):
+        restype = {'int': ctypes.c_int, 'size_t': ctypes.c_size_t}.get(ret, ctypes.c_char_p)
+        argtypes = [ctypes.c_void_p if '*' in a else _CT[a.replace('const ', '').split()[0]] for a in args]
         protos[name] = (restype, argtypes)
     return protos
 
@@ -69,8 +56,7 @@ class _Lib:
                 continue
             fn.restype = restype
             fn.argtypes = argtypes
-        want = int(re.search(r'#define\s+RGDA_ABI_VERSION\s+(\d+)', open(HEADER_PATH).read()).group(1))
-        if self._dll.rgda_abi_version() != want:
+        if self._dll.rgda_abi_version() != _header.constants()['RGDA_ABI_VERSION']:
             raise ImportError('librgda_hip.so ABI version mismatch: rebuild with `make -C regda_amd/csrc`')
 
     def raw(self, name):

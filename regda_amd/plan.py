@@ -17,9 +17,9 @@ import struct
 
 import torch
 
-from . import _lib
+from . import _header, _lib
 
-MAX_ARGS = 36
+MAX_ARGS = _header.constants()['RGDA_PLAN_MAX_ARGS']        # argument slots of one rgda_plan_entry row
 
 
 class PlanEntry(ctypes.Structure):
