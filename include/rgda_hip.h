@@ -1091,6 +1091,66 @@ int rgda_fourier_style(const float* img_s, const float* img_t, float* out, const
  * on rows that are switched off too: the table says what was drawn.) */
 int rgda_fourier_style_write_table(int32_t* table, const int32_t* host, int N, int M, int H, int W, rgda_stream_t stream);
 
+/* ------------------------------------------------------------- histogram matching of the source tile */
+
+/* Per-channel histogram matching of normalised source tiles to a target tile, image by image from a device table: the
+ * grey-level distribution of a source plane is mapped onto that of its partner's plane (scikit-image's
+ * exposure.match_histograms, albumentations' HistogramMatching with its blend_ratio).  The reference has no such pass;
+ * the semantics are this library's and tests/hist_ref.py restates them in numpy and Python integers.
+ *   img_s f32 [N][3][H][W], img_t f32 [M][3][H][W] (read only), out f32 [N][3][H][W], every pixel written, OUT OF PLACE.
+ *   table int32 [N][RGDA_STYLE_TABLE_COLS], 16-byte aligned, DEVICE memory: row n = {partner in [0, M), blend_q in
+ *     [0, RGDA_HIST_BLEND_ONE], on, 0}.  The blend is beta = blend_q / 65536, exact.
+ *   mean_s*, std_s*, mean_t*, std_t* (r, g, b): the normalisations the source and the target tiles carry; std > 0.
+ * Source and target tiles have one size, so both histograms of a pair sum to HW.
+ * Per source image n with on == 1, partner p, per channel c:
+ *   1. Grey levels: v(x) = clamp(rintf(fmaf(x, std, mean)), 0, 255), the source's normalisation for img_s, the target's
+ *      for img_t (a NaN counts as level 0).
+ *   2. hs[256] of the source plane and ht[256] of the partner's plane: exact integer histograms; cs, ct their inclusive
+ *      prefix sums; u_0 < ... < u_{k-1} the levels with ht > 0.
+ *   3. The matched level of each v with hs[v] > 0: let j be the largest index with ct[u_j] <= cs[v].
+ *        no such j:  L[v] = u_0
+ *        j == k - 1: L[v] = u_{k-1}
+ *        otherwise:  L[v] = u_j + ((cs[v] - ct[u_j]) * (u_{j+1} - u_j)) / (ct[u_{j+1}] - ct[u_j]), numerator and
+ *                    denominator formed in integers (below 2^32 at H, W <= 4096), both converted to fp64, ONE fp64
+ *                    division, then ONE fp64 addition.
+ *      L[v] = v where hs[v] == 0 (never read).  This is np.interp(cs / HW, ct / HW, u) with the comparisons made exact;
+ *      an image matched to itself gives L[v] == v exactly.
+ *   4. D[v] = (float)(beta * (L[v] - v) / (double)std_s[c]): fp64, rounded to fp32 once.
+ *   5. out = x + D[v(x)], one fp32 addition, no clamp (on the grey scale the result lies in [-0.5, 255.5]); the sub-level
+ *      part of the source pixel survives.  beta == 0, and a partner identical to the source under equal normalisations,
+ *      give D == 0: the source comes back (x + 0.0f: a -0.0 pixel becomes +0.0, every other value keeps its bits).
+ * A row with on == 0 is COPIED bit for bit (no arithmetic touches it; NaN and inf pass through).  The rows are read on the
+ * device and cannot be refused here: a row with a partner outside [0, M), blend_q outside [0, RGDA_HIST_BLEND_ONE] or on
+ * outside {0, 1} is copied unchanged and sets *flag (optional, device int) to 1.
+ * Four launches whatever the table holds, no host synchronisation, no runtime memset: the rows as served and the zeroed
+ * counters; the histograms of all N + M images (per-wave LDS bins, integer LDS atomics, then integer global atomics of
+ * the nonzero bins); L and D, one workgroup per (source image, channel); the apply pass, which reads the source tile once.
+ * Integer sums only: two runs give identical bits.
+ * Served: N and M in 1..RGDA_STYLE_MAX_IMAGES, H, W in 1..4096.
+ *   ws: rgda_hist_style_workspace(N, M, H, W) bytes (0 for a shape that is not served), 16-byte aligned; rewritten BY the
+ *     call, any contents on entry.
+ *   hist (optional) uint32 [N + M][3][256], 4-byte aligned: the histograms, the source images first.
+ *   lut (optional) f64 [N][3][256], 8-byte aligned: L; the identity (L[v] = v) for a row that is off or not served.
+ * Errors before any launch (RGDA_ERR_ARG): null img_s / img_t / out / ws; null or misaligned table; misaligned ws, hist
+ * or lut; N, M, H or W < 1; a std that is not positive and finite, a mean that is not finite; out overlapping img_s or
+ * img_t.  N or M above RGDA_STYLE_MAX_IMAGES, H or W above 4096: RGDA_ERR_UNSUPPORTED. */
+#define RGDA_HIST_BLEND_ONE 65536
+size_t rgda_hist_style_workspace(int N, int M, int H, int W);
+int rgda_hist_style(const float* img_s, const float* img_t, float* out, const int32_t* table, void* ws, int N, int M, int H,
+                    int W, float mean_sr, float mean_sg, float mean_sb, float std_sr, float std_sg, float std_sb,
+                    float mean_tr, float mean_tg, float mean_tb, float std_tr, float std_tg, float std_tb, uint32_t* hist,
+                    double* lut, int* flag, rgda_stream_t stream);
+
+/* The host's table -> device, carried IN THE KERNEL ARGUMENTS of one launch, as rgda_fourier_style_write_table carries its
+ * draw.
+ *   table int32 [N][RGDA_STYLE_TABLE_COLS] on the device, 16-byte aligned <- host, N * 4 int32 of HOST memory read during
+ *     the call; column 3 is written as 0.
+ *   M: the target images the partners index; H, W: the tiles the table is for.
+ * RGDA_ERR_ARG: null table / host; misaligned table; N, M, H or W < 1; a partner outside [0, M); blend_q outside
+ * [0, RGDA_HIST_BLEND_ONE]; on not 0 or 1 (rows that are off are checked too: the table says what was drawn).
+ * RGDA_ERR_UNSUPPORTED: N or M above RGDA_STYLE_MAX_IMAGES. */
+int rgda_hist_style_write_table(int32_t* table, const int32_t* host, int N, int M, int H, int W, rgda_stream_t stream);
+
 /* ------------------------------------------------------------- region maps without SAM */
 
 /* The region maps rgda_lrh and rgda_label_refine_sup read, generated from the raw tile.

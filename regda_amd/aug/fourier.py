@@ -13,11 +13,11 @@ MAX_B = 64              # RGDA_STYLE_MAX_B
 MAX_IMAGES = 16         # RGDA_STYLE_MAX_IMAGES
 
 
-def _norm(who, mean, std):
+def _norm(who, mean, std, cls='FourierStyle'):
     mean, std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
     if len(mean) != 3 or len(std) != 3 or not all(v > 0 and math.isfinite(v) for v in std) \
             or not all(math.isfinite(v) for v in mean):
-        raise ValueError('FourierStyle: %s are three finite values each, std positive' % who)
+        raise ValueError('%s: %s are three finite values each, std positive' % (cls, who))
     return mean, std
 
 
@@ -76,3 +76,16 @@ class FourierStyle:
             beta = r.uniform(self.beta[0], self.beta[1])
             t[i, :3] = (partner, self.half_width(h, w, beta), int(on))
         return t
+
+    # what a step's style= calls (regda_amd/step.py: _style_source); HistogramStyle has the same three
+    def workspace(self, n, m, h, w, device):
+        from .. import ops
+        return ops.fourier_style_workspace(n, m, h, w, device)
+
+    def write_table(self, table, rows, n_targets, size):
+        from .. import ops
+        return ops.fourier_style_write_table(table, rows, n_targets, size)
+
+    def apply(self, images_s, images_t, table, ws=None, flag=None):
+        from .. import ops
+        return ops.fourier_style(images_s, images_t, table, self.mean_s, self.std_s, self.mean_t, self.std_t, ws=ws, flag=flag)

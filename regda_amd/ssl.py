@@ -114,7 +114,7 @@ class SSLStep(PseudoLabelStep):
             # the same: the table is drawn on the host and travels as kernel arguments
             raise RuntimeError('the strong augmentation (strong=) draws on the host: use record_plan(), not capture()')
         if self.style is not None:
-            raise RuntimeError('the Fourier style transfer (style=) draws on the host: use record_plan(), not capture()')
+            raise RuntimeError('the style transfer of the source tile (style=) draws on the host: use record_plan(), not capture()')
         self._static = self._static_inputs(images_s, label_s, images_t, soft_t, regs_t)
         self._build_maps(images_s)
         torch.cuda.synchronize()

@@ -1,7 +1,7 @@
 """What the three fused training steps share:
 
     FusedStep               the model, the optimizer tail, the gradient exchange, the source loss, the training state,
-                            style= (the Fourier style transfer of the source tile)
+                            style= (the style transfer of the source tile: Fourier, or histogram matching)
       +-- SourceStep        stage 1 (regda_amd/source.py)
       +-- PseudoLabelStep   + prototypes, the selection thresholds, LRH
             +-- SSLStep     the self-training step: teacher, target loss, mix / strong, plans and graphs (regda_amd/ssl.py)
@@ -25,7 +25,7 @@ from .gast.balance import source_loss
 Part = namedtuple('Part', 'name obj check after hint', defaults=(None, None, ''))
 
 
-def check_generator(obj, saved, entry, strict):     # the host generators (DomainMix, StrongAugment, FourierStyle): load a copy
+def check_generator(obj, saved, entry, strict):     # the host generators (DomainMix, StrongAugment, the styles): load a copy
     try:
         copy.deepcopy(obj).load_state_dict(saved)
     except ValueError as e:
@@ -77,7 +77,8 @@ class FusedStep:
         self.debug = None
         self.world, self.group = self.reducer.world, process_group
         # style: a regda_amd.aug.fourier.FourierStyle -- Fourier style transfer of the source tile ahead of the forward
-        # (DESIGN.md 4.2j): the low-frequency amplitudes of each source image become those of a target image of the batch.
+        # (DESIGN.md 4.2j): the low-frequency amplitudes of each source image become those of a target image of the batch
+        # -- or a regda_amd.aug.histogram.HistogramStyle: its grey-level distribution becomes the target image's.
         # The caller's tensors are never written, the result is a buffer of the step's own.  None: no launch.
         self.style = style
         self.style_flag = torch.zeros(1, dtype=torch.int32, device=dev) if style is not None else None
@@ -132,9 +133,10 @@ class FusedStep:
         return 0 if self.overlap_flag is None else int(self.overlap_flag.item())
 
     def _style_source(self, images_s, images_t):
-        """The source tile the network sees: `images_s` itself without `style=`, else its Fourier style transfer towards
-        this batch's target tiles, out of place.  The draw and the launch that carries it (rgda_fourier_style_write_table:
-        values in the kernel arguments) are ONE host action, re-run at every replay of a recorded step."""
+        """The source tile the network sees: `images_s` itself without `style=`, else its style transfer (Fourier, or
+        histogram matching) towards this batch's target tiles, out of place.  The style object brings the three calls:
+        workspace, write_table and apply.  The draw and the launch that carries it (rgda_*_style_write_table: values in the
+        kernel arguments) are ONE host action, re-run at every replay of a recorded step."""
         st = self.style
         if st is None:
             return images_s
@@ -148,16 +150,15 @@ class FusedStep:
         m = images_t.shape[0]
         table = torch.empty(n, ops.STYLE_TABLE_COLS, dtype=torch.int32, device=images_s.device)
         if self._style_ws is None or self._style_ws[0] != (n, m, h, w):
-            self._style_ws = ((n, m, h, w), ops.fourier_style_workspace(n, m, h, w, images_s.device))
+            self._style_ws = ((n, m, h, w), st.workspace(n, m, h, w, images_s.device))
         here = torch.cuda.current_stream()
 
         def draw():
             self.last_style = st.draw(n, m, h, w)
             with ops.use_stream(here):      # (a replay runs host actions with the library's stream set to the plan's)
-                ops.fourier_style_write_table(table, self.last_style, m, (h, w))
+                st.write_table(table, self.last_style, m, (h, w))
         plan.host(draw)
-        return ops.fourier_style(images_s, images_t.contiguous().float(), table, st.mean_s, st.std_s, st.mean_t, st.std_t,
-                                 ws=self._style_ws[1], flag=self.style_flag)
+        return st.apply(images_s, images_t.contiguous().float(), table, ws=self._style_ws[1], flag=self.style_flag)
 
     def _keep_source(self, source_s):
         """keep_debug: the source tile as the network saw it, next to whatever the step kept"""
